@@ -29,6 +29,12 @@ frame are sharded by group key, every rank holds its shard in HBM, and the GATHE
 0 (RCCL point-to-point, piece by piece behind the compute) is inside the timed region.  `--scaling weak` keeps 1e6 groups
 per rank (no collective).  `scatter` reports, outside the timed region, what it costs to distribute a frame that is
 resident on rank 0 only.  See DESIGN.md "multi-GPU".
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline line (`value`,
+`ms_per_step`, ...): nothing else.  Everything above beside the headline -- roofline, gram_build, grouped_p8, grouped_by_key,
+cpu_baseline + parity_spot_check, dist_step, end_to_end, other_configs, grouped_c3spec, scatter -- runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step returned (a fixed, seeded sample of the groups' coefficients and null flags)
+as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -71,9 +77,16 @@ def main() -> int:
                     help="N > 1, strong scaling: how the coefficients reach rank 0 -- RCCL point-to-point per piece (default), or the peers' kernels "
                          "storing straight into rank 0's IPC-mapped result block (opt-in until it has run across two devices)")
     ap.add_argument("--cpu-sample-groups", type=int, default=400_000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip end_to_end / grouped_c3spec / scatter (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure roofline, gram_build, grouped_p8, grouped_by_key, cpu_baseline, dist_step, end_to_end, "
+                         "other_configs, grouped_c3spec and scatter (a plain run times the headline steps only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline and the CPU figures of other_configs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip end_to_end / other_configs / grouped_c3spec / scatter (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (seeded sample of the coefficients, null flags) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -171,23 +184,12 @@ def main() -> int:
 
     for _ in range(args.warmup):
         step()
-    if not dry:
-        ctx.get_timing(reset=True)
-        ctx.get_timing_samples("grouped_moments", reset=True)
-        ctx.set_timing(True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         coeffs, nulls = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    if dry:
-        timing = {"grouped_moments": (0.0, 0), "solve": (0.0, 0)}
-        launch_ms = []
-    else:
-        ctx.set_timing(False)
-        timing = ctx.get_timing(reset=True)
-        launch_ms = sorted(ctx.get_timing_samples("grouped_moments", reset=True))
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -195,11 +197,209 @@ def main() -> int:
     ms_per_step = 1e3 * elapsed / args.steps
     value = G_total / (elapsed / args.steps)
 
-    # ---- roofline of the dominant kernel (fused grouped Gram + solve), rank 0's launches
+    # ---- what the last timed step returned (rank 0: the gathered frame under strong scaling, its own shard under weak)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(np, torch, Path(args.dump_outputs), coeffs, nulls)
+
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel (fused grouped Gram + solve), rank 0's launches: the timed steps once more with the
+        # HIP-event hooks on (a pass of its own, so that the headline steps above carry no timing events)
+        if not dry:
+            ctx.get_timing(reset=True)
+            ctx.get_timing_samples("grouped_moments", reset=True)
+            ctx.set_timing(True)
+        barrier()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        if dry:
+            timing = {"grouped_moments": (0.0, 0), "solve": (0.0, 0)}
+            launch_ms = []
+        else:
+            ctx.set_timing(False)
+            timing = ctx.get_timing(reset=True)
+            launch_ms = sorted(ctx.get_timing_samples("grouped_moments", reset=True))
+        roofline = _roofline(timing, launch_ms, args.steps, G, R, P)
+
+    # ---- what this box's HBM delivers to a plain streaming copy (SURVEY.md 8d: quote the spec peak AND a measured figure)
+    if args.full and rank == 0 and not dry:
+        a = torch.empty(1 << 27, dtype=torch.float64, device=dev)  # 1 GiB
+        b = torch.empty_like(a)
+        b.copy_(a)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(5):
+            b.copy_(a)
+        torch.cuda.synchronize(dev)
+        copy_gbps = 5 * 2 * (1 << 30) / (time.perf_counter() - t0) / 1e9
+        # (read + write bytes of a 1 GiB device-to-device copy: a reference figure of the box, NOT a ceiling for a read-only stream --
+        #  the achievable read stream of this box is `read_stream_GBps` below, the single-OLS Gram kernel on the same frame)
+        roofline["measured_copy_GBps"] = round(copy_gbps, 1)
+        del a, b
+
+    # ---- fixed cost of the N-rank step, measured on this one GPU: the same frame through GroupedShardPlan over an RCCL process
+    # group of world size 1 (no peer: what is left is everything a step does beside its kernel -- Python, the prepared C call, the
+    # stream bookkeeping) against the plain call timed above.  At N ranks the kernel shrinks by N, this does not.
+    dist_overhead = None
+    if args.full and rank == 0 and world == 1:
+        try:
+            dist_overhead = _dist_step_overhead(torch, par, pds, ctx, dev, xs, y, off_pair, offsets, args, ms_per_step, use_dist)
+        except Exception as e:
+            dist_overhead = {"error": f"{type(e).__name__}: {e}"}
+
+    # ---- config 2 on the same frame: single OLS Gram build (pds_moments), HBM GB/s
+    gram = None
+    if args.full and rank == 0 and not dry:
+        for _ in range(2):
+            pds.gram_moments(*xs, target=y, ctx=ctx)
+        ctx.get_timing(reset=True)
+        ctx.set_timing(True)
+        reps = 5
+        for _ in range(reps):
+            pds.gram_moments(*xs, target=y, ctx=ctx)
+        ctx.set_timing(False)
+        ms, cnt = ctx.get_timing(reset=True)["moments"]
+        gb = N * (P + 1) * 8 / 1e9
+        g_ms = ms / max(cnt, 1)
+        gram = {"workload": f"single OLS Gram build, {N:.0e} rows x {P} f64 feats", "algorithmic_GB": round(gb, 3),
+                "avg_launch_ms": round(g_ms, 4), "achieved_GBps": round(gb / (g_ms * 1e-3), 1),
+                "frac_of_hbm_peak": round(gb / (g_ms * 1e-3) / HBM_PEAK_GBPS, 4)}
+        roofline["read_stream_GBps"] = gram["achieved_GBps"]  # what a pure read stream of these columns reaches on this box (Gram kernel)
+        roofline["frac_of_read_stream"] = round(roofline["achieved"] / gram["achieved_GBps"], 4) if gram["achieved_GBps"] else None
+
+    # ---- BASELINE.json configs[2] as written (8 features; the headline metric is quoted on 16 -- SURVEY.md 8d asks for
+    # both): the same groups on the first 8 feature columns
+    p8 = None
+    if args.full and rank == 0 and P >= 8 and not dry:
+        for _ in range(2):
+            pds.lin_reg_by(*xs[:8], target=y, group_offsets=offsets, add_bias=False, ctx=ctx)
+        torch.cuda.synchronize(dev)
+        reps = 5
+        ctx.get_timing(reset=True)
+        ctx.set_timing(True)
+        t8 = time.perf_counter()
+        for _ in range(reps):
+            pds.lin_reg_by(*xs[:8], target=y, group_offsets=offsets, add_bias=False, ctx=ctx)
+        torch.cuda.synchronize(dev)
+        t8 = (time.perf_counter() - t8) / reps
+        ctx.set_timing(False)
+        k8_ms, k8_cnt = ctx.get_timing(reset=True)["grouped_moments"]
+        b8 = G * (R * 9 * 8 + 16 + 8 * 8 + 1)
+        k8 = k8_ms / max(k8_cnt, 1)
+        p8 = {"workload": f"{G} groups x {R} rows x 8 f64 feats", "regressions_per_s": round(G / t8, 1),
+              "ms_per_step": round(t8 * 1e3, 4), "kernel_ms": round(k8, 4), "algorithmic_GBps": round(b8 / (k8 * 1e-3) / 1e9, 1),
+              "frac_of_hbm_peak": round(b8 / (k8 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+
+    # ---- the same step from the KEY COLUMN (sorted int64 keys, what group_by(key) starts from) instead of precomputed offsets: one pass
+    # over the keys (order check + run marks), a scan and a pass over the marks in front of the same fused kernel
+    by_key = None
+    if args.full and rank == 0 and not dry:
+        try:
+            by_key = _by_key(torch, pds, ctx, dev, xs, y, offsets, G, R, P)
+        except Exception as e:
+            by_key = {"error": f"{type(e).__name__}: {e}"}
+
+    # ---- CPU baseline + parity spot check on a bounded sample (rank 0, N = 1 only)
+    cpu = None
+    parity = None
+    host_cols = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not dry:
+        cpu, parity = _cpu_baseline(np, args, xs, y, coeffs, nulls, G, R, P)
+
+    # ---- the same workload from HOST Arrow buffers through the plugin boundary (rank 0, N = 1): the rate a Polars user sees
+    end_to_end = None
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not dry:
+        try:
+            end_to_end = _end_to_end(torch, np, pds, dev, xs, y, G, R, P, cpu)
+        except Exception as e:  # pyarrow / harness trouble must not cost the headline line
+            end_to_end = {"error": f"{type(e).__name__}: {e}"}
+
+    # ---- the other BASELINE configs, on the headline frame where they share it (C2) and on a C4 frame
+    other = None
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not dry:
+        try:
+            other = _other_configs(torch, pds, ctx, dev, xs, y, N, P, with_cpu=not args.no_cpu)
+        except Exception as e:
+            other = {"error": f"{type(e).__name__}: {e}"}
+
+    # ---- SURVEY.md 8(d) C3 data: Poisson sizes, collinear groups (the gate fires inside the timed run), sorted and shuffled keys
+    c3 = None
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not dry:
+        try:
+            del xs, y
+            torch.cuda.empty_cache()
+            c3 = _c3_spec(torch, pds, ctx, dev)
+        except Exception as e:
+            c3 = {"error": f"{type(e).__name__}: {e}"}
+
+    # ---- scatter leg (outside the timed region): what distributing a rank-0-resident frame of this size costs
+    scatter = None
+    if args.full and use_dist and strong and not args.no_extras:
+        try:
+            scatter = _scatter_leg(torch, dist, par, dev, rank, world, G_total, R, P)
+        except Exception as e:
+            scatter = {"error": f"{type(e).__name__}: {e}"}
+
+    if rank == 0:
+        per = "of the frame" if strong else "per GPU"
+        line = {
+            "metric": "grouped lstsq regressions/sec (1e8 rows x 16 f64 feats; Gram-build GB/s under gram_build)",
+            "value": round(value, 1), "unit": "regressions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic" if not dry else "synthetic -- DRY RUN on CPU (gloo, injected numpy compute): control-flow rehearsal, not a measurement",
+            "config": {"workload": f"group_by(key).agg(lin_reg): {args.groups} groups x {R} rows x {P} f64 feats {per} "
+                                   f"({args.groups * R:.0e} rows), OLS with rank gate (pl_lr default path), inputs resident in HBM; `value`: the groups "
+                                   f"given as row offsets (pre-segmented, as Polars hands groups to pl_lr -- the cpu_baseline gets the same); "
+                                   f"the same step starting from a sorted int64 key column: grouped_by_key"
+                                   + (", coefficients + null flags gathered to rank 0 inside the timed region" if gather else ""),
+                       "groups_total": G_total, "groups_per_gpu": G, "rows_per_group": R, "features": P,
+                       "parallelism": f"group-sharded x{world}", "gather_chunks": chunks if gather else None,
+                       "gather": (args.gather if gather else None)},
+        }
+        if args.full:
+            line.update({
+                "roofline": roofline, "gram_build": gram, "grouped_p8": p8, "grouped_by_key": by_key, "cpu_baseline": cpu, "parity_spot_check": parity,
+                "dist_step": dist_overhead, "end_to_end": end_to_end, "other_configs": other, "grouped_c3spec": c3, "scatter": scatter,
+            })
+        print(json.dumps(line), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+DUMP_SAMPLE_GROUPS = 262_144  # groups whose results --dump-outputs writes (fewer when the features would push it past DUMP_BYTES)
+DUMP_BYTES = 60_000_000
+DUMP_SEED = 20_240_607
+
+
+def _dump_outputs(np, torch, out_dir, coeffs, nulls):
+    """
+    What a caller of the timed path received from the last timed step, as out_dir/<name>.npy: the coefficients (float64, groups x
+    features) and null flags (float32, 1 = the group's fit is null) of a fixed, seeded sample of the groups, and the sampled group
+    indices (float64, ascending).  The sample depends on the group count only, so two builds given the same arguments write the
+    same groups.
+    """
+    n_groups, n_feats = int(coeffs.shape[0]), int(coeffs.shape[1])
+    n = min(n_groups, DUMP_SAMPLE_GROUPS, DUMP_BYTES // (8 * n_feats + 8 + 4))
+    if n < n_groups:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_groups, size=n, replace=False))
+    else:
+        idx = np.arange(n_groups)
+    sel = torch.from_numpy(idx).to(coeffs.device)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "coefficients.npy", coeffs.index_select(0, sel).cpu().numpy().astype(np.float64))
+    np.save(out_dir / "null_flags.npy", nulls.index_select(0, sel.to(nulls.device)).cpu().numpy().astype(np.float32))
+    np.save(out_dir / "group_index.npy", idx.astype(np.float64))
+
+
+def _roofline(timing, launch_ms, steps, G, R, P):
+    """HIP-event launch durations of the dominant kernel (`steps` steps) against its algorithmic bytes and the HBM peak."""
     q = P + 2
     gm_ms, gm_cnt = timing["grouped_moments"]
     sv_ms, sv_cnt = timing["solve"]
-    launches_per_step = max(gm_cnt // max(args.steps, 1), 1)
+    launches_per_step = max(gm_cnt // max(steps, 1), 1)
     groups_per_launch = G / launches_per_step
     fused = sv_cnt == 0  # Gram + solve in one kernel: no moment record traffic
     # algorithmic bytes per launch (DESIGN.md 4.2): every input element once + offsets, plus what the kernel must
@@ -228,151 +428,9 @@ def main() -> int:
         "avg_launch_ms": round(avg_ms, 4), "launches_per_step": launches_per_step,
         "launch_ms_min_median_max": [round(launch_ms[0], 4), round(launch_ms[len(launch_ms) // 2], 4), round(launch_ms[-1], 4)] if launch_ms else None,
         "algorithmic_bytes_per_launch": int(alg_bytes),
-        "solve_ms_per_step": round(sv_ms / max(args.steps, 1), 4), "gram_ms_per_step": round(gm_ms / max(args.steps, 1), 4),
+        "solve_ms_per_step": round(sv_ms / max(steps, 1), 4), "gram_ms_per_step": round(gm_ms / max(steps, 1), 4),
     }
-
-    # ---- what this box's HBM delivers to a plain streaming copy (SURVEY.md 8d: quote the spec peak AND a measured figure)
-    if rank == 0 and not dry:
-        a = torch.empty(1 << 27, dtype=torch.float64, device=dev)  # 1 GiB
-        b = torch.empty_like(a)
-        b.copy_(a)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(5):
-            b.copy_(a)
-        torch.cuda.synchronize(dev)
-        copy_gbps = 5 * 2 * (1 << 30) / (time.perf_counter() - t0) / 1e9
-        # (read + write bytes of a 1 GiB device-to-device copy: a reference figure of the box, NOT a ceiling for a read-only stream --
-        #  the achievable read stream of this box is `read_stream_GBps` below, the single-OLS Gram kernel on the same frame)
-        roofline["measured_copy_GBps"] = round(copy_gbps, 1)
-        del a, b
-
-    # ---- fixed cost of the N-rank step, measured on this one GPU: the same frame through GroupedShardPlan over an RCCL process
-    # group of world size 1 (no peer: what is left is everything a step does beside its kernel -- Python, the prepared C call, the
-    # stream bookkeeping) against the plain call timed above.  At N ranks the kernel shrinks by N, this does not.
-    dist_overhead = None
-    if rank == 0 and world == 1:
-        try:
-            dist_overhead = _dist_step_overhead(torch, par, pds, ctx, dev, xs, y, off_pair, offsets, args, ms_per_step, use_dist)
-        except Exception as e:
-            dist_overhead = {"error": f"{type(e).__name__}: {e}"}
-
-    # ---- config 2 on the same frame: single OLS Gram build (pds_moments), HBM GB/s
-    gram = None
-    if rank == 0 and not dry:
-        for _ in range(2):
-            pds.gram_moments(*xs, target=y, ctx=ctx)
-        ctx.get_timing(reset=True)
-        ctx.set_timing(True)
-        reps = 5
-        for _ in range(reps):
-            pds.gram_moments(*xs, target=y, ctx=ctx)
-        ctx.set_timing(False)
-        ms, cnt = ctx.get_timing(reset=True)["moments"]
-        gb = N * (P + 1) * 8 / 1e9
-        g_ms = ms / max(cnt, 1)
-        gram = {"workload": f"single OLS Gram build, {N:.0e} rows x {P} f64 feats", "algorithmic_GB": round(gb, 3),
-                "avg_launch_ms": round(g_ms, 4), "achieved_GBps": round(gb / (g_ms * 1e-3), 1),
-                "frac_of_hbm_peak": round(gb / (g_ms * 1e-3) / HBM_PEAK_GBPS, 4)}
-        roofline["read_stream_GBps"] = gram["achieved_GBps"]  # what a pure read stream of these columns reaches on this box (Gram kernel)
-        roofline["frac_of_read_stream"] = round(achieved / gram["achieved_GBps"], 4) if gram["achieved_GBps"] else None
-
-    # ---- BASELINE.json configs[2] as written (8 features; the headline metric is quoted on 16 -- SURVEY.md 8d asks for
-    # both): the same groups on the first 8 feature columns
-    p8 = None
-    if rank == 0 and P >= 8 and not dry:
-        for _ in range(2):
-            pds.lin_reg_by(*xs[:8], target=y, group_offsets=offsets, add_bias=False, ctx=ctx)
-        torch.cuda.synchronize(dev)
-        reps = 5
-        ctx.get_timing(reset=True)
-        ctx.set_timing(True)
-        t8 = time.perf_counter()
-        for _ in range(reps):
-            pds.lin_reg_by(*xs[:8], target=y, group_offsets=offsets, add_bias=False, ctx=ctx)
-        torch.cuda.synchronize(dev)
-        t8 = (time.perf_counter() - t8) / reps
-        ctx.set_timing(False)
-        k8_ms, k8_cnt = ctx.get_timing(reset=True)["grouped_moments"]
-        b8 = G * (R * 9 * 8 + 16 + 8 * 8 + 1)
-        k8 = k8_ms / max(k8_cnt, 1)
-        p8 = {"workload": f"{G} groups x {R} rows x 8 f64 feats", "regressions_per_s": round(G / t8, 1),
-              "ms_per_step": round(t8 * 1e3, 4), "kernel_ms": round(k8, 4), "algorithmic_GBps": round(b8 / (k8 * 1e-3) / 1e9, 1),
-              "frac_of_hbm_peak": round(b8 / (k8 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
-
-    # ---- the same step from the KEY COLUMN (sorted int64 keys, what group_by(key) starts from) instead of precomputed offsets: one pass
-    # over the keys (order check + run marks), a scan and a pass over the marks in front of the same fused kernel
-    by_key = None
-    if rank == 0 and not dry:
-        try:
-            by_key = _by_key(torch, pds, ctx, dev, xs, y, offsets, G, R, P)
-        except Exception as e:
-            by_key = {"error": f"{type(e).__name__}: {e}"}
-
-    # ---- CPU baseline + parity spot check on a bounded sample (rank 0, N = 1 only)
-    cpu = None
-    parity = None
-    host_cols = None
-    if rank == 0 and world == 1 and not args.no_cpu and not dry:
-        cpu, parity = _cpu_baseline(np, args, xs, y, coeffs, nulls, G, R, P)
-
-    # ---- the same workload from HOST Arrow buffers through the plugin boundary (rank 0, N = 1): the rate a Polars user sees
-    end_to_end = None
-    if rank == 0 and world == 1 and not args.no_extras and not dry:
-        try:
-            end_to_end = _end_to_end(torch, np, pds, dev, xs, y, G, R, P, cpu)
-        except Exception as e:  # pyarrow / harness trouble must not cost the headline line
-            end_to_end = {"error": f"{type(e).__name__}: {e}"}
-
-    # ---- the other BASELINE configs, on the headline frame where they share it (C2) and on a C4 frame
-    other = None
-    if rank == 0 and world == 1 and not args.no_extras and not dry:
-        try:
-            other = _other_configs(torch, pds, ctx, dev, xs, y, N, P, with_cpu=not args.no_cpu)
-        except Exception as e:
-            other = {"error": f"{type(e).__name__}: {e}"}
-
-    # ---- SURVEY.md 8(d) C3 data: Poisson sizes, collinear groups (the gate fires inside the timed run), sorted and shuffled keys
-    c3 = None
-    if rank == 0 and world == 1 and not args.no_extras and not dry:
-        try:
-            del xs, y
-            torch.cuda.empty_cache()
-            c3 = _c3_spec(torch, pds, ctx, dev)
-        except Exception as e:
-            c3 = {"error": f"{type(e).__name__}: {e}"}
-
-    # ---- scatter leg (outside the timed region): what distributing a rank-0-resident frame of this size costs
-    scatter = None
-    if use_dist and strong and not args.no_extras:
-        try:
-            scatter = _scatter_leg(torch, dist, par, dev, rank, world, G_total, R, P)
-        except Exception as e:
-            scatter = {"error": f"{type(e).__name__}: {e}"}
-
-    if rank == 0:
-        per = "of the frame" if strong else "per GPU"
-        line = {
-            "metric": "grouped lstsq regressions/sec (1e8 rows x 16 f64 feats; Gram-build GB/s under gram_build)",
-            "value": round(value, 1), "unit": "regressions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic" if not dry else "synthetic -- DRY RUN on CPU (gloo, injected numpy compute): control-flow rehearsal, not a measurement",
-            "config": {"workload": f"group_by(key).agg(lin_reg): {args.groups} groups x {R} rows x {P} f64 feats {per} "
-                                   f"({args.groups * R:.0e} rows), OLS with rank gate (pl_lr default path), inputs resident in HBM; `value`: the groups "
-                                   f"given as row offsets (pre-segmented, as Polars hands groups to pl_lr -- the cpu_baseline gets the same); "
-                                   f"the same step starting from a sorted int64 key column: grouped_by_key"
-                                   + (", coefficients + null flags gathered to rank 0 inside the timed region" if gather else ""),
-                       "groups_total": G_total, "groups_per_gpu": G, "rows_per_group": R, "features": P,
-                       "parallelism": f"group-sharded x{world}", "gather_chunks": chunks if gather else None,
-                       "gather": (args.gather if gather else None)},
-            "roofline": roofline, "gram_build": gram, "grouped_p8": p8, "grouped_by_key": by_key, "cpu_baseline": cpu, "parity_spot_check": parity,
-            "dist_step": dist_overhead, "end_to_end": end_to_end, "other_configs": other, "grouped_c3spec": c3, "scatter": scatter,
-        }
-        print(json.dumps(line), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+    return roofline
 
 
 def _by_key(torch, pds, ctx, dev, xs, y, offsets, G, R, P):

@@ -1,5 +1,5 @@
 """
-tests/golden/make_golden.py -- regenerates tests/golden/reference_notebook.json.
+tests/golden/make_golden.py -- regenerates tests/golden/reference_notebook.json and reference_polars_exprs.json.
 
 The reference (a Rust crate) cannot be built or imported in this image, so the only literal
 reference OUTPUTS available are the ones its authors committed: the rendered cells of
@@ -14,6 +14,7 @@ from pathlib import Path
 
 NB = Path("/root/reference/examples/basics.ipynb")
 OUT = Path(__file__).resolve().parent / "reference_notebook.json"
+EXPRS_OUT = Path(__file__).resolve().parent / "reference_polars_exprs.json"
 
 
 def cell_outputs(nb):
@@ -71,6 +72,14 @@ def main():
             gold["rolling_w5_tail"] = parsed[5:]
     OUT.write_text(json.dumps(gold, indent=1))
     print("wrote", OUT, list(gold))
+    # the `#[polars_expr] fn` names of the reference's two lstsq files (tests/test_plugin_abi.py)
+    src = NB.parent.parent / "src" / "num_ext"
+    exprs = {"source": "src/num_ext/linear_regression.rs and src/num_ext/linear_regression_f32.rs of the reference (v0.12.1): "
+                       "the name of every `#[polars_expr] fn`, in file order"}
+    for f in ("linear_regression.rs", "linear_regression_f32.rs"):
+        exprs[f] = re.findall(r"#\[polars_expr\([^\]]*\)\][^\n]*\n\s*fn\s+(\w+)", (src / f).read_text())
+    EXPRS_OUT.write_text(json.dumps(exprs, indent=1) + "\n")
+    print("wrote", EXPRS_OUT)
 
 
 if __name__ == "__main__":

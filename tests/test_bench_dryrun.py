@@ -30,7 +30,7 @@ def test_bench_multi_rank_control_flow(world, scaling):
     env = dict(os.environ, PDS_BENCH_DRYRUN="1", OMP_NUM_THREADS="1", MKL_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--groups", "4003", "--rows-per-group", "12", "--feats", "4", "--scaling", scaling]
+           "--groups", "4003", "--rows-per-group", "12", "--feats", "4", "--scaling", scaling, "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,4 +1,4 @@
-"""stdin: bench.py's JSON line -> one short line (A/B runs)."""
+"""stdin: the JSON line of `bench.py --full` -> one short line (A/B runs)."""
 import json
 import sys
 

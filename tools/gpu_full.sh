@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 O=$PWD/gpurun_out/full; mkdir -p $O
 timeout -k 5 1500 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 timeout -k 5 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
-timeout -k 5 700 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+timeout -k 5 700 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
 echo "---- pytest"; tail -12 $O/pytest.log
 echo "---- smoke"; tail -2 $O/smoke.log
 echo "---- bench"; python - <<'PY'

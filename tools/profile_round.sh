@@ -11,14 +11,14 @@ cd /tmp && export TMPDIR=/tmp
 # counter / trace CSVs carry every torch kernel of the frame generators: keep the header and the library's kernels only (gpurun merges
 # at most 64 MiB back; round 5 lost a whole call's output to that limit)
 slim() { for f in "$@"; do [ -f "$f" ] && { head -1 "$f" > "$f.tmp"; grep "pds::" "$f" >> "$f.tmp"; mv "$f.tmp" "$f"; }; done; }
-timeout -k 5 600 python -u $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout -k 5 600 python -u $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 # same flags as the bench line's timed region (warm-ups excluded from the averages by summarize_profiles.py: it drops the
 # first `warmup` launches of each kernel using the kernel trace, not the --stats table)
-rm -rf /tmp/p1 && timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o b -- python -u $ROOT/bench.py --steps 10 --warmup 3 --no-cpu --no-extras > $OUT/stats_run.log 2>&1
+rm -rf /tmp/p1 && timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o b -- python -u $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu --no-extras > $OUT/stats_run.log 2>&1
 cp $(find /tmp/p1 -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 cp $(find /tmp/p1 -name "*kernel_trace.csv" | head -1) $OUT/bench_kernel_trace.csv
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/p2 && timeout -k 5 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/p2 -o b -- python -u $ROOT/bench.py --steps 2 --warmup 1 --no-cpu --no-extras > $OUT/pmc_$c.log 2>&1
+  rm -rf /tmp/p2 && timeout -k 5 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/p2 -o b -- python -u $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu --no-extras > $OUT/pmc_$c.log 2>&1
   cp $(find /tmp/p2 -name "*counter_collection.csv" | head -1) $OUT/pmc_$c.csv
   rm -rf /tmp/p4 && timeout -k 5 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/p4 -o r -- python -u $ROOT/tools/rolling_bench.py c4 > $OUT/pmc_roll_$c.log 2>&1
   cp $(find /tmp/p4 -name "*counter_collection.csv" | head -1) $OUT/pmc_roll_$c.csv
@@ -54,7 +54,7 @@ PDS_GROUPED_MID_FUSED=0 timeout -k 5 300 python -u $ROOT/tools/grouped_width_cli
 k=0
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAVES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "GRBM_GUI_ACTIVE"; do
   k=$((k+1))
-  rm -rf /tmp/p11 && timeout -k 5 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d /tmp/p11 -o s -- python -u $ROOT/bench.py --steps 3 --warmup 1 --no-cpu --no-extras > $OUT/pmc_sq_$k.log 2>&1
+  rm -rf /tmp/p11 && timeout -k 5 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d /tmp/p11 -o s -- python -u $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras > $OUT/pmc_sq_$k.log 2>&1
   f=$(find /tmp/p11 -name "*counter_collection.csv" | head -1); [ -n "$f" ] && cp $f $OUT/pmc_sq_$k.csv
 done
 # round 5: the partition route's id-indexed prediction pass (grouped_pred MODE 3), the C5 wide Gram's counters (FETCH / WRITE, L2 hit rate,

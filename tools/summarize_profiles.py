@@ -78,8 +78,8 @@ for k in fetch:
 (OUT / f"{rnd}_traffic.json").write_text(json.dumps(traffic, indent=1) + "\n")
 
 md = [f"# profiles/{rnd} -- one MI355X (gfx950), ROCm 7.2", "",
-      f"* `{rnd}_bench_line.json` -- the `python bench.py` JSON line.",
-      f"* `{rnd}_bench_kernel_stats.csv` -- `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu --no-extras`.",
+      f"* `{rnd}_bench_line.json` -- the `python bench.py --full` JSON line.",
+      f"* `{rnd}_bench_kernel_stats.csv` -- `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu --no-extras`.",
       f"* `{rnd}_traffic.json` -- HBM bytes per launch from `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (two separate passes).",
       f"* `{rnd}_bench_extra.json` / `{rnd}_extra_kernel_stats.csv` -- `python tools/bench_extra.py`: the other BASELINE configs (single OLS + "
       "report, rolling, recursive, elastic net) and the host-buffer rate, and the rocprofv3 kernel stats of that run.",
@@ -174,7 +174,7 @@ if sq:
     table = {k: {c: sum(v) / len(v) for c, v in d.items()} for k, d in sq.items()}
     (OUT / f"{rnd}_pmc_grouped.json").write_text(json.dumps(table, indent=1) + "\n")
     names = sorted({c for d in table.values() for c in d})
-    md += ["## SQ counters per launch: the fused grouped kernel against the Gram kernel (`bench.py --steps 3 --warmup 1 --no-cpu --no-extras`, one counter set per pass)", "",
+    md += ["## SQ counters per launch: the fused grouped kernel against the Gram kernel (`bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras`, one counter set per pass)", "",
            "| counter | " + " | ".join(table) + " |", "|---|" + "---|" * len(table)]
     for c in names:
         md.append(f"| {c} | " + " | ".join(f"{table[k].get(c, float('nan')):.4g}" for k in table) + " |")
