@@ -82,7 +82,8 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             partition route appends records through cursor atomics, so its sums repeat to rounding only;
  *   "wide_f32_native" (PDS_WIDE_F32_NATIVE=1) f32 Gram builds beyond 64 features on the f32 matrix instructions (v_mfma_f32_32x32x2_f32,
  *                                             2.5e-7 from the f64 Gram) instead of three exact bf16 planes on the bf16 matrix cores (2e-6).
- * value: 0 / 1.  Unknown names are PDS_ERR_INVALID. */
+ *   "report_chunk_groups"                     pds_lin_reg_report_grouped_* / _by_key_*: groups per pass (<= 0: the default).
+ * value: 0 / 1 (report_chunk_groups: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host-frame staging (process wide): chunk_mb = bytes of one row chunk of a PDS_HOST frame (default 256, env
  * PDS_HOST_CHUNK_MB); resident_max_mb = largest host frame that pds_lr_pred_* still stages whole (one PCIe trip; larger
@@ -568,6 +569,63 @@ double pds_student_t_ppf(double q, double df);
  * kernel); wider frames write them as two columns and run the weighted wide Gram build on them. */
 int pds_glm_irls_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
                      int variance, double tol, int max_iter, double* coeffs, int* n_iter);
+/*
+ * pds_lin_reg_report_grouped_* / pds_lin_reg_report_by_key_*: `df.group_by(key).agg(pds.lin_reg_report(...))` in one call -- for
+ * every group g what pds_lin_reg_report_* returns on g's rows alone (same se_type / add_bias, beta = (X'X)^-1 X'y through the
+ * column-pivoted QR inverse, report_epilogue's formulas).  Deliberate deviations from a per-group pl_lin_reg_report call:
+ *   1. a group with fewer rows than coefficients (or none) gets is_null = 1 and NaN outputs (the reference raises
+ *      "#Data < #features" and aborts the whole query), as pds_lr_grouped_* does;
+ *   2. var(y) per group is the target's sample variance (ddof = 1) from f64 sums of y - y_first on the device, unless the offsets
+ *      form is given y_var (n_groups values, `space`-resident);
+ *   3. p-values are computed on the device, within 2e-13 relative of pds_student_t_sf (the device's exp / log may differ from
+ *      the host's in the last bit); the CI quantile is the host's student_t_ppf, once per distinct dof (bit-identical to the
+ *      single report's).
+ * Groups with n_g == p' (dof 0) or singular Gram matrices give what the single report gives (NaN / inf / QR values), not null.
+ * 1..64 features (more: PDS_ERR_UNSUPPORTED).  Output arrays are `space`-resident: beta .. ci_upper [n_groups][p'] row-major
+ * (bias last), r2 / adj_r2 [n_groups], is_null [n_groups] bytes.  Context option "report_chunk_groups" sets how many groups one
+ * pass works on (workspace bound; default from a 128 MiB record budget).
+ */
+typedef struct {
+    double* beta;
+    double* std_err;
+    double* t;
+    double* p;
+    double* ci_lower;
+    double* ci_upper;
+    double* r2;
+    double* adj_r2;
+    uint8_t* is_null;
+} pds_report_grouped_f64;
+typedef struct {
+    float* beta;
+    float* std_err;
+    float* t;
+    float* p;
+    float* ci_lower;
+    float* ci_upper;
+    float* r2;
+    float* adj_r2;
+    uint8_t* is_null;
+} pds_report_grouped_f32;
+int pds_lin_reg_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int add_bias, int se_type, const double* y_var,
+                                   pds_report_grouped_f64* out);
+int pds_lin_reg_report_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int add_bias, int se_type, const float* y_var,
+                                   pds_report_grouped_f32* out);
+/* keys: n_rows int64 values in any row order (`space`-resident); groups come back in ascending key order (out_keys, `space`);
+ * max_groups: capacity of the outputs; n_groups: out (host).  Ordered keys move no data; others take the sorting route of
+ * pds_lr_by_key_*.  var(y) is always derived per group. */
+int pds_lin_reg_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                  pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
+                                  pds_report_grouped_f64* out, int64_t* n_groups);
+int pds_lin_reg_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                  pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
+                                  pds_report_grouped_f32* out, int64_t* n_groups);
+/* TEST HOOK, not part of the supported interface: the grouped report's device Student-t survival function on host arrays
+ * x[n], df[n] -> out[n], so that tests can hold it against pds_student_t_sf.  May change or go away without notice. */
+int pds_student_t_sf_device(pds_ctx* ctx, const double* x, const double* df, int64_t n, double* out);
+
 int pds_glm_irls_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
                      int variance, float tol, int max_iter, float* coeffs, int* n_iter);
 

@@ -17,6 +17,8 @@ from .lstsq import (  # noqa: F401
     gram_moments,
     lin_reg,
     lin_reg_by,
+    lin_reg_report_by,
+    lin_reg_report_by_key,
     lin_reg_by_key,
     lin_reg_by_key_multi,
     lin_reg_by_key_pred_multi,

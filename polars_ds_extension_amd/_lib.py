@@ -23,6 +23,8 @@ EXPORTS = [
     "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_lr_rowmajor_f64", "pds_lr_rowmajor_f32", "pds_ctx_workspace_spills", "pds_ctx_workspace_bytes", "pds_ctx_set_timing", "pds_ctx_get_timing", "pds_ctx_get_timing_samples",
     "pds_lr_f64", "pds_lr_f32", "pds_lr_pred_f64", "pds_lr_pred_f32", "pds_lr_rcond_f64", "pds_lr_rcond_f32", "pds_elastic_net_f64", "pds_elastic_net_f32", "pds_lr_nullable_f64", "pds_lr_nullable_f32", "pds_lr_multi_f64", "pds_lr_multi_f32",
     "pds_lin_reg_report_f64", "pds_lin_reg_report_f32",
+    "pds_lin_reg_report_grouped_f64", "pds_lin_reg_report_grouped_f32", "pds_lin_reg_report_by_key_f64", "pds_lin_reg_report_by_key_f32",
+    "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
     "pds_report_finish_f64", "pds_report_finish_f32",
     "pds_lr_grouped_f64", "pds_lr_grouped_f32",
@@ -65,6 +67,11 @@ class ReportF32(C.Structure):
         ("r2", C.c_float),
         ("adj_r2", C.c_float),
     ]
+
+
+class ReportGrouped(C.Structure):
+    """pds_report_grouped_f64 / _f32: pointers only, so one layout serves both precisions."""
+    _fields_ = [(k, C.c_void_p) for k in ("beta", "std_err", "t", "p", "ci_lower", "ci_upper", "r2", "adj_r2", "is_null")]
 
 
 class PdsError(RuntimeError):

@@ -13,6 +13,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "grouped_report.hpp"
 
 namespace pds {
 
@@ -21,6 +22,7 @@ namespace pds {
 #include "capi_lr.hpp"
 #include "capi_report.hpp"
 #include "capi_grouped.hpp"
+#include "capi_report_grouped.hpp"
 #include "capi_multi.hpp"
 #include "capi_rolling.hpp"
 #include "capi_models.hpp"
@@ -120,6 +122,7 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     const std::string n(name);
     if (n == "keyed_sort") ctx->opt_keyed_sort = value != 0;
     else if (n == "wide_f32_native") ctx->opt_wide_f32_native = value != 0;
+    else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }
@@ -534,6 +537,33 @@ int pds_lr_by_key_pred_f32(pds_ctx* ctx, const float* const* cols, const float* 
                                       pred, resid, row_null);
 }
 
+int pds_lin_reg_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int add_bias, int se_type, const double* y_var,
+                                   pds_report_grouped_f64* out) {
+    return pds::report_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
+                                            reinterpret_cast<const pds::ReportGroupedOut<double>*>(out));
+}
+int pds_lin_reg_report_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int add_bias, int se_type, const float* y_var,
+                                   pds_report_grouped_f32* out) {
+    return pds::report_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
+                                           reinterpret_cast<const pds::ReportGroupedOut<float>*>(out));
+}
+int pds_lin_reg_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                  pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
+                                  pds_report_grouped_f64* out, int64_t* n_groups) {
+    return pds::report_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
+                                           reinterpret_cast<const pds::ReportGroupedOut<double>*>(out), n_groups);
+}
+int pds_lin_reg_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                  pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
+                                  pds_report_grouped_f32* out, int64_t* n_groups) {
+    return pds::report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
+                                          reinterpret_cast<const pds::ReportGroupedOut<float>*>(out), n_groups);
+}
+int pds_student_t_sf_device(pds_ctx* ctx, const double* x, const double* df, int64_t n, double* out) {
+    return pds::student_t_sf_device_impl(ctx, x, df, n, out);
+}
 int pds_lr_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                       const pds_lr_params* prm, int64_t max_groups, int64_t* out_keys, double* coeffs, uint8_t* is_null,
                       int64_t* n_groups) {

@@ -114,6 +114,7 @@ struct pds_ctx {
     // behaviour switches of the context (pds_ctx_set_option); their defaults come from the environment once, at pds_ctx_create
     bool opt_keyed_sort = false;       // "keyed_sort" / PDS_KEYED_SORT=1: unordered keys always take the sorting route (determinism)
     bool opt_wide_f32_native = false;  // "wide_f32_native" / PDS_WIDE_F32_NATIVE=1: f32 Gram beyond 64 features on the f32 matrix instructions
+    int64_t opt_report_chunk_groups = 0;  // "report_chunk_groups": groups per pass of the grouped report (0: from its record budget)
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<float> kind_samples[8];  // the individual bracketed durations (ms), newest kept up to 4096 per class

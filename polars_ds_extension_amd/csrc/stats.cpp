@@ -204,6 +204,13 @@ double student_t_sf(double x, double df, bool* err) {
     return x <= 0.0 ? 1.0 - ib : ib;
 }
 
+// the ln-gamma part of student_t_sf's incomplete beta prefactor, lnG(df / 2 + 1 / 2) - lnG(df / 2) - lnG(1 / 2), evaluated exactly as
+// beta_reg(df / 2, 0.5, .) evaluates it: the grouped report's device p-values (stats_dev.hpp) take it from here once per distinct dof
+double student_t_lng_term(double df) {
+    const double a = df / 2.0, b = 0.5;
+    return ln_gamma(a + b) - ln_gamma(a) - ln_gamma(b);
+}
+
 double student_t_ppf(double qv, double df) {
     const double x1 = qv >= 0.5 ? 1.0 - qv : qv;
     double y = inv_beta_reg(0.5 * df, 0.5, 2.0 * x1);

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib, config
 
 __all__ = [
-    "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "rolling_lin_reg",
+    "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg",
     "recursive_lin_reg", "lin_reg_w_rcond", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
@@ -562,6 +562,126 @@ def _report_dict(outs, rep, n_feat, add_bias, std_err, weighted, feature_names, 
         "0.025": outs["ci_lower"], "0.975": outs["ci_upper"],
         "r2": np.full(pp, rep.r2, dtype=dt), "adj_r2": np.full(pp, rep.adj_r2, dtype=dt),
     }
+
+
+_REPORT_KEYS = ("beta", "std_err", "t", "p", "ci_lower", "ci_upper")
+
+
+def _report_grouped_outs(cols: _Cols, ng: int, pp: int):
+    outs = {k: _out_like(cols, (ng, pp)) for k in _REPORT_KEYS}
+    outs["r2"] = _out_like(cols, (ng,))
+    outs["adj_r2"] = _out_like(cols, (ng,))
+    outs["is_null"] = _out_u8(cols, ng)
+    rep = _lib.ReportGrouped(*[outs[k][1] for k in (*_REPORT_KEYS, "r2", "adj_r2", "is_null")])
+    return outs, rep
+
+
+def _report_grouped_dict(outs, n_feat, add_bias, std_err, feature_names, g=None):
+    names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(n_feat)]
+    if add_bias:
+        names.append("__bias__")  # linear_regression.rs:843-845
+    se_name = {"se": "std_err", "hc0": "hc0_se", "hc1": "hc1_se", "hc2": "hc2_se", "hc3": "hc3_se"}.get(std_err, "std_err")
+    cut = (lambda a: a[:g]) if g is not None else (lambda a: a)
+    return {
+        "features": names, "beta": cut(outs["beta"][0]), se_name: cut(outs["std_err"][0]), "t": cut(outs["t"][0]),
+        "p>|t|": cut(outs["p"][0]), "0.025": cut(outs["ci_lower"][0]), "0.975": cut(outs["ci_upper"][0]),
+        "r2": cut(outs["r2"][0]), "adj_r2": cut(outs["adj_r2"][0]), "is_null": cut(outs["is_null"][0]),
+    }
+
+
+def lin_reg_report_by(*x, target, group_offsets, add_bias: bool = False, std_err: str = "se", y_var=None,
+                      feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+    """
+    The grouped form of `lin_reg_report`: `df.group_by(key).agg(pds.lin_reg_report(...))` for a frame whose groups are contiguous
+    row ranges (group g = rows [group_offsets[g], group_offsets[g+1])), in one call.  Every group's report equals the single
+    report on its rows, except that a group with fewer rows than coefficients is null (`is_null`, NaN values) instead of an error.
+    `y_var` (optional, one value per group): the target's variance per group; by default the sample variance (ddof=1) of each
+    group's target is computed on the device.
+    Returns a dict of [n_groups, p'] arrays ("beta", the standard-error column, "t", "p>|t|", "0.025", "0.975"), "r2" / "adj_r2" /
+    "is_null" [n_groups] and "features", in the memory space of the inputs.
+    """
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    off, off_p = _offsets_arg(cols, group_offsets)
+    ng = int(off.shape[0]) - 1
+    outs, rep = _report_grouped_outs(cols, ng, pp)
+    yv_p = C.c_void_p(None)
+    if y_var is not None:
+        if cols.space == _lib.PDS_DEVICE:
+            import torch
+
+            yv = y_var if _is_torch(y_var) else torch.as_tensor(np.asarray(y_var))
+            yv = yv.to(device=cols.keep[0].device, dtype=cols.keep[0].dtype).contiguous()
+            yv_p = C.c_void_p(int(yv.data_ptr()))
+        else:
+            yv = np.ascontiguousarray(np.asarray(y_var), dtype=_dtype())
+            yv_p = C.c_void_p(yv.ctypes.data)
+        if int(yv.shape[0]) != ng:
+            raise ValueError("`y_var` must have one value per group")
+    _lib.check(ctx.fn("pds_lin_reg_report_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng),
+                                                    cols.space, int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), yv_p,
+                                                    C.byref(rep)))
+    return _report_grouped_dict(outs, cols.n_feat, add_bias, std_err, feature_names)
+
+
+def lin_reg_report_by_key(*x, target, key, add_bias: bool = False, std_err: str = "se", max_groups: int | None = None,
+                          feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+    """
+    `lin_reg_report_by` for an int64 key column in ANY row order (the frame is brought into key order on the device, as
+    `lin_reg_by_key` does; nothing moves when the keys are already non-decreasing).  Returns the dict of `lin_reg_report_by`
+    plus "keys" (ascending).  var(y) is always the per-group sample variance.
+    """
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    n_rows = cols.n_rows
+    if cols.space == _lib.PDS_DEVICE:
+        import torch
+
+        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
+        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
+        k_p = C.c_void_p(int(k.data_ptr()))
+    else:
+        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
+        k_p = C.c_void_p(k.ctypes.data)
+    if int(k.shape[0]) != n_rows:
+        raise ValueError("`key` must have one entry per row")
+    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
+    ng = C.c_int64(0)
+    while True:
+        if cols.space == _lib.PDS_DEVICE:
+            ok = torch.empty(cap, dtype=torch.int64, device=k.device)
+            ok_p = C.c_void_p(int(ok.data_ptr()))
+        else:
+            ok = np.empty(cap, dtype=np.int64)
+            ok_p = C.c_void_p(ok.ctypes.data)
+        outs, rep = _report_grouped_outs(cols, cap, pp)
+        rc = ctx.fn("pds_lin_reg_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
+                                                 int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), C.c_int64(cap), ok_p,
+                                                 C.byref(rep), C.byref(ng))
+        if rc != 0 and max_groups is None and int(ng.value) > cap:
+            cap = int(ng.value)  # more distinct keys than the first guess
+            continue
+        _lib.check(rc)
+        break
+    g = int(ng.value)
+    d = _report_grouped_dict(outs, cols.n_feat, add_bias, std_err, feature_names, g)
+    d["keys"] = ok[:g]
+    return d
+
+
+def student_t_sf_device(x, df, ctx: Context | None = None):
+    """The grouped report's device Student-t survival function on host arrays (tests: against pds_student_t_sf)."""
+    ctx = ctx or default_context()
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    da = np.ascontiguousarray(np.broadcast_to(np.asarray(df, dtype=np.float64), xa.shape))
+    out = np.empty_like(xa)
+    _lib.check(_lib.load().pds_student_t_sf_device(ctx._h, C.c_void_p(xa.ctypes.data), C.c_void_p(da.ctypes.data),
+                                                   C.c_int64(xa.size), C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def lin_reg_by(*x, target, group_offsets, add_bias: bool = False, l1_reg: float = 0.0, l2_reg: float = 0.0,
