@@ -580,7 +580,10 @@ int pds_glm_irls_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_
  *   3. p-values are computed on the device, within 2e-13 relative of pds_student_t_sf (the device's exp / log may differ from
  *      the host's in the last bit); the CI quantile is the host's student_t_ppf, once per distinct dof (bit-identical to the
  *      single report's).
- * Groups with n_g == p' (dof 0) or singular Gram matrices give what the single report gives (NaN / inf / QR values), not null.
+ * Groups with n_g == p' (dof 0) or singular Gram matrices are not null (is_null = 0): a dof-0 group's beta is its exact-fit
+ * solution and its se / hc1 standard errors (which divide by dof) are not finite; a singular group's values are whatever the
+ * pivoted-QR inverse gives (not necessarily finite, nor equal to a single report's).  A group holding NaN / inf or a singular
+ * design does not change any other group's outputs (bit for bit).
  * 1..64 features (more: PDS_ERR_UNSUPPORTED).  Output arrays are `space`-resident: beta .. ci_upper [n_groups][p'] row-major
  * (bias last), r2 / adj_r2 [n_groups], is_null [n_groups] bytes.  Context option "report_chunk_groups" sets how many groups one
  * pass works on (workspace bound; default from a 128 MiB record budget).

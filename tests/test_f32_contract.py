@@ -1,5 +1,6 @@
 """
-The f32 contract (north_star: "f32 within 1e-4"), both distances for every f32 entry point.
+The f32 contract (north_star: "f32 within 1e-4"), both distances for every f32 entry point (the grouped report:
+pds_lin_reg_report_grouped_f32 and pds_lin_reg_report_by_key_f32, test_grouped_report*).
 
 For each f32 path three answers are formed on the same f32-rounded inputs:
     gpu     the HIP path (f32 symbols of the C ABI)
@@ -206,3 +207,59 @@ def test_coverage_paths(pds, orc, f32):
     assert not nw.cpu().numpy().any()
     hold("grouped > 64 features (500x70)", cw.cpu().numpy()[1], orc.pl_lr(Xh[400:], yh[400:], singular_x_tol=1e-6),
          orc.pl_lr(Xh[400:].astype(np.float64), yh[400:].astype(np.float64)))
+
+
+def _grouped_report_frame(rng, p, sizes):
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    X, y = make_xy(rng, int(off[-1]), p, noise=0.05)
+    return X.astype(np.float32), y.astype(np.float32), off
+
+
+def _hold_grouped_report(name, r, X32, y32, off, orc, se):
+    key = "std_err" if se == "se" else f"{se}_se"
+    for g in range(len(off) - 1):
+        sl = slice(off[g], off[g + 1])
+        Xb = np.c_[X32[sl], np.ones(off[g + 1] - off[g], np.float32)]
+        ro32 = orc.lin_reg_report(Xb, y32[sl], std_err=se)
+        ro = orc.lin_reg_report(Xb.astype(np.float64), y32[sl].astype(np.float64), std_err=se)
+        assert r["is_null"][g] == 0
+        hold(f"{name} {se} g{g} ({off[g + 1] - off[g]} rows): beta", r["beta"][g], ro32["beta"], ro["beta"])
+        hold(f"{name} {se} g{g}: std err", r[key][g], ro32["std_err"], ro["std_err"], frel)
+
+
+@pytest.mark.parametrize("p", [3, 8, 16, 17, 32, 64])
+def test_grouped_report(pds, orc, f32, p):
+    """pds_lin_reg_report_grouped_f32: every standard error, groups of one piece and of several (pieces are 4096 rows up to 16
+    features, 16384 beyond)."""
+    rng = np.random.default_rng(900 + p)
+    piece = 4096 if p <= 16 else 16384
+    X32, y32, off = _grouped_report_frame(rng, p, [3 * (p + 1) + 5, 700, 2 * piece + 333])
+    for se in ("se", "hc0", "hc1", "hc2", "hc3"):
+        r = pds.lin_reg_report_by(*cols_of(X32), target=dev(y32), group_offsets=dev(off), add_bias=True, std_err=se)
+        r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
+        assert r["beta"].dtype == np.float32
+        _hold_grouped_report(f"grouped report p={p}", r, X32, y32, off, orc, se)
+
+
+@pytest.mark.parametrize("space", ["device", "host"])
+def test_grouped_report_by_key(pds, orc, f32, space):
+    """pds_lin_reg_report_by_key_f32 on shuffled keys (the sorting route), device- and host-resident."""
+    rng = np.random.default_rng(950)
+    p = 8
+    X32, y32, off = _grouped_report_frame(rng, p, [40, 5000, 300, 9001])
+    keys = np.repeat(np.array([17, -3, 40, 5], np.int64), np.diff(off))
+    perm = rng.permutation(len(y32))
+    if space == "device":
+        r = pds.lin_reg_report_by_key(*cols_of(X32[perm]), target=dev(y32[perm]), key=dev(keys[perm]), add_bias=True, std_err="hc3")
+        r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
+    else:
+        r = pds.lin_reg_report_by_key(*[np.ascontiguousarray(X32[perm, j]) for j in range(p)], target=y32[perm], key=keys[perm],
+                                      add_bias=True, std_err="hc3")
+    assert np.array_equal(r["keys"], [-3, 5, 17, 40])
+    # groups in key order: the rows of each key (the rows' order within a group does not change the truth)
+    order = [1, 3, 0, 2]
+    Xg = np.concatenate([X32[off[g]:off[g + 1]] for g in order])
+    yg = np.concatenate([y32[off[g]:off[g + 1]] for g in order])
+    _hold_grouped_report(f"grouped report by key ({space})", r, Xg, yg, np.concatenate([[0], np.cumsum(np.diff(off)[order])]), orc,
+                         "hc3")
+
