@@ -516,6 +516,52 @@ int pds_recursive_lr_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int
                          float* coeffs, float* pred, uint8_t* valid);
 
 /*
+ * pds_rolling_lr_grouped_* / pds_recursive_lr_grouped_* / pds_rolling_lr_by_key_* / pds_recursive_lr_by_key_*:
+ * `pds.rolling_lin_reg(...).over(key)` / `pds.recursive_lin_reg(...).over(key)` in one call.  For group g = rows [s_g, e_g) in
+ * frame order (columns, SWWLRKwargs and the non-finite rule as in pds_rolling_lr_* / pds_recursive_lr_*):
+ *   rolling    row r is fitted on rows [max(s_g, r - window + 1), r] and is valid iff r - s_g >= window - 1 (and, with
+ *              min_size > 0 -- the skipping variant -- the window holds >= min_size finite rows);
+ *   expanding  row r is fitted on rows [s_g, r] and is valid iff r - s_g >= start_with - 1;
+ * i.e. exactly pds_rolling_lr_* / pds_recursive_lr_* on the group's rows alone.  The sums are segmented -- they restart at every
+ * group start and never hold a row of another group -- so a group's outputs depend on its own rows only: a group holding NaN /
+ * inf / huge values does not change any other group's coeffs, pred or valid (bit for bit).  Outputs are per row, IN THE FRAME'S
+ * OWN ROW ORDER and `space`-resident: coeffs [n_rows][n_feat + add_bias] (bias last), pred [n_rows], valid [n_rows] bytes;
+ * coeffs / pred of invalid rows are unspecified (NaN in practice), as in the ungrouped contract.
+ * group_offsets: n_groups + 1 non-decreasing int64 row offsets, `space`-resident, starting at 0 and ending at n_rows (anything
+ * else: PDS_ERR_INVALID).  keys (by key): n_rows int64 values in any row order, `space`-resident; rows with equal keys form a
+ * group (in frame order).  Ordered keys move no data; others take the stable sort of (key, row), the frame gather, the offsets
+ * form and a scatter back (fewer than 2^31 rows per call).  Deliberate deviations from a per-group reference call:
+ *   1. a group with fewer rows than window / start_with gets all rows invalid (the reference aborts the whole query);
+ *   2. empty groups are allowed;
+ *   3. 1 .. 64 coefficients (more: PDS_ERR_UNSUPPORTED); window / start_with >= 1 (else PDS_ERR_INVALID).
+ * Up to 8 coefficients the lane = 4 rows kernels run with segmented sums (a window of 256 takes the two-stream form, not the
+ * register-resident leaving rows); 9 .. 64 the per-row moment records and the batched pivoted QR.  Tile anchors are those of
+ * the ungrouped call on the same frame, so a group's bits can differ from a call on its slice alone (same tolerance).
+ * Group boundaries are found from the offsets by searches (O(log n_groups) per tile and stage, however many empty groups
+ * lie between two rows).  Device-space calls are synchronous on return like every other entry point.
+ */
+int pds_rolling_lr_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int64_t window, int64_t min_size, double lambda,
+                               double* coeffs, double* pred, uint8_t* valid);
+int pds_rolling_lr_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int64_t window, int64_t min_size, float lambda,
+                               float* coeffs, float* pred, uint8_t* valid);
+int pds_recursive_lr_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                 int64_t n_groups, pds_space space, int add_bias, int64_t start_with, double lambda, double* coeffs,
+                                 double* pred, uint8_t* valid);
+int pds_recursive_lr_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                 int64_t n_groups, pds_space space, int add_bias, int64_t start_with, float lambda, float* coeffs,
+                                 float* pred, uint8_t* valid);
+int pds_rolling_lr_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int64_t window, int64_t min_size, double lambda, double* coeffs, double* pred, uint8_t* valid);
+int pds_rolling_lr_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int64_t window, int64_t min_size, float lambda, float* coeffs, float* pred, uint8_t* valid);
+int pds_recursive_lr_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                int add_bias, int64_t start_with, double lambda, double* coeffs, double* pred, uint8_t* valid);
+int pds_recursive_lr_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                int add_bias, int64_t start_with, float lambda, float* coeffs, float* pred, uint8_t* valid);
+
+/*
  * pds_recursive_lr_seeded_*: the expanding fit of a frame that CONTINUES earlier rows -- the row-sharded
  * multi-GPU form of `pl_recursive_lr` ("recursive needs prefix Gram").  `seed_moments` is the
  * HOST-resident augmented moment matrix A = Z'Z ((n_feat+2)^2, layout of pds_moments_*) of all rows in

@@ -19,6 +19,10 @@ from .lstsq import (  # noqa: F401
     lin_reg_by,
     lin_reg_report_by,
     lin_reg_report_by_key,
+    rolling_lin_reg_by,
+    rolling_lin_reg_by_key,
+    recursive_lin_reg_by,
+    recursive_lin_reg_by_key,
     lin_reg_by_key,
     lin_reg_by_key_multi,
     lin_reg_by_key_pred_multi,

@@ -595,6 +595,47 @@ int pds_recursive_lr_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int
     return rolling_impl<float>(ctx, cols, n_feat, n_rows, space, add_bias, start_with, 0, lambda, true, coeffs, pred, valid);
 }
 
+int pds_rolling_lr_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int64_t window, int64_t min_size, double lambda,
+                               double* coeffs, double* pred, uint8_t* valid) {
+    return rolling_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, window, min_size, lambda, false,
+                                        coeffs, pred, valid);
+}
+int pds_rolling_lr_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int64_t window, int64_t min_size, float lambda,
+                               float* coeffs, float* pred, uint8_t* valid) {
+    return rolling_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, window, min_size, lambda, false,
+                                       coeffs, pred, valid);
+}
+int pds_recursive_lr_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                 int64_t n_groups, pds_space space, int add_bias, int64_t start_with, double lambda, double* coeffs,
+                                 double* pred, uint8_t* valid) {
+    return rolling_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, start_with, 0, lambda, true,
+                                        coeffs, pred, valid);
+}
+int pds_recursive_lr_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                 int64_t n_groups, pds_space space, int add_bias, int64_t start_with, float lambda, float* coeffs,
+                                 float* pred, uint8_t* valid) {
+    return rolling_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, start_with, 0, lambda, true,
+                                       coeffs, pred, valid);
+}
+int pds_rolling_lr_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int64_t window, int64_t min_size, double lambda, double* coeffs, double* pred, uint8_t* valid) {
+    return rolling_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, window, min_size, lambda, false, coeffs, pred, valid);
+}
+int pds_rolling_lr_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int64_t window, int64_t min_size, float lambda, float* coeffs, float* pred, uint8_t* valid) {
+    return rolling_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, window, min_size, lambda, false, coeffs, pred, valid);
+}
+int pds_recursive_lr_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                int add_bias, int64_t start_with, double lambda, double* coeffs, double* pred, uint8_t* valid) {
+    return rolling_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, start_with, 0, lambda, true, coeffs, pred, valid);
+}
+int pds_recursive_lr_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                int add_bias, int64_t start_with, float lambda, float* coeffs, float* pred, uint8_t* valid) {
+    return rolling_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, start_with, 0, lambda, true, coeffs, pred, valid);
+}
+
 int pds_recursive_lr_seeded_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, pds_space space,
                                 int add_bias, int64_t start_with, double lambda, const double* seed_moments,
                                 double* coeffs, double* pred, uint8_t* valid) {

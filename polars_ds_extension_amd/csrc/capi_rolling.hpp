@@ -50,3 +50,221 @@ static int rolling_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }
+
+// ---- grouped rolling / expanding fits: for every group g = rows [off[g], off[g+1]) what the plain call gives on g's rows alone
+// (segmented sums: launch_rolling_grouped).  Columns [y, x1..xp] as in rolling_impl.
+static int check_grouped_window(int n_feat, int add_bias, int64_t n_rows, int64_t window, int64_t min_size) {
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_feat + (add_bias ? 1 : 0) > 64)
+        return fail(PDS_ERR_UNSUPPORTED, "grouped rolling / recursive: at most 64 coefficients");
+    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (window < 1) return fail(PDS_ERR_INVALID, "window / start_with must be >= 1");
+    if (min_size < 0) return fail(PDS_ERR_INVALID, "min_size must be >= 0");
+    return PDS_OK;
+}
+// workspace of one grouped launch over n_rows rows (launch_rolling_grouped: tile totals, flags and chunk sums of the expanding
+// form, the record chunk of the wide form)
+static size_t rolling_grouped_need(int n_feat, int add_bias, int64_t n_rows, size_t elem) {
+    const int pp = n_feat + (add_bias ? 1 : 0);
+    size_t need = 131072 + ((size_t)(n_rows / 4096) + 2) * (96 * sizeof(double) + 1) + ((size_t)(n_rows / 4096 / 32) + 2) * (128 * sizeof(double) + 1);
+    if (pp > 8) need += rolling_wide_workspace(n_feat, n_rows, elem) + (size_t)(n_rows / 256) + 256;
+    return need;
+}
+
+// device-resident columns and offsets (validated), device outputs: the ws arena is reserved here
+template <typename T>
+static int rolling_grouped_device(pds_ctx* ctx, const T* const* d_cols, int n_feat, int64_t n_rows, const int64_t* d_off, int64_t n_groups,
+                                  int add_bias, int64_t window, int64_t min_size, double lambda, bool expanding, T* d_co, T* d_pr,
+                                  uint8_t* d_va) {
+    if (int rc = ws_reserve(ctx, rolling_grouped_need(n_feat, add_bias, n_rows, sizeof(T)))) return rc;
+    DeviceCols<T> dc;
+    if (int rc = make_device_cols<T>(ctx, d_cols, (const T*)nullptr, n_feat, n_rows, PDS_DEVICE, dc)) return rc;
+    return launch_rolling_grouped<T>(ctx, dc, n_feat, n_rows, add_bias, window, min_size, lambda, expanding, d_off, n_groups, d_co, d_pr,
+                                     d_va);
+}
+
+template <typename T>
+static int rolling_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                int64_t n_groups, pds_space space, int add_bias, int64_t window, int64_t min_size, double lambda,
+                                bool expanding, T* coeffs, T* pred, uint8_t* valid) {
+    if (!ctx || !cols || !group_offsets || !coeffs || !pred || !valid) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_grouped_window(n_feat, add_bias, n_rows, window, min_size)) return rc;
+    if (n_groups < 1) return fail(PDS_ERR_INVALID, "n_groups must be >= 1");
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int pp = n_feat + (add_bias ? 1 : 0), nc = n_feat + 1;
+    // the offsets on the host: validated (the kernels walk rows with them)
+    std::vector<int64_t> h_off((size_t)n_groups + 1);
+    if (space == PDS_DEVICE) {
+        PDS_HIP_CHECK(hipMemcpyAsync(h_off.data(), group_offsets, h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    } else {
+        std::copy(group_offsets, group_offsets + n_groups + 1, h_off.begin());
+    }
+    if (h_off[0] != 0 || h_off[n_groups] != n_rows) return fail(PDS_ERR_INVALID, "group offsets must start at 0 and end at n_rows");
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (h_off[g + 1] < h_off[g]) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing");
+    if (space == PDS_DEVICE) {
+        if (int rc = rolling_grouped_device<T>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, add_bias, window, min_size, lambda,
+                                               expanding, coeffs, pred, valid))
+            return rc;
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (synchronous on return; dc's pointer table is an async copy source)
+        return PDS_OK;
+    }
+    // host frame: columns, offsets and outputs staged in the keyed workspace (the ws arena belongs to the launch)
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t col_bytes = up((size_t)n_rows * sizeof(T));
+    const size_t need = col_bytes * nc + up(h_off.size() * 8) + up((size_t)n_rows * pp * sizeof(T)) + col_bytes + up((size_t)n_rows) + 4096;
+    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
+    char* w = static_cast<char*>(ctx->keyed.ptr);
+    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
+    std::vector<const T*> src(nc);
+    for (int c = 0; c < nc; ++c) {
+        T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+        PDS_HIP_CHECK(hipMemcpyAsync(dcol, cols[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        src[c] = dcol;
+    }
+    int64_t* d_off = reinterpret_cast<int64_t*>(take(h_off.size() * 8));
+    PDS_HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    T* d_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
+    T* d_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+    uint8_t* d_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+    if (int rc = rolling_grouped_device<T>(ctx, src.data(), n_feat, n_rows, d_off, n_groups, add_bias, window, min_size, lambda, expanding,
+                                           d_co, d_pr, d_va))
+        return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_rows * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pr, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(valid, d_va, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (h_off: source of an async copy)
+    return PDS_OK;
+}
+
+// int64 keys in any row order.  Ordered keys: the order check's run marks give the offsets, nothing moves.  Otherwise the stable
+// radix sort of (key, row) (rows keep their order inside a group), the frame gather, the offsets form on the sorted frame and a
+// scatter of coeffs / pred / valid back to frame order.
+template <typename T>
+static int rolling_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                               int add_bias, int64_t window, int64_t min_size, double lambda, bool expanding, T* coeffs, T* pred,
+                               uint8_t* valid) {
+    if (!ctx || !cols || !keys || !coeffs || !pred || !valid) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_grouped_window(n_feat, add_bias, n_rows, window, min_size)) return rc;
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
+    const int64_t* d_keys = keys;
+    if (space == PDS_HOST) {
+        if (int rc = ensure_ws(ctx, ctx->stage, key_bytes + 256)) return rc;
+        PDS_HIP_CHECK(hipMemcpyAsync(ctx->stage.ptr, keys, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_keys = static_cast<const int64_t*>(ctx->stage.ptr);
+    }
+    const size_t run_slots = key_run_slots(n_rows);
+    const size_t mask_bytes = key_run_mask_bytes(n_rows);
+    if (int rc = ensure_ws(ctx, ctx->solve_ws, 8192 + 2 * up((run_slots + 1) * sizeof(uint32_t)) + mask_bytes)) return rc;
+    char* sw = static_cast<char*>(ctx->solve_ws.ptr);
+    int64_t* d_state = reinterpret_cast<int64_t*>(sw + 256);
+    int64_t* d_minmax = d_state + 2;
+    uint32_t* d_run_counts = reinterpret_cast<uint32_t*>(sw + 4096);
+    uint32_t* d_run_prefix = reinterpret_cast<uint32_t*>(sw + 4096 + up((run_slots + 1) * sizeof(uint32_t)));
+    unsigned long long* d_run_masks = reinterpret_cast<unsigned long long*>(sw + 4096 + 2 * up((run_slots + 1) * sizeof(uint32_t)));
+    bool sorted = false;
+    int64_t mm[2] = {0, 0};
+    int64_t n_runs = 0;
+    if (int rc = keys_order_minmax(ctx, d_keys, n_rows, d_state, &sorted, mm, d_run_counts, d_run_masks, &n_runs)) return rc;
+    if (!sorted && n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "keyed grouping of unordered keys: fewer than 2^31 rows per call");
+    const size_t temp_bytes = sorted ? keyed_ordered_temp_bytes(n_rows) : keyed_temp_bytes(n_rows);
+    const int64_t run_cap = sorted ? n_runs + 1 : n_rows;
+    size_t need = temp_bytes + 3 * up((size_t)(run_cap + 1) * 8) + 8192;
+    const bool stage_out = space == PDS_HOST || !sorted;  // outputs through the workspace (host frame, or scattered back)
+    if (space == PDS_HOST) need += col_bytes * nc;
+    const size_t out_bytes = up((size_t)n_rows * pp * sizeof(T)) + col_bytes + up((size_t)n_rows);
+    if (stage_out) need += out_bytes;
+    if (!sorted && space == PDS_HOST) need += out_bytes;  // the scatter's target
+    if (!sorted) need += 2 * key_bytes + 2 * idx_bytes + col_bytes * nc + up((size_t)n_rows * nc * sizeof(T)) + up(2 * (size_t)nc * sizeof(T*)) + 1024;
+    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
+    char* w = static_cast<char*>(ctx->keyed.ptr);
+    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
+    void* d_temp = take(temp_bytes);
+    int64_t* d_unique = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
+    int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
+    int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
+    int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
+    std::vector<const T*> src(nc);  // [y, x1..xp], device resident
+    for (int c = 0; c < nc; ++c) src[c] = cols[c];
+    if (space == PDS_HOST)
+        for (int c = 0; c < nc; ++c) {
+            T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+            PDS_HIP_CHECK(hipMemcpyAsync(dcol, src[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            src[c] = dcol;
+        }
+    uint32_t* perm = nullptr;
+    if (!sorted) {
+        int64_t* sk = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
+        uint32_t* idx_in = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
+        perm = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
+        int64_t* sk2 = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
+        if (int rc = keyed_sort(ctx, d_keys, n_rows, idx_in, sk, perm, d_temp, temp_bytes, sk2, d_minmax, mm)) return rc;
+        d_keys = sk;
+        if (!gather_frame_fits<T>(nc)) {
+            for (int c = 0; c < nc; ++c) {
+                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+                if (int rc = launch_gather_rows<T>(ctx, src[c], perm, n_rows, dcol)) return rc;
+                src[c] = dcol;
+            }
+        } else {
+            std::vector<const T*> tbl(2 * (size_t)nc);
+            for (int c = 0; c < nc; ++c) tbl[c] = src[c];
+            for (int c = 0; c < nc; ++c) {
+                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+                tbl[nc + c] = dcol;
+                src[c] = dcol;
+            }
+            T* records = reinterpret_cast<T*>(take((size_t)n_rows * nc * sizeof(T)));
+            const T** d_tbl = reinterpret_cast<const T**>(take(2 * (size_t)nc * sizeof(T*)));
+            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), 2 * (size_t)nc * sizeof(T*), hipMemcpyHostToDevice, ctx->stream));
+            if (int rc = launch_gather_frame<T>(ctx, d_tbl, perm, nc, n_rows, records, (T* const*)(d_tbl + nc))) return rc;
+            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
+        }
+    }
+    int64_t ng = 0;
+    if (sorted) {
+        ng = n_runs + 1;
+        if (int rc = keyed_runs_ordered(ctx, d_keys, n_rows, d_run_counts, d_run_prefix, d_run_masks, run_cap, d_unique, d_offsets, d_temp,
+                                        temp_bytes))
+            return rc;
+    } else if (int rc = keyed_runs(ctx, d_keys, n_rows, d_unique, d_counts, d_offsets, d_nruns, d_temp, temp_bytes, &ng)) {
+        return rc;
+    }
+    T* d_co = coeffs;
+    T* d_pr = pred;
+    uint8_t* d_va = valid;
+    if (stage_out) {
+        d_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
+        d_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+        d_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+    }
+    if (int rc = rolling_grouped_device<T>(ctx, src.data(), n_feat, n_rows, d_offsets, ng, add_bias, window, min_size, lambda, expanding, d_co,
+                                           d_pr, d_va))
+        return rc;
+    if (!sorted) {
+        // back to frame order: in place when the caller's buffers are on the device, else into the staged outputs' own slots
+        T* o_co = coeffs;
+        T* o_pr = pred;
+        uint8_t* o_va = valid;
+        if (space == PDS_HOST) {
+            o_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
+            o_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+            o_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+        }
+        if (int rc = launch_rolling_scatter<T>(ctx, d_co, d_pr, d_va, perm, n_rows, pp, o_co, o_pr, o_va)) return rc;
+        d_co = o_co;
+        d_pr = o_pr;
+        d_va = o_va;
+    }
+    if (space == PDS_HOST) {
+        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_rows * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pr, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(valid, d_va, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return PDS_OK;
+}

@@ -349,12 +349,23 @@ template <typename T>
 int launch_rolling(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int add_bias,
                    int64_t window, int64_t min_size, double lambda, bool expanding, const double* seed_moments,
                    T* d_coeffs, T* d_pred, uint8_t* d_valid);
+// grouped fits: segmented sums over the groups [d_off[g], d_off[g+1]) (device offsets, ng + 1 entries, already validated);
+// 1 .. 64 coefficients; workspace comes out of ctx->ws
+template <typename T>
+int launch_rolling_grouped(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int add_bias, int64_t window,
+                           int64_t min_size, double lambda, bool expanding, const int64_t* d_off, int64_t ng, T* d_coeffs, T* d_pred,
+                           uint8_t* d_valid);
+// rolling.hip: the grouped outputs of a group-contiguous frame back to frame order (row i -> perm[i])
+template <typename T>
+int launch_rolling_scatter(pds_ctx* ctx, const T* d_co, const T* d_pr, const uint8_t* d_va, const uint32_t* d_perm, int64_t n, int pp,
+                           T* coeffs, T* pred, uint8_t* valid);
 
-// rolling_wide.hip: 13 .. 64 coefficients (per-row moment records + launch_solve); workspace comes out of ctx->ws
+// rolling_wide.hip: 13 .. 64 coefficients (per-row moment records + launch_solve); workspace comes out of ctx->ws.
+// d_off / ng: the segmented (grouped) form, used from 9 coefficients on
 template <typename T>
 int launch_rolling_wide(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int add_bias, int64_t window,
                         int64_t min_size, double lambda, bool expanding, const double* seed_moments, T* d_coeffs, T* d_pred,
-                        uint8_t* d_valid);
+                        uint8_t* d_valid, const int64_t* d_off = nullptr, int64_t ng = 0);
 size_t rolling_wide_workspace(int n_feat, int64_t n_rows, size_t elem);
 
 // ---- keyed.hip: int64 keys in any row order -> sorted keys, permutation, distinct keys, group offsets

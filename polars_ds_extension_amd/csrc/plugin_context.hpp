@@ -99,6 +99,8 @@ template <> struct Api<double> {
     static constexpr auto report_nullable = pds_lin_reg_report_nullable_f64;
     static constexpr auto rolling = pds_rolling_lr_f64;
     static constexpr auto recursive = pds_recursive_lr_f64;
+    static constexpr auto rolling_by_key = pds_rolling_lr_by_key_f64;
+    static constexpr auto recursive_by_key = pds_recursive_lr_by_key_f64;
     static constexpr auto by_key = pds_lr_by_key_f64;
     static constexpr auto by_key_pred = pds_lr_by_key_pred_f64;
     static constexpr auto by_key_multi = pds_lr_by_key_multi_f64;
@@ -119,6 +121,8 @@ template <> struct Api<float> {
     static constexpr auto report_nullable = pds_lin_reg_report_nullable_f32;
     static constexpr auto rolling = pds_rolling_lr_f32;
     static constexpr auto recursive = pds_recursive_lr_f32;
+    static constexpr auto rolling_by_key = pds_rolling_lr_by_key_f32;
+    static constexpr auto recursive_by_key = pds_recursive_lr_by_key_f32;
     static constexpr auto by_key = pds_lr_by_key_f32;
     static constexpr auto by_key_pred = pds_lr_by_key_pred_f32;
     static constexpr auto by_key_multi = pds_lr_by_key_multi_f32;

@@ -187,10 +187,52 @@ void do_report(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
 }
 
 // ------------------------------------------------------------------------------------------------- rolling / recursive
+// keyed (pl_rolling_lr_by / pl_recursive_lr_by): inputs [key (integer, any row order, nulls = one group), y, x1..xp]; the result
+// is what `.over(key)` of the plain symbol gives -- the same struct per input row, in frame order -- from ONE grouped call
+// (pds_*_lr_by_key_*).  The null policies act per row as in the plain symbols; the recursive compaction carries the key along, so
+// group membership and order survive.  PDS_REFERENCE_QUIRKS' compacted-row pred is not applied to keyed calls (pred is
+// x_row . coeffs_row).
+// Polars' group_by / over make the null keys ONE group.  They take a key value no valid row uses -- max + 1, so that group comes
+// last (min - 1 when the maximum is INT64_MAX); returns whether there were null keys (and the stand-in)
+inline bool null_key_stand_in(Column<int64_t>& key, int64_t n, const char* who, int64_t* stand_in) {
+    if (key.null_count <= 0) return false;
+    const int64_t* k = key.data();
+    int64_t mx = std::numeric_limits<int64_t>::min(), mn = std::numeric_limits<int64_t>::max();
+    bool any_valid = false;
+    for (int64_t i = 0; i < n; ++i)
+        if (bit_get(key.validity.data(), i)) {
+            mx = std::max(mx, k[i]);
+            mn = std::min(mn, k[i]);
+            any_valid = true;
+        }
+    int64_t v = 0;
+    if (!any_valid) v = 0;
+    else if (mx < std::numeric_limits<int64_t>::max()) v = mx + 1;
+    else if (mn > std::numeric_limits<int64_t>::min()) v = mn - 1;
+    else raise(std::string(who) + ": the keys span the whole int64 range, no value is left for the null group");
+    auto& kv = key.own();
+    for (int64_t i = 0; i < n; ++i)
+        if (!bit_get(key.validity.data(), i)) kv[i] = v;
+    *stand_in = v;
+    return true;
+}
+
 template <typename T>
-void do_windowed(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool rolling) {
+void do_windowed(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool rolling, bool keyed = false) {
+    Column<int64_t> key;
+    if (keyed) {
+        if (n_in < 3) raise("need a key, a target and at least one feature");
+        key = import_series<int64_t>(in[0]);
+        ++in;
+        --n_in;
+    }
     auto cols = import_all<T>(in, n_in);
     if (n_in < 2) raise("need a target and at least one feature");
+    if (keyed) {
+        if (key.size() != cols[0].size()) raise("input columns differ in length");
+        int64_t stand_in = 0;
+        null_key_stand_in(key, key.size(), rolling ? "pl_rolling_lr_by" : "pl_recursive_lr_by", &stand_in);
+    }
     const bool bias = kw_bool(kw, "bias");
     const int64_t nwin = kw_i64(kw, "n");
     const double lambda = kw_f64(kw, "lambda");
@@ -229,6 +271,13 @@ void do_windowed(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* 
                 if (keep[i]) v[j++] = v[i];
             c.shrink(nk);
         }
+        if (keyed) {  // (the key travels with its rows: null stand-ins are already in place)
+            auto& kv = key.own();
+            int64_t j = 0;
+            for (int64_t i = 0; i < n; ++i)
+                if (keep[i]) kv[j++] = kv[i];
+            key.shrink(nk);
+        }
         has_null = false;
     }
     if (has_null) {
@@ -253,18 +302,28 @@ void do_windowed(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* 
     T* const coeffs = as<T>(cbuf);
     T* const pred = as<T>(pbuf);
     std::vector<uint8_t> valid(n);
-    if (rolling)
+    if (keyed && rolling)
+        check(Api<T>::rolling_by_key(thread_ctx(), ptrs.data(), key.data(), n_feat, n, PDS_HOST, bias, nwin, min_size, (T)lambda, coeffs, pred,
+                                     valid.data()));
+    else if (keyed && keep.empty())
+        check(Api<T>::recursive_by_key(thread_ctx(), ptrs.data(), key.data(), n_feat, n, PDS_HOST, bias, nwin, (T)lambda, coeffs, pred,
+                                       valid.data()));
+    else if (rolling)
         check(Api<T>::rolling(thread_ctx(), ptrs.data(), n_feat, n, PDS_HOST, bias, nwin, min_size, (T)lambda, coeffs, pred, valid.data()));
     else if (keep.empty())
         check(Api<T>::recursive(thread_ctx(), ptrs.data(), n_feat, n, PDS_HOST, bias, nwin, (T)lambda, coeffs, pred, valid.data()));
     else {
         const int64_t nk = cols[0].size();
         std::fill(valid.begin(), valid.end(), (uint8_t)0);
-        if (nk >= nwin && nk >= pp) {  // fewer kept rows than the initial fit needs: every row stays null
+        if (keyed || (nk >= nwin && nk >= pp)) {  // fewer kept rows than the initial fit needs: every row stays null
             std::vector<T> cc((size_t)nk * pp), pc(nk);
             std::vector<uint8_t> vc(nk);
-            check(Api<T>::recursive(thread_ctx(), ptrs.data(), n_feat, nk, PDS_HOST, bias, nwin, (T)lambda, cc.data(), pc.data(), vc.data()));
-            if (reference_quirks())  // pred of fitted row j from compacted row j - (n - 1)
+            if (keyed)  // (groups shorter than start_with are all invalid, not an error)
+                check(Api<T>::recursive_by_key(thread_ctx(), ptrs.data(), key.data(), n_feat, nk, PDS_HOST, bias, nwin, (T)lambda, cc.data(),
+                                               pc.data(), vc.data()));
+            else
+                check(Api<T>::recursive(thread_ctx(), ptrs.data(), n_feat, nk, PDS_HOST, bias, nwin, (T)lambda, cc.data(), pc.data(), vc.data()));
+            if (reference_quirks() && !keyed)  // pred of fitted row j from compacted row j - (n - 1)
                 for (int64_t j = nwin - 1; j < nk; ++j) {
                     const int64_t r = j - (nwin - 1);
                     T acc = bias ? cc[(size_t)j * pp + n_feat] : (T)0;
@@ -395,27 +454,8 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
     }
     // Polars' group_by makes the null keys ONE group.  They take a key value no valid row uses -- max + 1, so that group comes
     // last (min - 1 when the maximum is INT64_MAX) -- and the group that carries it is reported with a null key.
-    bool null_group = false;
     int64_t null_stand_in = 0;
-    if (key.null_count > 0) {
-        const int64_t* k = key.data();
-        int64_t mx = std::numeric_limits<int64_t>::min(), mn = std::numeric_limits<int64_t>::max();
-        bool any_valid = false;
-        for (int64_t i = 0; i < n; ++i)
-            if (bit_get(key.validity.data(), i)) {
-                mx = std::max(mx, k[i]);
-                mn = std::min(mn, k[i]);
-                any_valid = true;
-            }
-        if (!any_valid) null_stand_in = 0;
-        else if (mx < std::numeric_limits<int64_t>::max()) null_stand_in = mx + 1;
-        else if (mn > std::numeric_limits<int64_t>::min()) null_stand_in = mn - 1;
-        else raise("pl_lr_by: the keys span the whole int64 range, no value is left for the null group");
-        auto& kv = key.own();
-        for (int64_t i = 0; i < n; ++i)
-            if (!bit_get(key.validity.data(), i)) kv[i] = null_stand_in;
-        null_group = true;
-    }
+    const bool null_group = null_key_stand_in(key, n, "pl_lr_by", &null_stand_in);
     const int n_feat = (int)n_in - 2 - (weighted ? 1 : 0);
     const int pp = n_feat + prm.add_bias;
     const int64_t* ikey = key.data();

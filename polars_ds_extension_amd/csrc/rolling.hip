@@ -425,6 +425,65 @@ static int launch_tile_prefix(pds_ctx* ctx, double* tot, int64_t ntiles, int nv,
     return PDS_OK;
 }
 
+// SEGMENTED exclusive prefix over the tile totals of a grouped expanding fit: a tile that holds a group start (tflag) hands on
+// its own total -- the rows from its last start to its end -- instead of adding it to the running sum, so the carry into tile
+// t is the sum of [start of t0's group, t0) and never a difference of two prefixes (which would cancel and tie a group's bits
+// to the groups in front of it).  Same three launches and fixed order as the plain prefix.
+__global__ __launch_bounds__(64) void tile_chunk_sum_seg_kernel(const double* __restrict__ tot, const uint8_t* __restrict__ tflag,
+                                                                int64_t ntiles, int nv, double* __restrict__ chunk_sum,
+                                                                uint8_t* __restrict__ cflag) {
+    const int64_t c = blockIdx.x;
+    const int64_t t0 = c * kPrefixChunk, t1 = (t0 + kPrefixChunk < ntiles) ? t0 + kPrefixChunk : ntiles;
+    for (int v = threadIdx.x; v < nv; v += 64) {
+        double sum = 0.0;
+        for (int64_t t = t0; t < t1; ++t) sum = tflag[t] ? tot[t * nv + v] : sum + tot[t * nv + v];
+        chunk_sum[c * nv + v] = sum;
+    }
+    if (threadIdx.x == 0) {
+        uint8_t f = 0;
+        for (int64_t t = t0; t < t1; ++t) f |= tflag[t];
+        cflag[c] = f;
+    }
+}
+__global__ __launch_bounds__(128) void chunk_prefix_seg_kernel(double* __restrict__ chunk_sum, const uint8_t* __restrict__ cflag,
+                                                               int64_t nchunks, int nv) {
+    const int v = threadIdx.x;
+    if (v >= nv) return;
+    double run = 0.0;
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const double x = chunk_sum[c * nv + v];
+        chunk_sum[c * nv + v] = run;
+        run = cflag[c] ? x : run + x;
+    }
+}
+__global__ __launch_bounds__(64) void tile_prefix_write_seg_kernel(double* __restrict__ tot, const uint8_t* __restrict__ tflag,
+                                                                   int64_t ntiles, int nv, const double* __restrict__ chunk_base) {
+    const int64_t c = blockIdx.x;
+    const int64_t t0 = c * kPrefixChunk, t1 = (t0 + kPrefixChunk < ntiles) ? t0 + kPrefixChunk : ntiles;
+    for (int v = threadIdx.x; v < nv; v += 64) {
+        double run = chunk_base[c * nv + v];
+        for (int64_t t = t0; t < t1; ++t) {
+            const double x = tot[t * nv + v];
+            tot[t * nv + v] = run;
+            run = tflag[t] ? x : run + x;
+        }
+    }
+}
+static int launch_tile_prefix_seg(pds_ctx* ctx, double* tot, const uint8_t* tflag, int64_t ntiles, int nv) {
+    if (nv > 128) return fail(PDS_ERR_INVALID, "internal: tile prefix handles up to 128 moments");
+    const int64_t nchunks = (ntiles + kPrefixChunk - 1) / kPrefixChunk;
+    double* chunk = reinterpret_cast<double*>(ws_take(ctx, (size_t)nchunks * nv * sizeof(double)));
+    uint8_t* cflag = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)nchunks));
+    if (!chunk || !cflag) return fail(PDS_ERR_HIP, "workspace allocation failed");
+    hipLaunchKernelGGL(tile_chunk_sum_seg_kernel, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, (const double*)tot, tflag, ntiles, nv,
+                       chunk, cflag);
+    hipLaunchKernelGGL(chunk_prefix_seg_kernel, dim3(1), dim3(128), 0, ctx->stream, chunk, (const uint8_t*)cflag, nchunks, nv);
+    hipLaunchKernelGGL(tile_prefix_write_seg_kernel, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, tot, tflag, ntiles, nv,
+                       (const double*)chunk);
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
 template <typename T, int PP, int FULLP>
 static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool expanding, const double* seed_moments,
                        T* d_coeffs, T* d_pred, uint8_t* d_valid) {
@@ -460,12 +519,12 @@ static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool 
                 if constexpr (M == 0) {
                     using SD = SegDims<T, PP, 1>;
                     hipLaunchKernelGGL((rolling_seg_kernel<T, PP, 0, FULLP, 1>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES,
-                                       ctx->stream, dc.d_ptrs, ra, tot, d_coeffs, d_pred, d_valid);
+                                       ctx->stream, dc.d_ptrs, ra, tot, d_coeffs, d_pred, d_valid, RollGroups{});
                 }
             } else {
                 using SD = SegDims<T, PP, 0>;
                 hipLaunchKernelGGL((rolling_seg_kernel<T, PP, M, FULLP, 0>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES,
-                                   ctx->stream, dc.d_ptrs, ra, tot, d_coeffs, d_pred, d_valid);
+                                   ctx->stream, dc.d_ptrs, ra, tot, d_coeffs, d_pred, d_valid, RollGroups{});
             }
         }
     };
@@ -501,7 +560,7 @@ static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool 
                 using SD = SegDims<T, PP>;
                 const int64_t tb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12);
                 hipLaunchKernelGGL((rolling_totals_kernel<T, PP, FULLP>), dim3((unsigned)tb), dim3(64),
-                                   (size_t)SD::NV * kSegStride * sizeof(double), ctx->stream, dc.d_ptrs, ra, tot);
+                                   (size_t)SD::NV * kSegStride * sizeof(double), ctx->stream, dc.d_ptrs, ra, tot, RollGroups{});
                 totals_done = true;
             }
         }
@@ -553,6 +612,97 @@ int launch_rolling(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_
                                   d_pred, d_valid);
 }
 
+// ---- grouped fits (pds_rolling_lr_grouped_* / pds_recursive_lr_grouped_*): segmented sums, group g = rows [off[g], off[g+1])
+// Up to 8 coefficients: rolling_seg_kernel / rolling_totals_kernel with GROUPED = 1 (the two-stream form also for w == 256);
+// 9 .. 64: the segmented record kernel of rolling_wide.hip (the lane = row kernel has no grouped form).
+template <typename T, int PP, int FULLP>
+static int launch_grouped_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool expanding, const int64_t* d_off, int64_t ng,
+                               T* d_coeffs, T* d_pred, uint8_t* d_valid) {
+    using SD = SegDims<T, PP, 0>;
+    RollGroups grp{d_off, ng, nullptr};
+    KernelTimer timer(ctx, kKindRolling);
+    if (!expanding) {
+        ra.mode = 0;
+        const int64_t seg_tiles = (ra.n + kSegTileRoll - 1) / kSegTileRoll;
+        const int64_t sb = std::min<int64_t>(std::max<int64_t>(seg_tiles, 1), (int64_t)ctx->num_cus * 4);
+        hipLaunchKernelGGL((rolling_seg_kernel<T, PP, 0, FULLP, 0, 1>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES, ctx->stream,
+                           dc.d_ptrs, ra, (const double*)nullptr, d_coeffs, d_pred, d_valid, grp);
+    } else {
+        constexpr int NV = SD::NV;
+        const int64_t ntiles = (ra.n + kSegTile - 1) / kSegTile;
+        double* tot = reinterpret_cast<double*>(ws_take(ctx, (size_t)ntiles * NV * sizeof(double)));
+        grp.tile_flag = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)ntiles));
+        if (!tot || !grp.tile_flag) return fail(PDS_ERR_HIP, "workspace allocation failed");
+        ra.mode = 1;
+        const int64_t tb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12);
+        hipLaunchKernelGGL((rolling_totals_kernel<T, PP, FULLP, 1>), dim3((unsigned)tb), dim3(64), (size_t)NV * kSegStride * sizeof(double),
+                           ctx->stream, dc.d_ptrs, ra, tot, grp);
+        if (int rc = launch_tile_prefix_seg(ctx, tot, grp.tile_flag, ntiles, NV)) return rc;
+        ra.mode = 2;
+        const int64_t sb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 4);
+        hipLaunchKernelGGL((rolling_seg_kernel<T, PP, 2, FULLP, 0, 1>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES, ctx->stream,
+                           dc.d_ptrs, ra, (const double*)tot, d_coeffs, d_pred, d_valid, grp);
+    }
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+template <typename T, int PP>
+static int launch_grouped_pp(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool expanding, const int64_t* d_off, int64_t ng,
+                             T* d_coeffs, T* d_pred, uint8_t* d_valid) {
+    if (ra.p == PP && !ra.bias) return launch_grouped_pp_f<T, PP, 1>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    if (ra.p == PP - 1 && ra.bias) return launch_grouped_pp_f<T, PP, 2>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    return launch_grouped_pp_f<T, PP, 0>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+}
+
+template <typename T>
+int launch_rolling_grouped(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int add_bias, int64_t window,
+                           int64_t min_size, double lambda, bool expanding, const int64_t* d_off, int64_t ng, T* d_coeffs, T* d_pred,
+                           uint8_t* d_valid) {
+    RollArgs ra;
+    ra.p = n_feat;
+    ra.bias = add_bias ? 1 : 0;
+    ra.pp = n_feat + ra.bias;
+    ra.n = n_rows;
+    ra.window = window;
+    ra.min_size = min_size;
+    ra.lambda = lambda > 0.0 ? lambda : 0.0;
+    ra.mode = 0;
+    ra.tile_rows = kTileRows;
+    const int pp = ra.pp;
+    if (pp <= 2) return launch_grouped_pp<T, 2>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    if (pp <= 4) return launch_grouped_pp<T, 4>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    if (pp <= 6) return launch_grouped_pp<T, 6>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    if (pp <= 8) return launch_grouped_pp<T, 8>(ctx, dc, ra, expanding, d_off, ng, d_coeffs, d_pred, d_valid);
+    return launch_rolling_wide<T>(ctx, dc, n_feat, n_rows, add_bias, window, min_size, lambda, expanding, nullptr, d_coeffs, d_pred,
+                                  d_valid, d_off, ng);
+}
+
+// the grouped outputs of a sorted (group-contiguous) frame back to frame order: row i of the sorted frame is row perm[i] of the
+// frame; lane = row, its p' coefficients as one contiguous record
+template <typename T>
+__global__ __launch_bounds__(256) void rolling_scatter_kernel(const T* __restrict__ co, const T* __restrict__ pr,
+                                                              const uint8_t* __restrict__ va, const uint32_t* __restrict__ perm, int64_t n,
+                                                              int pp, T* __restrict__ coeffs, T* __restrict__ pred, uint8_t* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = perm[i];
+    const T* src = co + i * (int64_t)pp;
+    T* dst = coeffs + j * (int64_t)pp;
+    for (int a = 0; a < pp; ++a) dst[a] = src[a];
+    pred[j] = pr[i];
+    valid[j] = va[i];
+}
+template <typename T>
+int launch_rolling_scatter(pds_ctx* ctx, const T* d_co, const T* d_pr, const uint8_t* d_va, const uint32_t* d_perm, int64_t n, int pp,
+                           T* coeffs, T* pred, uint8_t* valid) {
+    if (n <= 0) return PDS_OK;
+    KernelTimer timer(ctx, kKindRolling);
+    hipLaunchKernelGGL((rolling_scatter_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_co, d_pr, d_va, d_perm, n,
+                       pp, coeffs, pred, valid);
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
 #ifdef PDS_PROFILE_ROLLING
 extern "C" int pds_debug_rolling_cycles(unsigned long long* out, int reset) {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -566,5 +716,13 @@ template int launch_rolling<double>(pds_ctx*, const DeviceCols<double>&, int, in
                                     bool, const double*, double*, double*, uint8_t*);
 template int launch_rolling<float>(pds_ctx*, const DeviceCols<float>&, int, int64_t, int, int64_t, int64_t, double, bool,
                                    const double*, float*, float*, uint8_t*);
+template int launch_rolling_grouped<double>(pds_ctx*, const DeviceCols<double>&, int, int64_t, int, int64_t, int64_t, double, bool,
+                                            const int64_t*, int64_t, double*, double*, uint8_t*);
+template int launch_rolling_grouped<float>(pds_ctx*, const DeviceCols<float>&, int, int64_t, int, int64_t, int64_t, double, bool,
+                                           const int64_t*, int64_t, float*, float*, uint8_t*);
+template int launch_rolling_scatter<double>(pds_ctx*, const double*, const double*, const uint8_t*, const uint32_t*, int64_t, int,
+                                            double*, double*, uint8_t*);
+template int launch_rolling_scatter<float>(pds_ctx*, const float*, const float*, const uint8_t*, const uint32_t*, int64_t, int,
+                                           float*, float*, uint8_t*);
 
 }  // namespace pds

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "moments_dev.hpp"
+#include "rolling_groups_dev.hpp"
 
 // The next stage's rows go global -> LDS directly (below); -DPDS_ROLL_NO_LDS_DIRECT keeps the register-staged prefetch (A/B:
 // 5.31 -> 4.54 ms at C4, profiles/r02_rolling_variants_ab.txt)
@@ -111,11 +112,17 @@ __device__ __forceinline__ void seg_zero(SegRow<PP>& r) {
 // stage earlier -- the same lane's rows of the previous stage, still in its registers.  The second read stream (7.2 GB at C4,
 // re-fetched from HBM because the output stream had evicted it: profiles/r02_traffic.json) and its half of the LDS image and
 // of the LDS -> register hand-over disappear; only the first stage of a tile fetches its leaving rows (straight into registers).
-template <typename T, int PP, int MODE, int FULLP, int OLDREG = 0>
+// GROUPED (grouped fits, rolling_groups_dev.hpp): the sums are SEGMENTED -- they restart from zero at every group start and a
+// leaving row is subtracted only if it belongs to the entering row's group, so a group's outputs depend on its own rows alone.
+// The tile anchor starts at max(t0 - w, start of t0's group); the scan over the lanes is a segmented scan of (lane holds a
+// start, value) pairs whose flags are one wave-uniform ballot mask; tile_tot holds the segmented exclusive prefix.  Grouped
+// calls do not take the OLDREG form (its leaving rows are the previous stage's, across group starts as well).
+template <typename T, int PP, int MODE, int FULLP, int OLDREG = 0, int GROUPED = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void rolling_seg_kernel(
     const T* const* __restrict__ cols, RollArgs ra_in, const double* __restrict__ tile_tot, T* __restrict__ coeffs,
-    T* __restrict__ pred, uint8_t* __restrict__ valid) {
+    T* __restrict__ pred, uint8_t* __restrict__ valid, RollGroups grp) {
     static_assert(!OLDREG || MODE == 0, "the register-resident leaving rows belong to the rolling form");
+    static_assert(!(OLDREG && GROUPED), "grouped fits take the two-stream form");
     using SD = SegDims<T, PP, OLDREG>;
     constexpr int kTile = MODE == 0 ? kSegTileRoll : kSegTile;
     constexpr int K = kSegK, NG = SD::NG, NV = SD::NV, E16 = SD::E16, PIECES = SD::PIECES;
@@ -207,6 +214,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         RT0();
         const int64_t t0 = t * kTile, t1 = (t0 + kTile < n) ? t0 + kTile : n;
+        int64_t gcur = 0;  // GROUPED: group of the current stage's first row (wave-uniform)
+        if constexpr (GROUPED) gcur = grp_find(grp.off, 0, grp.ng - 1, t0);
         // ---- anchor: lane v < NV carries moment v of the window that ends at row t0 - 1
         double carry = 0.0;
         if constexpr (MODE == 2) {
@@ -215,7 +224,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             double A[NV];
 #pragma unroll
             for (int v = 0; v < NV; ++v) A[v] = 0.0;
-            const int64_t a0 = t0 - w;
+            int64_t a0 = t0 - w;
+            if constexpr (GROUPED) a0 = a0 > grp.off[gcur] ? a0 : grp.off[gcur];  // the window stays inside t0's group
             for (int64_t r = a0 + lane; r < t0; r += 64) {
                 SegRow<PP> row;
                 const bool in = r >= 0;
@@ -322,6 +332,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                     if constexpr (!OLDREG) ro[i].y = (MODE == 0) ? b[i] : 0.0;
                 }
             }
+            double S[NV];
+            // GROUPED: dg[i] = row - start of its group (0: the row opens a group); smask: lanes holding a group start
+            int64_t dg[K];
+            unsigned long long smask = 0;
+            if constexpr (GROUPED) {
+                const int64_t last = (base + kSegStage < t1 ? base + kSegStage : t1) - 1;
+                const int64_t ge = grp_advance(grp.off, grp.ng, gcur, last);
+                int64_t g = grp_find(grp.off, gcur, ge, r0 < last ? r0 : last);
+                bool opens = false;
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+                    const int64_t r = r0 + i < last ? r0 + i : last;
+                    g = grp_find(grp.off, g, ge, r);  // (none or one step for groups longer than a stage)
+                    dg[i] = r - grp.off[g];
+                    opens = opens || (dg[i] == 0 && r0 + i < t1);
+                }
+                smask = __ballot(opens);
+                gcur = ge;
+            }
 #pragma unroll
             for (int i = 0; i < K; ++i) {
                 const int64_t r = r0 + i;
@@ -330,21 +359,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 okn[i] = (r < t1) && seg_finite<PP>(rn[i]);
                 if constexpr (MODE == 0 && !OLDREG) {
                     oko[i] = (r < t1) && (r - w >= 0) && seg_finite<PP>(ro[i]);
+                    if constexpr (GROUPED) oko[i] = oko[i] && (dg[i] >= w);  // the leaving row is in the entering row's group
                 } else if constexpr (MODE != 0) {
                     oko[i] = false;
                 }
             }
+            // GROUPED: a row that opens a group restarts the running sums (a select, not a subtraction: nothing of the
+            // group before leaks in); only stages holding a start pay for it
+            auto restart = [&](int i) __attribute__((always_inline)) {
+                if constexpr (GROUPED) {
+                    if (smask != 0 && dg[i] == 0 && r0 + i < t1) {
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) S[v] = 0.0;
+                    }
+                }
+            };
 #ifdef PDS_PROFILE_ROLLING
             asm volatile("" :: "v"(rn[0].z[0]), "v"(rn[K - 1].y));
 #endif
             RT1(1);  // rows LDS -> registers, finiteness
             RTA();
-            // ---- pass 1: the lane's own increments
-            double S[NV];
+            // ---- pass 1: the lane's own increments (GROUPED: those behind the lane's last group start)
 #pragma unroll
             for (int v = 0; v < NV; ++v) S[v] = 0.0;
 #pragma unroll
             for (int i = 0; i < K; ++i) {
+                restart(i);
                 if (okn[i]) seg_accumulate<PP, NV, 1>(S, rn[i], true);
                 if constexpr (MODE == 0) {
                     if (oko[i]) seg_accumulate<PP, NV, -1>(S, ro[i], true);
@@ -360,7 +400,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
             for (int v = 0; v < NV; ++v) D[v * kSegStride + lane] = S[v];
             PDS_WAVE_LDS_SYNC();
-            if (lane < NV) {
+            if (lane < NV && (!GROUPED || smask == 0)) {
                 lds_dp rowp = D + lane * kSegStride;
                 double run = carry;
 #pragma unroll
@@ -373,6 +413,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                         const double inc = x[i];
                         x[i] = run;  // exclusive prefix, carry included
                         run += inc;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) rowp[i0 + i] = x[i];
+                }
+                carry = run;
+            } else if (GROUPED && lane < NV) {
+                // segmented: a lane holding a group start hands on its own total (the rows behind its last start)
+                lds_dp rowp = D + lane * kSegStride;
+                double run = carry;
+#pragma unroll
+                for (int i0 = 0; i0 < 64; i0 += 16) {
+                    double x[16];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) x[i] = rowp[i0 + i];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const double inc = x[i];
+                        x[i] = run;
+                        run = ((smask >> (i0 + i)) & 1ull) ? inc : run + inc;
                     }
 #pragma unroll
                     for (int i = 0; i < 16; ++i) rowp[i0 + i] = x[i];
@@ -457,7 +516,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 const int64_t r = r0 + i;
                 if (r < t1) {
                     const T nanv = (T)__builtin_nan("");
-                    bool v_ok = r >= w - 1;
+                    bool v_ok = GROUPED ? (dg[i] >= w - 1) : (r >= w - 1);
                     if (ra.min_size > 0) v_ok = v_ok && (cnt >= (double)ra.min_size);
                     double pr = 0.0;
 #pragma unroll
@@ -483,6 +542,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 }
             };
             auto advance = [&](int i) __attribute__((always_inline)) {  // the window moves on by row i of the lane
+                restart(i);
                 if (okn[i]) seg_accumulate<PP, NV, 1>(S, rn[i], true);
                 if constexpr (MODE == 0) {
                     if (oko[i]) seg_accumulate<PP, NV, -1>(S, ro[i], true);
@@ -614,10 +674,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // coalesced per instruction, non-temporal), moments in registers, three waves per SIMD,
 // one cross-lane reduction per tile.  (It was the lane = row rolling kernel in its totals mode: 3.06 ms for the 7.2 GB of
 // C4's frame.)  Same moment order and non-finite rule as rolling_seg_kernel (seg_accumulate).
+// GROUPED: a tile's total is that of its last open segment -- the rows from the last group start inside the tile (if any) to
+// the tile's end -- and grp.tile_flag[t] says whether the tile holds a start (the segmented prefix, tile_prefix_seg_*).
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T, int PP, int FULLP>
+template <typename T, int PP, int FULLP, int GROUPED = 0>
 __global__ __launch_bounds__(64) void rolling_totals_kernel(const T* const* __restrict__ cols, RollArgs ra_in,
-                                                            double* __restrict__ tile_tot) {
+                                                            double* __restrict__ tile_tot, RollGroups grp) {
     using SD = SegDims<T, PP>;
     constexpr int NV = SD::NV, E16 = SD::E16;
     constexpr int STEP = 64 * E16;  // rows per load step
@@ -652,6 +714,12 @@ __global__ __launch_bounds__(64) void rolling_totals_kernel(const T* const* __re
     };
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int64_t t0 = t * kSegTile, t1 = (t0 + kSegTile < n) ? t0 + kSegTile : n;
+        int64_t ts = t0;  // GROUPED: first row of the tile's last open segment
+        if constexpr (GROUPED) {
+            const int64_t ls = grp.off[grp_find(grp.off, 0, grp.ng - 1, t1 - 1)];
+            if (ls >= t0) ts = ls;
+            if (lane == 0) grp.tile_flag[t] = ls >= t0 ? 1 : 0;
+        }
         double S[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) S[v] = 0.0;
@@ -667,7 +735,8 @@ __global__ __launch_bounds__(64) void rolling_totals_kernel(const T* const* __re
 #pragma unroll
                 for (int c = 0; c < PP; ++c) row.z[c] = (c < p) ? (double)cur[c][e] : ((c == p && ra.bias) ? 1.0 : 0.0);
                 row.y = (double)cur[p][e];
-                const bool ok = (base + (int64_t)lane * E16 + e < t1) && seg_finite<PP>(row);
+                const int64_t r = base + (int64_t)lane * E16 + e;
+                const bool ok = (r < t1) && (!GROUPED || r >= ts) && seg_finite<PP>(row);
                 if (!ok) seg_zero<PP>(row);
                 seg_accumulate<PP, NV, 1>(S, row, ok);
             }

@@ -16,7 +16,12 @@
 //      variant's min_size on the finite-row count, which is the [1,1] entry of the record), NaN fill.
 // The records of a chunk (q^2 values per row) are sized to stay in the 256 MiB Infinity Cache between 1 and 2.
 // Coverage path: correct and parallel, not tuned (p' <= 12 is the measured one).
+// GROUPED (pds_rolling_lr_grouped_* / pds_recursive_lr_grouped_* from 9 coefficients on): segmented sums -- the running
+// matrix restarts from zero at every group start (a wave-uniform ballot mask of the step's starting rows), a leaving row is
+// subtracted only inside the entering row's group, the warm-up stays inside the segment's first group, and the expanding
+// totals are those of the segment's last open group (plus a flag) under a segmented prefix.
 #include "common.hpp"
+#include "rolling_groups_dev.hpp"
 
 namespace pds {
 
@@ -29,10 +34,10 @@ struct RollWideArgs {
     int mode;  // 0 rolling, 1 expanding: per-segment totals, 2 expanding: main pass from the prefix
 };
 
-template <typename T, int KMAX>
+template <typename T, int KMAX, int GROUPED = 0>
 __global__ __launch_bounds__(64) void rolling_wide_kernel(const T* const* __restrict__ cols, RollWideArgs ra, int64_t c0,
                                                           int64_t c1, double* __restrict__ seg_tot,
-                                                          T* __restrict__ mom) {
+                                                          T* __restrict__ mom, RollGroups grp) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int lane = threadIdx.x;
     const int p = ra.p, q = ra.q, qq = q * q;
@@ -43,6 +48,16 @@ __global__ __launch_bounds__(64) void rolling_wide_kernel(const T* const* __rest
     if (r0 >= c1) return;
     const int64_t r1 = (r0 + kSegRows < c1) ? r0 + kSegRows : c1;
     const int64_t w = ra.window;
+    int64_t gcur = 0, gstart = 0, ts = r0;  // GROUPED: group of the step's first row, start of r0's group, totals' first row
+    if constexpr (GROUPED) {
+        gcur = grp_find(grp.off, 0, grp.ng - 1, r0);
+        gstart = grp.off[gcur];
+        if (ra.mode == 1) {  // the segment's total is that of its last open group
+            const int64_t ls = grp.off[grp_find(grp.off, gcur, grp.ng - 1, r1 - 1)];
+            if (ls >= r0) ts = ls;
+            if (lane == 0) grp.tile_flag[s] = ls >= r0 ? 1 : 0;
+        }
+    }
 
     int ia[KMAX], ja[KMAX];  // LDS offsets of the two factors of entry e = lane + 64 k
     double W[KMAX];
@@ -61,6 +76,20 @@ __global__ __launch_bounds__(64) void rolling_wide_kernel(const T* const* __rest
         const int64_t r = base + lane;
         // ---- the 64 rows of this step (and the 64 rows leaving the window), lane = row
         bool fin_n = r >= 0 && r < ra.n && (warm ? r >= r0 - w : r < r1);
+        // GROUPED: dgl = row - start of its group; smask: the step's rows that open a group
+        int64_t dgl = 0;
+        unsigned long long smask = 0;
+        if constexpr (GROUPED) {
+            fin_n = fin_n && (warm ? r >= gstart : (ra.mode != 1 || r >= ts));
+            if (!warm && ra.mode != 1) {
+                const int64_t last = (base + 63 < r1 - 1) ? base + 63 : r1 - 1;
+                const int64_t ge = grp_advance(grp.off, grp.ng, gcur, last);
+                const int64_t rr = r < last ? r : last;
+                dgl = rr - grp.off[grp_find(grp.off, gcur, ge, rr)];
+                smask = __ballot(dgl == 0 && r < r1);
+                gcur = ge;
+            }
+        }
         {
             const bool in = fin_n;
             for (int c = 0; c <= p; ++c) {
@@ -74,6 +103,7 @@ __global__ __launch_bounds__(64) void rolling_wide_kernel(const T* const* __rest
         if (ra.mode == 0 && !warm) {
             const int64_t ro = r - w;
             fin_o = ro >= 0 && r < r1;
+            if constexpr (GROUPED) fin_o = fin_o && dgl >= w;  // the leaving row is in the entering row's group
             const bool in = fin_o;
             for (int c = 0; c <= p; ++c) {
                 const double v = in ? (double)as_global(cols[c])[ro] : 0.0;
@@ -87,6 +117,12 @@ __global__ __launch_bounds__(64) void rolling_wide_kernel(const T* const* __rest
         PDS_WAVE_LDS_SYNC();
         const int steps = (int)((r1 - base < 64) ? r1 - base : 64);
         for (int t = 0; t < steps; ++t) {
+            if constexpr (GROUPED) {
+                if ((smask >> t) & 1ull) {  // the row opens a group: the sums restart
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k) W[k] = 0.0;
+                }
+            }
             if ((mask_n >> t) & 1ull) {
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) W[k] = fma(Zn[ia[k] + t], Zn[ja[k] + t], W[k]);
@@ -218,6 +254,20 @@ __global__ __launch_bounds__(1024) void rolling_big_kernel(const T* const* __res
     }
 }
 
+// the segmented form (grouped expanding fits): a segment holding a group start hands on its own total (rolling.hip,
+// tile_chunk_sum_seg_kernel)
+__global__ __launch_bounds__(256) void seg_prefix_grouped_kernel(double* __restrict__ tot, const uint8_t* __restrict__ flag, int64_t nseg,
+                                                                 int qq) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= qq) return;
+    double run = 0.0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const double x = tot[s * qq + e];
+        tot[s * qq + e] = run;
+        run = flag[s] ? x : run + x;
+    }
+}
+
 // exclusive prefix over the per-segment totals, thread = matrix entry (fixed order: results do not depend on scheduling)
 __global__ __launch_bounds__(256) void seg_prefix_kernel(double* __restrict__ tot, int64_t nseg, int qq,
                                                          const double* __restrict__ seed) {
@@ -235,12 +285,14 @@ template <typename T>
 __global__ __launch_bounds__(256) void rolling_wide_finish_kernel(const T* const* __restrict__ cols, RollWideArgs ra, int64_t c0,
                                                                   int64_t c1, const T* __restrict__ mom,
                                                                   const uint8_t* __restrict__ flags, T* __restrict__ coeffs,
-                                                                  T* __restrict__ pred, uint8_t* __restrict__ valid) {
+                                                                  T* __restrict__ pred, uint8_t* __restrict__ valid, RollGroups grp) {
     const int64_t r = c0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= c1) return;
     const int p = ra.p, pp = ra.pp, q = ra.q;
     const double cnt = (double)mom[(r - c0) * (int64_t)(q * q) + p + p * q];  // finite rows in the window
-    bool v_ok = r >= ra.window - 1;
+    // (grouped: rows counted from the start of the row's group)
+    const int64_t r_in = grp.off ? r - grp.off[grp_find(grp.off, 0, grp.ng - 1, r)] : r;
+    bool v_ok = r_in >= ra.window - 1;
     if (ra.min_size > 0) v_ok = v_ok && (cnt >= (double)ra.min_size);
     const bool ok = v_ok && !flags[r - c0];
     T* b = coeffs + r * (int64_t)pp;
@@ -270,7 +322,7 @@ size_t rolling_wide_workspace(int n_feat, int64_t n_rows, size_t elem) {
 // KMAX > 0: the one-wavefront kernel (q <= 66); QB > 0: the 1024-thread kernel
 template <typename T, int KMAX, int QB>
 static int launch_wide_k(pds_ctx* ctx, const DeviceCols<T>& dc, RollWideArgs ra, double lambda, bool expanding,
-                         const double* seed_moments, T* d_coeffs, T* d_pred, uint8_t* d_valid) {
+                         const double* seed_moments, T* d_coeffs, T* d_pred, uint8_t* d_valid, RollGroups grp) {
     const int q = ra.q, qq = q * q;
     const int64_t chunk = wide_chunk_rows(q, ra.n, sizeof(T));
     const int64_t nseg = (ra.n + kSegRows - 1) / kSegRows;
@@ -281,17 +333,27 @@ static int launch_wide_k(pds_ctx* ctx, const DeviceCols<T>& dc, RollWideArgs ra,
     const size_t lds = BIG ? (size_t)2 * q * kBigZStride * sizeof(double) + 256 : (size_t)2 * q * kZStride * sizeof(double);
     const void* kptr;
     if constexpr (BIG) kptr = reinterpret_cast<const void*>(&rolling_big_kernel<T, QB>);
+    else if (grp.off) kptr = reinterpret_cast<const void*>(&rolling_wide_kernel<T, KMAX, 1>);
     else kptr = reinterpret_cast<const void*>(&rolling_wide_kernel<T, KMAX>);
     if (lds > 64 * 1024) PDS_HIP_CHECK(hipFuncSetAttribute(kptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     auto run = [&](unsigned nblocks, int64_t c0, int64_t c1, double* tot, T* mom) {
         if constexpr (BIG)
             hipLaunchKernelGGL((rolling_big_kernel<T, QB>), dim3(nblocks), dim3(1024), lds, ctx->stream, dc.d_ptrs, ra, c0, c1, tot, mom);
+        else if (grp.off)
+            hipLaunchKernelGGL((rolling_wide_kernel<T, KMAX, 1>), dim3(nblocks), dim3(64), lds, ctx->stream, dc.d_ptrs, ra, c0, c1, tot, mom,
+                               grp);
         else
-            hipLaunchKernelGGL((rolling_wide_kernel<T, KMAX>), dim3(nblocks), dim3(64), lds, ctx->stream, dc.d_ptrs, ra, c0, c1, tot, mom);
+            hipLaunchKernelGGL((rolling_wide_kernel<T, KMAX>), dim3(nblocks), dim3(64), lds, ctx->stream, dc.d_ptrs, ra, c0, c1, tot, mom,
+                               grp);
     };
     double* d_tot = nullptr;
     if (expanding) {
         d_tot = reinterpret_cast<double*>(ws_take(ctx, (size_t)nseg * qq * sizeof(double)));
+        if (!d_tot) return fail(PDS_ERR_HIP, "workspace allocation failed");
+        if (grp.off) {
+            grp.tile_flag = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)nseg));
+            if (!grp.tile_flag) return fail(PDS_ERR_HIP, "workspace allocation failed");
+        }
         double* d_seed = nullptr;
         if (seed_moments) {  // rows in front of this frame (row-sharded expanding fit): already in the record layout
             d_seed = reinterpret_cast<double*>(ws_take(ctx, (size_t)qq * sizeof(double)));
@@ -301,7 +363,11 @@ static int launch_wide_k(pds_ctx* ctx, const DeviceCols<T>& dc, RollWideArgs ra,
         KernelTimer timer(ctx, kKindRolling);
         ra.mode = 1;
         run((unsigned)nseg, (int64_t)0, ra.n, d_tot, (T*)nullptr);
-        hipLaunchKernelGGL(seg_prefix_kernel, dim3((qq + 255) / 256), dim3(256), 0, ctx->stream, d_tot, nseg, qq, d_seed);
+        if (grp.off)
+            hipLaunchKernelGGL(seg_prefix_grouped_kernel, dim3((qq + 255) / 256), dim3(256), 0, ctx->stream, d_tot, (const uint8_t*)grp.tile_flag,
+                               nseg, qq);
+        else
+            hipLaunchKernelGGL(seg_prefix_kernel, dim3((qq + 255) / 256), dim3(256), 0, ctx->stream, d_tot, nseg, qq, d_seed);
         PDS_HIP_CHECK(hipGetLastError());
     }
     ra.mode = expanding ? 2 : 0;
@@ -316,7 +382,7 @@ static int launch_wide_k(pds_ctx* ctx, const DeviceCols<T>& dc, RollWideArgs ra,
         if (int rc = launch_solve<T>(ctx, d_mom, c1 - c0, sp, d_coeffs + c0 * ra.pp, d_flags, nullptr, nullptr)) return rc;
         KernelTimer timer(ctx, kKindRolling);
         hipLaunchKernelGGL((rolling_wide_finish_kernel<T>), dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, ctx->stream,
-                           dc.d_ptrs, ra, c0, c1, d_mom, d_flags, d_coeffs, d_pred, d_valid);
+                           dc.d_ptrs, ra, c0, c1, d_mom, d_flags, d_coeffs, d_pred, d_valid, grp);
         PDS_HIP_CHECK(hipGetLastError());
     }
     return PDS_OK;
@@ -325,7 +391,8 @@ static int launch_wide_k(pds_ctx* ctx, const DeviceCols<T>& dc, RollWideArgs ra,
 template <typename T>
 int launch_rolling_wide(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int add_bias, int64_t window,
                         int64_t min_size, double lambda, bool expanding, const double* seed_moments, T* d_coeffs, T* d_pred,
-                        uint8_t* d_valid) {
+                        uint8_t* d_valid, const int64_t* d_off, int64_t ng) {
+    const RollGroups grp{d_off, ng, nullptr};
     RollWideArgs ra;
     ra.p = n_feat;
     ra.bias = add_bias ? 1 : 0;
@@ -339,23 +406,24 @@ int launch_rolling_wide(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64
     const int qq = ra.q * ra.q;
     if (n_feat > 254)
         return fail(PDS_ERR_UNSUPPORTED, "rolling / recursive: at most 254 feature columns in this build");
-    if (qq <= 64 * 6) return launch_wide_k<T, 6, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-    if (qq <= 64 * 19) return launch_wide_k<T, 19, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-    if (ra.q <= 66) return launch_wide_k<T, 69, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
+    if (d_off && ra.q > 66) return fail(PDS_ERR_UNSUPPORTED, "grouped rolling / recursive: at most 64 coefficients");
+    if (qq <= 64 * 6) return launch_wide_k<T, 6, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+    if (qq <= 64 * 19) return launch_wide_k<T, 19, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+    if (ra.q <= 66) return launch_wide_k<T, 69, 0>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
     const int qb = (ra.q + 31) / 32;  // 3 .. 8
     switch (qb) {
-        case 3: return launch_wide_k<T, 0, 3>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-        case 4: return launch_wide_k<T, 0, 4>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-        case 5: return launch_wide_k<T, 0, 5>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-        case 6: return launch_wide_k<T, 0, 6>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-        case 7: return launch_wide_k<T, 0, 7>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
-        default: return launch_wide_k<T, 0, 8>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid);
+        case 3: return launch_wide_k<T, 0, 3>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+        case 4: return launch_wide_k<T, 0, 4>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+        case 5: return launch_wide_k<T, 0, 5>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+        case 6: return launch_wide_k<T, 0, 6>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+        case 7: return launch_wide_k<T, 0, 7>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
+        default: return launch_wide_k<T, 0, 8>(ctx, dc, ra, lam, expanding, seed_moments, d_coeffs, d_pred, d_valid, grp);
     }
 }
 
 template int launch_rolling_wide<double>(pds_ctx*, const DeviceCols<double>&, int, int64_t, int, int64_t, int64_t, double, bool,
-                                         const double*, double*, double*, uint8_t*);
+                                         const double*, double*, double*, uint8_t*, const int64_t*, int64_t);
 template int launch_rolling_wide<float>(pds_ctx*, const DeviceCols<float>&, int, int64_t, int, int64_t, int64_t, double, bool,
-                                        const double*, float*, float*, uint8_t*);
+                                        const double*, float*, float*, uint8_t*, const int64_t*, int64_t);
 
 }  // namespace pds

@@ -20,7 +20,8 @@ import numpy as np
 from . import _lib, config
 
 __all__ = [
-    "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg",
+    "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
+    "recursive_lin_reg_by_key",
     "recursive_lin_reg", "lin_reg_w_rcond", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
@@ -1150,15 +1151,21 @@ def lin_reg_by_key_pred_multi(*x, target, key, contexts, n_slices: int = 0, add_
     return pred, resid, rnull
 
 
-def _windowed(name, x, target, n, add_bias, l2_reg, min_size, ctx, seed_moments=None):
-    ctx = ctx or default_context()
-    cols = _Cols(target, x)
-    _follow(ctx, cols)
+def _windowed_outs(cols, add_bias, l2_reg):
+    """coeffs [N, p'], pred [N], valid [N] in the inputs' space (+ their pointers) and the `lambda` argument of the windowed fits."""
     pp = cols.n_feat + int(bool(add_bias))
     coeffs, co_p = _out_like(cols, (cols.n_rows, pp))
     pred, pr_p = _out_like(cols, cols.n_rows)
     valid, va_p = _out_u8(cols, cols.n_rows)
     lam = C.c_double(abs(l2_reg)) if config.LIN_REG_EXPR_F64 else C.c_float(abs(l2_reg))  # `lambda`: abs(l2_reg) :546-552
+    return (coeffs, pred, valid), (co_p, pr_p, va_p), lam
+
+
+def _windowed(name, x, target, n, add_bias, l2_reg, min_size, ctx, seed_moments=None):
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    (coeffs, pred, valid), (co_p, pr_p, va_p), lam = _windowed_outs(cols, add_bias, l2_reg)
     if name == "pds_rolling_lr":
         _lib.check(ctx.fn(name)(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(bool(add_bias)),
                                 C.c_int64(n), C.c_int64(min_size), lam, co_p, pr_p, va_p))
@@ -1184,16 +1191,7 @@ def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg
     window_size-1 rows are invalid (null in the reference).  skip_non_finite=True selects the
     null_policy="skip" window algorithm (faer_rolling_skipping_lr) with min_valid_rows.
     """
-    n_features = len(x) + int(bool(add_bias))
-    if window_size < 2:
-        raise ValueError("`window_size` must be >= 2.")  # expr_linear.py:524-526
-    if n_features > window_size:
-        raise ValueError("# features > window size. Linear regression is not well-defined.")  # :527-531
-    min_size = 0
-    if skip_non_finite:
-        min_size = min(n_features, window_size) if min_valid_rows is None else int(min_valid_rows)  # :535-543
-        if min_size < n_features or min_size > window_size:
-            raise ValueError("`min_valid_rows` must be in [#features, window_size].")
+    min_size = _check_rolling(len(x) + int(bool(add_bias)), window_size, min_valid_rows, skip_non_finite)
     return _windowed("pds_rolling_lr", x, target, window_size, add_bias, l2_reg, min_size, ctx)
 
 
@@ -1204,10 +1202,81 @@ def recursive_lin_reg(*x, target, start_with: int, add_bias: bool = False, l2_re
     seed_moments (the gram_moments matrix of rows that precede this frame) continues an earlier frame: the
     row-sharded multi-GPU form, see parallel.recursive_lin_reg_row_sharded.
     """
-    n_features = len(x) + int(bool(add_bias))
+    _check_recursive(len(x) + int(bool(add_bias)), start_with)
+    return _windowed("pds_recursive_lr", x, target, start_with, add_bias, l2_reg, 0, ctx, seed_moments=seed_moments)
+
+
+def _check_rolling(n_features, window_size, min_valid_rows, skip_non_finite):
+    if window_size < 2:
+        raise ValueError("`window_size` must be >= 2.")  # expr_linear.py:524-526
+    if n_features > window_size:
+        raise ValueError("# features > window size. Linear regression is not well-defined.")  # :527-531
+    min_size = 0
+    if skip_non_finite:
+        min_size = min(n_features, window_size) if min_valid_rows is None else int(min_valid_rows)  # :535-543
+        if min_size < n_features or min_size > window_size:
+            raise ValueError("`min_valid_rows` must be in [#features, window_size].")
+    return min_size
+
+
+def _check_recursive(n_features, start_with):
     if start_with < n_features:
         raise ValueError("# features > number of rows for the initial fit.")  # expr_linear.py:455-459
-    return _windowed("pds_recursive_lr", x, target, start_with, add_bias, l2_reg, 0, ctx, seed_moments=seed_moments)
+
+
+def _windowed_grouped(kind, form, x, target, groups, n, add_bias, l2_reg, min_size, ctx):
+    """pds_{rolling,recursive}_lr_{grouped,by_key}_*: per-row outputs in frame order (coeffs [N, p'], pred [N], valid [N])."""
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    (coeffs, pred, valid), (co_p, pr_p, va_p), lam = _windowed_outs(cols, add_bias, l2_reg)
+    g, g_p = _offsets_arg(cols, groups)  # (int64, in the inputs' space: offsets or keys)
+    if form == "grouped":
+        if g.ndim != 1 or g.shape[0] < 2:
+            raise ValueError("group_offsets must hold n_groups + 1 >= 2 offsets")
+        lead = (ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), g_p, C.c_int64(int(g.shape[0]) - 1), cols.space)
+    else:
+        if g.ndim != 1 or int(g.shape[0]) != cols.n_rows:
+            raise ValueError("key must hold one value per row")
+        lead = (ctx._h, cols.cols, g_p, cols.n_feat, C.c_int64(cols.n_rows), cols.space)
+    wargs = (C.c_int64(n), C.c_int64(min_size)) if kind == "rolling" else (C.c_int64(n),)
+    _lib.check(ctx.fn(f"pds_{kind}_lr_{form}")(*lead, int(bool(add_bias)), *wargs, lam, co_p, pr_p, va_p))
+    return coeffs, pred, valid
+
+
+def rolling_lin_reg_by(*x, target, group_offsets, window_size: int, add_bias: bool = False, l2_reg: float = 0.0,
+                       min_valid_rows: int | None = None, skip_non_finite: bool = False, ctx: Context | None = None):
+    """
+    rolling_lin_reg on every group of contiguous rows (group g = rows [group_offsets[g], group_offsets[g+1])) in one call:
+    what `pds.rolling_lin_reg(...).over(group)` gives.  Row r of group g is fitted on rows [max(s_g, r - w + 1), r] and is
+    valid iff r - s_g >= w - 1.  Returns (coeffs [N, p'], pred [N], valid [N]) in frame order, on the inputs' device.
+    """
+    min_size = _check_rolling(len(x) + int(bool(add_bias)), window_size, min_valid_rows, skip_non_finite)
+    return _windowed_grouped("rolling", "grouped", x, target, group_offsets, window_size, add_bias, l2_reg, min_size, ctx)
+
+
+def rolling_lin_reg_by_key(*x, target, key, window_size: int, add_bias: bool = False, l2_reg: float = 0.0,
+                           min_valid_rows: int | None = None, skip_non_finite: bool = False, ctx: Context | None = None):
+    """rolling_lin_reg_by with int64 keys in any row order (rows of equal key form a group, in frame order)."""
+    min_size = _check_rolling(len(x) + int(bool(add_bias)), window_size, min_valid_rows, skip_non_finite)
+    return _windowed_grouped("rolling", "by_key", x, target, key, window_size, add_bias, l2_reg, min_size, ctx)
+
+
+def recursive_lin_reg_by(*x, target, group_offsets, start_with: int, add_bias: bool = False, l2_reg: float = 0.0,
+                         ctx: Context | None = None):
+    """
+    recursive_lin_reg on every group of contiguous rows in one call (`pds.recursive_lin_reg(...).over(group)`): row r of
+    group g is fitted on rows [s_g, r] and is valid iff r - s_g >= start_with - 1.
+    """
+    _check_recursive(len(x) + int(bool(add_bias)), start_with)
+    return _windowed_grouped("recursive", "grouped", x, target, group_offsets, start_with, add_bias, l2_reg, 0, ctx)
+
+
+def recursive_lin_reg_by_key(*x, target, key, start_with: int, add_bias: bool = False, l2_reg: float = 0.0,
+                             ctx: Context | None = None):
+    """recursive_lin_reg_by with int64 keys in any row order."""
+    _check_recursive(len(x) + int(bool(add_bias)), start_with)
+    return _windowed_grouped("recursive", "by_key", x, target, key, start_with, add_bias, l2_reg, 0, ctx)
 
 
 def gram_moments(*x, target, weights=None, ctx: Context | None = None, out_device: bool = False):

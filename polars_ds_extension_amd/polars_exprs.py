@@ -175,7 +175,12 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
 
 
 def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg: float = 0.0, min_valid_rows: int | None = None,
-                    null_policy: str = "raise"):
+                    null_policy: str = "raise", by=None):
+    """
+    expr_linear.py:482-558.  `by` (an integer key column, any row order, nulls = one group): what `.over(by)` gives -- the same
+    Struct{coeffs, pred} per row, in frame order -- from ONE `pl_rolling_lr_by` call instead of one `pl_rolling_lr` call per group.
+    Keys of other dtypes or several key columns: `rolling_lin_reg_over`.
+    """
     n_features = len(x) + int(add_bias)
     if window_size < 2:
         raise ValueError("`window_size` must be >= 2.")
@@ -184,16 +189,54 @@ def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg
     min_size = min(n_features, window_size) if min_valid_rows is None else int(min_valid_rows)
     kwargs = {"null_policy": null_policy, "n": window_size, "bias": add_bias, "lambda": abs(l2_reg), "min_size": min_size}
     cols = [_formula(target).cast(_dtype())] + [_formula(z) for z in x]
+    if by is not None:
+        return _plugin("pl_rolling_lr_by", [_formula(by), *cols], kwargs).alias("rolling_lin_reg")
     return _plugin("pl_rolling_lr", cols, kwargs).alias("rolling_lin_reg")
 
 
-def recursive_lin_reg(*x, target, start_with: int, add_bias: bool = False, l2_reg: float = 0.0, null_policy: str = "raise"):
+def recursive_lin_reg(*x, target, start_with: int, add_bias: bool = False, l2_reg: float = 0.0, null_policy: str = "raise", by=None):
+    """expr_linear.py:413-479; `by` as in rolling_lin_reg (one `pl_recursive_lr_by` call; other key dtypes: recursive_lin_reg_over)."""
     n_features = len(x) + int(add_bias)
     if start_with < n_features:
         raise ValueError("# features > number of rows for the initial fit.")
     kwargs = {"null_policy": null_policy, "n": start_with, "bias": add_bias, "lambda": abs(l2_reg), "min_size": 0}
     cols = [_formula(target).cast(_dtype())] + [_formula(z) for z in x]
+    if by is not None:
+        return _plugin("pl_recursive_lr_by", [_formula(by), *cols], kwargs).alias("recursive_lin_reg")
     return _plugin("pl_recursive_lr", cols, kwargs).alias("recursive_lin_reg")
+
+
+def _dense_ids(df, by):
+    """
+    One dense Int64 id per row for keys of any dtype or several columns (null keys: one group, as in Polars), IN THE FRAME'S ROW
+    ORDER: the ids are built on the host from the key rows themselves, without a join, so no engine's join order can move a row.
+    """
+    cols = [by] if isinstance(by, str) else list(by)
+    import numpy as np
+
+    seen: dict = {}
+    rows = zip(*[df[c].to_list() for c in cols])
+    return _pl().Series(_GID, np.fromiter((seen.setdefault(k, len(seen)) for k in rows), dtype=np.int64, count=len(df)))
+
+
+def _windowed_over(fn, df, by, x, target, kwargs):
+    if _is_integer_key(df, by):
+        return df.with_columns(fn(*x, target=target, by=by, **kwargs))
+    ids = _dense_ids(df, by)
+    return df.with_columns(fn(*x, target=target, by=ids, **kwargs))
+
+
+def rolling_lin_reg_over(df, by, *x, target, **kwargs):
+    """
+    `df.with_columns(pds.rolling_lin_reg(*x, target=...).over(by))` in one plugin call, for a key of any dtype or several key
+    columns (null keys form one group): the frame with a `rolling_lin_reg` Struct{coeffs, pred} column, row for row.
+    """
+    return _windowed_over(rolling_lin_reg, df, by, x, target, kwargs)
+
+
+def recursive_lin_reg_over(df, by, *x, target, **kwargs):
+    """`df.with_columns(pds.recursive_lin_reg(*x, target=...).over(by))` in one plugin call (see rolling_lin_reg_over)."""
+    return _windowed_over(recursive_lin_reg, df, by, x, target, kwargs)
 
 
 def query_ar_coeffs(x, lag: int, add_bias: bool = True, null_policy: str = "raise"):
