@@ -82,7 +82,7 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             partition route appends records through cursor atomics, so its sums repeat to rounding only;
  *   "wide_f32_native" (PDS_WIDE_F32_NATIVE=1) f32 Gram builds beyond 64 features on the f32 matrix instructions (v_mfma_f32_32x32x2_f32,
  *                                             2.5e-7 from the f64 Gram) instead of three exact bf16 planes on the bf16 matrix cores (2e-6).
- *   "report_chunk_groups"                     pds_lin_reg_report_grouped_* / _by_key_*: groups per pass (<= 0: the default).
+ *   "report_chunk_groups"                     pds_lin_reg_report_grouped_* / _by_key_*, pds_wls_report_*: groups per pass (<= 0: the default).
  * value: 0 / 1 (report_chunk_groups: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host-frame staging (process wide): chunk_mb = bytes of one row chunk of a PDS_HOST frame (default 256, env
@@ -671,6 +671,32 @@ int pds_lin_reg_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const
 int pds_lin_reg_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
                                   pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
                                   pds_report_grouped_f32* out, int64_t* n_groups);
+/*
+ * pds_wls_report_grouped_* / pds_wls_report_by_key_*: the weighted form of the grouped report -- for every group g what
+ * pds_lin_reg_report_* returns on g's rows with `weights` given (pl_wls_report, linear_regression.rs:982-1117): beta =
+ * (X'WX)^-1 X'Wy through the column-pivoted QR inverse, mse = sum w e^2 / dof with dof = n_g - p', std_err_i = sqrt(mse inv_ii),
+ * t / p / CI as in the unweighted grouped report, r2 = 1 - sum e^2 / (var(y) n_g) with the UNWEIGHTED sum e^2 and the unweighted
+ * sample variance of the group's target (ddof = 1).  Plain standard error only (pl_wls_report knows no HC estimator).
+ * weights: n_rows values, `space`-resident; NULL gives PDS_ERR_INVALID.  Weights enter X'WX as they are, whatever their sign (they
+ * are never square-rooted and no scaled copy of the frame is made).  Zero weights are legal: such rows still count in n_g, in dof
+ * and in the unweighted sum e^2.  Output struct, null rule (n_g < p': is_null = 1, NaN outputs), dof-0 and singular groups, the
+ * isolation of groups, y_var (nullable, offsets form only), the 1..64 feature range, both memory spaces and the
+ * "report_chunk_groups" option are those of pds_lin_reg_report_grouped_* / _by_key_* above.  By key, unordered keys take the
+ * weights through the sort and the gather as one more column (fewer than 2^31 rows); ordered keys move nothing.  Repeated calls
+ * give the same bits.
+ */
+int pds_wls_report_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, const double* y_var,
+                               pds_report_grouped_f64* out);
+int pds_wls_report_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, const float* y_var,
+                               pds_report_grouped_f32* out);
+int pds_wls_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const int64_t* keys, int n_feat,
+                              int64_t n_rows, pds_space space, int add_bias, int64_t max_groups, int64_t* out_keys,
+                              pds_report_grouped_f64* out, int64_t* n_groups);
+int pds_wls_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const int64_t* keys, int n_feat,
+                              int64_t n_rows, pds_space space, int add_bias, int64_t max_groups, int64_t* out_keys,
+                              pds_report_grouped_f32* out, int64_t* n_groups);
 /* TEST HOOK, not part of the supported interface: the grouped report's device Student-t survival function on host arrays
  * x[n], df[n] -> out[n], so that tests can hold it against pds_student_t_sf.  May change or go away without notice. */
 int pds_student_t_sf_device(pds_ctx* ctx, const double* x, const double* df, int64_t n, double* out);

@@ -24,6 +24,7 @@ EXPORTS = [
     "pds_lr_f64", "pds_lr_f32", "pds_lr_pred_f64", "pds_lr_pred_f32", "pds_lr_rcond_f64", "pds_lr_rcond_f32", "pds_elastic_net_f64", "pds_elastic_net_f32", "pds_lr_nullable_f64", "pds_lr_nullable_f32", "pds_lr_multi_f64", "pds_lr_multi_f32",
     "pds_lin_reg_report_f64", "pds_lin_reg_report_f32",
     "pds_lin_reg_report_grouped_f64", "pds_lin_reg_report_grouped_f32", "pds_lin_reg_report_by_key_f64", "pds_lin_reg_report_by_key_f32",
+    "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
     "pds_report_finish_f64", "pds_report_finish_f32",

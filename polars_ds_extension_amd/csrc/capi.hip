@@ -540,26 +540,54 @@ int pds_lr_by_key_pred_f32(pds_ctx* ctx, const float* const* cols, const float* 
 int pds_lin_reg_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
                                    int64_t n_groups, pds_space space, int add_bias, int se_type, const double* y_var,
                                    pds_report_grouped_f64* out) {
-    return pds::report_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
+    return pds::report_grouped_impl<double>(ctx, cols, (const double*)nullptr, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
                                             reinterpret_cast<const pds::ReportGroupedOut<double>*>(out));
 }
 int pds_lin_reg_report_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
                                    int64_t n_groups, pds_space space, int add_bias, int se_type, const float* y_var,
                                    pds_report_grouped_f32* out) {
-    return pds::report_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
+    return pds::report_grouped_impl<float>(ctx, cols, (const float*)nullptr, n_feat, n_rows, group_offsets, n_groups, space, add_bias, se_type, y_var,
                                            reinterpret_cast<const pds::ReportGroupedOut<float>*>(out));
 }
 int pds_lin_reg_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
                                   pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
                                   pds_report_grouped_f64* out, int64_t* n_groups) {
-    return pds::report_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
+    return pds::report_by_key_impl<double>(ctx, cols, (const double*)nullptr, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
                                            reinterpret_cast<const pds::ReportGroupedOut<double>*>(out), n_groups);
 }
 int pds_lin_reg_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
                                   pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
                                   pds_report_grouped_f32* out, int64_t* n_groups) {
-    return pds::report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
+    return pds::report_by_key_impl<float>(ctx, cols, (const float*)nullptr, keys, n_feat, n_rows, space, add_bias, se_type, max_groups, out_keys,
                                           reinterpret_cast<const pds::ReportGroupedOut<float>*>(out), n_groups);
+}
+int pds_wls_report_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, const double* y_var,
+                               pds_report_grouped_f64* out) {
+    if (!weights) return pds::fail(PDS_ERR_INVALID, "null argument");
+    return pds::report_grouped_impl<double>(ctx, cols, weights, n_feat, n_rows, group_offsets, n_groups, space, add_bias, PDS_SE, y_var,
+                                            reinterpret_cast<const pds::ReportGroupedOut<double>*>(out));
+}
+int pds_wls_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const int64_t* keys, int n_feat,
+                              int64_t n_rows, pds_space space, int add_bias, int64_t max_groups, int64_t* out_keys,
+                              pds_report_grouped_f64* out, int64_t* n_groups) {
+    if (!weights) return pds::fail(PDS_ERR_INVALID, "null argument");
+    return pds::report_by_key_impl<double>(ctx, cols, weights, keys, n_feat, n_rows, space, add_bias, PDS_SE, max_groups, out_keys,
+                                           reinterpret_cast<const pds::ReportGroupedOut<double>*>(out), n_groups);
+}
+int pds_wls_report_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, const float* y_var,
+                               pds_report_grouped_f32* out) {
+    if (!weights) return pds::fail(PDS_ERR_INVALID, "null argument");
+    return pds::report_grouped_impl<float>(ctx, cols, weights, n_feat, n_rows, group_offsets, n_groups, space, add_bias, PDS_SE, y_var,
+                                            reinterpret_cast<const pds::ReportGroupedOut<float>*>(out));
+}
+int pds_wls_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const int64_t* keys, int n_feat,
+                              int64_t n_rows, pds_space space, int add_bias, int64_t max_groups, int64_t* out_keys,
+                              pds_report_grouped_f32* out, int64_t* n_groups) {
+    if (!weights) return pds::fail(PDS_ERR_INVALID, "null argument");
+    return pds::report_by_key_impl<float>(ctx, cols, weights, keys, n_feat, n_rows, space, add_bias, PDS_SE, max_groups, out_keys,
+                                           reinterpret_cast<const pds::ReportGroupedOut<float>*>(out), n_groups);
 }
 int pds_student_t_sf_device(pds_ctx* ctx, const double* x, const double* df, int64_t n, double* out) {
     return pds::student_t_sf_device_impl(ctx, x, df, n, out);

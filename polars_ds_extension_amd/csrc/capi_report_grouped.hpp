@@ -6,6 +6,11 @@
 // report_impl's factorisation) -> the residual / leverage / meat stream (grouped_report_pass.hip) -> the epilogue on the device.
 // Chunking bounds the records, inverses and meats (at 1e6 groups x 17^2 each would be 2.3 - 2.6 GB); context option
 // "report_chunk_groups" overrides the chunk size.
+//
+// With a weight column (pds_wls_report_grouped_* / _by_key_*) the same pipeline is pl_wls_report per group (linear_regression.rs:
+// 982-1117): the records are Z'WZ (the WEIGHTED Gram kernels: the weights are read as one more column, never a scaled copy of the
+// frame), the pass adds sum w e^2 to every item's sums slot and the epilogue's mse reads it.  r2 keeps the unweighted sum e^2 and
+// the unweighted var(y), as the reference does.  Plain standard error only.
 #pragma once
 
 double student_t_lng_term(double df);  // stats.cpp
@@ -68,10 +73,12 @@ static size_t report_dof_table_bytes(int64_t n_groups) {
     return (size_t)2 * 8 * (1 << 16) + (size_t)3 * 8 * (size_t)n_groups + 3 * 512;
 }
 
-// cols [y, x1..xp]; offsets n_groups + 1 (absolute rows, non-decreasing); d_yvar (nullable) n_groups values; all in `space`
+// cols [y, x1..xp]; weights (nullable: the unweighted report) n_rows values; offsets n_groups + 1 (absolute rows, non-decreasing);
+// d_yvar (nullable) n_groups values; all in `space`
 template <typename T>
-static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups,
-                               pds_space space, int add_bias, int se_type, const T* y_var, const ReportGroupedOut<T>* out) {
+static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weights, int n_feat, int64_t n_rows, const int64_t* offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int se_type, const T* y_var,
+                               const ReportGroupedOut<T>* out) {
     if (!ctx || !cols || !offsets || !out) return fail(PDS_ERR_INVALID, "null argument");
     if (!out->beta || !out->std_err || !out->t || !out->p || !out->ci_lower || !out->ci_upper || !out->r2 || !out->adj_r2 || !out->is_null)
         return fail(PDS_ERR_INVALID, "null output pointer");
@@ -79,6 +86,8 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
     if (n_feat > kMaxFeatWide) return fail(PDS_ERR_UNSUPPORTED, "grouped lin_reg_report: at most 64 features");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (se_type < PDS_SE || se_type > PDS_HC3) return fail(PDS_ERR_INVALID, "unknown standard-error type");
+    const bool weighted = weights != nullptr;
+    if (weighted) se_type = PDS_SE;  // pl_wls_report only knows "std_err"
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int p = n_feat, bias = add_bias ? 1 : 0, pp = p + bias, q = p + 2;
     const int hc = (se_type == PDS_SE) ? 0 : (se_type == PDS_HC2 ? 2 : (se_type == PDS_HC3 ? 3 : 1));
@@ -130,7 +139,7 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
     }
     if (int rc = ws_reserve(ctx, need)) return rc;
     DeviceCols<T> dc;
-    if (int rc = make_device_cols<T>(ctx, cols, (const T*)nullptr, p, n_rows, space, dc)) return rc;
+    if (int rc = make_device_cols<T>(ctx, cols, weights, p, n_rows, space, dc)) return rc;
     if (!dc.d_ptrs) return fail(PDS_ERR_HIP, "workspace allocation failed");
     bool ws_ok = true;
     auto take = [&](size_t b) { void* r = ws_take(ctx, b); if (!r) ws_ok = false; return r; };
@@ -204,19 +213,19 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
         const int64_t n_fin = chunk_pieces[ci] > 0 ? (int64_t)fin.size() / 3 : 0;
         if (n_pieces > 0) {  // groups longer than a piece: their rows' records on many waves, summed back in piece order
             const int64_t nv = (int64_t)vofs.size() - 1;
-            if (int rc = launch_grouped_moments<T>(ctx, dc, p, d_vofs, nv, d_vmom)) return rc;
+            if (int rc = launch_grouped_moments<T>(ctx, dc, p, d_vofs, nv, d_vmom, nullptr, weighted)) return rc;
             if (int rc = launch_grouped_report_sum_records<T>(ctx, d_vmom, d_vfirst, gc, q * q, d_mom)) return rc;
-        } else if (int rc = launch_grouped_moments<T>(ctx, dc, p, d_o, gc, d_mom)) {
+        } else if (int rc = launch_grouped_moments<T>(ctx, dc, p, d_o, gc, d_mom, nullptr, weighted)) {
             return rc;
         }
         if (int rc = launch_solve<T>(ctx, d_mom, gc, sp, beta, d_flag, d_inv, nullptr)) return rc;
         if (int rc = launch_grouped_report_pass<T>(ctx, dc.d_ptrs, p, bias, d_o, gc, beta, d_inv, hc, d_sums, d_meat, d_pieces, n_pieces,
-                                                   piece_rows, d_fin, n_fin))
+                                                   piece_rows, d_fin, n_fin, weighted))
             return rc;
         if (int rc = launch_grouped_report_epilogue<T>(ctx, d_o, gc, p, bias, se_type, d_yv ? d_yv + g0 : nullptr, beta, d_inv, d_sums,
                                                        d_meat, tab, d.std_err + g0 * pp, d.t + g0 * pp, d.p + g0 * pp,
                                                        d.ci_lower + g0 * pp, d.ci_upper + g0 * pp, d.r2 + g0, d.adj_r2 + g0,
-                                                       d.is_null + g0))
+                                                       d.is_null + g0, weighted))
             return rc;
     }
     if (space == PDS_HOST) {
@@ -238,9 +247,9 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
 // int64 keys in any row order: ordered keys take the order check's run marks (nothing moves); otherwise the stable radix sort of
 // (key, row) and the frame gather of the sorting route (capi_grouped.hpp, lr_by_key_impl).  Groups come back in ascending key order.
 template <typename T>
-static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
-                              int add_bias, int se_type, int64_t max_groups, int64_t* out_keys, const ReportGroupedOut<T>* out,
-                              int64_t* n_groups) {
+static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* weights, const int64_t* keys, int n_feat, int64_t n_rows,
+                              pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
+                              const ReportGroupedOut<T>* out, int64_t* n_groups) {
     if (!ctx || !cols || !keys || !out || !out_keys || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_feat > kMaxFeatWide) return fail(PDS_ERR_UNSUPPORTED, "grouped lin_reg_report: at most 64 features");
@@ -248,7 +257,8 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t*
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (se_type < PDS_SE || se_type > PDS_HC3) return fail(PDS_ERR_INVALID, "unknown standard-error type");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
+    // (a weight column rides through the staging, the sort and the gather as one more column of the frame: src[nc - 1])
+    const int nc = n_feat + 1 + (weights ? 1 : 0), pp = n_feat + (add_bias ? 1 : 0);
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
     const int64_t* d_keys = keys;
@@ -285,8 +295,9 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t*
     int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
     int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
     int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
-    std::vector<const T*> src(nc);  // [y, x1..xp], device resident
-    for (int c = 0; c < nc; ++c) src[c] = cols[c];
+    std::vector<const T*> src(nc);  // [y, x1..xp (, w)], device resident
+    for (int c = 0; c < n_feat + 1; ++c) src[c] = cols[c];
+    if (weights) src[n_feat + 1] = weights;
     if (space == PDS_HOST)
         for (int c = 0; c < nc; ++c) {
             T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
@@ -341,7 +352,8 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t*
         d.adj_r2 = reinterpret_cast<T*>(take((size_t)cap * sizeof(T)));
         d.is_null = reinterpret_cast<uint8_t*>(take((size_t)cap));
     }
-    if (int rc = report_grouped_impl<T>(ctx, src.data(), n_feat, n_rows, d_offsets, ng, PDS_DEVICE, add_bias, se_type, (const T*)nullptr, &d))
+    if (int rc = report_grouped_impl<T>(ctx, src.data(), weights ? src[n_feat + 1] : (const T*)nullptr, n_feat, n_rows, d_offsets, ng,
+                                        PDS_DEVICE, add_bias, se_type, (const T*)nullptr, &d))
         return rc;
     if (space == PDS_HOST) {
         const size_t cb = (size_t)ng * pp * sizeof(T);

@@ -215,7 +215,7 @@ int launch_moments_mid(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_
 // d_group_index[g] of the offsets array instead of group g.
 template <typename T>
 int launch_grouped_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, const int64_t* d_offsets,
-                           int64_t n_groups, T* d_moments, const int32_t* d_group_index = nullptr);
+                           int64_t n_groups, T* d_moments, const int32_t* d_group_index = nullptr, bool weighted = false);
 
 struct SolveParams;
 // grouped_fused.hip: per-group Gram + gated Cholesky in one streaming kernel (p <= 16, OLS / ridge); unless the caller asked

@@ -19,6 +19,8 @@ struct ReportDofTable {
 //   d_sums[4 g + 0..2] = sum e^2, sum (y - y_first), sum (y - y_first)^2
 //   hc > 0: d_meat[g] = X' diag(s) X as p' x p' column-major f64 (bias last), s = e^2 (hc 1), e^2 / (1 - h) (2), e^2 / (1 - h)^2 (3)
 // Groups with fewer than p' rows are skipped (the epilogue nulls them).  d_cols: x_0 .. x_{p-1}, y.  1 .. 64 features.
+// weighted (hc == 0 only): d_cols[p + 1] is the weight column and d_sums[4 g + 3] = sum w e^2 (0.0 otherwise), which the weighted
+// epilogue's mse reads; sum e^2 and the y sums stay unweighted.
 // Groups of more than piece_rows rows are split so that their rows stream on many waves: the first piece_rows rows stay the group's
 // own item, the rest are the n_pieces extra items d_pieces[3 k ..] = (group, first row, end row) with their own sums / meat slots
 // (d_sums / d_meat hold n_groups + n_pieces slots), folded back per group in piece order by d_fin[3 j ..] = (group, first extra
@@ -26,14 +28,15 @@ struct ReportDofTable {
 template <typename T>
 int launch_grouped_report_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int64_t n_groups,
                                const T* d_beta, const T* d_inv, int hc, double* d_sums, double* d_meat, const int64_t* d_pieces,
-                               int64_t n_pieces, int64_t piece_rows, const int64_t* d_fin, int64_t n_fin);
+                               int64_t n_pieces, int64_t piece_rows, const int64_t* d_fin, int64_t n_fin, bool weighted = false);
 
 // report_epilogue (capi_report.hpp) per group, on the device: se, t, p, CI, r2, adj_r2 and the null flag.  d_beta is read and, for
 // null groups, overwritten with NaN.  d_yvar (nullable): the caller's var(y) per group; null -> from d_sums (ddof = 1).
 template <typename T>
 int launch_grouped_report_epilogue(pds_ctx* ctx, const int64_t* d_off, int64_t n_groups, int n_feat, int bias, int se_type,
                                    const T* d_yvar, T* d_beta, const T* d_inv, const double* d_sums, const double* d_meat,
-                                   const ReportDofTable& tab, T* se, T* t, T* p, T* lo, T* hi, T* r2, T* adj_r2, uint8_t* is_null);
+                                   const ReportDofTable& tab, T* se, T* t, T* p, T* lo, T* hi, T* r2, T* adj_r2, uint8_t* is_null,
+                                   bool weighted = false);
 
 // pass 1 of groups split into pieces: d_rec[g] = sum over k in [d_vfirst[g], d_vfirst[g + 1]) of d_vrec[k] ((p+2)^2 records, f64 sums)
 template <typename T>

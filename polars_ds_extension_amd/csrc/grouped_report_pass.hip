@@ -14,10 +14,15 @@
 // matrix cores: the wave writes its 64 rows transposed into LDS and feeds them to v_mfma_f64_16x16x4 (A = s x, B = x, 4 rows per
 // step), as the Gram kernels of moments.hip do; the bias row of the meat (sum s x, sum s) stays in per-lane registers.  Every sum
 // is a per-lane register folded by a fixed butterfly at the end of the group: no atomics, repeated calls are bit-identical.
+//
+// WEIGHTED (the grouped wls_report, plain standard error only -- pl_wls_report knows no HC estimator, linear_regression.rs:982-1117):
+// cols[p + 1] is the weight column, loaded like one more column of the frame, and the fourth value of an item's sums slot carries
+// sum w e^2 (the mse's numerator); sum e^2 and the y sums stay unweighted, as the reference's r2 has them.
 #include "grouped_report.hpp"
 #include "stats_dev.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace pds {
 
@@ -56,7 +61,7 @@ __device__ __forceinline__ bool report_item(int64_t it, const int64_t* __restric
     return true;
 }
 
-template <typename T, int P>
+template <typename T, int P, bool WEIGHTED = false>
 __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T* const* __restrict__ cols, int bias,
                                                                          const int64_t* __restrict__ off, int64_t n_groups,
                                                                          const T* __restrict__ beta, const T* __restrict__ inv,
@@ -75,6 +80,7 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
+    const gptr<T> cw = as_global(cols[WEIGHTED ? P + 1 : P]);
     const int f = lane & 15, kq = lane >> 4;
     const int64_t nwaves = (int64_t)gridDim.x * (kRpThreads / 64);
     for (int64_t it = (int64_t)blockIdx.x * (kRpThreads / 64) + wv; it < n_items; it += nwaves) {
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
             for (int i = lane; i < pp * pp; i += 64) is[i] = (double)inv[g * pp * pp + i];
         PDS_WAVE_LDS_SYNC();
         const double y0 = (double)cy[off[g]];  // (the group's first row: the pieces' shifted sums add up)
-        double sse = 0.0, sy = 0.0, syy = 0.0, ss = 0.0;
+        double sse = 0.0, sy = 0.0, syy = 0.0, ss = 0.0, swe = 0.0;
         double sb[P];
 #pragma unroll
         for (int c = 0; c < P; ++c) sb[c] = 0.0;
@@ -98,12 +104,15 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
 #pragma unroll
             for (int c = 0; c < P; ++c) x[c] = live ? (double)cx[c][r] : 0.0;
             const double yv = live ? (double)cy[r] : 0.0;
+            double wr = 0.0;
+            if constexpr (WEIGHTED) wr = live ? (double)cw[r] : 0.0;
             double pr = bias ? bs[P] : 0.0;
 #pragma unroll
             for (int c = 0; c < P; ++c) pr = fma(x[c], bs[c], pr);
             const double e = live ? yv - pr : 0.0;
             const double e2 = e * e;
             sse += e2;
+            if constexpr (WEIGHTED) swe += live ? wr * e2 : 0.0;
             const double dy = live ? yv - y0 : 0.0;
             sy += dy;
             syy += dy * dy;
@@ -142,11 +151,12 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
         sse = wave_sum(sse);
         sy = wave_sum(sy);
         syy = wave_sum(syy);
+        if constexpr (WEIGHTED) swe = wave_sum(swe);
         if (lane == 0) {
             sums[it * 4 + 0] = sse;
             sums[it * 4 + 1] = sy;
             sums[it * 4 + 2] = syy;
-            sums[it * 4 + 3] = 0.0;
+            sums[it * 4 + 3] = swe;
         }
         if (hc) {
             double* mo = meat + it * pp * pp;
@@ -175,7 +185,7 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
 constexpr int kRwStride = 65;
 constexpr int kRwTri = 65 * 66 / 2;
 
-template <typename T>
+template <typename T, bool WEIGHTED = false>
 __global__ __launch_bounds__(64) void grouped_report_pass_wide_kernel(const T* const* __restrict__ cols, int p, int bias,
                                                                       const int64_t* __restrict__ off, int64_t n_groups,
                                                                       const T* __restrict__ beta, const T* __restrict__ inv, int hc,
@@ -198,7 +208,7 @@ __global__ __launch_bounds__(64) void grouped_report_pass_wide_kernel(const T* c
         PDS_WAVE_LDS_SYNC();
         const T* ig = inv + g * pp * pp;
         const double y0 = (double)cy[off[g]];  // (the group's first row: the pieces' shifted sums add up)
-        double sse = 0.0, sy = 0.0, syy = 0.0;
+        double sse = 0.0, sy = 0.0, syy = 0.0, swe = 0.0;
         double* xr = xt + lane * kRwStride;
         for (int64_t base = r0; base < r1; base += 64) {
             const int64_t r = base + lane;
@@ -215,6 +225,7 @@ __global__ __launch_bounds__(64) void grouped_report_pass_wide_kernel(const T* c
             const double e = live ? yv - pr : 0.0;
             const double e2 = e * e;
             sse += e2;
+            if constexpr (WEIGHTED) swe += live ? (double)as_global(cols[p + 1])[r] * e2 : 0.0;
             const double dy = live ? yv - y0 : 0.0;
             sy += dy;
             syy += dy * dy;
@@ -246,11 +257,12 @@ __global__ __launch_bounds__(64) void grouped_report_pass_wide_kernel(const T* c
         sse = wave_sum(sse);
         sy = wave_sum(sy);
         syy = wave_sum(syy);
+        if constexpr (WEIGHTED) swe = wave_sum(swe);
         if (lane == 0) {
             sums[it * 4 + 0] = sse;
             sums[it * 4 + 1] = sy;
             sums[it * 4 + 2] = syy;
-            sums[it * 4 + 3] = 0.0;
+            sums[it * 4 + 3] = swe;
         }
         if (hc) {
             PDS_WAVE_LDS_SYNC();
@@ -269,20 +281,21 @@ __global__ __launch_bounds__(64) void grouped_report_pass_wide_kernel(const T* c
 
 // split groups: slot of the group += its extra pieces' slots, in piece order (fin[3 j ..]: group, first extra item, count) -- a fixed
 // order, so the result does not depend on which wave finished first
+// (nsum: 3 sums per slot, 4 when the slot's fourth value carries sum w e^2)
 __global__ __launch_bounds__(256) void grouped_report_finish_kernel(const int64_t* __restrict__ fin, int64_t n_fin, int pp, int hc,
-                                                                    double* __restrict__ sums, double* __restrict__ meat) {
-    const int per = 3 + (hc ? pp * pp : 0);
+                                                                    int nsum, double* __restrict__ sums, double* __restrict__ meat) {
+    const int per = nsum + (hc ? pp * pp : 0);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_fin * per) return;
     const int64_t j = i / per;
     const int e = (int)(i - j * per);
     const int64_t g = fin[3 * j], first = fin[3 * j + 1], cnt = fin[3 * j + 2];
-    if (e < 3) {
+    if (e < nsum) {
         double v = sums[g * 4 + e];
         for (int64_t k = 0; k < cnt; ++k) v += sums[(first + k) * 4 + e];
         sums[g * 4 + e] = v;
     } else {
-        const int64_t m = e - 3, sz = (int64_t)pp * pp;
+        const int64_t m = e - nsum, sz = (int64_t)pp * pp;
         double v = meat[g * sz + m];
         for (int64_t k = 0; k < cnt; ++k) v += meat[(first + k) * sz + m];
         meat[g * sz + m] = v;
@@ -314,7 +327,8 @@ __device__ __forceinline__ void dof_lookup(const ReportDofTable& tab, int64_t k,
 // coefficient: report_epilogue (capi_report.hpp) in its own operation order and types
 template <typename T>
 __global__ __launch_bounds__(256) void grouped_report_epilogue_kernel(const int64_t* __restrict__ off, int64_t n_groups, int p, int bias,
-                                                                      int se_type, const T* __restrict__ yvar, T* __restrict__ beta,
+                                                                      int se_type, int weighted, const T* __restrict__ yvar,
+                                                                      T* __restrict__ beta,
                                                                       const T* __restrict__ inv, const double* __restrict__ sums,
                                                                       const double* __restrict__ meat, ReportDofTable tab,
                                                                       T* __restrict__ o_se, T* __restrict__ o_t, T* __restrict__ o_p,
@@ -364,7 +378,7 @@ __global__ __launch_bounds__(256) void grouped_report_epilogue_kernel(const int6
         const T* ig = inv + g * (int64_t)pp * pp;
         T se;
         if (se_type == PDS_SE) {
-            const T mse = ssr / dof;
+            const T mse = (weighted ? (T)sums[g * 4 + 3] : ssr) / dof;  // (report_epilogue: sum w e^2 / dof when weighted)
             se = (T)sqrt((double)(mse * ig[i + i * pp]));
         } else {
             const double* mg = meat + g * (int64_t)pp * pp;
@@ -415,21 +429,25 @@ __global__ __launch_bounds__(256) void student_t_sf_grid_kernel(const double* __
 template <typename T>
 int launch_grouped_report_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int64_t n_groups,
                                const T* d_beta, const T* d_inv, int hc, double* d_sums, double* d_meat, const int64_t* d_pieces,
-                               int64_t n_pieces, int64_t piece_rows, const int64_t* d_fin, int64_t n_fin) {
+                               int64_t n_pieces, int64_t piece_rows, const int64_t* d_fin, int64_t n_fin, bool weighted) {
     if (n_groups <= 0) return PDS_OK;
+    if (weighted && hc) return fail(PDS_ERR_INVALID, "internal: the weighted grouped report has the plain standard error only");
     if (n_feat < 1 || n_feat > kMaxFeatWide) return fail(PDS_ERR_UNSUPPORTED, "grouped report: 1..64 features supported");
     KernelTimer timer(ctx, kKindPass2);
     const int64_t n_items = n_groups + n_pieces;
-    if (n_feat > kMaxFeatSmall) {
-        const int nb = (int)std::min<int64_t>(n_items, (int64_t)ctx->num_cus * 4);
-        hipLaunchKernelGGL((grouped_report_pass_wide_kernel<T>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, n_feat, bias, d_off, n_groups,
-                           d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);
-    } else {
+    auto launch = [&](auto w_c) {
+        constexpr bool W = decltype(w_c)::value;
+        if (n_feat > kMaxFeatSmall) {
+            const int nb = (int)std::min<int64_t>(n_items, (int64_t)ctx->num_cus * 4);
+            hipLaunchKernelGGL((grouped_report_pass_wide_kernel<T, W>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, n_feat, bias, d_off,
+                               n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);
+            return;
+        }
         const int nb = (int)std::min<int64_t>((n_items + 3) / 4, (int64_t)ctx->num_cus * 8);
-#define PDS_RP_CASE(PV)                                                                                                          \
-    case PV:                                                                                                                     \
-        hipLaunchKernelGGL((grouped_report_pass_kernel<T, PV>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,   \
-                           n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);                          \
+#define PDS_RP_CASE(PV)                                                                                                            \
+    case PV:                                                                                                                       \
+        hipLaunchKernelGGL((grouped_report_pass_kernel<T, PV, W>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,  \
+                           n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);                            \
         break;
         switch (n_feat) {
             PDS_RP_CASE(1)
@@ -448,16 +466,19 @@ int launch_grouped_report_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat,
             PDS_RP_CASE(14)
             PDS_RP_CASE(15)
             default:
-                hipLaunchKernelGGL((grouped_report_pass_kernel<T, 16>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,
+                hipLaunchKernelGGL((grouped_report_pass_kernel<T, 16, W>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,
                                    n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);
         }
 #undef PDS_RP_CASE
-    }
+    };
+    if (weighted) launch(std::true_type{});
+    else launch(std::false_type{});
     PDS_HIP_CHECK(hipGetLastError());
     if (n_fin > 0) {
-        const int per = 3 + (hc ? (n_feat + bias) * (n_feat + bias) : 0);
+        const int nsum = weighted ? 4 : 3;
+        const int per = nsum + (hc ? (n_feat + bias) * (n_feat + bias) : 0);
         hipLaunchKernelGGL(grouped_report_finish_kernel, dim3((unsigned)((n_fin * per + 255) / 256)), dim3(256), 0, ctx->stream, d_fin,
-                           n_fin, n_feat + bias, hc, d_sums, d_meat);
+                           n_fin, n_feat + bias, hc, nsum, d_sums, d_meat);
         PDS_HIP_CHECK(hipGetLastError());
     }
     return PDS_OK;
@@ -466,12 +487,13 @@ int launch_grouped_report_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat,
 template <typename T>
 int launch_grouped_report_epilogue(pds_ctx* ctx, const int64_t* d_off, int64_t n_groups, int n_feat, int bias, int se_type,
                                    const T* d_yvar, T* d_beta, const T* d_inv, const double* d_sums, const double* d_meat,
-                                   const ReportDofTable& tab, T* se, T* t, T* p, T* lo, T* hi, T* r2, T* adj_r2, uint8_t* is_null) {
+                                   const ReportDofTable& tab, T* se, T* t, T* p, T* lo, T* hi, T* r2, T* adj_r2, uint8_t* is_null,
+                                   bool weighted) {
     if (n_groups <= 0) return PDS_OK;
     KernelTimer timer(ctx, kKindSolve);
     const int nb = (int)std::min<int64_t>((n_groups * (n_feat + bias) + 255) / 256, (int64_t)ctx->num_cus * 16);
     hipLaunchKernelGGL((grouped_report_epilogue_kernel<T>), dim3(nb), dim3(256), 0, ctx->stream, d_off, n_groups, n_feat, bias, se_type,
-                       d_yvar, d_beta, d_inv, d_sums, d_meat, tab, se, t, p, lo, hi, r2, adj_r2, is_null);
+                       weighted ? 1 : 0, d_yvar, d_beta, d_inv, d_sums, d_meat, tab, se, t, p, lo, hi, r2, adj_r2, is_null);
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
@@ -497,15 +519,15 @@ int launch_student_t_sf_grid(pds_ctx* ctx, const double* d_x, const double* d_df
 
 template int launch_grouped_report_pass<double>(pds_ctx*, const double* const*, int, int, const int64_t*, int64_t, const double*,
                                                 const double*, int, double*, double*, const int64_t*, int64_t, int64_t, const int64_t*,
-                                                int64_t);
+                                                int64_t, bool);
 template int launch_grouped_report_pass<float>(pds_ctx*, const float* const*, int, int, const int64_t*, int64_t, const float*,
                                                const float*, int, double*, double*, const int64_t*, int64_t, int64_t, const int64_t*,
-                                               int64_t);
+                                               int64_t, bool);
 template int launch_grouped_report_epilogue<double>(pds_ctx*, const int64_t*, int64_t, int, int, int, const double*, double*,
                                                     const double*, const double*, const double*, const ReportDofTable&, double*, double*,
-                                                    double*, double*, double*, double*, double*, uint8_t*);
+                                                    double*, double*, double*, double*, double*, uint8_t*, bool);
 template int launch_grouped_report_epilogue<float>(pds_ctx*, const int64_t*, int64_t, int, int, int, const float*, float*,
                                                    const float*, const double*, const double*, const ReportDofTable&, float*, float*,
-                                                   float*, float*, float*, float*, float*, uint8_t*);
+                                                   float*, float*, float*, float*, float*, uint8_t*, bool);
 
 }  // namespace pds

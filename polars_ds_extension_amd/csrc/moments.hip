@@ -535,7 +535,9 @@ __global__ __launch_bounds__(64) void moments_finalize_kernel(const double* __re
 // grouped: one wave per group at a time (rows of a group are contiguous, group starts are only
 // element-aligned -> 8/4-byte lane loads, still 512/256 B coalesced per instruction)
 // =============================================================================================
-template <typename T>
+// WEIGHTED: cols[p + 1] is a weight column, loaded like one more column of the frame; one MFMA operand is w z, the other z, so the
+// record is Z'WZ (X'WX, X'Wy, sum w x, sum w) with the weights of any sign as they are -- no sqrt(w)-scaled copy of the frame
+template <typename T, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, 2) void grouped_moments_kernel(const T* const* __restrict__ cols, int p,
                                                                  const int64_t* __restrict__ offsets,
                                                                  int64_t n_groups, T* __restrict__ out,
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(256, 2) void grouped_moments_kernel(const T* const*
     const int64_t wid = (int64_t)blockIdx.x * kWaves + wave, nw = (int64_t)gridDim.x * kWaves;
     GroupRegs<T> regs;
     ColPtrs<T> cp;
-    fetch_col_ptrs<T, false>(cols, p, cp);
+    fetch_col_ptrs<T, WEIGHTED>(cols, p, cp);
     int64_t g = wid;
     int64_t r0 = 0, rend = 0;
     // gidx != null: record g is the Gram matrix of group gidx[g] (the pivoted-QR pass over the groups the fused kernel
@@ -560,35 +562,35 @@ __global__ __launch_bounds__(256, 2) void grouped_moments_kernel(const T* const*
     };
     if (g < n_groups) {
         bounds(g);
-        load_group_tile<T>(cp, p, r0, rend, lane, regs);
+        load_group_tile<T, WEIGHTED>(cp, p, r0, rend, lane, regs);
     }
     for (; g < n_groups; g += nw) {
         WaveAcc acc;
         zero_acc(acc);
         const int64_t gr0 = r0, grend = rend;
         // first 128 rows of this group are already in registers
-        store_group_lds<T>(wl, p, lane, regs);
+        store_group_lds<T, WEIGHTED>(wl, p, lane, regs);
         int64_t done = 128;
         const int64_t ng = grend - gr0;
         const int64_t gn = g + nw;
         if (ng <= 128 && gn < n_groups) {  // prefetch the next group's first tile
             bounds(gn);
-            load_group_tile<T>(cp, p, r0, rend, lane, regs);
+            load_group_tile<T, WEIGHTED>(cp, p, r0, rend, lane, regs);
         }
         {
             const int rows = (int)(ng < 128 ? ng : 128);
-            consume_tile<T, false>(wl, lane, (rows + 3) >> 2, acc);
+            consume_tile<T, WEIGHTED>(wl, lane, (rows + 3) >> 2, acc);
         }
         while (done < ng) {  // long groups: stream the rest 128 rows at a time
-            load_group_tile<T>(cp, p, gr0 + done, grend, lane, regs);
-            store_group_lds<T>(wl, p, lane, regs);
+            load_group_tile<T, WEIGHTED>(cp, p, gr0 + done, grend, lane, regs);
+            store_group_lds<T, WEIGHTED>(wl, p, lane, regs);
             const int64_t left = ng - done;
             const int rows = (int)(left < 128 ? left : 128);
-            consume_tile<T, false>(wl, lane, (rows + 3) >> 2, acc);
+            consume_tile<T, WEIGHTED>(wl, lane, (rows + 3) >> 2, acc);
             done += 128;
             if (done >= ng && gn < n_groups) {
                 bounds(gn);
-                load_group_tile<T>(cp, p, r0, rend, lane, regs);
+                load_group_tile<T, WEIGHTED>(cp, p, r0, rend, lane, regs);
             }
         }
         // assemble A for this group
@@ -599,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void grouped_moments_kernel(const T* const*
             if (i > j) { int tmp = i; i = j; j = tmp; }
             double v;
             if (j < p) v = rec[kPartD + i + 16 * j];
-            else if (j == p) v = (i < p) ? rec[kPartCS + i] : (double)ng;
+            else if (j == p) v = (i < p) ? rec[kPartCS + i] : (WEIGHTED ? rec[kPartSW] : (double)ng);
             else v = (i < p) ? rec[kPartXY + i] : (i == p ? rec[kPartYS] : rec[kPartYY]);
             o[idx] = (T)v;
         }
@@ -680,7 +682,8 @@ int launch_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_
 constexpr int kMidRows = 32;
 constexpr int kMidStride = 34;  // doubles per LDS column: 68 dwords = 4 mod 64 -> conflict-free b64 operand reads
 
-template <typename T, int NB>
+// WEIGHTED: the 32 rows' weights (cols[p + 1]) are staged behind the tile; the first MFMA operand of every block pair is w z
+template <typename T, int NB, bool WEIGHTED = false>
 __global__ __launch_bounds__(64) void grouped_moments_mid_kernel(const T* const* __restrict__ cols, int p,
                                                                  const int64_t* __restrict__ offsets, int64_t n_groups,
                                                                  T* __restrict__ moments) {
@@ -689,6 +692,7 @@ __global__ __launch_bounds__(64) void grouped_moments_mid_kernel(const T* const*
     const int lane = threadIdx.x;
     const int q = p + 2;
     const int f = lane & 15, kq = lane >> 4;
+    double* wt = tile + NB * 16 * kMidStride;  // [kMidRows], WEIGHTED only
     for (int i = lane; i < NB * 16 * kMidStride; i += 64) tile[i] = 0.0;  // columns >= q stay zero for good
     PDS_WAVE_LDS_SYNC();
     for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
@@ -712,25 +716,33 @@ __global__ __launch_bounds__(64) void grouped_moments_mid_kernel(const T* const*
                 const int cc = c < p ? c : p;  // (column p of the table is y: it serves c == p + 1, the ones column and the padding)
                 vreg[k] = as_global(cols[cc])[rc];
             }
+            T wreg = T(0);
+            if constexpr (WEIGHTED) wreg = as_global(cols[p + 1])[rc];
 #pragma unroll
             for (int k = 0; k < NB * 8; ++k) {
                 const int c = 2 * k + (lane >> 5);
                 if (c < q) tile[c * kMidStride + row] = !in ? 0.0 : (c == p ? 1.0 : (double)vreg[k]);
             }
+            if constexpr (WEIGHTED)
+                if (lane < kMidRows) wt[row] = in ? (double)wreg : 0.0;
             PDS_WAVE_LDS_SYNC();
 #pragma unroll
             for (int s = 0; s < kMidRows / 4; ++s) {
                 double a[NB];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) a[b] = tile[(16 * b + f) * kMidStride + 4 * s + kq];
+                double wv = 1.0;
+                if constexpr (WEIGHTED) wv = wt[4 * s + kq];
                 int t = 0;
 #pragma unroll
-                for (int bi = 0; bi < NB; ++bi)
+                for (int bi = 0; bi < NB; ++bi) {
+                    const double ab = WEIGHTED ? a[bi] * wv : a[bi];
 #pragma unroll
                     for (int bj = bi; bj < NB; ++bj) {
-                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[bi], a[bj], acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ab, a[bj], acc[t], 0, 0, 0);
                         ++t;
                     }
+                }
             }
             PDS_WAVE_LDS_SYNC();
         }
@@ -755,19 +767,20 @@ __global__ __launch_bounds__(64) void grouped_moments_mid_kernel(const T* const*
     }
 }
 
-template <typename T, int NB>
+template <typename T, int NB, bool WEIGHTED = false>
 static void launch_mid_nb(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, const int64_t* d_offsets, int64_t n_groups,
                           T* d_moments) {
-    const size_t lds = (size_t)NB * 16 * kMidStride * sizeof(double);
+    const size_t lds = ((size_t)NB * 16 * kMidStride + (WEIGHTED ? kMidRows : 0)) * sizeof(double);
     const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / lds)));
     const int nblocks = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * per_cu);
-    hipLaunchKernelGGL((grouped_moments_mid_kernel<T, NB>), dim3(nblocks), dim3(64), lds, ctx->stream, dc.d_ptrs, n_feat,
+    hipLaunchKernelGGL((grouped_moments_mid_kernel<T, NB, WEIGHTED>), dim3(nblocks), dim3(64), lds, ctx->stream, dc.d_ptrs, n_feat,
                        d_offsets, n_groups, d_moments);
 }
 
 template <typename T>
 int launch_grouped_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, const int64_t* d_offsets,
-                           int64_t n_groups, T* d_moments, const int32_t* d_group_index) {
+                           int64_t n_groups, T* d_moments, const int32_t* d_group_index, bool weighted) {
+    if (weighted && dc.nc < n_feat + 2) return fail(PDS_ERR_INVALID, "internal: weighted grouped Gram build without a weight column");
     if (n_feat < 1 || n_feat > kMaxFeatWide)
         return fail(PDS_ERR_UNSUPPORTED, "grouped regressions: 1..64 features supported");
     if (n_groups <= 0) return PDS_OK;
@@ -775,12 +788,17 @@ int launch_grouped_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, co
     if (n_feat > kMaxFeatSmall) {
         const int nb = (n_feat + 2 + 15) / 16;  // 2 .. 5
         KernelTimer timer(ctx, kKindGroupedMoments);
-        switch (nb) {
-            case 2: launch_mid_nb<T, 2>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
-            case 3: launch_mid_nb<T, 3>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
-            case 4: launch_mid_nb<T, 4>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
-            default: launch_mid_nb<T, 5>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
-        }
+        auto by_nb = [&](auto w_c) {
+            constexpr bool W = decltype(w_c)::value;
+            switch (nb) {
+                case 2: launch_mid_nb<T, 2, W>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
+                case 3: launch_mid_nb<T, 3, W>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
+                case 4: launch_mid_nb<T, 4, W>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
+                default: launch_mid_nb<T, 5, W>(ctx, dc, n_feat, d_offsets, n_groups, d_moments); break;
+            }
+        };
+        if (weighted) by_nb(std::true_type{});
+        else by_nb(std::false_type{});
         PDS_HIP_CHECK(hipGetLastError());
         return PDS_OK;
     }
@@ -788,8 +806,12 @@ int launch_grouped_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, co
     int nblocks = (int)std::min<int64_t>(want, (int64_t)ctx->num_cus * 2);
     size_t lds = (size_t)kWaves * kWaveLds;
     KernelTimer timer(ctx, kKindGroupedMoments);
-    hipLaunchKernelGGL((grouped_moments_kernel<T>), dim3(nblocks), dim3(256), lds, ctx->stream, dc.d_ptrs, n_feat,
-                       d_offsets, n_groups, d_moments, d_group_index);
+    if (weighted)  // (+ 64 B: the pipelined operand fetch reads two steps past the weight slot, the last of the wave's tile)
+        hipLaunchKernelGGL((grouped_moments_kernel<T, true>), dim3(nblocks), dim3(256), lds + 64, ctx->stream, dc.d_ptrs, n_feat,
+                           d_offsets, n_groups, d_moments, d_group_index);
+    else
+        hipLaunchKernelGGL((grouped_moments_kernel<T>), dim3(nblocks), dim3(256), lds, ctx->stream, dc.d_ptrs, n_feat,
+                           d_offsets, n_groups, d_moments, d_group_index);
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
@@ -1021,8 +1043,8 @@ template int launch_moments<double>(pds_ctx*, const DeviceCols<double>&, int, in
 template int launch_moments<float>(pds_ctx*, const DeviceCols<float>&, int, int64_t, bool, float*, const float*, int, double*, double*,
                                    const IrlsArgs*, double*);
 template int launch_grouped_moments<double>(pds_ctx*, const DeviceCols<double>&, int, const int64_t*, int64_t,
-                                            double*, const int32_t*);
+                                            double*, const int32_t*, bool);
 template int launch_grouped_moments<float>(pds_ctx*, const DeviceCols<float>&, int, const int64_t*, int64_t,
-                                           float*, const int32_t*);
+                                           float*, const int32_t*, bool);
 
 }  // namespace pds

@@ -325,9 +325,11 @@ template <typename T>
 struct GroupRegs {
     T x[16][2];
     T y[2];
+    T w[2];  // (WEIGHTED forms only: the unweighted kernels never touch it)
 };
 
-template <typename T>
+// WEIGHTED: the weight column (cp.w) is loaded like one more column of the frame; rows past the group carry weight 0
+template <typename T, bool WEIGHTED = false>
 __device__ __forceinline__ void load_group_tile(const ColPtrs<T>& cp, int p, int64_t r0, int64_t rend, int lane,
                                                 GroupRegs<T>& g) {
     const int64_t ra = r0 + lane, rb = r0 + 64 + lane;
@@ -340,9 +342,13 @@ __device__ __forceinline__ void load_group_tile(const ColPtrs<T>& cp, int p, int
         }
     g.y[0] = va ? cp.y[ra] : T(0);
     g.y[1] = vb ? cp.y[rb] : T(0);
+    if constexpr (WEIGHTED) {
+        g.w[0] = va ? cp.w[ra] : T(0);
+        g.w[1] = vb ? cp.w[rb] : T(0);
+    }
 }
 
-template <typename T>
+template <typename T, bool WEIGHTED = false>
 __device__ __forceinline__ void store_group_lds(char* wl, int p, int lane, const GroupRegs<T>& g) {
     // every feature slot is (re)written: slots >= p get exact zeros (the wave's result record
     // aliases the head of the tile region between groups)
@@ -355,6 +361,11 @@ __device__ __forceinline__ void store_group_lds(char* wl, int p, int lane, const
     T* ycol = reinterpret_cast<T*>(wl + kSlotY * kColStride);
     ycol[lane] = g.y[0];
     ycol[64 + lane] = g.y[1];
+    if constexpr (WEIGHTED) {
+        T* wcol = reinterpret_cast<T*>(wl + kSlotW * kColStride);
+        wcol[lane] = g.w[0];
+        wcol[64 + lane] = g.w[1];
+    }
 }
 
 

@@ -92,6 +92,10 @@ bool reference_quirks() { return settings().reference_quirks; }
 template <typename T> struct Api;
 template <> struct Api<double> {
     using Report = pds_report_f64;
+    using ReportGrouped = pds_report_grouped_f64;
+    static constexpr auto report_grouped = pds_lin_reg_report_grouped_f64;
+    static constexpr auto report_by_key = pds_lin_reg_report_by_key_f64;
+    static constexpr auto wls_report_by_key = pds_wls_report_by_key_f64;
     static constexpr auto lr_nullable = pds_lr_nullable_f64;
     static constexpr auto lr = pds_lr_f64;
     static constexpr auto lr_pred = pds_lr_pred_f64;
@@ -114,6 +118,10 @@ template <> struct Api<double> {
 };
 template <> struct Api<float> {
     using Report = pds_report_f32;
+    using ReportGrouped = pds_report_grouped_f32;
+    static constexpr auto report_grouped = pds_lin_reg_report_grouped_f32;
+    static constexpr auto report_by_key = pds_lin_reg_report_by_key_f32;
+    static constexpr auto wls_report_by_key = pds_wls_report_by_key_f32;
     static constexpr auto lr_nullable = pds_lr_nullable_f32;
     static constexpr auto lr = pds_lr_f32;
     static constexpr auto lr_pred = pds_lr_pred_f32;

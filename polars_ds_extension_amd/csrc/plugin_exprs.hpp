@@ -661,6 +661,211 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
     export_series(out, make_schema("+s", "", std::move(sk)), struct_array(ng, std::move(kids)));
 }
 
+// ------------------------------------------------------------------------------------------------- pl_lin_reg_report_by / pl_wls_report_by (new)
+// inputs: [key (integer, any row order, nulls = one group), weights?, y, x1..xp] -- no var(y) input: Polars' `target.var()` in front
+// of a keyed call would be the frame's variance, not the group's, so it is derived per group.  One Struct "lin_reg_report" in long
+// format: n_groups x p' rows {key, features, beta, <se>, t, p>|t|, 0.025, 0.975, r2, adj_r2}, groups in ascending key order (the null
+// key's group last, with a null key), coefficients in input order with __bias__ last, r2 / adj_r2 broadcast over a group's rows --
+// after `unnest` what `group_by(key).agg(lin_reg_report(...)).explode(...)` gives, from ONE grouped call
+// (pds_lin_reg_report_by_key_* / pds_wls_report_by_key_*).  A group with fewer rows than coefficients keeps its p' rows with key and
+// features set and every numeric field null (the reference's per-group call would raise and abort the query; the deviation the C
+// ABI documents).  Nulls in y / x: "raise" fails on the first one; the other policies act on every group as pl_lin_reg_report acts
+// on that group's rows alone, var(y) being the variance of the group's ORIGINAL non-null target values (what Polars hands a
+// per-group call): the rows are prepared on the host in key order and go to the offsets entry with y_var.  pl_wls_report_by with
+// nulls raises, as pl_wls_report does (linear_regression.rs:1013-1020: the weights are never compacted).
+// (test seam: the capacity guess of the by-key call; <= 0 = the default rule of do_lr_by)
+int64_t g_report_by_first_cap = 0;
+template <typename T>
+void do_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool wls) {
+    const size_t iy = wls ? 2 : 1;  // cols: [key, weights?, y, x1..xp]
+    if (n_in < iy + 2) raise("need a key, a target and at least one feature");
+    auto key = import_series<int64_t>(in[0]);
+    std::vector<Column<T>> cols;  // [weights?, y, x1..xp]
+    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
+    const size_t cy = iy - 1;  // index of y in cols
+    const bool bias = kw_bool(kw, "bias");
+    const std::string se = kw_str(kw, "std_err", "se");
+    const int se_type = wls ? PDS_SE : se == "hc0" ? PDS_HC0 : se == "hc1" ? PDS_HC1 : se == "hc2" ? PDS_HC2 : se == "hc3" ? PDS_HC3 : PDS_SE;
+    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
+    bool any_null = false;
+    for (size_t i = cy; i < cols.size(); ++i) any_null |= cols[i].null_count > 0;
+    if (wls && cols[0].null_count > 0) any_null = true;
+    if (any_null && (wls || pol.kind == Policy::RAISE)) raise("Nulls found in data");
+    const int64_t n = key.size();
+    for (auto& c : cols)
+        if (c.size() != n) raise("input columns differ in length");
+    if (n == 0) raise("Empty data");
+    const int n_feat = (int)(n_in - iy - 1);
+    const int pp = n_feat + (bias ? 1 : 0);
+    int64_t null_stand_in = 0;
+    const bool null_group = null_key_stand_in(key, n, wls ? "pl_wls_report_by" : "pl_lin_reg_report_by", &null_stand_in);
+    const int64_t* ikey = key.data();
+    RawVec<int64_t> keys;
+    ByteVec vb[6], r2b, ar2b;  // beta, se, t, p, lo, hi [ng][p'], r2 / adj_r2 [ng]
+    RawVec<uint8_t> nulls;
+    int64_t ng = 0;
+    typename Api<T>::ReportGrouped rep;
+    auto size_outputs = [&](int64_t cap) {
+        keys.resize(cap);
+        for (auto& b : vb) b = raw_buffer<T>((size_t)cap * pp);
+        r2b = raw_buffer<T>((size_t)cap);
+        ar2b = raw_buffer<T>((size_t)cap);
+        nulls.resize(cap);
+        rep.beta = as<T>(vb[0]); rep.std_err = as<T>(vb[1]); rep.t = as<T>(vb[2]); rep.p = as<T>(vb[3]);
+        rep.ci_lower = as<T>(vb[4]); rep.ci_upper = as<T>(vb[5]); rep.r2 = as<T>(r2b); rep.adj_r2 = as<T>(ar2b);
+        rep.is_null = nulls.data();
+    };
+    if (!any_null) {
+        std::vector<const T*> ptrs;
+        for (size_t c = cy; c < cols.size(); ++c) ptrs.push_back(cols[c].data());
+        // the group count is unknown until the device has counted the runs: guess, then repeat once with the count (do_lr_by)
+        int64_t cap = g_report_by_first_cap > 0 ? std::min<int64_t>(g_report_by_first_cap, n)
+                                                : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
+        for (int attempt = 0;; ++attempt) {
+            size_outputs(cap);
+            const int rc = wls ? Api<T>::wls_report_by_key(thread_ctx(), ptrs.data(), cols[0].data(), ikey, n_feat, n, PDS_HOST, bias, cap,
+                                                           keys.data(), &rep, &ng)
+                               : Api<T>::report_by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, se_type, cap, keys.data(),
+                                                       &rep, &ng);
+            if (rc != 0 && attempt == 0 && ng > cap) {
+                cap = ng;
+                continue;
+            }
+            check(rc);
+            break;
+        }
+    } else {
+        // rows with nulls: a stable sort of the row indices by key, the policy applied row by row (series_to_mat_for_lr,
+        // linear_regression.rs:187-248, per group: "skip" drops a row with any null, a fill policy fills the features and drops the
+        // rows whose target is null, everything else keeps the rows with NaN for the nulls), the surviving rows written in key order
+        std::vector<int64_t> perm(n);
+        for (int64_t i = 0; i < n; ++i) perm[i] = i;
+        bool ordered = true;
+        for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
+        if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
+        const int code = pol.kind == Policy::FILL ? PDS_NULL_FILL : pol.kind == Policy::SKIP ? PDS_NULL_SKIP : PDS_NULL_IGNORE;
+        const size_t nc = cols.size();
+        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
+        std::vector<std::vector<T>> kept(nc);
+        for (auto& v : kept) v.reserve((size_t)n);
+        std::vector<int64_t> off;
+        std::vector<T> yvar;
+        const T nanv = std::numeric_limits<T>::quiet_NaN();
+        // var(y) of a group: the sample variance (ddof = 1) of its non-null target values, two passes in f64
+        auto close_group = [&](int64_t a, int64_t b) {
+            double sum = 0.0;
+            int64_t m = 0;
+            for (int64_t i = a; i < b; ++i)
+                if (!is_null(0, perm[i])) {
+                    sum += (double)cols[0].data()[perm[i]];
+                    ++m;
+                }
+            if (m < 2) {
+                yvar.push_back(nanv);
+                return;
+            }
+            const double mean = sum / (double)m;
+            double ss = 0.0;
+            for (int64_t i = a; i < b; ++i)
+                if (!is_null(0, perm[i])) {
+                    const double d = (double)cols[0].data()[perm[i]] - mean;
+                    ss += d * d;
+                }
+            yvar.push_back((T)(ss / (double)(m - 1)));
+        };
+        int64_t g_first = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t r = perm[i];
+            if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
+                if (i) close_group(g_first, i);
+                g_first = i;
+                off.push_back((int64_t)kept[0].size());
+                keys.push_back(ikey[r]);
+            }
+            bool keep = true;
+            if (code == PDS_NULL_SKIP)
+                for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
+            else if (code == PDS_NULL_FILL)
+                keep = !is_null(0, r);
+            if (!keep) continue;
+            for (size_t c = 0; c < nc; ++c)
+                kept[c].push_back(is_null(c, r) ? (code == PDS_NULL_FILL ? (T)pol.fill : nanv) : cols[c].data()[r]);
+        }
+        close_group(g_first, n);
+        off.push_back((int64_t)kept[0].size());
+        ng = (int64_t)keys.size();
+        const int64_t nk = (int64_t)kept[0].size();
+        if (nk == 0) raise("Empty data");
+        std::vector<const T*> ptrs;
+        for (auto& v : kept) ptrs.push_back(v.data());
+        size_outputs(ng);  // (keys already holds its ng values)
+        check(Api<T>::report_grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, se_type, yvar.data(), &rep));
+    }
+    // ---- the long frame
+    const int64_t rows = ng * pp;
+    std::vector<std::string> names;
+    for (size_t i = cy + 1; i < cols.size(); ++i) names.push_back(cols[i].name);
+    if (bias) names.push_back("__bias__");
+    std::vector<std::unique_ptr<ArrowArray>> kids;
+    {
+        ByteVec kb = raw_buffer<int64_t>((size_t)rows);
+        int64_t* kd = as<int64_t>(kb);
+        std::vector<uint8_t> kvalid;
+        if (null_group) kvalid.assign((size_t)rows, 1);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int i = 0; i < pp; ++i) {
+                kd[g * pp + i] = keys[g];
+                if (null_group && keys[g] == null_stand_in) kvalid[g * pp + i] = 0;
+            }
+        kids.push_back(prim_array_take<int64_t>(std::move(kb), rows, null_group ? kvalid.data() : nullptr));
+    }
+    {   // features: the p' names, once per group (large-utf8: int64 offsets)
+        std::string one;
+        std::vector<int64_t> o1 = {0};
+        for (auto& s : names) {
+            one += s;
+            o1.push_back((int64_t)one.size());
+        }
+        ByteVec ob = raw_buffer<int64_t>((size_t)rows + 1), db = raw_buffer<char>((size_t)ng * one.size());
+        int64_t* od = as<int64_t>(ob);
+        for (int64_t g = 0; g < ng; ++g) {
+            for (int i = 0; i < pp; ++i) od[g * pp + i] = g * (int64_t)one.size() + o1[i];
+            if (!one.empty()) std::memcpy(db.data() + g * one.size(), one.data(), one.size());
+        }
+        od[rows] = ng * (int64_t)one.size();
+        std::vector<ByteVec> bufs;
+        bufs.emplace_back();
+        bufs.push_back(std::move(ob));
+        bufs.push_back(std::move(db));
+        kids.push_back(make_array(rows, 0, std::move(bufs), {false, true, true}));
+    }
+    std::vector<uint8_t> valid((size_t)rows, 1);
+    bool any_group_null = false;
+    for (int64_t g = 0; g < ng; ++g)
+        if (nulls[g]) {
+            any_group_null = true;
+            for (int i = 0; i < pp; ++i) valid[g * pp + i] = 0;
+        }
+    const uint8_t* vf = any_group_null ? valid.data() : nullptr;
+    for (auto& b : vb) kids.push_back(prim_array_take<T>(std::move(b), rows, vf));
+    for (ByteVec* b : {&r2b, &ar2b}) {
+        ByteVec wide = raw_buffer<T>((size_t)rows);
+        const T* sv = as<T>(*b);
+        T* dv = as<T>(wide);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
+        kids.push_back(prim_array_take<T>(std::move(wide), rows, vf));
+    }
+    const char* se_name = se_type == PDS_HC0 ? "hc0_se" : se_type == PDS_HC1 ? "hc1_se" : se_type == PDS_HC2 ? "hc2_se"
+                          : se_type == PDS_HC3 ? "hc3_se" : "std_err";
+    const char* fnames[9] = {"features", "beta", se_name, "t", "p>|t|", "0.025", "0.975", "r2", "adj_r2"};
+    std::vector<std::unique_ptr<ArrowSchema>> sk;
+    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(make_schema("U", fnames[0]));
+    for (int i = 1; i < 9; ++i) sk.push_back(make_schema(fmt_of<T>(), fnames[i]));
+    export_series(out, make_schema("+s", "lin_reg_report", std::move(sk)), struct_array(rows, std::move(kids)));
+}
+
 // ------------------------------------------------------------------------------------------------- pl_lr_multi(_pred)
 template <typename T>
 void do_lr_multi(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {

@@ -590,8 +590,18 @@ def _report_grouped_dict(outs, n_feat, add_bias, std_err, feature_names, g=None)
     }
 
 
+def _check_report_weights(x, target, weights) -> None:
+    """Argument checks of the weighted grouped report that need no device: one weight per row, at most 64 features."""
+    n = int(target.shape[0]) if hasattr(target, "shape") else len(target)
+    nw = int(weights.shape[0]) if hasattr(weights, "shape") else len(weights)
+    if nw != n:
+        raise ValueError("`weights` must have one entry per row")
+    if len(x) > 64:
+        raise _lib.PdsError(-5, "grouped lin_reg_report: at most 64 features")  # PDS_ERR_UNSUPPORTED, as the C entry answers
+
+
 def lin_reg_report_by(*x, target, group_offsets, add_bias: bool = False, std_err: str = "se", y_var=None,
-                      feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+                      feature_names: Sequence[str] | None = None, weights=None, ctx: Context | None = None) -> dict:
     """
     The grouped form of `lin_reg_report`: `df.group_by(key).agg(pds.lin_reg_report(...))` for a frame whose groups are contiguous
     row ranges (group g = rows [group_offsets[g], group_offsets[g+1])), in one call.  Every group's report equals the single
@@ -600,9 +610,14 @@ def lin_reg_report_by(*x, target, group_offsets, add_bias: bool = False, std_err
     group's target is computed on the device.
     Returns a dict of [n_groups, p'] arrays ("beta", the standard-error column, "t", "p>|t|", "0.025", "0.975"), "r2" / "adj_r2" /
     "is_null" [n_groups] and "features", in the memory space of the inputs.
+    `weights` (one per row, cast and placed like the columns): every group's report is the weighted one (`lin_reg_report(...,
+    weights=w)` on its rows: pl_wls_report); the standard-error column is then "std_err" and `std_err` is ignored.
     """
+    if weights is not None:
+        _check_report_weights(x, target, weights)
+        std_err = "se"
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
+    cols = _Cols(target, x, weights)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     off, off_p = _offsets_arg(cols, group_offsets)
@@ -621,21 +636,29 @@ def lin_reg_report_by(*x, target, group_offsets, add_bias: bool = False, std_err
             yv_p = C.c_void_p(yv.ctypes.data)
         if int(yv.shape[0]) != ng:
             raise ValueError("`y_var` must have one value per group")
-    _lib.check(ctx.fn("pds_lin_reg_report_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng),
-                                                    cols.space, int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), yv_p,
-                                                    C.byref(rep)))
+    if weights is not None:
+        _lib.check(ctx.fn("pds_wls_report_grouped")(ctx._h, cols.cols, cols.weights, cols.n_feat, C.c_int64(cols.n_rows), off_p,
+                                                    C.c_int64(ng), cols.space, int(bool(add_bias)), yv_p, C.byref(rep)))
+    else:
+        _lib.check(ctx.fn("pds_lin_reg_report_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng),
+                                                        cols.space, int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), yv_p,
+                                                        C.byref(rep)))
     return _report_grouped_dict(outs, cols.n_feat, add_bias, std_err, feature_names)
 
 
 def lin_reg_report_by_key(*x, target, key, add_bias: bool = False, std_err: str = "se", max_groups: int | None = None,
-                          feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+                          feature_names: Sequence[str] | None = None, weights=None, ctx: Context | None = None) -> dict:
     """
     `lin_reg_report_by` for an int64 key column in ANY row order (the frame is brought into key order on the device, as
     `lin_reg_by_key` does; nothing moves when the keys are already non-decreasing).  Returns the dict of `lin_reg_report_by`
-    plus "keys" (ascending).  var(y) is always the per-group sample variance.
+    plus "keys" (ascending).  var(y) is always the per-group sample variance.  `weights`: as in `lin_reg_report_by` (with unordered
+    keys they are reordered with the frame).
     """
+    if weights is not None:
+        _check_report_weights(x, target, weights)
+        std_err = "se"
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
+    cols = _Cols(target, x, weights)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
@@ -660,9 +683,13 @@ def lin_reg_report_by_key(*x, target, key, add_bias: bool = False, std_err: str 
             ok = np.empty(cap, dtype=np.int64)
             ok_p = C.c_void_p(ok.ctypes.data)
         outs, rep = _report_grouped_outs(cols, cap, pp)
-        rc = ctx.fn("pds_lin_reg_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
-                                                 int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), C.c_int64(cap), ok_p,
-                                                 C.byref(rep), C.byref(ng))
+        if weights is not None:
+            rc = ctx.fn("pds_wls_report_by_key")(ctx._h, cols.cols, cols.weights, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
+                                                 int(bool(add_bias)), C.c_int64(cap), ok_p, C.byref(rep), C.byref(ng))
+        else:
+            rc = ctx.fn("pds_lin_reg_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
+                                                     int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), C.c_int64(cap), ok_p,
+                                                     C.byref(rep), C.byref(ng))
         if rc != 0 and max_groups is None and int(ng.value) > cap:
             cap = int(ng.value)  # more distinct keys than the first guess
             continue

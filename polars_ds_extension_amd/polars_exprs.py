@@ -163,15 +163,43 @@ def lin_reg_w_rcond(*x, target, add_bias: bool = False, rcond: float = 0.0, l2_r
     return _plugin("pl_lr_w_rcond", cols, kwargs)
 
 
-def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise"):
+def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None):
+    """
+    expr_linear.py:561-631.  `by` (an integer key column, any row order, nulls = one group): every group's report from ONE
+    `pl_lin_reg_report_by` / `pl_wls_report_by` call, in long format -- a Struct {<key>, features, beta, <se>, t, p>|t|, 0.025, 0.975,
+    r2, adj_r2} with p' rows per group, groups in ascending key order: after `unnest` what
+    `group_by(by).agg(lin_reg_report(...)).explode(...)` gives.  var(y) is each group's own.  A group with fewer rows than
+    coefficients keeps its rows with null numeric fields.  Keys of other dtypes or several key columns: `lin_reg_report_by_group`.
+    """
     dt = _dtype()
     t = _formula(target).cast(dt)
     kwargs = {"bias": add_bias, "null_policy": null_policy, "std_err": std_err, "solver": "qr", "l1_reg": 0.0, "l2_reg": 0.0, "tol": 0.0}
     feats: List[Any] = [_formula(z) for z in x]
+    if by is not None:  # (no t.var() input: in front of a keyed call it would be the frame's variance, not the group's)
+        if weights is None:
+            return _plugin("pl_lin_reg_report_by", [_formula(by), t, *feats], kwargs, changes_length=True).alias("lin_reg_report")
+        return _plugin("pl_wls_report_by", [_formula(by), _formula(weights).cast(dt).rechunk(), t, *feats], kwargs,
+                       changes_length=True).alias("lin_reg_report")
     if weights is None:
         return _plugin("pl_lin_reg_report", [t.var(), t, *feats], kwargs, changes_length=True).alias("lin_reg_report")
     return _plugin("pl_wls_report", [_formula(weights).cast(dt).rechunk(), t.var(), t, *feats], kwargs,
                    changes_length=True).alias("lin_reg_report")
+
+
+def lin_reg_report_by_group(df, by, *x, target, **kwargs):
+    """
+    The replacement for `df.group_by(by).agg(pds.lin_reg_report(*x, target=...)).explode(...)` on this backend: ONE plugin call over
+    the whole frame (`lin_reg_report(..., by=)`) instead of one `pl_lin_reg_report` call per group.  `by`: one key column of any
+    dtype or a list of key columns; null keys form one group.  Returns the long frame [*by, features, beta, <se>, t, p>|t|, 0.025,
+    0.975, r2, adj_r2] with p' rows per group; integer keys come back ascending, other keys in order of first appearance
+    (`lin_reg_by_group`'s conventions).
+    """
+    if _is_integer_key(df, by):
+        res = df.select(lin_reg_report(*x, target=target, by=by, **kwargs)).unnest("lin_reg_report")
+        return res.with_columns(_pl().col(by).cast(df.schema[by]))
+    ids, keys = _with_group_ids(df, by)
+    res = ids.select(lin_reg_report(*x, target=target, by=_GID, **kwargs)).unnest("lin_reg_report")
+    return _join(res, keys, on=[_GID]).select([*keys.columns[1:], *res.columns[1:]])
 
 
 def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg: float = 0.0, min_valid_rows: int | None = None,

@@ -3,8 +3,12 @@ Grouped lin_reg_report (pds_lin_reg_report_grouped_*) on one MI355X, inputs resi
 after warm-up, the grouped fit (`lin_reg_by`) on the same frame in the same process, algorithmic bytes and the fraction of 8 TB/s.
 Headline: 1e6 groups x 100 rows x 16 f64 features (and 8), for se / hc1 / hc3.  `--skewed`: one group of most of the rows beside
 many small ones, against the single-frame report on the big group's rows (the case that splits groups across waves).
+`--weights`: the weighted report (pds_wls_report_grouped_*, se only) on the same frame as well; its streams read one more column, so
+its bytes are (p + 2) / (p + 1) of the unweighted call's.  A library without the entry point (an older build in an A/B run) says so
+and times the unweighted calls only.  Every record carries the median, the best and the worst repetition.
 A per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/grouped_report_bench.py ...`.
 Usage: python tools/grouped_report_bench.py [--groups 1000000] [--rows 100] [--feats 16,8] [--se se,hc1,hc3] [--reps 5] [--skewed]
+                                            [--weights]
 """
 import argparse
 import json
@@ -32,7 +36,7 @@ def timed(fn, reps, warm=2):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     ms.sort()
-    return ms[len(ms) // 2], ms[0]
+    return ms[len(ms) // 2], ms[0], ms[-1]
 
 
 def main():
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--se", default="se,hc1,hc3")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skewed", action="store_true")
+    ap.add_argument("--weights", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = pds.Context(0)
@@ -60,22 +65,33 @@ def main():
         else:
             off = torch.arange(0, n + 1, m, dtype=torch.int64, device=dev)
         ng = int(off.numel()) - 1
-        by_ms, _ = timed(lambda: pds.lin_reg_by(*X, target=y, group_offsets=off, add_bias=True, ctx=ctx), a.reps)
+        by_ms, _, _ = timed(lambda: pds.lin_reg_by(*X, target=y, group_offsets=off, add_bias=True, ctx=ctx), a.reps)
         pp = p + 1
         for se in a.se.split(","):
-            ms, best = timed(lambda: pds.lin_reg_report_by(*X, target=y, group_offsets=off, add_bias=True, std_err=se, ctx=ctx),
-                             a.reps)
+            ms, best, worst = timed(lambda: pds.lin_reg_report_by(*X, target=y, group_offsets=off, add_bias=True, std_err=se, ctx=ctx),
+                                    a.reps)
             # the frame is read twice (Gram records, residual pass); outputs: 6 p' values + r2 / adj_r2 per group + the null byte
             nbytes = 2 * n * (p + 1) * 8 + ng * (6 * pp + 2) * 8 + ng
             rec = {"bench": "grouped_report", "shape": "skewed" if a.skewed else "uniform", "groups": ng, "rows": n, "p": p,
-                   "se": se, "ms": round(ms, 3), "ms_best": round(best, 3), "lin_reg_by_ms": round(by_ms, 3),
+                   "se": se, "ms": round(ms, 3), "ms_best": round(best, 3), "ms_worst": round(worst, 3), "lin_reg_by_ms": round(by_ms, 3),
                    "ratio_to_lin_reg_by": round(ms / by_ms, 2), "algorithmic_GB": round(nbytes / 1e9, 2),
                    "fraction_of_8TBps": round(nbytes / (ms * 1e-3) / HBM, 3)}
             if a.skewed:
                 bigX = [c[:big] for c in X]
-                sms, _ = timed(lambda: pds.lin_reg_report(*bigX, target=y[:big], add_bias=True, std_err=se, ctx=ctx), a.reps)
+                sms, _, _ = timed(lambda: pds.lin_reg_report(*bigX, target=y[:big], add_bias=True, std_err=se, ctx=ctx), a.reps)
                 rec["single_report_big_group_ms"] = round(sms, 3)
             print(json.dumps(rec), flush=True)
+        if a.weights and not hasattr(ctx._lib, "pds_wls_report_grouped_f64"):
+            print(json.dumps({"bench": "grouped_wls_report", "p": p, "skipped": "this library has no pds_wls_report_grouped_*"}), flush=True)
+        elif a.weights:
+            w = 0.25 + 3.75 * torch.rand(n, generator=gen, device=dev, dtype=torch.float64)
+            ms, best, worst = timed(lambda: pds.lin_reg_report_by(*X, target=y, group_offsets=off, add_bias=True, weights=w, ctx=ctx), a.reps)
+            nbytes = 2 * n * (p + 2) * 8 + ng * (6 * pp + 2) * 8 + ng
+            print(json.dumps({"bench": "grouped_wls_report", "shape": "skewed" if a.skewed else "uniform", "groups": ng, "rows": n, "p": p,
+                              "se": "se", "ms": round(ms, 3), "ms_best": round(best, 3), "ms_worst": round(worst, 3),
+                              "lin_reg_by_ms": round(by_ms, 3), "ratio_to_lin_reg_by": round(ms / by_ms, 2),
+                              "algorithmic_GB": round(nbytes / 1e9, 2), "fraction_of_8TBps": round(nbytes / (ms * 1e-3) / HBM, 3)}), flush=True)
+            del w
         del X, y
 
 
