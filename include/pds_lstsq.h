@@ -83,7 +83,9 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *   "wide_f32_native" (PDS_WIDE_F32_NATIVE=1) f32 Gram builds beyond 64 features on the f32 matrix instructions (v_mfma_f32_32x32x2_f32,
  *                                             2.5e-7 from the f64 Gram) instead of three exact bf16 planes on the bf16 matrix cores (2e-6).
  *   "report_chunk_groups"                     pds_lin_reg_report_grouped_* / _by_key_*, pds_wls_report_*: groups per pass (<= 0: the default).
- * value: 0 / 1 (report_chunk_groups: a count).  Unknown names are PDS_ERR_INVALID. */
+ *   "glm_split_rows"                          pds_glm_irls_grouped_* / _by_key_*: groups of more rows are fitted by the full-device
+ *                                             iteration, one by one (<= 0: the default, 16384; at least 64).
+ * value: 0 / 1 (report_chunk_groups, glm_split_rows: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host-frame staging (process wide): chunk_mb = bytes of one row chunk of a PDS_HOST frame (default 256, env
  * PDS_HOST_CHUNK_MB); resident_max_mb = largest host frame that pds_lr_pred_* still stages whole (one PCIe trip; larger
@@ -615,6 +617,32 @@ double pds_student_t_ppf(double q, double df);
  * kernel); wider frames write them as two columns and run the weighted wide Gram build on them. */
 int pds_glm_irls_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
                      int variance, double tol, int max_iter, double* coeffs, int* n_iter);
+/*
+ * pds_glm_irls_grouped_* / pds_glm_irls_by_key_*: a GLM per group in one call -- for every group g what pds_glm_irls_* computes on
+ * g's rows alone (faer_irls per group: same start, weights, working response, pivoted-QR weighted solve and stopping rule), all
+ * iterations of a group on chip (grouped_irls.hip: one wave per group; a group of up to 128 rows is read from memory once).
+ * cols = [y, x1..xp], 1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED); f32 frames are fitted in f64 arithmetic.
+ * Outputs, `space`-resident: coeffs [n_groups][n_feat + add_bias] (bias last), n_iter [n_groups] int32, is_null [n_groups] bytes:
+ * 1 for a group with fewer rows than coefficients (NaN coefficients, n_iter = 0) and for a group whose final coefficients are not
+ * all finite (a separated binomial group, NaN / inf in its rows); a bad group never changes another group's bits.
+ * pred / row_null (each nullable, n_rows): the fitted mean g^-1(x . beta_group) of every row in the frame's row order, NaN and
+ * row_null = 1 for the rows of a null group.  Groups longer than the context option "glm_split_rows" are fitted one by one with
+ * the full-device iteration of pds_glm_irls_*.  By key: int64 keys in any row order, groups returned in ascending key order
+ * (ordered keys: nothing moves; unordered keys: sort + gather, per-row outputs sent back through the permutation); *n_groups
+ * receives the number of distinct keys, also when it exceeds max_groups (PDS_ERR_INVALID, nothing fitted).
+ */
+int pds_glm_irls_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                             double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred, uint8_t* row_null);
+int pds_glm_irls_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                             float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null);
+int pds_glm_irls_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, double tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                            double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, double* pred, uint8_t* row_null);
+int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                            float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null);
 /*
  * pds_lin_reg_report_grouped_* / pds_lin_reg_report_by_key_*: `df.group_by(key).agg(pds.lin_reg_report(...))` in one call -- for
  * every group g what pds_lin_reg_report_* returns on g's rows alone (same se_type / add_bias, beta = (X'X)^-1 X'y through the

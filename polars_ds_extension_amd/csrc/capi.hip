@@ -26,6 +26,7 @@ namespace pds {
 #include "capi_multi.hpp"
 #include "capi_rolling.hpp"
 #include "capi_models.hpp"
+#include "capi_glm_grouped.hpp"
 
 }  // namespace pds
 
@@ -122,6 +123,7 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     const std::string n(name);
     if (n == "keyed_sort") ctx->opt_keyed_sort = value != 0;
     else if (n == "wide_f32_native") ctx->opt_wide_f32_native = value != 0;
+    else if (n == "glm_split_rows") ctx->opt_glm_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
@@ -134,6 +136,31 @@ int pds_glm_irls_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_
 int pds_glm_irls_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
                      int variance, float tol, int max_iter, float* coeffs, int* n_iter) {
     return pds::glm_irls_impl<float>(ctx, cols, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs, n_iter);
+}
+
+int pds_glm_irls_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                             double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred, uint8_t* row_null) {
+    return pds::glm_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol, max_iter,
+                                         coeffs, n_iter, is_null, pred, row_null);
+}
+int pds_glm_irls_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                             float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null) {
+    return pds::glm_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol, max_iter,
+                                        coeffs, n_iter, is_null, pred, row_null);
+}
+int pds_glm_irls_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, double tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                            double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, double* pred, uint8_t* row_null) {
+    return pds::glm_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups, out_keys,
+                                        coeffs, n_iter, is_null, n_groups, pred, row_null);
+}
+int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                            float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null) {
+    return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups, out_keys,
+                                       coeffs, n_iter, is_null, n_groups, pred, row_null);
 }
 
 int pds_lr_rowmajor_f64(pds_ctx* ctx, const double* X, int64_t ld, const double* y, int64_t n_rows, int n_feat, pds_space space,

@@ -114,6 +114,7 @@ struct pds_ctx {
     // behaviour switches of the context (pds_ctx_set_option); their defaults come from the environment once, at pds_ctx_create
     bool opt_keyed_sort = false;       // "keyed_sort" / PDS_KEYED_SORT=1: unordered keys always take the sorting route (determinism)
     bool opt_wide_f32_native = false;  // "wide_f32_native" / PDS_WIDE_F32_NATIVE=1: f32 Gram beyond 64 features on the f32 matrix instructions
+    int64_t opt_glm_split_rows = 0;       // "glm_split_rows": groups above this many rows leave the grouped IRLS kernel (0: the default)
     int64_t opt_report_chunk_groups = 0;  // "report_chunk_groups": groups per pass of the grouped report (0: from its record budget)
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -297,6 +298,18 @@ template <typename T>
 int launch_grouped_pred_by_id_table(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_keys,
                                     const int64_t* d_kmin, const uint32_t* d_ids /* dense id of group g */, int64_t n_groups, const T* d_coeffs,
                                     const uint8_t* d_flags, T* d_table /* n_ids x grouped_pred_table_stride(p') workspace */, T* d_pred, T* d_resid, uint8_t* d_row_null);  // grouped_pred.hip
+// ---- grouped_irls.hip: a GLM per group (IRLS), one wave per group, all iterations on chip; 1 .. 16 features.  Groups of more than
+// `split_rows` rows are not fitted: their indices are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it)
+template <typename T>
+int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                        int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
+                        int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
+                        const uint32_t* d_perm /*nullable: row r of the frame in group order is row d_perm[r] of the outputs*/,
+                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+// per-row means g^-1(x . beta) of the rows [r0, r1) from one coefficient vector in device memory
+template <typename T>
+int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
+                          const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream

@@ -13,6 +13,7 @@
 //   * no atomics: per-block partials + a fixed-order finalize kernel => run-to-run bit reproducible.
 #include <type_traits>
 
+#include "glm_dev.hpp"  // link / variance functions of the GLM (WM = 3)
 #include "moments_dev.hpp"
 
 #ifndef PDS_LEV_NB
@@ -20,45 +21,6 @@
 #endif
 
 namespace pds {
-
-// link / variance functions of the GLM (link_functions.rs:5-77): 0 identity / gaussian, 1 log / poisson, 2 logit / binomial,
-// 3 inverse / gamma -- evaluated in T, like the reference's `T: RealField + Float`
-template <typename T>
-__device__ __forceinline__ T glm_link(int link, T mu) {
-    switch (link) {
-        case 1: return (T)log(mu);
-        case 2: return (T)log(mu / (T(1) - mu));
-        case 3: return T(1) / mu;
-        default: return mu;
-    }
-}
-template <typename T>
-__device__ __forceinline__ T glm_inv(int link, T eta) {
-    switch (link) {
-        case 1: return (T)exp(eta);
-        case 2: { const T e = (T)exp(eta); return e / (T(1) + e); }
-        case 3: return T(1) / eta;
-        default: return eta;
-    }
-}
-template <typename T>
-__device__ __forceinline__ T glm_deriv(int link, T mu) {
-    switch (link) {
-        case 1: return T(1) / mu;
-        case 2: return T(1) / (mu * (T(1) - mu));
-        case 3: { const T r = T(1) / mu; return -(r * r); }
-        default: return T(1);
-    }
-}
-template <typename T>
-__device__ __forceinline__ T glm_var(int variance, T mu) {
-    switch (variance) {
-        case 1: return mu;
-        case 2: return mu * (T(1) - mu);
-        case 3: return mu * mu;
-        default: return T(1);
-    }
-}
 
 // =============================================================================================
 // single big system: grid-stride over 128-row (f64) / 256-row (f32) tiles, register prefetch of the

@@ -1,0 +1,270 @@
+// plugin_glm.hpp -- pl_logistic_coeffs / pl_logistic_pred (the reference's symbols, src/num_ext/logistic_regression.rs) and the
+// key-aware pl_glm_by / pl_glm_by_pred (+ _f32): GLM fits by IRLS through pds_glm_irls_grouped_* / pds_glm_irls_by_key_*
+// Part of the one translation unit plugin.cpp (included there, inside its anonymous namespace, after plugin_exprs.hpp).
+#pragma once
+
+template <typename T> struct GlmApi;
+template <> struct GlmApi<double> {
+    static constexpr auto grouped = pds_glm_irls_grouped_f64;
+    static constexpr auto by_key = pds_glm_irls_by_key_f64;
+};
+template <> struct GlmApi<float> {
+    static constexpr auto grouped = pds_glm_irls_grouped_f32;
+    static constexpr auto by_key = pds_glm_irls_by_key_f32;
+};
+
+// family -> (link, variance) ids of include/pds_lstsq.h, the names of linear_models.GLM_FAMILIES
+inline void glm_family_codes(const std::string& family, int* link, int* variance) {
+    std::string s;
+    for (char c : family) s.push_back((char)std::tolower((unsigned char)c));
+    int id = -1;
+    if (s == "gaussian" || s == "normal") id = 0;
+    else if (s == "poisson") id = 1;
+    else if (s == "binomial" || s == "logistic") id = 2;
+    else if (s == "gamma") id = 3;
+    if (id < 0) raise("unknown GLM family '" + family + "': gaussian / normal, poisson, binomial / logistic, gamma");
+    *link = id;
+    *variance = id;
+}
+
+// test seam: the first capacity guess of pl_glm_by (<= 0: the default rule of do_lr_by), so that the retry can be exercised
+int64_t g_glm_by_first_cap = 0;
+
+// ------------------------------------------------------------------------------------------------- pl_glm_by / pl_glm_by_pred (new)
+// inputs: [key (integer, any row order, nulls = one group), y, x1..xp]; kwargs bias, null_policy, family, tol, max_iter.
+// pl_glm_by: Struct{<key>, coeffs: List<T>, n_iter: Int32}, one row per group, keys ascending (the null key's group last, with a null
+// key), a null list for a null group (fewer rows than coefficients, or a fit that does not end in finite coefficients).
+// pl_glm_by_pred: the fitted mean of every row, row for row, null where the row's group is null or a null policy dropped the row.
+// Null-free frames make ONE pds_glm_irls_by_key_* call (capacity guess and one retry as do_lr_by); frames with nulls are prepared on
+// the host as do_report_by prepares them -- rows in key order, the policy applied row by row inside every group ("skip" drops a row
+// with any null, a fill policy fills the features and drops the rows whose target is null, "ignore" keeps the rows with NaN for the
+// nulls: that group's fit is not finite, so it is a null group) -- and go to the offsets entry point.
+template <typename T>
+void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
+    if (n_in < 3) raise("pl_glm_by needs a key, a target and at least one feature");
+    int link = 0, variance = 0;
+    glm_family_codes(kw_str(kw, "family", "gaussian"), &link, &variance);
+    const int max_iter = (int)kw_i64(kw, "max_iter", 100);
+    if (max_iter < 1) raise("`max_iter` must be > 1.");
+    const T tol = (T)std::fabs(kw_f64(kw, "tol", 1e-8));
+    const int bias = kw_bool(kw, "bias") ? 1 : 0;
+    const int n_feat = (int)n_in - 2;
+    if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
+    const int pp = n_feat + bias;
+    auto key = import_series<int64_t>(in[0]);
+    std::vector<Column<T>> cols;  // [y, x1..xp]
+    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
+    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
+    bool any_null = false;
+    for (auto& c : cols) any_null |= c.null_count > 0;
+    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
+    const int64_t n = key.size();
+    for (auto& c : cols)
+        if (c.size() != n) raise("input columns differ in length");
+    if (n == 0) raise("Empty data");
+    int64_t null_stand_in = 0;
+    const bool null_group = null_key_stand_in(key, n, "pl_glm_by", &null_stand_in);
+    const int64_t* ikey = key.data();
+    RawVec<int64_t> keys;
+    ByteVec cobuf, itbuf, pred_b;
+    RawVec<uint8_t> nulls, row_null;
+    std::vector<uint8_t> row_valid;  // pred: one validity byte per row of the frame
+    int64_t ng = 0;
+    if (!any_null) {
+        std::vector<const T*> ptrs;
+        for (auto& c : cols) ptrs.push_back(c.data());
+        if (want_pred) {
+            pred_b = raw_buffer<T>((size_t)n);
+            row_null.resize(n);
+        }
+        int64_t cap = g_glm_by_first_cap > 0 ? std::min<int64_t>(g_glm_by_first_cap, n)
+                                             : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
+        for (int attempt = 0;; ++attempt) {
+            keys.resize(cap);
+            cobuf = raw_buffer<T>((size_t)cap * pp);
+            itbuf = raw_buffer<int32_t>((size_t)cap);
+            nulls.resize(cap);
+            const int rc = GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
+                                             keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, want_pred ? as<T>(pred_b) : nullptr,
+                                             want_pred ? row_null.data() : nullptr);
+            if (rc != 0 && attempt == 0 && ng > cap) {
+                cap = ng;
+                continue;
+            }
+            check(rc);
+            break;
+        }
+        if (want_pred) {
+            row_valid.resize((size_t)n);
+            for (int64_t i = 0; i < n; ++i) row_valid[i] = row_null[i] ? 0 : 1;
+        }
+    } else {
+        std::vector<int64_t> perm(n);
+        for (int64_t i = 0; i < n; ++i) perm[i] = i;
+        bool ordered = true;
+        for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
+        if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
+        const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
+        const size_t nc = cols.size();
+        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
+        std::vector<std::vector<T>> kept(nc);
+        for (auto& v : kept) v.reserve((size_t)n);
+        std::vector<int64_t> off, src_row;
+        src_row.reserve((size_t)n);
+        const T nanv = std::numeric_limits<T>::quiet_NaN();
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t r = perm[i];
+            if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
+                off.push_back((int64_t)kept[0].size());
+                keys.push_back(ikey[r]);
+            }
+            bool keep = true;
+            if (skip)
+                for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
+            else if (fill)
+                keep = !is_null(0, r);
+            if (!keep) continue;
+            for (size_t c = 0; c < nc; ++c) kept[c].push_back(is_null(c, r) ? (fill ? (T)pol.fill : nanv) : cols[c].data()[r]);
+            src_row.push_back(r);
+        }
+        off.push_back((int64_t)kept[0].size());
+        ng = (int64_t)keys.size();
+        const int64_t nk = (int64_t)kept[0].size();
+        if (nk == 0) raise("Empty data");
+        std::vector<const T*> ptrs;
+        for (auto& v : kept) ptrs.push_back(v.data());
+        cobuf = raw_buffer<T>((size_t)ng * pp);
+        itbuf = raw_buffer<int32_t>((size_t)ng);
+        nulls.resize(ng);
+        ByteVec pk;
+        RawVec<uint8_t> rk;
+        if (want_pred) {
+            pk = raw_buffer<T>((size_t)nk);
+            rk.resize(nk);
+        }
+        check(GlmApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter,
+                                 as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), want_pred ? as<T>(pk) : nullptr,
+                                 want_pred ? rk.data() : nullptr));
+        if (want_pred) {  // back to the frame's rows: a dropped row is a null row
+            pred_b = raw_buffer<T>((size_t)n);
+            row_valid.assign((size_t)n, 0);
+            T* pd = as<T>(pred_b);
+            for (int64_t i = 0; i < n; ++i) pd[i] = nanv;
+            const T* ps = as<T>(pk);
+            for (int64_t k = 0; k < nk; ++k) {
+                pd[src_row[k]] = ps[k];
+                row_valid[src_row[k]] = rk[k] ? 0 : 1;
+            }
+        }
+    }
+    if (want_pred) {
+        bool all_valid = true;
+        for (int64_t i = 0; i < n && all_valid; ++i) all_valid = row_valid[i] != 0;
+        export_series(out, make_schema(fmt_of<T>(), "pred"), prim_array_take<T>(std::move(pred_b), n, all_valid ? nullptr : row_valid.data()));
+        return;
+    }
+    std::vector<uint8_t> ok(ng);
+    for (int64_t g = 0; g < ng; ++g) ok[g] = nulls[g] ? 0 : 1;
+    std::vector<std::unique_ptr<ArrowArray>> kids;
+    {
+        std::vector<uint8_t> kvalid;
+        if (null_group) {
+            kvalid.assign(ng, 1);
+            for (int64_t g = 0; g < ng; ++g)
+                if (keys[g] == null_stand_in) kvalid[g] = 0;
+        }
+        kids.push_back(prim_array_take<int64_t>(bytes_of(keys.data(), (size_t)ng), ng, null_group ? kvalid.data() : nullptr));
+    }
+    kids.push_back(list_array_take_rows<T>(std::move(cobuf), ng, pp, ok.data()));
+    kids.push_back(prim_array_take<int32_t>(std::move(itbuf), ng, nullptr));
+    std::vector<std::unique_ptr<ArrowSchema>> sk;
+    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(list_schema<T>("coeffs"));
+    sk.push_back(make_schema("i", "n_iter"));
+    export_series(out, make_schema("+s", "", std::move(sk)), struct_array(ng, std::move(kids)));
+}
+
+// ------------------------------------------------------------------------------------------------- pl_logistic_coeffs / pl_logistic_pred
+// inputs [y, x1..xp] (Float64, as the reference casts them), kwargs = the reference's lr_kwargs dict (bias, null_policy, l1_reg,
+// l2_reg, solver, tol, max_iter).  Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random
+// start; this backend runs IRLS (binomial family, logit link) to the same unpenalised maximum-likelihood point through
+// pds_glm_irls_grouped_f64 with ONE group (offsets [0, n]): a frame above the context's glm_split_rows takes the full-device
+// iteration, a shorter one the one-wave kernel.  A positive l1_reg / l2_reg is an error, not an unpenalised fit.
+// Nulls as series_to_mat_for_lr's mask has them (logistic_regression.rs:76-94): "skip" fits on the rows without a null, a fill policy
+// fills the features and drops the rows whose target is null; pred is null where the mask drops a row.
+inline void do_logistic(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
+    if (n_in < 2) raise("pl_logistic needs a target and at least one feature");
+    if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0) raise("logistic_reg: l1_reg / l2_reg are not supported on this backend");
+    const int max_iter = (int)kw_i64(kw, "max_iter", 200);
+    if (max_iter < 1) raise("Input `max_iter` must be a positive.");
+    const double tol = std::fabs(kw_f64(kw, "tol", 1e-5));
+    const int bias = kw_bool(kw, "bias") ? 1 : 0;
+    const int n_feat = (int)n_in - 1, pp = n_feat + bias;
+    std::vector<Column<double>> cols = import_all<double>(in, n_in);
+    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
+    bool any_null = false;
+    for (auto& c : cols) any_null |= c.null_count > 0;
+    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
+    const int64_t n = cols[0].size();
+    for (auto& c : cols)
+        if (c.size() != n) raise("input columns differ in length");
+    if (n == 0) raise("Empty data");
+    std::vector<int64_t> src_row;  // non-empty: the fit runs on these rows of the frame
+    std::vector<std::vector<double>> kept;
+    std::vector<const double*> ptrs;
+    int64_t nk = n;
+    if (any_null) {
+        const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
+        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
+        kept.resize(cols.size());
+        const double nanv = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t r = 0; r < n; ++r) {
+            bool keep = true;
+            if (skip)
+                for (size_t c = 0; c < cols.size() && keep; ++c) keep = !is_null(c, r);
+            else if (fill)
+                keep = !is_null(0, r);
+            if (!keep) continue;
+            for (size_t c = 0; c < cols.size(); ++c) kept[c].push_back(is_null(c, r) ? (fill ? pol.fill : nanv) : cols[c].data()[r]);
+            src_row.push_back(r);
+        }
+        nk = (int64_t)src_row.size();
+        for (auto& v : kept) ptrs.push_back(v.data());
+    } else {
+        for (auto& c : cols) ptrs.push_back(c.data());
+    }
+    if (nk == 0) raise("Empty data");
+    if (nk < pp) raise("#Data < #features. No conclusive result.");
+    const int64_t off[2] = {0, nk};
+    ByteVec cobuf = raw_buffer<double>((size_t)pp), pk;
+    int32_t its = 0;
+    uint8_t gnull = 0;
+    RawVec<uint8_t> rk;
+    if (want_pred) {
+        pk = raw_buffer<double>((size_t)nk);
+        rk.resize(nk);
+    }
+    check(pds_glm_irls_grouped_f64(thread_ctx(), ptrs.data(), n_feat, nk, off, 1, PDS_HOST, bias, 2, 2, tol, max_iter, as<double>(cobuf), &its,
+                                   &gnull, want_pred ? as<double>(pk) : nullptr, want_pred ? rk.data() : nullptr));
+    if (!want_pred) {
+        const uint8_t ok = 1;  // (a fit that did not end in finite coefficients shows them as they are)
+        std::vector<int64_t> lo = {0, (int64_t)pp};
+        export_series(out, list_schema<double>("coeffs"), list_array<double>(lo, &ok, as<double>(cobuf), pp));
+        return;
+    }
+    if (src_row.empty() && !gnull) {
+        export_series(out, make_schema("g", "pred"), prim_array_take<double>(std::move(pk), n, nullptr));
+        return;
+    }
+    ByteVec pf = raw_buffer<double>((size_t)n);
+    std::vector<uint8_t> valid((size_t)n, 0);
+    double* pd = as<double>(pf);
+    for (int64_t i = 0; i < n; ++i) pd[i] = std::numeric_limits<double>::quiet_NaN();
+    const double* ps = as<double>(pk);
+    for (int64_t k = 0; k < nk; ++k) {
+        const int64_t r = src_row.empty() ? k : src_row[k];
+        pd[r] = ps[k];
+        valid[r] = rk[k] ? 0 : 1;
+    }
+    export_series(out, make_schema("g", "pred"), prim_array_take<double>(std::move(pf), n, valid.data()));
+}

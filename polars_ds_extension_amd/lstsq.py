@@ -21,7 +21,7 @@ from . import _lib, config
 
 __all__ = [
     "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
-    "recursive_lin_reg_by_key",
+    "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "logistic_reg",
     "recursive_lin_reg", "lin_reg_w_rcond", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
@@ -109,7 +109,8 @@ class Context:
         _lib.check(self._lib.pds_ctx_synchronize(self._h))
 
     def set_option(self, name: str, value) -> None:
-        """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native"; the
+        """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
+        "glm_split_rows"; the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
 
@@ -1352,3 +1353,165 @@ def lin_reg_from_moments(moments, *, add_bias: bool = False, l1_reg: float = 0.0
     _lib.check(ctx.fn("pds_lr_from_moments")(ctx._h, mp, space, p, C.byref(prm), C.c_void_p(coeffs.ctypes.data),
                                              C.byref(is_null)))
     return None if is_null.value else coeffs
+
+
+# ---------------------------------------------------------------------------------------------
+# GLM per group (IRLS) and logistic_reg
+# ---------------------------------------------------------------------------------------------
+def _glm_family(family):
+    from .linear_models import GLM_FAMILIES  # (linear_models imports this module)
+
+    if family not in GLM_FAMILIES:
+        raise NotImplementedError(f"GLM family {family!r}: one of {sorted(GLM_FAMILIES)}")  # as GLM.__init__
+    return GLM_FAMILIES[family]
+
+
+def _glm_check(x, max_iter, what):
+    if max_iter < 1:
+        raise ValueError("`max_iter` must be > 1.")  # GLM.__init__ (linear_models.py:756-757 of the reference)
+    if len(x) < 1:
+        raise ValueError(f"{what}: need at least one feature column")
+    if len(x) > 16:
+        raise NotImplementedError("grouped GLM (IRLS): up to 16 feature columns")
+
+
+def _out_i32(cols: _Cols, n):
+    if cols.space == _lib.PDS_DEVICE:
+        import torch
+
+        t = torch.empty(n, dtype=torch.int32, device=cols.keep[0].device)
+        return t, C.c_void_p(int(t.data_ptr()))
+    a = np.empty(n, dtype=np.int32)
+    return a, C.c_void_p(a.ctypes.data)
+
+
+def _tol_arg(tol):
+    return C.c_double(abs(float(tol))) if config.LIN_REG_EXPR_F64 else C.c_float(abs(float(tol)))
+
+
+def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+           return_pred: bool = False, ctx: Context | None = None):
+    """
+    One GLM per group in one call: for every group g = rows [group_offsets[g], group_offsets[g+1]) what `GLM(family=...).fit` computes
+    on g's rows alone (iteratively re-weighted least squares, the reference's faer_irls), every iteration of a group on chip
+    (`pds_glm_irls_grouped_*`).  Families as `linear_models.GLM_FAMILIES`; 1 .. 16 feature columns.
+    Returns (coeffs [G, p'] bias last, n_iter [G] int32, is_null [G]) in the memory space of the inputs, plus (pred [n_rows],
+    row_null [n_rows]) with `return_pred`: the fitted mean g^-1(x . beta_group) of every row.  A group with fewer rows than
+    coefficients, or whose fit does not end in finite coefficients (a separated binomial group, NaN / inf in its rows), is null:
+    is_null = 1 (NaN pred, row_null = 1).
+    """
+    _glm_check(x, max_iter, "glm_by")
+    link, var = _glm_family(family)
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    off, off_p = _offsets_arg(cols, group_offsets)
+    ng = int(off.shape[0]) - 1
+    coeffs, co_p = _out_like(cols, (ng, pp))
+    iters, it_p = _out_i32(cols, ng)
+    nulls, nu_p = _out_u8(cols, ng)
+    pred = rnull = None
+    pr_p = rn_p = None
+    if return_pred:
+        pred, pr_p = _out_like(cols, cols.n_rows)
+        rnull, rn_p = _out_u8(cols, cols.n_rows)
+    _lib.check(ctx.fn("pds_glm_irls_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
+                                              int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)),
+                                              co_p, it_p, nu_p, pr_p, rn_p))
+    if return_pred:
+        return coeffs, iters, nulls, pred, rnull
+    return coeffs, iters, nulls
+
+
+def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+               return_pred: bool = False, max_groups: int | None = None, ctx: Context | None = None):
+    """
+    `glm_by` for an integer key column in ANY row order (`pds_glm_irls_by_key_*`): the frame is brought into key order on the device
+    (nothing moves when the keys are already non-decreasing), every group is fitted, per-row means come back at the rows' own
+    positions.  Returns (keys [G] ascending, coeffs, n_iter, is_null), plus (pred, row_null) with `return_pred`.
+    """
+    _glm_check(x, max_iter, "glm_by_key")
+    link, var = _glm_family(family)
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    n_rows = cols.n_rows
+    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
+    if cols.space == _lib.PDS_DEVICE:
+        import torch
+
+        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
+        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
+        k_p = C.c_void_p(int(k.data_ptr()))
+    else:
+        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
+        k_p = C.c_void_p(k.ctypes.data)
+    if int(k.shape[0]) != n_rows:
+        raise ValueError("`key` must have one entry per row")
+    pred = rnull = None
+    pr_p = rn_p = None
+    if return_pred:
+        pred, pr_p = _out_like(cols, n_rows)
+        rnull, rn_p = _out_u8(cols, n_rows)
+    ng = C.c_int64(0)
+    while True:
+        if cols.space == _lib.PDS_DEVICE:
+            ok = torch.empty(cap, dtype=torch.int64, device=k.device)
+            ok_p = C.c_void_p(int(ok.data_ptr()))
+        else:
+            ok = np.empty(cap, dtype=np.int64)
+            ok_p = C.c_void_p(ok.ctypes.data)
+        coeffs, co_p = _out_like(cols, (cap, pp))
+        iters, it_p = _out_i32(cols, cap)
+        nulls, nu_p = _out_u8(cols, cap)
+        rc = ctx.fn("pds_glm_irls_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
+                                           C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p,
+                                           co_p, it_p, nu_p, C.byref(ng), pr_p, rn_p)
+        if rc != 0 and max_groups is None and int(ng.value) > cap:
+            cap = int(ng.value)  # more distinct keys than the first guess
+            continue
+        _lib.check(rc)
+        break
+    g = int(ng.value)
+    if return_pred:
+        return ok[:g], coeffs[:g], iters[:g], nulls[:g], pred, rnull
+    return ok[:g], coeffs[:g], iters[:g], nulls[:g]
+
+
+def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,
+                 return_pred: bool = False, ctx: Context | None = None):
+    """
+    `pds.logistic_reg` (expr_linear.py:277-353 of the reference): the reference's signature and defaults; returns the coefficients
+    (bias last) as a NumPy vector whatever the inputs' memory space (one model: `pds_glm_irls_*` hands them to the host, as
+    `GLM.fit` takes them), or with `return_pred` the fitted probabilities of every row in the inputs' memory space.
+    Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random start and stops at a gradient
+    norm; this backend runs IRLS (binomial family, logit link, `pds_glm_irls_*` on the whole frame) to the same unpenalised
+    maximum-likelihood point and stops when no coefficient moves by `tol`.  The two agree to the reference's own test tolerance, not
+    bit for bit.  Penalised fits (`l1_reg` / `l2_reg` > 0) are not supported and raise rather than return an unpenalised fit.
+    """
+    if l1_reg > 0.0 or l2_reg > 0.0:
+        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend")
+    if max_iter <= 0:
+        raise ValueError("Input `max_iter` must be a positive.")  # expr_linear.py:231-232
+    if len(x) < 1:
+        raise ValueError("logistic_reg: need at least one feature column")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    co = np.empty(pp, dtype=_dtype())
+    n_iter = C.c_int(0)
+    _lib.check(ctx.fn("pds_glm_irls")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(bool(add_bias)), C.c_int(2),
+                                      C.c_int(2), _tol_arg(tol), C.c_int(int(max_iter)), C.c_void_p(co.ctypes.data), C.byref(n_iter)))
+    if not return_pred:
+        return co
+    if cols.space == _lib.PDS_DEVICE:
+        import torch
+
+        b = torch.as_tensor(co, device=cols.keep[0].device)
+        eta = torch.stack(cols.keep[1:1 + cols.n_feat], dim=1) @ b[:cols.n_feat]
+        return torch.sigmoid(eta + b[-1] if add_bias else eta)
+    eta = np.stack(cols.keep[1:1 + cols.n_feat], axis=1) @ co[:cols.n_feat] + (co[-1] if add_bias else 0.0)
+    return 1.0 / (1.0 + np.exp(-eta))

@@ -3,7 +3,8 @@ Polars expression builders that route through libpds_lstsq_hip.so's `_polars_plu
 
 Same call signatures as /root/reference/python/polars_ds/exprs/expr_linear.py (`lin_reg` :105-274 incl. the multi-target
 form, `lin_reg_w_rcond` :356-410, `lin_reg_report` :561-631, `rolling_lin_reg` :482-558, `recursive_lin_reg` :413-479) plus the key-aware
-`lin_reg(..., by=key)` of SURVEY.md 8(b) and `lin_reg_by_group`, the frame-level replacement of `group_by().agg(lin_reg)`.
+`lin_reg(..., by=key)` of SURVEY.md 8(b) and `lin_reg_by_group`, the frame-level replacement of `group_by().agg(lin_reg)`,
+`logistic_reg` (:277-353) and the grouped GLM fits `logistic_reg(..., by=key)` / `glm_by_group`.
 Importing this module needs `polars` (>= 1.4), which is NOT installable in the build image: tests/test_polars_exprs.py runs
 every builder end to end with tests/mini_polars standing in for the engine (it implements the documented plugin calling
 convention and the per-group evaluation of `group_by().agg()`); against a REAL Polars the module is still unverified.
@@ -200,6 +201,74 @@ def lin_reg_report_by_group(df, by, *x, target, **kwargs):
     ids, keys = _with_group_ids(df, by)
     res = ids.select(lin_reg_report(*x, target=target, by=_GID, **kwargs)).unnest("lin_reg_report")
     return _join(res, keys, on=[_GID]).select([*keys.columns[1:], *res.columns[1:]])
+
+
+def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,
+                 null_policy: str = "skip", return_pred: bool = False, by=None):
+    """
+    expr_linear.py:277-353: `pl_logistic_coeffs` / `pl_logistic_pred` (Float64 only, as there), aliases `__coeffs__` / `__pred__`.
+    Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random start and stops at a gradient
+    norm; this backend runs IRLS (binomial family) to the same unpenalised maximum-likelihood point and stops when no coefficient
+    moves by `tol`.  `l1_reg` / `l2_reg` > 0 raise rather than return an unpenalised fit.
+    `by` (an integer key column, any row order, nulls = one group): one logistic model per group from ONE `pl_glm_by` /
+    `pl_glm_by_pred` call with family "binomial" -- Struct{<key>, coeffs, n_iter} per group, keys ascending, or the fitted
+    probability of every row.  Keys of other dtypes or several key columns: `glm_by_group`.
+    """
+    if l1_reg > 0.0 or l2_reg > 0.0:
+        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend")
+    if max_iter <= 0:
+        raise ValueError("Input `max_iter` must be a positive.")
+    if by is not None:
+        return _glm_by(x, target, by, "binomial", add_bias, abs(tol), max_iter, null_policy, return_pred)
+    from polars.plugins import register_plugin_function
+
+    pl = _pl()
+    kwargs = {"bias": add_bias, "null_policy": null_policy, "l1_reg": l1_reg, "l2_reg": l2_reg, "solver": "", "tol": abs(tol),
+              "max_iter": max_iter}
+    cols = [_formula(target).cast(pl.Float64)] + [_formula(z) for z in x]
+    if return_pred:
+        return register_plugin_function(plugin_path=PLUGIN_PATH, function_name="pl_logistic_pred", args=cols, kwargs=kwargs,
+                                        pass_name_to_apply=True).alias("__pred__")
+    return register_plugin_function(plugin_path=PLUGIN_PATH, function_name="pl_logistic_coeffs", args=cols, kwargs=kwargs,
+                                    pass_name_to_apply=True).alias("__coeffs__")
+
+
+def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_pred):
+    from .linear_models import GLM_FAMILIES
+
+    if family not in GLM_FAMILIES:
+        raise NotImplementedError(f"GLM family {family!r}: one of {sorted(GLM_FAMILIES)}")
+    if max_iter < 1:
+        raise ValueError("`max_iter` must be > 1.")
+    kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
+    cols = [_formula(by), _formula(target).cast(_dtype())] + [_formula(z) for z in x]
+    if return_pred:
+        return _plugin("pl_glm_by_pred", cols, kwargs).alias("glm_pred")
+    return _plugin("pl_glm_by", cols, kwargs, changes_length=True).alias("glm_by")
+
+
+def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool = False, add_bias: bool = False, tol: float = 1e-8,
+                 max_iter: int = 100, null_policy: str = "raise"):
+    """
+    One GLM per group of a frame (families of `linear_models.GLM_FAMILIES`) from ONE plugin call (`pl_glm_by`: keys in any row
+    order, every iteration of a group on chip) -- what fitting `GLM(family=...)` on every group of `df.group_by(by)` computes.
+    `by`: one key column of any dtype or a list of key columns; null keys form one group, as in Polars (`lin_reg_by_group`'s
+    conventions).  Returns a frame with one row per distinct key: columns *by, `coeffs` (bias last; a null list for a group with
+    fewer rows than coefficients or a fit that does not end in finite coefficients) and `n_iter`; integer keys come back ascending,
+    other keys in order of first appearance.  `return_pred=True`: the input frame with a `glm_pred` column, row for row.
+    """
+    args = (family, add_bias, tol, max_iter, null_policy)
+    if return_pred:
+        if _is_integer_key(df, by):
+            return df.with_columns(_glm_by(x, target, by, *args, True))
+        ids, _ = _with_group_ids(df, by)
+        return ids.with_columns(_glm_by(x, target, _GID, *args, True)).drop(_GID)
+    if _is_integer_key(df, by):
+        res = df.select(_glm_by(x, target, by, *args, False)).unnest("glm_by")
+        return res.with_columns(_pl().col(by).cast(df.schema[by]))
+    ids, keys = _with_group_ids(df, by)
+    res = ids.select(_glm_by(x, target, _GID, *args, False)).unnest("glm_by")
+    return _join(keys, res, on=[_GID]).drop(_GID)
 
 
 def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg: float = 0.0, min_valid_rows: int | None = None,
