@@ -29,32 +29,23 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     const bool host_out = space == PDS_HOST;
     const int64_t split = std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
     const int64_t long_cap = std::min<int64_t>(n_groups, n_rows / split + 1);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
     size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)long_cap * 8) + 256;
     if (host_frame) need += col_bytes * nc;
     if (host_out) need += up((size_t)(n_groups + 1) * 8) + up((size_t)n_groups * pp * sizeof(T)) + up((size_t)n_groups * 4) + up((size_t)n_groups) +
                           (pred ? col_bytes : 0) + (row_null ? up((size_t)n_rows) : 0);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->wkeyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
+    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     // ---- the frame: device pointers in the kernels' order x_0 .. x_{p-1}, y
-    std::vector<const T*> src(nc);  // reference order [y, x1..xp], device resident
-    for (int c = 0; c < nc; ++c) {
-        src[c] = cols[c];
-        if (host_frame) {
-            T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d, cols[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = d;
-        }
-    }
-    std::vector<const T*> tbl(18, src[0]);
-    for (int c = 0; c < n_feat; ++c) tbl[c] = src[c + 1];
-    tbl[n_feat] = src[0];
-    const T** d_tbl = reinterpret_cast<const T**>(take(sizeof(T*) * tbl.size()));
-    PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), sizeof(T*) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
-    int64_t* d_long = reinterpret_cast<int64_t*>(take((size_t)long_cap * 8));
-    unsigned* d_count = reinterpret_cast<unsigned*>(take(256));
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
+    if (host_frame)
+        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
+    std::vector<const T*> tbl;
+    const T** d_tbl = nullptr;
+    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+    int64_t* d_long = w.take<int64_t>((size_t)long_cap);
+    unsigned* d_count = w.take<unsigned>(64);
     PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
     const int64_t* d_off = offsets;
     T* d_co = coeffs;
@@ -63,14 +54,14 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     T* d_pred = pred;
     uint8_t* d_rn = row_null;
     if (host_out) {
-        int64_t* t = reinterpret_cast<int64_t*>(take((size_t)(n_groups + 1) * 8));
+        int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
         PDS_HIP_CHECK(hipMemcpyAsync(t, offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         d_off = t;
-        d_co = reinterpret_cast<T*>(take((size_t)n_groups * pp * sizeof(T)));
-        d_it = reinterpret_cast<int32_t*>(take((size_t)n_groups * 4));
-        d_nu = reinterpret_cast<uint8_t*>(take((size_t)n_groups));
-        if (pred) d_pred = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        if (row_null) d_rn = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+        d_co = w.take<T>((size_t)n_groups * pp);
+        d_it = w.take<int32_t>((size_t)n_groups);
+        d_nu = w.take<uint8_t>((size_t)n_groups);
+        if (pred) d_pred = w.take<T>((size_t)n_rows);
+        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
     }
     if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
                                         d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap))
@@ -143,108 +134,37 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
         if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
-    // ---- keys on the device, and are they already in order?
-    const int64_t* d_keys = keys;
-    if (space == PDS_HOST) {
-        if (int rc = ensure_ws(ctx, ctx->stage, key_bytes + 256)) return rc;
-        PDS_HIP_CHECK(hipMemcpyAsync(ctx->stage.ptr, keys, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = static_cast<const int64_t*>(ctx->stage.ptr);
-    }
-    if (int rc = ensure_pinned(ctx, 4096)) return rc;
-    const size_t run_slots = key_run_slots(n_rows);
-    const size_t mask_bytes = key_run_mask_bytes(n_rows);
-    if (int rc = ensure_ws(ctx, ctx->solve_ws, 8192 + 2 * up((run_slots + 1) * sizeof(uint32_t)) + mask_bytes)) return rc;
-    bool sorted = false;
-    int64_t mm[2] = {0, 0};
-    int64_t n_runs = 0;
-    int64_t* d_state = reinterpret_cast<int64_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 256);
-    int64_t* d_minmax = d_state + 2;
-    uint32_t* d_run_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096);
-    uint32_t* d_run_prefix = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096 + up((run_slots + 1) * sizeof(uint32_t)));
-    unsigned long long* d_run_masks =
-        reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096 + 2 * up((run_slots + 1) * sizeof(uint32_t)));
-    if (int rc = keys_order_minmax(ctx, d_keys, n_rows, d_state, &sorted, mm, d_run_counts, d_run_masks, &n_runs)) return rc;
-    if (!sorted && n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "keyed grouping of unordered keys: fewer than 2^31 rows per call");
+    KeyOrder ko;
+    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
     const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const size_t temp_bytes = sorted ? keyed_ordered_temp_bytes(n_rows) : keyed_temp_bytes(n_rows);
-    const int64_t run_cap = sorted ? std::min<int64_t>(n_runs + 1, cap) : n_rows;
-    size_t need = temp_bytes + 3 * up((size_t)(run_cap + 1) * 8) + 8192;
-    if (space == PDS_HOST) need += col_bytes * nc + up((size_t)cap * pp * sizeof(T)) + up((size_t)cap * 4) + up((size_t)cap) + col_bytes + up((size_t)n_rows);
-    if (!sorted) need += 2 * key_bytes + 2 * idx_bytes + col_bytes * nc + up((size_t)n_rows * nc * sizeof(T)) + up(2 * (size_t)nc * sizeof(T*)) + 1024;
+    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
+    size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap);
+    if (space == PDS_HOST)
+        need += Bump::up((size_t)cap * pp * sizeof(T)) + Bump::up((size_t)cap * 4) + Bump::up((size_t)cap) + Bump::up((size_t)n_rows * sizeof(T)) +
+                Bump::up((size_t)n_rows);
     if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->keyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    void* d_temp = take(temp_bytes);
-    int64_t* d_unique = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
-    std::vector<const T*> src(nc);  // reference order [y, x1..xp], device resident
-    for (int c = 0; c < nc; ++c) {
-        src[c] = cols[c];
-        if (space == PDS_HOST) {
-            T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d, cols[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = d;
-        }
-    }
-    const uint32_t* d_perm = nullptr;
-    int64_t ng = 0;
-    if (!sorted) {
-        int64_t* sk = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        uint32_t* idx_in = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        uint32_t* perm = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        int64_t* sk2 = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        if (int rc = keyed_sort(ctx, d_keys, n_rows, idx_in, sk, perm, d_temp, temp_bytes, sk2, d_minmax, mm)) return rc;
-        d_perm = perm;
-        if (!gather_frame_fits<T>(nc)) {
-            for (int c = 0; c < nc; ++c) {
-                T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (int rc = launch_gather_rows<T>(ctx, src[c], perm, n_rows, d)) return rc;
-                src[c] = d;
-            }
-        } else {  // transpose to row-major records, then one random access per ROW (keyed.hip)
-            std::vector<const T*> tbl(2 * (size_t)nc);
-            for (int c = 0; c < nc; ++c) tbl[c] = src[c];
-            for (int c = 0; c < nc; ++c) {
-                T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                tbl[nc + c] = d;
-                src[c] = d;
-            }
-            T* records = reinterpret_cast<T*>(take((size_t)n_rows * nc * sizeof(T)));
-            const T** d_tbl = reinterpret_cast<const T**>(take(2 * (size_t)nc * sizeof(T*)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), 2 * (size_t)nc * sizeof(T*), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_gather_frame<T>(ctx, d_tbl, perm, nc, n_rows, records, (T* const*)(d_tbl + nc))) return rc;
-            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-        }
-        if (int rc = keyed_runs(ctx, sk, n_rows, d_unique, d_counts, d_offsets, d_nruns, d_temp, temp_bytes, &ng)) return rc;
-    } else {
-        ng = n_runs + 1;
-        if (ng <= max_groups)
-            if (int rc = keyed_runs_ordered(ctx, d_keys, n_rows, d_run_counts, d_run_prefix, d_run_masks, run_cap, d_unique, d_offsets, d_temp, temp_bytes))
-                return rc;
-    }
-    *n_groups = ng;
-    if (ng > max_groups) return fail(PDS_ERR_INVALID, "more distinct keys than max_groups");
+    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat);
+    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf)) return rc;
+    const int64_t ng = kf.ng;
     T* d_co = coeffs;
     int32_t* d_it = n_iter;
     uint8_t* d_nu = is_null;
     T* d_pred = pred;
     uint8_t* d_rn = row_null;
     if (space == PDS_HOST) {
-        d_co = reinterpret_cast<T*>(take((size_t)cap * pp * sizeof(T)));
-        d_it = reinterpret_cast<int32_t*>(take((size_t)cap * 4));
-        d_nu = reinterpret_cast<uint8_t*>(take((size_t)cap));
-        if (pred) d_pred = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        if (row_null) d_rn = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+        d_co = w.take<T>((size_t)cap * pp);
+        d_it = w.take<int32_t>((size_t)cap);
+        d_nu = w.take<uint8_t>((size_t)cap);
+        if (pred) d_pred = w.take<T>((size_t)n_rows);
+        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
     }
-    if (int rc = glm_grouped_impl<T>(ctx, src.data(), n_feat, n_rows, d_offsets, ng, PDS_DEVICE, add_bias, link, variance, tol, max_iter, d_co,
-                                     d_it, d_nu, d_pred, d_rn, d_perm))
+    if (int rc = glm_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, link, variance, tol, max_iter, d_co,
+                                     d_it, d_nu, d_pred, d_rn, kf.d_perm))
         return rc;
     const hipMemcpyKind back = space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, back, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, back, ctx->stream));
     if (space == PDS_HOST) {
         PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), back, ctx->stream));
         PDS_HIP_CHECK(hipMemcpyAsync(n_iter, d_it, (size_t)ng * 4, back, ctx->stream));

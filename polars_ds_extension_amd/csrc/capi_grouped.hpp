@@ -309,7 +309,7 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int bias = prm->add_bias ? 1 : 0, pf = n_feat + bias, nc_in = n_feat + 1;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
     size_t need = col_bytes * (pf + 1) + up(sizeof(T*) * (size_t)std::max(nc_in, 18)) + up((size_t)n_groups) + 4096;
     if (space == PDS_HOST || !coeffs) need += up((size_t)n_groups * pf * sizeof(T));
@@ -317,39 +317,29 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
     if (want_pred && space == PDS_HOST) need += 2 * col_bytes + up((size_t)n_rows);
     // (its own workspace: pds_lr_by_key_* calls this with its sorted frame living in ctx->keyed)
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->wkeyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    std::vector<const T*> src(nc_in);
-    const T* d_w = weights;
+    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat, weights);  // [y, x1..xp, w]
     const int64_t* d_off = offsets;
     T* d_co = coeffs;
     uint8_t* d_nu = is_null;
     if (space == PDS_HOST) {
-        for (int c = 0; c < nc_in; ++c) {
-            T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d, cols[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = d;
-        }
-        T* dw = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        PDS_HIP_CHECK(hipMemcpyAsync(dw, weights, (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        d_w = dw;
-        int64_t* doff = reinterpret_cast<int64_t*>(take((size_t)(n_groups + 1) * 8));
+        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
+        int64_t* doff = w.take<int64_t>((size_t)n_groups + 1);
         PDS_HIP_CHECK(hipMemcpyAsync(doff, offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         d_off = doff;
-    } else {
-        for (int c = 0; c < nc_in; ++c) src[c] = cols[c];
     }
-    if (space == PDS_HOST || !coeffs) d_co = reinterpret_cast<T*>(take((size_t)n_groups * pf * sizeof(T)));
-    if (space == PDS_HOST || !d_nu) d_nu = reinterpret_cast<uint8_t*>(take((size_t)n_groups));
+    const T* d_w = src[nc_in];
+    if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)n_groups * pf);
+    if (space == PDS_HOST || !d_nu) d_nu = w.take<uint8_t>((size_t)n_groups);
     // scaled frame in reference order [y, x1..xp, (sqrt w)]
     std::vector<const T*> scaled(pf + 1);
     for (int c = 0; c < nc_in; ++c) {
-        T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+        T* d = w.take<T>((size_t)n_rows);
         if (int rc = launch_scale_sqrt_w<T>(ctx, src[c], d_w, n_rows, d)) return rc;
         scaled[c] = d;
     }
     if (bias) {
-        T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
+        T* d = w.take<T>((size_t)n_rows);
         if (int rc = launch_scale_sqrt_w<T>(ctx, (const T*)nullptr, d_w, n_rows, d)) return rc;
         scaled[nc_in] = d;
     }
@@ -362,18 +352,17 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
     if (int rc = grouped_impl<T>(ctx, scaled.data(), pf, n_rows, d_off, n_groups, PDS_DEVICE, &p2, d_co, d_nu)) return rc;
     if (want_pred) {
         // device pointer table of the unscaled frame in kernel order (x_0 .. x_{p-1}, y)
-        std::vector<const T*> tbl((size_t)std::max(nc_in, 18), src[0]);
-        for (int c = 0; c < n_feat; ++c) tbl[c] = src[c + 1];
-        tbl[n_feat] = src[0];
-        const T** d_tbl = reinterpret_cast<const T**>(take(sizeof(T*) * tbl.size()));
-        PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), sizeof(T*) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
+        src.pop_back();  // (the weights)
+        std::vector<const T*> tbl;
+        const T** d_tbl = nullptr;
+        if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
         T* d_pred = pred;
         T* d_resid = resid;
         uint8_t* d_rn = row_null;
         if (space == PDS_HOST) {
-            if (pred) d_pred = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            if (resid) d_resid = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            if (row_null) d_rn = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+            if (pred) d_pred = w.take<T>((size_t)n_rows);
+            if (resid) d_resid = w.take<T>((size_t)n_rows);
+            if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
         }
         if (int rc = launch_grouped_pred<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, d_co, d_nu, d_perm, d_pred, d_resid, d_rn))
             return rc;
@@ -468,31 +457,9 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int nc = n_feat + 1 + (weights ? 1 : 0), pp = n_feat + (prm->add_bias ? 1 : 0);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
+    const size_t col_bytes = Bump::up((size_t)n_rows * sizeof(T));
     StageTrace tr(ctx, "pds_lr_by_key");
     // ---- keys on the device, and are they already in order?
-    const int64_t* d_keys = keys;
-    if (space == PDS_HOST) {
-        if (int rc = ensure_ws(ctx, ctx->stage, key_bytes + 256)) return rc;
-        PDS_HIP_CHECK(hipMemcpyAsync(ctx->stage.ptr, keys, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = static_cast<const int64_t*>(ctx->stage.ptr);
-    }
-    if (int rc = ensure_pinned(ctx, 4096)) return rc;
-    // order flag + key range + the run counts of the order check (keyed.hip): they outlive the workspace sizing below
-    const size_t run_slots = key_run_slots(n_rows);
-    const size_t slot_bytes = (size_t)kKeySlots * 8 * sizeof(unsigned);
-    const size_t mask_bytes = key_run_mask_bytes(n_rows);
-    if (int rc = ensure_ws(ctx, ctx->solve_ws, 8192 + 2 * up((run_slots + 1) * sizeof(uint32_t)) + up(slot_bytes) + mask_bytes)) return rc;
-    bool sorted = false;
-    int64_t mm[2] = {0, 0};
-    int64_t n_runs = 0;  // keys that differ from their successor: n_groups - 1 of an ordered column
-    int64_t* d_state = reinterpret_cast<int64_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 256);
-    int64_t* d_minmax = d_state + 2;
-    uint32_t* d_run_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096);
-    uint32_t* d_run_prefix = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096 + up((run_slots + 1) * sizeof(uint32_t)));
-    unsigned long long* d_run_masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096 +
-                                                                            2 * up((run_slots + 1) * sizeof(uint32_t)) + up(slot_bytes));
     // dense-key candidates (unweighted, <= 16 features): the order check takes the partition route's bucket histogram along
     // context option "keyed_sort" (default from PDS_KEYED_SORT=1 at pds_ctx_create): the sorting route for every unordered frame -- the DETERMINISM switch: the partition route's
     // record order follows cursor atomics, so its sums are reproducible to rounding only.  solver = "svd" with the
@@ -500,20 +467,23 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     const bool force_sort = ctx->opt_keyed_sort || (prm->solver == PDS_SOLVER_SVD && prm->singular_x_tol > 0.0);
     const bool part_candidate = !force_sort && !weights && n_feat <= 16 && !place;
     const int part_shift = part_candidate ? keyed_partition_shift<T>(n_feat) : -1;
-    unsigned* d_slots = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->solve_ws.ptr) + 4096 + 2 * up((run_slots + 1) * sizeof(uint32_t)));
-    bool hist_taken = false;
-    if (int rc = keys_order_minmax(ctx, d_keys, n_rows, d_state, &sorted, mm, d_run_counts, d_run_masks, &n_runs, part_shift,
-                                   part_candidate ? d_slots : nullptr, &hist_taken))
-        return rc;
+    KeyOrder ko;
+    if (int rc = keyed_order_check(ctx, keys, n_rows, space, true, part_shift, ko)) return rc;
     tr.mark("keys H2D + order check");
-    // ORDERED keys have no row bound of their own (the order check, the run marks and the fits index rows with 64 bits; 2^31 + rows x 8
-    // f64 features fit this device's HBM, and the reference's series_to_mat_for_lr has no bound either, linear_regression.rs:151-267);
-    // the routes for keys in ANY order carry 32-bit row ranks through the sort / the partition
-    if (!sorted && n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "keyed grouping of unordered keys: fewer than 2^31 rows per call");
+    const bool sorted = ko.sorted;
     if (place && !sorted) {
         place->unsorted();
         return fail(PDS_ERR_UNSUPPORTED, "sliced fit: the slice's keys are not in order");
     }
+    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
+    // output staging, either route (the same predicates as the take() sites below: a device frame with coeffs but no is_null still takes
+    // its flags here)
+    size_t out_need = 0;
+    if (space == PDS_HOST || !coeffs) out_need += Bump::up((size_t)cap * pp * sizeof(T));
+    if (space == PDS_HOST || !is_null) out_need += Bump::up((size_t)cap);
+    if (want_pred) out_need += Bump::up(sizeof(T*) * (size_t)std::max(nc, 18)) + (space == PDS_HOST ? 2 * col_bytes + Bump::up((size_t)n_rows) : 0);
+    std::vector<const T*> tbl;  // (source of a table copy: lives until the last synchronisation)
+    const T** d_tbl = nullptr;
     // ---- keys in any order: smallest / largest key decide the route.  Dense integer keys (group ids) of an unweighted
     // fit with up to 16 features take the partition route (keyed_partition.hip: no sort, no random-access pass; per-row
     // predictions then look the row's group up from its key -- grouped_pred.hip MODE 2 -- and nothing is ever permuted);
@@ -523,74 +493,47 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     uint64_t part_range = 0;
     if (!sorted && part_candidate) {
         const int64_t wdt = (int64_t)1 << part_shift;
-        part_base = mm[0] - (((mm[0] % wdt) + wdt) % wdt);
-        part_range = (uint64_t)mm[1] - (uint64_t)part_base + 1;
+        part_base = ko.mm[0] - (((ko.mm[0] % wdt) + wdt) % wdt);
+        part_range = (uint64_t)ko.mm[1] - (uint64_t)part_base + 1;
         part_buckets = keyed_partition_buckets<T>(n_feat, n_rows, part_range);
     }
-    const bool partition = part_buckets > 0;
-    int64_t* d_part_base = d_state + 1;  // (the unused slot of the order check's state)
-    if (partition) PDS_HIP_CHECK(hipMemcpyAsync(d_part_base, &part_base, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    // ---- workspace: [raw columns (host frames)] [sorted keys, index in/out, gathered columns (unsorted frames)] runs, temp
-    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const size_t temp_bytes = sorted ? keyed_ordered_temp_bytes(n_rows) : keyed_temp_bytes(n_rows);
-    // unique keys, counts, offsets: at most one per group (the partition route; ordered keys: the order check has counted them) / per row
-    const int64_t run_cap = partition ? cap : (sorted ? std::min<int64_t>(n_runs + 1, cap) : n_rows);
-    size_t need = temp_bytes + 3 * up((size_t)(run_cap + 1) * 8) + 8192;
-    if (space == PDS_HOST) need += col_bytes * nc;
-    // (the same predicates as the take() sites below: a device frame with coeffs but no is_null still takes its flags here)
-    if (space == PDS_HOST || !coeffs) need += up((size_t)cap * pp * sizeof(T));
-    if (space == PDS_HOST || !is_null) need += up((size_t)cap);
-    if (partition) need += keyed_partition_workspace<T>(n_feat, n_rows, part_buckets) + up(sizeof(T*) * (size_t)std::max(nc, 18));
-    // per-row predictions on the partition route: an id-indexed copy of the coefficient block (one randomly read object per row) when
-    // the id space is small enough to live in the memory-side cache like the block itself -- up to 2^25 ids and 1 GiB
-    const int64_t part_ids = partition ? keyed_partition_table_ids<T>(n_feat, part_buckets) : 0;
-    const size_t cbi_bytes = (size_t)part_ids * grouped_pred_table_stride<T>(pp) * sizeof(T);
-    const bool pred_table = partition && want_pred && part_ids <= ((int64_t)1 << 25) && cbi_bytes <= ((size_t)1 << 30);
-    if (pred_table) need += up(cbi_bytes);
-    // the sort + gather route's buffers: only when neither the order check nor the partition route serves the frame
-    if (!partition && !sorted) need += 2 * key_bytes + 2 * idx_bytes + col_bytes * nc + up((size_t)n_rows * nc * sizeof(T)) + up(2 * (size_t)nc * sizeof(T*)) + 1024;
-    if (want_pred) need += up(sizeof(T*) * (size_t)std::max(nc, 18)) + (space == PDS_HOST ? 2 * col_bytes + up((size_t)n_rows) : 0);
-    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    tr.mark("workspace");
-    char* w = static_cast<char*>(ctx->keyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    void* d_temp = take(temp_bytes);
-    int64_t* d_unique = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
-    std::vector<const T*> src(nc);  // reference order [y, x1..xp, (w)], device resident
-    for (int c = 0; c < n_feat + 1; ++c) src[c] = cols[c];
-    if (weights) src[n_feat + 1] = weights;
-    if (space == PDS_HOST)
-        for (int c = 0; c < nc; ++c) {
-            T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d, src[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = d;
-        }
-    tr.mark("columns H2D");
-    if (partition) {
-        std::vector<const T*> tbl((size_t)std::max(nc, 18), src[0]);
-        for (int c = 0; c < n_feat; ++c) tbl[c] = src[c + 1];
-        tbl[n_feat] = src[0];
-        const T** d_tbl = reinterpret_cast<const T**>(take(sizeof(T*) * tbl.size()));
-        PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), sizeof(T*) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
-        char* pws = take(keyed_partition_workspace<T>(n_feat, n_rows, part_buckets));
+    if (part_buckets > 0) {
+        int64_t* d_part_base = ko.d_state + 1;  // (the unused slot of the order check's state)
+        PDS_HIP_CHECK(hipMemcpyAsync(d_part_base, &part_base, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        // ---- workspace: unique keys, offsets (at most one per group) [raw columns (host frames)] table, partition, outputs
+        size_t need = out_need + 2 * Bump::up((size_t)(cap + 1) * 8) + 8192;
+        if (space == PDS_HOST) need += col_bytes * nc;
+        need += keyed_partition_workspace<T>(n_feat, n_rows, part_buckets) + Bump::up(sizeof(T*) * (size_t)std::max(nc, 18));
+        // per-row predictions on the partition route: an id-indexed copy of the coefficient block (one randomly read object per row) when
+        // the id space is small enough to live in the memory-side cache like the block itself -- up to 2^25 ids and 1 GiB
+        const int64_t part_ids = keyed_partition_table_ids<T>(n_feat, part_buckets);
+        const size_t cbi_bytes = (size_t)part_ids * grouped_pred_table_stride<T>(pp) * sizeof(T);
+        const bool pred_table = want_pred && part_ids <= ((int64_t)1 << 25) && cbi_bytes <= ((size_t)1 << 30);
+        if (pred_table) need += Bump::up(cbi_bytes);
+        if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
+        tr.mark("workspace");
+        Bump w{static_cast<char*>(ctx->keyed.ptr)};
+        int64_t* d_unique = w.take<int64_t>((size_t)cap + 1);
+        int64_t* d_offsets = w.take<int64_t>((size_t)cap + 1);
+        std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
+        if (space == PDS_HOST)
+            if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
+        tr.mark("columns H2D");
+        if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+        char* pws = w.take<char>(keyed_partition_workspace<T>(n_feat, n_rows, part_buckets));
         KeyedPartitionState st;
         int64_t ng = 0;
-        const bool use_slots = hist_taken && part_buckets <= kKeySlots;
+        const bool use_slots = ko.hist_taken && part_buckets <= kKeySlots;
         const unsigned first_slot = (unsigned)((part_base >> part_shift) & (int64_t)(kKeySlots - 1));
-        const int rc0 = keyed_partition_build<T>(ctx, d_tbl, d_keys, d_part_base, part_range, n_feat, n_rows, part_buckets, pws, cap, d_unique,
-                                                 d_offsets, &ng, st, use_slots ? d_slots : nullptr, first_slot);
+        const int rc0 = keyed_partition_build<T>(ctx, d_tbl, ko.d_keys, d_part_base, part_range, n_feat, n_rows, part_buckets, pws, cap, d_unique,
+                                                 d_offsets, &ng, st, use_slots ? ko.d_slots : nullptr, first_slot);
         if (n_groups) *n_groups = ng;
         if (rc0) return rc0;
         tr.mark("partition + moments");
-        if (place)
-            if (int rc = place->at(ng, &out_keys, &coeffs, &is_null)) return rc;
         T* d_co = coeffs;
         uint8_t* d_nu = is_null;
-        if (space == PDS_HOST || !coeffs) d_co = reinterpret_cast<T*>(take((size_t)cap * pp * sizeof(T)));
-        if (space == PDS_HOST || !is_null) d_nu = reinterpret_cast<uint8_t*>(take((size_t)cap));
+        if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)cap * pp);
+        if (space == PDS_HOST || !is_null) d_nu = w.take<uint8_t>((size_t)cap);
         if (int rc = solve_partition_table<T>(ctx, st, n_feat, ng, d_offsets, prm, d_co, d_nu)) return rc;
         tr.mark("solve");
         if (want_pred) {
@@ -598,16 +541,16 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
             T* d_resid = resid;
             uint8_t* d_rn = row_null;
             if (space == PDS_HOST) {
-                if (pred) d_pred = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (resid) d_resid = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (row_null) d_rn = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+                if (pred) d_pred = w.take<T>((size_t)n_rows);
+                if (resid) d_resid = w.take<T>((size_t)n_rows);
+                if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
             }
             if (pred_table) {
-                T* d_cbi = reinterpret_cast<T*>(take(cbi_bytes));
-                if (int rc = launch_grouped_pred_by_id_table<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, d_keys, d_part_base, st.ids, ng, d_co,
+                T* d_cbi = w.take<T>(cbi_bytes / sizeof(T));
+                if (int rc = launch_grouped_pred_by_id_table<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, ko.d_keys, d_part_base, st.ids, ng, d_co,
                                                                 d_nu, d_cbi, d_pred, d_resid, d_rn))
                     return rc;
-            } else if (int rc = launch_grouped_pred_by_id<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, d_keys, d_part_base, st.rank, ng, d_co,
+            } else if (int rc = launch_grouped_pred_by_id<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, ko.d_keys, d_part_base, st.rank, ng, d_co,
                                                              d_nu, d_pred, d_resid, d_rn)) {
                 return rc;
             }
@@ -629,81 +572,38 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         tr.mark("results D2H");
         return PDS_OK;
     }
-    const int64_t* d_sorted_keys = d_keys;
-    const uint32_t* d_perm = nullptr;
-    if (!sorted) {
-        int64_t* sk = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        uint32_t* idx_in = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        uint32_t* perm = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        int64_t* sk2 = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        if (int rc = keyed_sort(ctx, d_keys, n_rows, idx_in, sk, perm, d_temp, temp_bytes, sk2, d_minmax, mm)) return rc;
-        d_sorted_keys = sk;
-        d_perm = perm;
-        static const bool by_column = [] { const char* e = dev_env("PDS_KEYED_GATHER_BY_COLUMN"); return e && e[0] == '1'; }();
-        // frames too wide for the 256-row transposition tile (32 f64 / 64 f32 columns and beyond) gather column by column
-        if (by_column || !gather_frame_fits<T>(nc)) {  // (one random 8-byte read per element; the env switch is the A/B)
-            for (int c = 0; c < nc; ++c) {
-                T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (int rc = launch_gather_rows<T>(ctx, src[c], perm, n_rows, d)) return rc;
-                src[c] = d;
-            }
-        } else {
-            // transpose to row-major records, then one random access per ROW (keyed.hip)
-            std::vector<const T*> tbl(2 * (size_t)nc);
-            for (int c = 0; c < nc; ++c) tbl[c] = src[c];
-            for (int c = 0; c < nc; ++c) {
-                T* d = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                tbl[nc + c] = d;
-                src[c] = d;
-            }
-            T* records = reinterpret_cast<T*>(take((size_t)n_rows * nc * sizeof(T)));
-            const T** d_tbl = reinterpret_cast<const T**>(take(2 * (size_t)nc * sizeof(T*)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), 2 * (size_t)nc * sizeof(T*), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_gather_frame<T>(ctx, d_tbl, perm, nc, n_rows, records, (T* const*)(d_tbl + nc)))
-                return rc;
-            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-        }
-    }
-    tr.mark("sort + gather");
-    int64_t ng = 0;
-    if (sorted) {  // keys in order: the order check has counted and marked the run starts already -- a scan and one pass over the marks,
-        ng = n_runs + 1;  // left on the stream in front of the fit (the number of groups came back with the order flag)
-        if (ng <= max_groups)
-            if (int rc = keyed_runs_ordered(ctx, d_keys, n_rows, d_run_counts, d_run_prefix, d_run_masks, run_cap, d_unique, d_offsets, d_temp, temp_bytes))
-                return rc;
-    } else if (int rc = keyed_runs(ctx, d_sorted_keys, n_rows, d_unique, d_counts, d_offsets, d_nruns, d_temp, temp_bytes, &ng)) {
-        return rc;
-    }
-    tr.mark("run lengths + offsets");
-    if (n_groups) *n_groups = ng;
-    if (ng > max_groups) return fail(PDS_ERR_INVALID, "more distinct keys than max_groups");
+    // ---- the frame in key order (capi_keyed_frame.hpp), then the fit on contiguous groups
+    const int64_t run_cap = sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
+    if (int rc = ensure_ws(ctx, ctx->keyed, keyed_frame_bytes<T>(sorted, n_rows, nc, space, run_cap) + out_need)) return rc;
+    tr.mark("workspace");
+    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat, weights);
+    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf, &tr)) return rc;
+    const int64_t ng = kf.ng;
     if (place)
         if (int rc = place->at(ng, &out_keys, &coeffs, &is_null)) return rc;
     T* d_co = coeffs;
     uint8_t* d_nu = is_null;
-    if (space == PDS_HOST || !coeffs) d_co = reinterpret_cast<T*>(take((size_t)cap * pp * sizeof(T)));
-    if (space == PDS_HOST || !is_null) d_nu = reinterpret_cast<uint8_t*>(take((size_t)cap));
+    if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)cap * pp);
+    if (space == PDS_HOST || !is_null) d_nu = w.take<uint8_t>((size_t)cap);
     T* d_pred = pred;
     T* d_resid = resid;
     uint8_t* d_rn = row_null;
     if (want_pred && space == PDS_HOST) {
-        if (pred) d_pred = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        if (resid) d_resid = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        if (row_null) d_rn = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+        if (pred) d_pred = w.take<T>((size_t)n_rows);
+        if (resid) d_resid = w.take<T>((size_t)n_rows);
+        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
     }
     if (weights) {
-        if (int rc = grouped_weighted_impl<T>(ctx, src.data(), src[n_feat + 1], n_feat, n_rows, d_offsets, ng, PDS_DEVICE, prm, d_co, d_nu,
-                                              d_pred, d_resid, d_rn, d_perm))
+        if (int rc = grouped_weighted_impl<T>(ctx, kf.src.data(), kf.src[n_feat + 1], n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, prm, d_co, d_nu,
+                                              d_pred, d_resid, d_rn, kf.d_perm))
             return rc;
     } else {
-        if (int rc = grouped_impl<T>(ctx, src.data(), n_feat, n_rows, d_offsets, ng, PDS_DEVICE, prm, d_co, d_nu)) return rc;
+        if (int rc = grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, prm, d_co, d_nu)) return rc;
         if (want_pred) {
-            std::vector<const T*> tbl((size_t)std::max(nc, 18), src[0]);
-            for (int c = 0; c < n_feat; ++c) tbl[c] = src[c + 1];
-            tbl[n_feat] = src[0];
-            const T** d_tbl = reinterpret_cast<const T**>(take(sizeof(T*) * tbl.size()));
-            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), sizeof(T*) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_grouped_pred<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, d_offsets, ng, d_co, d_nu, d_perm, d_pred,
+            if (int rc = kernel_order_table<T>(ctx, w, kf.src, n_feat, tbl, d_tbl)) return rc;
+            if (int rc = launch_grouped_pred<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, kf.d_offsets, ng, d_co, d_nu, kf.d_perm, d_pred,
                                                 d_resid, d_rn))
                 return rc;
             PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
@@ -713,12 +613,12 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     if (space == PDS_HOST) {
         if (coeffs) PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         if (coeffs && is_null) PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)ng, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         if (resid) PDS_HIP_CHECK(hipMemcpyAsync(resid, d_resid, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
     } else if (out_keys) {
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     tr.mark("results D2H");

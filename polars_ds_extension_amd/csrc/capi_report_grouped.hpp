@@ -245,7 +245,7 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weig
 }
 
 // int64 keys in any row order: ordered keys take the order check's run marks (nothing moves); otherwise the stable radix sort of
-// (key, row) and the frame gather of the sorting route (capi_grouped.hpp, lr_by_key_impl).  Groups come back in ascending key order.
+// (key, row) and the frame gather (capi_keyed_frame.hpp).  Groups come back in ascending key order.
 template <typename T>
 static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* weights, const int64_t* keys, int n_feat, int64_t n_rows,
                               pds_space space, int add_bias, int se_type, int64_t max_groups, int64_t* out_keys,
@@ -257,102 +257,29 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* weigh
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (se_type < PDS_SE || se_type > PDS_HC3) return fail(PDS_ERR_INVALID, "unknown standard-error type");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    // (a weight column rides through the staging, the sort and the gather as one more column of the frame: src[nc - 1])
+    // (a weight column rides through the staging, the sort and the gather as one more column of the frame: kf.src[nc - 1])
     const int nc = n_feat + 1 + (weights ? 1 : 0), pp = n_feat + (add_bias ? 1 : 0);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
-    const int64_t* d_keys = keys;
-    if (space == PDS_HOST) {
-        if (int rc = ensure_ws(ctx, ctx->stage, key_bytes + 256)) return rc;
-        PDS_HIP_CHECK(hipMemcpyAsync(ctx->stage.ptr, keys, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = static_cast<const int64_t*>(ctx->stage.ptr);
-    }
-    const size_t run_slots = key_run_slots(n_rows);
-    const size_t mask_bytes = key_run_mask_bytes(n_rows);
-    if (int rc = ensure_ws(ctx, ctx->solve_ws, 8192 + 2 * up((run_slots + 1) * sizeof(uint32_t)) + mask_bytes)) return rc;
-    char* sw = static_cast<char*>(ctx->solve_ws.ptr);
-    int64_t* d_state = reinterpret_cast<int64_t*>(sw + 256);
-    int64_t* d_minmax = d_state + 2;
-    uint32_t* d_run_counts = reinterpret_cast<uint32_t*>(sw + 4096);
-    uint32_t* d_run_prefix = reinterpret_cast<uint32_t*>(sw + 4096 + up((run_slots + 1) * sizeof(uint32_t)));
-    unsigned long long* d_run_masks = reinterpret_cast<unsigned long long*>(sw + 4096 + 2 * up((run_slots + 1) * sizeof(uint32_t)));
-    bool sorted = false;
-    int64_t mm[2] = {0, 0};
-    int64_t n_runs = 0;
-    if (int rc = keys_order_minmax(ctx, d_keys, n_rows, d_state, &sorted, mm, d_run_counts, d_run_masks, &n_runs)) return rc;
-    if (!sorted && n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "keyed grouping of unordered keys: fewer than 2^31 rows per call");
+    KeyOrder ko;
+    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
     const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const size_t temp_bytes = sorted ? keyed_ordered_temp_bytes(n_rows) : keyed_temp_bytes(n_rows);
-    const int64_t run_cap = sorted ? std::min<int64_t>(n_runs + 1, cap) : n_rows;
-    size_t need = temp_bytes + 3 * up((size_t)(run_cap + 1) * 8) + 8192;
-    if (space == PDS_HOST) need += col_bytes * nc + 6 * up((size_t)cap * pp * sizeof(T)) + 2 * up((size_t)cap * sizeof(T)) + up((size_t)cap);
-    if (!sorted) need += 2 * key_bytes + 2 * idx_bytes + col_bytes * nc + up((size_t)n_rows * nc * sizeof(T)) + up(2 * (size_t)nc * sizeof(T*)) + 1024;
+    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
+    size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap);
+    if (space == PDS_HOST) need += 6 * Bump::up((size_t)cap * pp * sizeof(T)) + 2 * Bump::up((size_t)cap * sizeof(T)) + Bump::up((size_t)cap);
     if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->keyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    void* d_temp = take(temp_bytes);
-    int64_t* d_unique = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
-    std::vector<const T*> src(nc);  // [y, x1..xp (, w)], device resident
-    for (int c = 0; c < n_feat + 1; ++c) src[c] = cols[c];
-    if (weights) src[n_feat + 1] = weights;
-    if (space == PDS_HOST)
-        for (int c = 0; c < nc; ++c) {
-            T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(dcol, src[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = dcol;
-        }
-    if (!sorted) {
-        int64_t* sk = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        uint32_t* idx_in = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        uint32_t* perm = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        int64_t* sk2 = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        if (int rc = keyed_sort(ctx, d_keys, n_rows, idx_in, sk, perm, d_temp, temp_bytes, sk2, d_minmax, mm)) return rc;
-        d_keys = sk;
-        if (!gather_frame_fits<T>(nc)) {
-            for (int c = 0; c < nc; ++c) {
-                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (int rc = launch_gather_rows<T>(ctx, src[c], perm, n_rows, dcol)) return rc;
-                src[c] = dcol;
-            }
-        } else {
-            std::vector<const T*> tbl(2 * (size_t)nc);
-            for (int c = 0; c < nc; ++c) tbl[c] = src[c];
-            for (int c = 0; c < nc; ++c) {
-                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                tbl[nc + c] = dcol;
-                src[c] = dcol;
-            }
-            T* records = reinterpret_cast<T*>(take((size_t)n_rows * nc * sizeof(T)));
-            const T** d_tbl = reinterpret_cast<const T**>(take(2 * (size_t)nc * sizeof(T*)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), 2 * (size_t)nc * sizeof(T*), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_gather_frame<T>(ctx, d_tbl, perm, nc, n_rows, records, (T* const*)(d_tbl + nc))) return rc;
-            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-        }
-    }
-    int64_t ng = 0;
-    if (sorted) {
-        ng = n_runs + 1;
-        if (ng <= max_groups)
-            if (int rc = keyed_runs_ordered(ctx, d_keys, n_rows, d_run_counts, d_run_prefix, d_run_masks, run_cap, d_unique, d_offsets, d_temp,
-                                            temp_bytes))
-                return rc;
-    } else if (int rc = keyed_runs(ctx, d_keys, n_rows, d_unique, d_counts, d_offsets, d_nruns, d_temp, temp_bytes, &ng)) {
-        return rc;
-    }
-    *n_groups = ng;
-    if (ng > max_groups) return fail(PDS_ERR_INVALID, "more distinct keys than max_groups");
+    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat, weights);
+    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf)) return rc;
+    const int64_t ng = kf.ng;
     ReportGroupedOut<T> d = *out;
     if (space == PDS_HOST) {
         T** vec[6] = {&d.beta, &d.std_err, &d.t, &d.p, &d.ci_lower, &d.ci_upper};
-        for (T** v : vec) *v = reinterpret_cast<T*>(take((size_t)cap * pp * sizeof(T)));
-        d.r2 = reinterpret_cast<T*>(take((size_t)cap * sizeof(T)));
-        d.adj_r2 = reinterpret_cast<T*>(take((size_t)cap * sizeof(T)));
-        d.is_null = reinterpret_cast<uint8_t*>(take((size_t)cap));
+        for (T** v : vec) *v = w.take<T>((size_t)cap * pp);
+        d.r2 = w.take<T>((size_t)cap);
+        d.adj_r2 = w.take<T>((size_t)cap);
+        d.is_null = w.take<uint8_t>((size_t)cap);
     }
-    if (int rc = report_grouped_impl<T>(ctx, src.data(), weights ? src[n_feat + 1] : (const T*)nullptr, n_feat, n_rows, d_offsets, ng,
+    if (int rc = report_grouped_impl<T>(ctx, kf.src.data(), weights ? kf.src[n_feat + 1] : (const T*)nullptr, n_feat, n_rows, kf.d_offsets, ng,
                                         PDS_DEVICE, add_bias, se_type, (const T*)nullptr, &d))
         return rc;
     if (space == PDS_HOST) {
@@ -366,9 +293,9 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* weigh
         PDS_HIP_CHECK(hipMemcpyAsync(out->r2, d.r2, (size_t)ng * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         PDS_HIP_CHECK(hipMemcpyAsync(out->adj_r2, d.adj_r2, (size_t)ng * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         PDS_HIP_CHECK(hipMemcpyAsync(out->is_null, d.is_null, (size_t)ng, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
     } else {
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;

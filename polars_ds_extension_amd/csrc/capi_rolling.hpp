@@ -111,23 +111,18 @@ static int rolling_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, 
         return PDS_OK;
     }
     // host frame: columns, offsets and outputs staged in the keyed workspace (the ws arena belongs to the launch)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
     const size_t need = col_bytes * nc + up(h_off.size() * 8) + up((size_t)n_rows * pp * sizeof(T)) + col_bytes + up((size_t)n_rows) + 4096;
     if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->keyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    std::vector<const T*> src(nc);
-    for (int c = 0; c < nc; ++c) {
-        T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        PDS_HIP_CHECK(hipMemcpyAsync(dcol, cols[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        src[c] = dcol;
-    }
-    int64_t* d_off = reinterpret_cast<int64_t*>(take(h_off.size() * 8));
+    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);
+    if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
+    int64_t* d_off = w.take<int64_t>(h_off.size());
     PDS_HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    T* d_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
-    T* d_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-    uint8_t* d_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+    T* d_co = w.take<T>((size_t)n_rows * pp);
+    T* d_pr = w.take<T>((size_t)n_rows);
+    uint8_t* d_va = w.take<uint8_t>((size_t)n_rows);
     if (int rc = rolling_grouped_device<T>(ctx, src.data(), n_feat, n_rows, d_off, n_groups, add_bias, window, min_size, lambda, expanding,
                                            d_co, d_pr, d_va))
         return rc;
@@ -149,101 +144,30 @@ static int rolling_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t
     if (int rc = check_grouped_window(n_feat, add_bias, n_rows, window, min_size)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t key_bytes = up((size_t)n_rows * 8), col_bytes = up((size_t)n_rows * sizeof(T)), idx_bytes = up((size_t)n_rows * 4);
-    const int64_t* d_keys = keys;
-    if (space == PDS_HOST) {
-        if (int rc = ensure_ws(ctx, ctx->stage, key_bytes + 256)) return rc;
-        PDS_HIP_CHECK(hipMemcpyAsync(ctx->stage.ptr, keys, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = static_cast<const int64_t*>(ctx->stage.ptr);
-    }
-    const size_t run_slots = key_run_slots(n_rows);
-    const size_t mask_bytes = key_run_mask_bytes(n_rows);
-    if (int rc = ensure_ws(ctx, ctx->solve_ws, 8192 + 2 * up((run_slots + 1) * sizeof(uint32_t)) + mask_bytes)) return rc;
-    char* sw = static_cast<char*>(ctx->solve_ws.ptr);
-    int64_t* d_state = reinterpret_cast<int64_t*>(sw + 256);
-    int64_t* d_minmax = d_state + 2;
-    uint32_t* d_run_counts = reinterpret_cast<uint32_t*>(sw + 4096);
-    uint32_t* d_run_prefix = reinterpret_cast<uint32_t*>(sw + 4096 + up((run_slots + 1) * sizeof(uint32_t)));
-    unsigned long long* d_run_masks = reinterpret_cast<unsigned long long*>(sw + 4096 + 2 * up((run_slots + 1) * sizeof(uint32_t)));
-    bool sorted = false;
-    int64_t mm[2] = {0, 0};
-    int64_t n_runs = 0;
-    if (int rc = keys_order_minmax(ctx, d_keys, n_rows, d_state, &sorted, mm, d_run_counts, d_run_masks, &n_runs)) return rc;
-    if (!sorted && n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "keyed grouping of unordered keys: fewer than 2^31 rows per call");
-    const size_t temp_bytes = sorted ? keyed_ordered_temp_bytes(n_rows) : keyed_temp_bytes(n_rows);
-    const int64_t run_cap = sorted ? n_runs + 1 : n_rows;
-    size_t need = temp_bytes + 3 * up((size_t)(run_cap + 1) * 8) + 8192;
+    KeyOrder ko;
+    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
+    const bool sorted = ko.sorted;
+    const int64_t run_cap = sorted ? ko.n_runs + 1 : n_rows;  // (no max_groups here)
+    size_t need = keyed_frame_bytes<T>(sorted, n_rows, nc, space, run_cap);
     const bool stage_out = space == PDS_HOST || !sorted;  // outputs through the workspace (host frame, or scattered back)
-    if (space == PDS_HOST) need += col_bytes * nc;
-    const size_t out_bytes = up((size_t)n_rows * pp * sizeof(T)) + col_bytes + up((size_t)n_rows);
+    const size_t out_bytes = Bump::up((size_t)n_rows * pp * sizeof(T)) + Bump::up((size_t)n_rows * sizeof(T)) + Bump::up((size_t)n_rows);
     if (stage_out) need += out_bytes;
     if (!sorted && space == PDS_HOST) need += out_bytes;  // the scatter's target
-    if (!sorted) need += 2 * key_bytes + 2 * idx_bytes + col_bytes * nc + up((size_t)n_rows * nc * sizeof(T)) + up(2 * (size_t)nc * sizeof(T*)) + 1024;
     if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    char* w = static_cast<char*>(ctx->keyed.ptr);
-    auto take = [&](size_t b) { char* r = w; w += up(b); return r; };
-    void* d_temp = take(temp_bytes);
-    int64_t* d_unique = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_counts = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_offsets = reinterpret_cast<int64_t*>(take((size_t)(run_cap + 1) * 8));
-    int64_t* d_nruns = reinterpret_cast<int64_t*>(take(256));
-    std::vector<const T*> src(nc);  // [y, x1..xp], device resident
-    for (int c = 0; c < nc; ++c) src[c] = cols[c];
-    if (space == PDS_HOST)
-        for (int c = 0; c < nc; ++c) {
-            T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            PDS_HIP_CHECK(hipMemcpyAsync(dcol, src[c], (size_t)n_rows * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            src[c] = dcol;
-        }
-    uint32_t* perm = nullptr;
-    if (!sorted) {
-        int64_t* sk = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        uint32_t* idx_in = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        perm = reinterpret_cast<uint32_t*>(take((size_t)n_rows * 4));
-        int64_t* sk2 = reinterpret_cast<int64_t*>(take((size_t)n_rows * 8));
-        if (int rc = keyed_sort(ctx, d_keys, n_rows, idx_in, sk, perm, d_temp, temp_bytes, sk2, d_minmax, mm)) return rc;
-        d_keys = sk;
-        if (!gather_frame_fits<T>(nc)) {
-            for (int c = 0; c < nc; ++c) {
-                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                if (int rc = launch_gather_rows<T>(ctx, src[c], perm, n_rows, dcol)) return rc;
-                src[c] = dcol;
-            }
-        } else {
-            std::vector<const T*> tbl(2 * (size_t)nc);
-            for (int c = 0; c < nc; ++c) tbl[c] = src[c];
-            for (int c = 0; c < nc; ++c) {
-                T* dcol = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-                tbl[nc + c] = dcol;
-                src[c] = dcol;
-            }
-            T* records = reinterpret_cast<T*>(take((size_t)n_rows * nc * sizeof(T)));
-            const T** d_tbl = reinterpret_cast<const T**>(take(2 * (size_t)nc * sizeof(T*)));
-            PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), 2 * (size_t)nc * sizeof(T*), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_gather_frame<T>(ctx, d_tbl, perm, nc, n_rows, records, (T* const*)(d_tbl + nc))) return rc;
-            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-        }
-    }
-    int64_t ng = 0;
-    if (sorted) {
-        ng = n_runs + 1;
-        if (int rc = keyed_runs_ordered(ctx, d_keys, n_rows, d_run_counts, d_run_prefix, d_run_masks, run_cap, d_unique, d_offsets, d_temp,
-                                        temp_bytes))
-            return rc;
-    } else if (int rc = keyed_runs(ctx, d_keys, n_rows, d_unique, d_counts, d_offsets, d_nruns, d_temp, temp_bytes, &ng)) {
-        return rc;
-    }
+    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat);
+    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, /*max_groups=*/n_rows, nullptr, kf)) return rc;
     T* d_co = coeffs;
     T* d_pr = pred;
     uint8_t* d_va = valid;
     if (stage_out) {
-        d_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
-        d_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-        d_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+        d_co = w.take<T>((size_t)n_rows * pp);
+        d_pr = w.take<T>((size_t)n_rows);
+        d_va = w.take<uint8_t>((size_t)n_rows);
     }
-    if (int rc = rolling_grouped_device<T>(ctx, src.data(), n_feat, n_rows, d_offsets, ng, add_bias, window, min_size, lambda, expanding, d_co,
-                                           d_pr, d_va))
+    if (int rc = rolling_grouped_device<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, add_bias, window, min_size, lambda, expanding,
+                                           d_co, d_pr, d_va))
         return rc;
     if (!sorted) {
         // back to frame order: in place when the caller's buffers are on the device, else into the staged outputs' own slots
@@ -251,11 +175,11 @@ static int rolling_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t
         T* o_pr = pred;
         uint8_t* o_va = valid;
         if (space == PDS_HOST) {
-            o_co = reinterpret_cast<T*>(take((size_t)n_rows * pp * sizeof(T)));
-            o_pr = reinterpret_cast<T*>(take((size_t)n_rows * sizeof(T)));
-            o_va = reinterpret_cast<uint8_t*>(take((size_t)n_rows));
+            o_co = w.take<T>((size_t)n_rows * pp);
+            o_pr = w.take<T>((size_t)n_rows);
+            o_va = w.take<uint8_t>((size_t)n_rows);
         }
-        if (int rc = launch_rolling_scatter<T>(ctx, d_co, d_pr, d_va, perm, n_rows, pp, o_co, o_pr, o_va)) return rc;
+        if (int rc = launch_rolling_scatter<T>(ctx, d_co, d_pr, d_va, kf.d_perm, n_rows, pp, o_co, o_pr, o_va)) return rc;
         d_co = o_co;
         d_pr = o_pr;
         d_va = o_va;

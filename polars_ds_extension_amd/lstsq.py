@@ -207,14 +207,18 @@ def _out_like(cols: _Cols, shape):
     return a, C.c_void_p(a.ctypes.data)
 
 
-def _out_u8(cols: _Cols, n):
+def _out_int(cols: _Cols, n, dtype: str):
     if cols.space == _lib.PDS_DEVICE:
         import torch
 
-        t = torch.empty(n, dtype=torch.uint8, device=cols.keep[0].device)
+        t = torch.empty(n, dtype=getattr(torch, dtype), device=cols.keep[0].device)
         return t, C.c_void_p(int(t.data_ptr()))
-    a = np.empty(n, dtype=np.uint8)
+    a = np.empty(n, dtype=dtype)
     return a, C.c_void_p(a.ctypes.data)
+
+
+def _out_u8(cols: _Cols, n):
+    return _out_int(cols, n, "uint8")
 
 
 def parse_null_policy(value: str):
@@ -663,42 +667,22 @@ def lin_reg_report_by_key(*x, target, key, add_bias: bool = False, std_err: str 
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
+    k, k_p = _key_arg(cols, key)
 
-        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
-        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-        k_p = C.c_void_p(int(k.data_ptr()))
-    else:
-        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-        k_p = C.c_void_p(k.ctypes.data)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
-    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
-    ng = C.c_int64(0)
-    while True:
-        if cols.space == _lib.PDS_DEVICE:
-            ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-            ok_p = C.c_void_p(int(ok.data_ptr()))
-        else:
-            ok = np.empty(cap, dtype=np.int64)
-            ok_p = C.c_void_p(ok.ctypes.data)
+    def call(cap, ok_p, ng_p):
         outs, rep = _report_grouped_outs(cols, cap, pp)
         if weights is not None:
             rc = ctx.fn("pds_wls_report_by_key")(ctx._h, cols.cols, cols.weights, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
-                                                 int(bool(add_bias)), C.c_int64(cap), ok_p, C.byref(rep), C.byref(ng))
+                                                 int(bool(add_bias)), C.c_int64(cap), ok_p, C.byref(rep), ng_p)
         else:
             rc = ctx.fn("pds_lin_reg_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space,
                                                      int(bool(add_bias)), _lib.SE_TYPES.get(std_err, 0), C.c_int64(cap), ok_p,
-                                                     C.byref(rep), C.byref(ng))
-        if rc != 0 and max_groups is None and int(ng.value) > cap:
-            cap = int(ng.value)  # more distinct keys than the first guess
-            continue
-        _lib.check(rc)
-        break
-    g = int(ng.value)
+                                                     C.byref(rep), ng_p)
+        return rc, outs
+
+    keys, outs, g = _by_key_retry(cols, max_groups, call)
     d = _report_grouped_dict(outs, cols.n_feat, add_bias, std_err, feature_names, g)
-    d["keys"] = ok[:g]
+    d["keys"] = keys
     return d
 
 
@@ -936,40 +920,18 @@ def lin_reg_by_key(*x, target, key, add_bias: bool = False, l1_reg: float = 0.0,
     _follow(ctx, cols)
     prm = _params(add_bias, l1_reg, l2_reg, tol, solver, positive, max_iter, singular_x_tol)
     pp = cols.n_feat + int(bool(add_bias))
-    # outputs are sized for max_groups distinct keys; without a hint start from n_rows / 16 (at least 2^20) and repeat with
-    # the exact count when there are more -- sizing for one key per row would allocate p' x n_rows coefficients
     n_rows = cols.n_rows
-    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
+    k, k_p = _key_arg(cols, key)
 
-        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
-        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-        k_p = C.c_void_p(int(k.data_ptr()))
-    else:
-        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-        k_p = C.c_void_p(k.ctypes.data)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
-    ng = C.c_int64(0)
-    while True:
-        if cols.space == _lib.PDS_DEVICE:
-            ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-            ok_p = C.c_void_p(int(ok.data_ptr()))
-        else:
-            ok = np.empty(cap, dtype=np.int64)
-            ok_p = C.c_void_p(ok.ctypes.data)
+    def call(cap, ok_p, ng_p):
         coeffs, co_p = _out_like(cols, (cap, pp))
         nulls, nu_p = _out_u8(cols, cap)
         rc = ctx.fn("pds_lr_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, C.byref(prm),
-                                     C.c_int64(cap), ok_p, co_p, nu_p, C.byref(ng))
-        if rc != 0 and max_groups is None and int(ng.value) > cap:
-            cap = int(ng.value)  # more distinct keys than the first guess
-            continue
-        _lib.check(rc)
-        break
-    g = int(ng.value)
-    return ok[:g], coeffs[:g], nulls[:g]
+                                     C.c_int64(cap), ok_p, co_p, nu_p, ng_p)
+        return rc, (coeffs, nulls)
+
+    keys, (coeffs, nulls), g = _by_key_retry(cols, max_groups, call)
+    return keys, coeffs[:g], nulls[:g]
 
 
 def lin_reg_by_key_multi(*x, target, key, contexts, n_slices: int = 0, add_bias: bool = False, l1_reg: float = 0.0, l2_reg: float = 0.0,
@@ -990,26 +952,19 @@ def lin_reg_by_key_multi(*x, target, key, contexts, n_slices: int = 0, add_bias:
     prm = _params(add_bias, l1_reg, l2_reg, tol, solver, positive, max_iter, singular_x_tol)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
-    k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
-    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
+    k, k_p = _key_arg(cols, key)
     handles = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    ng = C.c_int64(0)
     fn = contexts[0].fn("pds_lr_by_key_multi")
-    while True:
-        ok = np.empty(cap, dtype=np.int64)
-        coeffs = np.empty((cap, pp), dtype=_dtype())
-        nulls = np.empty(cap, dtype=np.uint8)
-        rc = fn(handles, len(contexts), int(n_slices), cols.cols, C.c_void_p(k.ctypes.data), cols.n_feat, C.c_int64(n_rows), C.byref(prm),
-                C.c_int64(cap), C.c_void_p(ok.ctypes.data), C.c_void_p(coeffs.ctypes.data), C.c_void_p(nulls.ctypes.data), C.byref(ng))
-        if rc != 0 and max_groups is None and int(ng.value) > cap:
-            cap = int(ng.value)
-            continue
-        _lib.check(rc)
-        break
-    g = int(ng.value)
-    return ok[:g], coeffs[:g], nulls[:g]
+
+    def call(cap, ok_p, ng_p):
+        coeffs, co_p = _out_like(cols, (cap, pp))
+        nulls, nu_p = _out_u8(cols, cap)
+        rc = fn(handles, len(contexts), int(n_slices), cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), C.byref(prm), C.c_int64(cap), ok_p,
+                co_p, nu_p, ng_p)
+        return rc, (coeffs, nulls)
+
+    keys, (coeffs, nulls), g = _by_key_retry(cols, max_groups, call)
+    return keys, coeffs[:g], nulls[:g]
 
 
 # ---- the exchange steps of SURVEY.md 8(e) between the contexts of ONE process (include/pds_lstsq.h: pds_allreduce_sum_*,
@@ -1086,6 +1041,35 @@ def _offsets_arg(cols: "_Cols", group_offsets):
     return off, C.c_void_p(off.ctypes.data)
 
 
+def _key_arg(cols: "_Cols", key):
+    """The key column as int64 in the inputs' space (and its address): one entry per row."""
+    k, k_p = _offsets_arg(cols, key)
+    if int(k.shape[0]) != cols.n_rows:
+        raise ValueError("`key` must have one entry per row")
+    return k, k_p
+
+
+def _by_key_retry(cols: "_Cols", max_groups, call):
+    """
+    The by-key entry points write at most `cap` groups and report the number of distinct keys.  `call(cap, keys_p, ng_p)` allocates
+    the outputs for `cap` groups, makes the C call and returns (rc, outputs).  Outputs are sized for max_groups distinct keys;
+    without a hint start from n_rows / 16 (at least 2^20) and repeat with the exact count when there are more -- sizing for one key
+    per row would allocate p' x n_rows coefficients.  Returns (keys [g] ascending, the outputs of the call that fitted, g).
+    """
+    n_rows = cols.n_rows
+    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
+    ng = C.c_int64(0)
+    while True:
+        keys, keys_p = _out_int(cols, cap, "int64")
+        rc, outs = call(cap, keys_p, C.byref(ng))
+        if rc != 0 and max_groups is None and int(ng.value) > cap:
+            cap = int(ng.value)  # more distinct keys than the first guess
+            continue
+        _lib.check(rc)
+        g = int(ng.value)
+        return keys[:g], outs, g
+
+
 def lin_reg_by_pred(*x, target, group_offsets, add_bias: bool = False, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5,
                     solver: str = "qr", max_iter: int = 200, positive: bool = False, singular_x_tol: float | None = None,
                     weights=None, ctx: Context | None = None):
@@ -1131,17 +1115,7 @@ def lin_reg_by_key_pred(*x, target, key, add_bias: bool = False, l1_reg: float =
     prm = (_params(add_bias, 0.0, 0.0, tol, solver, False, max_iter, 0.0) if weights is not None
            else _params(add_bias, l1_reg, l2_reg, tol, solver, positive, max_iter, singular_x_tol))
     n_rows = cols.n_rows
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
-
-        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
-        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-        k_p = C.c_void_p(int(k.data_ptr()))
-    else:
-        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-        k_p = C.c_void_p(k.ctypes.data)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
+    k, k_p = _key_arg(cols, key)
     pred, pr_p = _out_like(cols, n_rows)
     resid, re_p = _out_like(cols, n_rows)
     rnull, rn_p = _out_u8(cols, n_rows)
@@ -1166,14 +1140,12 @@ def lin_reg_by_key_pred_multi(*x, target, key, contexts, n_slices: int = 0, add_
     prm = (_params(add_bias, 0.0, 0.0, tol, solver, False, max_iter, 0.0) if weights is not None
            else _params(add_bias, l1_reg, l2_reg, tol, solver, positive, max_iter, singular_x_tol))
     n_rows = cols.n_rows
-    k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
+    k, k_p = _key_arg(cols, key)
     pred, resid = np.empty(n_rows, dtype=_dtype()), np.empty(n_rows, dtype=_dtype())
     rnull = np.empty(n_rows, dtype=np.uint8)
     handles = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
     _lib.check(contexts[0].fn("pds_lr_by_key_pred_multi")(handles, len(contexts), int(n_slices), cols.cols, cols.weights,
-                                                          C.c_void_p(k.ctypes.data), cols.n_feat, C.c_int64(n_rows), C.byref(prm),
+                                                          k_p, cols.n_feat, C.c_int64(n_rows), C.byref(prm),
                                                           C.c_void_p(pred.ctypes.data), C.c_void_p(resid.ctypes.data),
                                                           C.c_void_p(rnull.ctypes.data)))
     return pred, resid, rnull
@@ -1376,13 +1348,7 @@ def _glm_check(x, max_iter, what):
 
 
 def _out_i32(cols: _Cols, n):
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
-
-        t = torch.empty(n, dtype=torch.int32, device=cols.keep[0].device)
-        return t, C.c_void_p(int(t.data_ptr()))
-    a = np.empty(n, dtype=np.int32)
-    return a, C.c_void_p(a.ctypes.data)
+    return _out_int(cols, n, "int32")
 
 
 def _tol_arg(tol):
@@ -1438,46 +1404,26 @@ def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
-    cap = int(max_groups) if max_groups is not None else (n_rows if n_rows <= (1 << 20) else max(1 << 20, n_rows // 16))
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
-
-        k = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
-        k = k.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-        k_p = C.c_void_p(int(k.data_ptr()))
-    else:
-        k = np.ascontiguousarray(np.asarray(key), dtype=np.int64)
-        k_p = C.c_void_p(k.ctypes.data)
-    if int(k.shape[0]) != n_rows:
-        raise ValueError("`key` must have one entry per row")
+    k, k_p = _key_arg(cols, key)
     pred = rnull = None
     pr_p = rn_p = None
     if return_pred:
         pred, pr_p = _out_like(cols, n_rows)
         rnull, rn_p = _out_u8(cols, n_rows)
-    ng = C.c_int64(0)
-    while True:
-        if cols.space == _lib.PDS_DEVICE:
-            ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-            ok_p = C.c_void_p(int(ok.data_ptr()))
-        else:
-            ok = np.empty(cap, dtype=np.int64)
-            ok_p = C.c_void_p(ok.ctypes.data)
+
+    def call(cap, ok_p, ng_p):
         coeffs, co_p = _out_like(cols, (cap, pp))
         iters, it_p = _out_i32(cols, cap)
         nulls, nu_p = _out_u8(cols, cap)
         rc = ctx.fn("pds_glm_irls_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
                                            C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p,
-                                           co_p, it_p, nu_p, C.byref(ng), pr_p, rn_p)
-        if rc != 0 and max_groups is None and int(ng.value) > cap:
-            cap = int(ng.value)  # more distinct keys than the first guess
-            continue
-        _lib.check(rc)
-        break
-    g = int(ng.value)
+                                           co_p, it_p, nu_p, ng_p, pr_p, rn_p)
+        return rc, (coeffs, iters, nulls)
+
+    keys, (coeffs, iters, nulls), g = _by_key_retry(cols, max_groups, call)
     if return_pred:
-        return ok[:g], coeffs[:g], iters[:g], nulls[:g], pred, rnull
-    return ok[:g], coeffs[:g], iters[:g], nulls[:g]
+        return keys, coeffs[:g], iters[:g], nulls[:g], pred, rnull
+    return keys, coeffs[:g], iters[:g], nulls[:g]
 
 
 def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,
