@@ -7,7 +7,8 @@
  * /root/reference/src/num_ext/linear_regression.rs:419,704,822,1121,1206 and the *_f32 twins in
  * linear_regression_f32.rs) would bind over `extern "C"` after unwrapping the Arrow column buffers.
  * They replace the calls those functions make into src/linear/lr/lr_solvers.rs and
- * src/linear/online_lr/lr_online_solvers.rs.  INTEGRATION.md shows the Rust-side binding.
+ * src/linear/online_lr/lr_online_solvers.rs; pds_glm_irls_* and pds_mixed_reml_* stand behind the pyclasses PyGLM and
+ * PyMixedModel (src/linear/glm/glm_solvers.rs, src/linear/mixed/mod.rs).  INTEGRATION.md shows the Rust-side binding.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in any signature.
@@ -85,7 +86,9 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *   "report_chunk_groups"                     pds_lin_reg_report_grouped_* / _by_key_*, pds_wls_report_*: groups per pass (<= 0: the default).
  *   "glm_split_rows"                          pds_glm_irls_grouped_* / _by_key_*: groups of more rows are fitted by the full-device
  *                                             iteration, one by one (<= 0: the default, 16384; at least 64).
- * value: 0 / 1 (report_chunk_groups, glm_split_rows: a count).  Unknown names are PDS_ERR_INVALID. */
+ *   "mixed_split_rows"                        pds_mixed_*: groups of more rows are cut into row chunks that are separate work items
+ *                                             (<= 0: the default, 16384; at least 64).
+ * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host-frame staging (process wide): chunk_mb = bytes of one row chunk of a PDS_HOST frame (default 256, env
  * PDS_HOST_CHUNK_MB); resident_max_mb = largest host frame that pds_lr_pred_* still stages whole (one PCIe trip; larger
@@ -643,6 +646,52 @@ int pds_glm_irls_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64
 int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                             int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null);
+/*
+ * pds_mixed_reml_grouped_* / pds_mixed_reml_by_key_* / pds_mixed_profile_grouped_*: the random-intercept linear mixed model
+ * y = X beta + Z u + e, u ~ N(0, sigma_g^2 I), e ~ N(0, sigma_e^2 I), fitted by REML as fit_reml does (src/linear/mixed/mod.rs:173-272):
+ * golden section over gamma = sigma_g^2 / sigma_e^2 in [0, 1e6] on the profiled deviance
+ *   dev(gamma) = (n - p') ln(r' H^-1 r / (n - p')) + sum_g ln(1 + gamma n_g) + ln det(X' H^-1 X),   H = I + gamma Z Z',
+ * bracket and update order as lines 195-219, stop at hi - lo < tol or after max_iter steps, gamma = (lo + hi) / 2.
+ * cols = [y, x1..xp], 1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED); X = [1 | x1..xp], p' = p + 1, the intercept FIRST.  f32
+ * frames are fitted in f64 arithmetic.  Groups: contiguous rows [group_offsets[g], group_offsets[g+1]) (`space`-resident, n_groups + 1
+ * values, non-decreasing, inside the frame; empty groups are allowed and ignored), or int64 keys in any row order (ordered keys move
+ * nothing; otherwise sort + gather).  The frame is streamed a fixed number of times (group means, the within-group scatter W, which
+ * features vary inside a group: mixed.hip); an evaluation is then a reduction over the groups,
+ *   [X y]' H^-1 [X y] = W + sum_g n_g / (1 + gamma n_g) [1, m_g] [1, m_g]',
+ * one blocking copy of a 296-double record per evaluation, factored on the host.  Two calls give the same bits.
+ * Outputs are doubles in HOST memory whatever `space` is: coeffs / std_errors / dfs [p'] (std_errors = sqrt(resid_variance
+ * diag((X' H^-1 X)^-1)) at the optimum; dfs by containment, mod.rs:233-263: the intercept and every feature that is constant inside
+ * every group get G - rank(those columns), the others n - rank([X | Z]), G = non-empty groups), *gamma, *resid_variance,
+ * *n_groups_fit = G, *n_eval = deviance evaluations (two to start, one per step, one at the optimum).
+ * Deliberate deviations: (1) the two ranks come from column-pivoted Cholesky factors of Gram matrices (rank([X | Z]) = G +
+ * rank(W_xx)), a pivot counting above 1e-12 of the first; the reference's cutoff is 1e-9 on |R_ii| / |R_00| of a QR of the rows,
+ * i.e. 1e-18 on a Gram pivot, which f64 cannot resolve -- this matters only for within-group column dependence between 1e-9 and 1e-6;
+ * (2) the leading block counts as not positive definite when a Cholesky pivot falls below 1e-13 of its diagonal entry (an exactly
+ * duplicated column would otherwise pass or fail by rounding).
+ * pds_mixed_profile_grouped_*: the search-free form -- for each of n_gammas values (host array, finite, >= 0) deviance [k],
+ * beta [k][p'] (the GLS coefficients at that gamma) and resid_variance [k], host arrays.
+ * Errors: PDS_ERR_INVALID (null arguments, offsets that decrease or leave the frame, max_iter < 0, tol not finite);
+ * PDS_ERR_TOO_FEW_ROWS "Not enough rows to fit a mixed model with this many fixed effects." (n <= p'); PDS_ERR_NUMERIC "X'HiX is not
+ * positive definite; design may be rank-deficient." / "Residual variance estimate is non-positive." (NaN included).
+ */
+int pds_mixed_reml_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int max_iter, double tol, double* coeffs, double* std_errors, double* dfs,
+                               double* gamma, double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval);
+int pds_mixed_reml_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int max_iter, double tol, double* coeffs, double* std_errors, double* dfs,
+                               double* gamma, double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval);
+int pds_mixed_reml_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int max_iter, double tol, double* coeffs, double* std_errors, double* dfs, double* gamma,
+                              double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval);
+int pds_mixed_reml_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int max_iter, double tol, double* coeffs, double* std_errors, double* dfs, double* gamma,
+                              double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval);
+int pds_mixed_profile_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                  int64_t n_groups, pds_space space, const double* gammas, int n_gammas, double* deviance, double* beta,
+                                  double* resid_variance);
+int pds_mixed_profile_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                  int64_t n_groups, pds_space space, const double* gammas, int n_gammas, double* deviance, double* beta,
+                                  double* resid_variance);
 /*
  * pds_lin_reg_report_grouped_* / pds_lin_reg_report_by_key_*: `df.group_by(key).agg(pds.lin_reg_report(...))` in one call -- for
  * every group g what pds_lin_reg_report_* returns on g's rows alone (same se_type / add_bias, beta = (X'X)^-1 X'y through the

@@ -2,7 +2,7 @@
 polars_ds_extension_amd -- MI355X (gfx950) implementation of polars_ds's least-squares expression path.
 
 Only that path (pds.lin_reg / lin_reg_report / rolling_lin_reg / recursive_lin_reg, OLS / ridge / lasso /
-elastic net / NNLS / WLS, pds.logistic_reg and GLMs per group by IRLS) is implemented; see DESIGN.md for the scope table and INTEGRATION.md for how
+elastic net / NNLS / WLS, pds.logistic_reg, GLMs per group by IRLS and the random-intercept MixedModel by REML) is implemented; see DESIGN.md for the scope table and INTEGRATION.md for how
 the C ABI (include/pds_lstsq.h) drops in behind the reference's `#[polars_expr]` functions.
 """
 from . import config  # noqa: F401
@@ -34,6 +34,8 @@ from .lstsq import (  # noqa: F401
     lin_reg_from_moments,
     lin_reg_report,
     lin_reg_w_rcond,
+    mixed_reml,
+    mixed_reml_profile,
     query_ar_coeffs,
     recursive_lin_reg,
     rolling_lin_reg,

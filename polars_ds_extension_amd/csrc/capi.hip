@@ -28,6 +28,7 @@ namespace pds {
 #include "capi_rolling.hpp"
 #include "capi_models.hpp"
 #include "capi_glm_grouped.hpp"
+#include "capi_mixed.hpp"
 
 }  // namespace pds
 
@@ -125,6 +126,7 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     if (n == "keyed_sort") ctx->opt_keyed_sort = value != 0;
     else if (n == "wide_f32_native") ctx->opt_wide_f32_native = value != 0;
     else if (n == "glm_split_rows") ctx->opt_glm_split_rows = value > 0 ? (int64_t)value : 0;
+    else if (n == "mixed_split_rows") ctx->opt_mixed_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
@@ -162,6 +164,43 @@ int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null) {
     return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups, out_keys,
                                        coeffs, n_iter, is_null, n_groups, pred, row_null);
+}
+
+int pds_mixed_reml_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int max_iter, double tol, double* coeffs, double* std_errors, double* dfs,
+                               double* gamma, double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval) {
+    return pds::mixed_reml_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, max_iter, tol, coeffs, std_errors, dfs, gamma,
+                                        resid_variance, n_groups_fit, n_eval);
+}
+int pds_mixed_reml_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int max_iter, double tol, double* coeffs, double* std_errors, double* dfs,
+                               double* gamma, double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval) {
+    return pds::mixed_reml_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, max_iter, tol, coeffs, std_errors, dfs, gamma,
+                                       resid_variance, n_groups_fit, n_eval);
+}
+int pds_mixed_reml_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int max_iter, double tol, double* coeffs, double* std_errors, double* dfs, double* gamma,
+                              double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval) {
+    return pds::mixed_reml_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, max_iter, tol, coeffs, std_errors, dfs, gamma,
+                                               resid_variance, n_groups_fit, n_eval);
+}
+int pds_mixed_reml_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int max_iter, double tol, double* coeffs, double* std_errors, double* dfs, double* gamma,
+                              double* resid_variance, int64_t* n_groups_fit, int32_t* n_eval) {
+    return pds::mixed_reml_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, max_iter, tol, coeffs, std_errors, dfs, gamma,
+                                              resid_variance, n_groups_fit, n_eval);
+}
+int pds_mixed_profile_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                  int64_t n_groups, pds_space space, const double* gammas, int n_gammas, double* deviance, double* beta,
+                                  double* resid_variance) {
+    return pds::mixed_profile_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, gammas, n_gammas, deviance, beta,
+                                           resid_variance);
+}
+int pds_mixed_profile_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                  int64_t n_groups, pds_space space, const double* gammas, int n_gammas, double* deviance, double* beta,
+                                  double* resid_variance) {
+    return pds::mixed_profile_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, gammas, n_gammas, deviance, beta,
+                                          resid_variance);
 }
 
 int pds_lr_rowmajor_f64(pds_ctx* ctx, const double* X, int64_t ld, const double* y, int64_t n_rows, int n_feat, pds_space space,

@@ -116,6 +116,7 @@ struct pds_ctx {
     bool opt_wide_f32_native = false;  // "wide_f32_native" / PDS_WIDE_F32_NATIVE=1: f32 Gram beyond 64 features on the f32 matrix instructions
     int64_t opt_glm_split_rows = 0;       // "glm_split_rows": groups above this many rows leave the grouped IRLS kernel (0: the default)
     int64_t opt_report_chunk_groups = 0;  // "report_chunk_groups": groups per pass of the grouped report (0: from its record budget)
+    int64_t opt_mixed_split_rows = 0;     // "mixed_split_rows": groups above this many rows are cut into row chunks (0: the default)
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<float> kind_samples[8];  // the individual bracketed durations (ms), newest kept up to 4096 per class
@@ -310,6 +311,32 @@ int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bi
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
                           const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm);
+// ---- mixed.hip: the random-intercept mixed model's passes (capi_mixed.hpp).  One record layout for the scatter partials and the
+// per-gamma sums (doubles): [0,256) the 16 x 16 feature block [i * 16 + j]; [256,272) the y column; [272,288) sum c m_f (profile
+// only); 288 the y diagonal; 289 sum c; 290 sum c m_y; 291 sum ln(1 + gamma n_g)
+constexpr int kMixedRecW = 0, kMixedRecXY = 256, kMixedRecCM = 272, kMixedRecYY = 288, kMixedRecC = 289, kMixedRecCY = 290, kMixedRecLD = 291;
+constexpr int kMixedRecStride = 296;
+// the row chunks of the groups above the split threshold (device arrays the host filled); n_chunks = 0: none
+struct MixedChunks {
+    int64_t n_chunks = 0, n_long = 0;
+    const int64_t *d_chunk_r0 = nullptr, *d_chunk_n = nullptr, *d_chunk_g = nullptr, *d_chunk_first = nullptr;  // per chunk
+    const int64_t *d_long_g = nullptr, *d_long_c0 = nullptr, *d_long_nc = nullptr, *d_long_first = nullptr, *d_long_n = nullptr;  // per group
+    double* d_sums = nullptr;     // n_chunks x (p + 1)
+    unsigned* d_varies = nullptr;  // n_chunks
+};
+int mixed_stats_blocks(const pds_ctx* ctx, int64_t n_work);    // partial records a stats / chunk launch writes
+int mixed_profile_blocks(const pds_ctx* ctx, int64_t n_groups);
+// group means (feature-major, d_means[(p + 1) x n_groups]: features, then y), the "varies within some group" bits of the features
+// (*d_flags) and the within scatter W (one record at d_w).  d_cols: x_0 .. x_{p-1}, y.  d_partials: room for
+// mixed_stats_blocks(n_groups) + mixed_stats_blocks(n_chunks) records, d_stage for a 64th of that (rounded up).  d_beta0 (nullable,
+// p + 1 values, intercept first): the target is read as y - [1, x] . beta0.
+template <typename T>
+int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                       const MixedChunks& ch, const double* d_beta0, double* d_means, unsigned* d_flags, double* d_partials,
+                       double* d_stage, double* d_w);
+// one gamma: sum_g c_g [m m' | m m_y | m], sum c, sum c m_y, sum c m_y^2, sum ln(1 + gamma n_g) -> one record at d_out
+int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const int64_t* d_off, int64_t n_groups, double gamma,
+                         double* d_partials, double* d_stage, double* d_out);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream

@@ -1,0 +1,438 @@
+// mixed.hip -- the device side of the random-intercept mixed model (REML, capi_mixed.hpp): everything the profiled deviance needs
+// from the frame, in a fixed number of passes over it, and the per-gamma reduction over the groups.
+//
+// With z_i = [x_i, y_i], m_g the mean of z over group g and n_g its row count,
+//     [X y]' H^-1 [X y] = W + sum_g c_g(gamma) [1, m_g] [1, m_g]',   c_g = n_g / (1 + gamma n_g),   H = I + gamma Z Z',
+// where W = sum_g sum_{i in g} (z_i - m_g)(z_i - m_g)' is the within-group scatter (its intercept row and column are exactly zero
+// and never formed).  Every term is positive semi-definite: nothing cancels, whatever the size of the group means.
+//
+//   * mixed_stats_kernel: ONE wave walks groups (grid stride).  A group of up to kMxCap = 128 rows is loaded once into a
+//     wave-private LDS tile (feature-major, row stride kMxStride = 2 mod 32, the layout of grouped_irls.hip), summed and centred
+//     there; a longer group reads its rows twice (sums, then centred products through the first 64 row slots of the tile).  The
+//     16 x 16 feature block of W comes from one v_mfma_f64_16x16x4 accumulator with operands (x - m, x - m), W_xy from a second
+//     matrix instruction with B = [y - m_y | 0 ..], W_yy from a per-lane register folded by a fixed butterfly.  The wave keeps its
+//     accumulators across all the groups it walks and writes ONE partial record at its end.  It also writes the group's means
+//     (feature-major, G values per column) and ORs into a word the features that vary inside some group (an exact comparison
+//     of every row with the group's first row; integer OR, so the order does not matter).  A column that does not vary inside a
+//     group has that group's first value as its mean, exactly.
+//   * groups above `split_rows` are cut by the host into row chunks that are separate work items: mixed_chunk_sums_kernel (a wave
+//     per chunk), mixed_chunk_means_kernel (a group's chunk sums added in chunk order) and mixed_chunk_scatter_kernel (centred
+//     products of a chunk with its group's mean; again one partial record per wave).
+//   * mixed_sum_records_kernel adds partial records in index order (two stages); no floating-point atomics anywhere, so two calls
+//     give the same bits.
+//   * mixed_profile_kernel: for one gamma, 64 groups per step through the same LDS layout: sum_g c_g m m' (matrix instruction,
+//     operands (c m, m)), sum_g c_g m m_y and sum_g c_g m (second instruction), and sum c, sum c m_y, sum c m_y^2,
+//     sum ln(1 + gamma n_g) from per-lane registers; records summed by mixed_sum_records_kernel.  Empty groups contribute nothing.
+//   * every frame kernel takes an optional coefficient vector beta0 (intercept first): the target column is then read as
+//     y - [1, x] . beta0, formed per row in registers.  The host runs the passes twice (capi_mixed.hpp): on y itself, then on the
+//     residual of a first GLS solution, so that r' H^-1 r comes out of sums of its own size instead of a difference of large ones.
+// Arithmetic is f64 for f64 and f32 frames alike (an f32 frame is converted on load).
+#include "common.hpp"
+
+#include <algorithm>
+
+namespace pds {
+
+namespace {
+
+typedef double mx_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int kMxCap = 128;            // resident rows of a group (two 64-row steps)
+constexpr int kMxStride = kMxCap + 2;  // doubles per feature row of the tile: = 2 (mod 32), conflict-free operand reads
+constexpr int kMxPStride = 64 + 2;     // the profile kernel's tile: 64 groups per step
+
+__device__ __forceinline__ double mx_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return __shfl(v, 0, 64);  // (lane 0's order for every lane)
+}
+
+// the target of a row: y, or y - [1, x] . beta0 (b0: intercept first; x: the row's features)
+template <int P>
+__device__ __forceinline__ double mx_target(double yv, const double* x, const double* b0, bool has_b0) {
+    if (has_b0) {
+        yv -= b0[0];
+#pragma unroll
+        for (int c = 0; c < P; ++c) yv = fma(-x[c], b0[1 + c], yv);
+    }
+    return yv;
+}
+
+template <int P>
+__device__ __forceinline__ bool mx_load_beta0(const double* __restrict__ beta0, double* b0) {
+#pragma unroll
+    for (int c = 0; c <= P; ++c) b0[c] = beta0 ? beta0[c] : 0.0;
+    return beta0 != nullptr;
+}
+
+// centred products of the rows [r0, r0 + n) with the means `mean` (features, then y), 64 rows per step through the first 64 row
+// slots of the tile
+template <typename T, int P>
+__device__ __forceinline__ void mx_stream_centred(const gptr<T>* cx, gptr<T> cy, int64_t r0, int64_t n, const double* mean, const double* b0,
+                                                  bool has_b0, double* xt, int lane, mx_d4& acc, mx_d4& acc2, double& yy) {
+    const int f = lane & 15, kq = lane >> 4;
+    for (int64_t base = 0; base < n; base += 64) {
+        const int64_t r = base + lane;
+        const bool live = r < n;
+        PDS_WAVE_LDS_SYNC();  // (the previous step's operand reads are done)
+        double x[P];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            x[c] = live ? (double)cx[c][r0 + r] : 0.0;
+            xt[c * kMxStride + lane] = live ? x[c] - mean[c] : 0.0;
+        }
+        const double yc = live ? mx_target<P>((double)cy[r0 + r], x, b0, has_b0) - mean[P] : 0.0;
+        xt[P * kMxStride + lane] = yc;
+        yy = fma(yc, yc, yy);
+        PDS_WAVE_LDS_SYNC();
+        const int steps = (int)((std::min<int64_t>(64, n - base) + 3) >> 2);
+        for (int m = 0; m < steps; ++m) {
+            const int row = 4 * m + kq;
+            const double xv = f < P ? xt[f * kMxStride + row] : 0.0;
+            const double yv = xt[P * kMxStride + row];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, xv, acc, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, f == 0 ? yv : 0.0, acc2, 0, 0, 0);  // B column 0 = y - m_y
+        }
+    }
+}
+
+// D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 reg
+__device__ __forceinline__ void mx_write_record(double* rec, int lane, const mx_d4& acc, const mx_d4& acc2, double yy) {
+    const int f = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int i = kq + 4 * reg;
+        rec[kMixedRecW + i * 16 + f] = acc[reg];
+        if (f == 0) rec[kMixedRecXY + i] = acc2[reg];
+    }
+    yy = mx_wave_sum(yy);
+    if (lane == 0) rec[kMixedRecYY] = yy;
+    // the slots only the profile records use: the record sum reads all of them
+    if (lane < 16) rec[kMixedRecCM + lane] = 0.0;
+    if (lane > 0 && lane < kMixedRecStride - kMixedRecYY) rec[kMixedRecYY + lane] = 0.0;
+}
+
+template <typename T, int P>
+__global__ __launch_bounds__(64) void mixed_stats_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ off, int64_t n_groups,
+                                                         int64_t split_rows, const double* __restrict__ beta0, double* __restrict__ means,
+                                                         unsigned* __restrict__ flags, double* __restrict__ partials) {
+    __shared__ double xt[(P + 1) * kMxStride];  // features 0 .. P - 1, then y: [c * kMxStride + row]
+    const int lane = threadIdx.x;
+    const int f = lane & 15, kq = lane >> 4;
+    double b0[P + 1];
+    const bool has_b0 = mx_load_beta0<P>(beta0, b0);
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    double yy = 0.0;
+    unsigned vary_all = 0;
+    for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const int64_t r0 = off[g], n = off[g + 1] - r0;  // (the host has validated the offsets)
+        if (n > split_rows) continue;                    // cut into chunks: the chunk kernels
+        if (n <= 0) {
+            if (lane <= P) means[(int64_t)lane * n_groups + g] = 0.0;
+            continue;
+        }
+        const bool resident = n <= kMxCap;
+        PDS_WAVE_LDS_SYNC();  // (the previous group's operand reads are done)
+        double s[P + 1], first[P + 1], mean[P + 1];
+        unsigned vary = 0;
+#pragma unroll
+        for (int c = 0; c <= P; ++c) s[c] = 0.0;
+        for (int64_t base = 0; base < n; base += 64) {
+            const int64_t r = base + lane;
+            const bool live = r < n;
+            double x[P];
+#pragma unroll
+            for (int c = 0; c < P; ++c) x[c] = live ? (double)cx[c][r0 + r] : 0.0;
+            const double yv = live ? mx_target<P>((double)cy[r0 + r], x, b0, has_b0) : 0.0;
+#pragma unroll
+            for (int c = 0; c <= P; ++c) {
+                const double v = c < P ? x[c] : yv;
+                if (base == 0) first[c] = __shfl(v, 0, 64);
+                s[c] += v;
+                if (__any(live && v != first[c])) vary |= 1u << c;
+                if (resident) xt[c * kMxStride + r] = v;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c <= P; ++c) {
+            const double sum = mx_wave_sum(s[c]);
+            mean[c] = ((vary >> c) & 1u) ? sum / (double)n : first[c];
+            if (lane == c) means[(int64_t)c * n_groups + g] = mean[c];
+        }
+        vary_all |= vary;
+        if (resident) {
+            for (int64_t base = 0; base < n; base += 64) {  // (a lane centres the slots it wrote)
+                const int64_t r = base + lane;
+                const bool live = r < n;
+#pragma unroll
+                for (int c = 0; c < P; ++c) xt[c * kMxStride + r] = live ? xt[c * kMxStride + r] - mean[c] : 0.0;
+                const double yc = live ? xt[P * kMxStride + r] - mean[P] : 0.0;
+                xt[P * kMxStride + r] = yc;
+                yy = fma(yc, yc, yy);
+            }
+            PDS_WAVE_LDS_SYNC();
+            const int steps = (int)((n + 3) >> 2);  // (rows n .. 4 steps - 1 hold zeros)
+            for (int m = 0; m < steps; ++m) {
+                const int row = 4 * m + kq;
+                const double xv = f < P ? xt[f * kMxStride + row] : 0.0;
+                const double yv = xt[P * kMxStride + row];
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, xv, acc, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, f == 0 ? yv : 0.0, acc2, 0, 0, 0);
+            }
+        } else {
+            mx_stream_centred<T, P>(cx, cy, r0, n, mean, b0, has_b0, xt, lane, acc, acc2, yy);
+        }
+    }
+    if (lane == 0 && (vary_all & ((1u << P) - 1u))) atomicOr(flags, vary_all & ((1u << P) - 1u));
+    mx_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, acc, acc2, yy);
+}
+
+// column sums of one chunk, and which columns differ from the first row of the chunk's GROUP
+template <typename T, int P>
+__global__ __launch_bounds__(64) void mixed_chunk_sums_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ chunk_r0,
+                                                              const int64_t* __restrict__ chunk_n, const int64_t* __restrict__ chunk_first,
+                                                              int64_t n_chunks, const double* __restrict__ beta0, double* __restrict__ sums,
+                                                              unsigned* __restrict__ varies) {
+    const int lane = threadIdx.x;
+    gptr<T> cx[P + 1];
+#pragma unroll
+    for (int c = 0; c <= P; ++c) cx[c] = as_global(cols[c]);
+    double b0[P + 1];
+    const bool has_b0 = mx_load_beta0<P>(beta0, b0);
+    for (int64_t k = blockIdx.x; k < n_chunks; k += gridDim.x) {
+        const int64_t r0 = chunk_r0[k], n = chunk_n[k], rf = chunk_first[k];
+        double s[P + 1], first[P + 1];
+        unsigned vary = 0;
+#pragma unroll
+        for (int c = 0; c <= P; ++c) {
+            s[c] = 0.0;
+            first[c] = (double)cx[c][rf];
+        }
+        first[P] = mx_target<P>(first[P], first, b0, has_b0);
+        for (int64_t base = 0; base < n; base += 64) {
+            const int64_t r = base + lane;
+            const bool live = r < n;
+            double x[P];
+#pragma unroll
+            for (int c = 0; c < P; ++c) x[c] = live ? (double)cx[c][r0 + r] : 0.0;
+            const double yv = live ? mx_target<P>((double)cx[P][r0 + r], x, b0, has_b0) : 0.0;
+#pragma unroll
+            for (int c = 0; c <= P; ++c) {
+                const double v = c < P ? x[c] : yv;
+                s[c] += v;
+                if (__any(live && v != first[c])) vary |= 1u << c;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c <= P; ++c) {
+            const double sum = mx_wave_sum(s[c]);
+            if (lane == c) sums[k * (P + 1) + c] = sum;
+        }
+        if (lane == 0) varies[k] = vary;
+    }
+}
+
+// a long group's chunk sums in chunk order -> its means; lane c = column c
+template <typename T>
+__global__ __launch_bounds__(64) void mixed_chunk_means_kernel(const T* const* __restrict__ cols, int p, const int64_t* __restrict__ long_g,
+                                                               const int64_t* __restrict__ long_c0, const int64_t* __restrict__ long_nc,
+                                                               const int64_t* __restrict__ long_first, const int64_t* __restrict__ long_n,
+                                                               const double* __restrict__ sums, const unsigned* __restrict__ varies,
+                                                               const double* __restrict__ beta0, int64_t n_groups,
+                                                               double* __restrict__ means, unsigned* __restrict__ flags) {
+    const int lane = threadIdx.x;
+    const int64_t j = blockIdx.x;
+    const int64_t c0 = long_c0[j], nc = long_nc[j];
+    unsigned vary = 0;
+    double sum = 0.0;
+    for (int64_t k = 0; k < nc; ++k) {
+        vary |= varies[c0 + k];
+        if (lane <= p) sum += sums[(c0 + k) * (p + 1) + lane];
+    }
+    if (lane <= p) {
+        double first = (double)as_global(cols[lane])[long_first[j]];
+        if (lane == p && beta0) {  // (the order of mx_target)
+            first -= beta0[0];
+            for (int c = 0; c < p; ++c) first = fma(-(double)as_global(cols[c])[long_first[j]], beta0[1 + c], first);
+        }
+        means[(int64_t)lane * n_groups + long_g[j]] = ((vary >> lane) & 1u) ? sum / (double)long_n[j] : first;
+    }
+    vary &= (1u << p) - 1u;
+    if (lane == 0 && vary) atomicOr(flags, vary);
+}
+
+// centred products of the chunks with their groups' means: the wave keeps its accumulators across the chunks it walks
+template <typename T, int P>
+__global__ __launch_bounds__(64) void mixed_chunk_scatter_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ chunk_r0,
+                                                                 const int64_t* __restrict__ chunk_n, const int64_t* __restrict__ chunk_g,
+                                                                 int64_t n_chunks, int64_t n_groups, const double* __restrict__ beta0,
+                                                                 const double* __restrict__ means, double* __restrict__ partials) {
+    __shared__ double xt[(P + 1) * kMxStride];
+    const int lane = threadIdx.x;
+    double b0[P + 1];
+    const bool has_b0 = mx_load_beta0<P>(beta0, b0);
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    double yy = 0.0;
+    for (int64_t k = blockIdx.x; k < n_chunks; k += gridDim.x) {
+        const int64_t g = chunk_g[k];
+        double mean[P + 1];
+#pragma unroll
+        for (int c = 0; c <= P; ++c) mean[c] = means[(int64_t)c * n_groups + g];
+        mx_stream_centred<T, P>(cx, cy, chunk_r0[k], chunk_n[k], mean, b0, has_b0, xt, lane, acc, acc2, yy);
+    }
+    mx_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, acc, acc2, yy);
+}
+
+// block b: out[b] = in[b per] + in[b per + 1] + ... in index order, element by element
+__global__ __launch_bounds__(320) void mixed_sum_records_kernel(const double* __restrict__ in, int n_rec, int per, double* __restrict__ out) {
+    const int e = threadIdx.x;
+    if (e >= kMixedRecStride) return;
+    const int r0 = blockIdx.x * per, r1 = std::min(n_rec, r0 + per);
+    double s = 0.0;
+    for (int r = r0; r < r1; ++r) s += in[(int64_t)r * kMixedRecStride + e];
+    out[(int64_t)blockIdx.x * kMixedRecStride + e] = s;
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void mixed_profile_kernel(const double* __restrict__ means, const int64_t* __restrict__ off, int64_t n_groups,
+                                                           double gamma, double* __restrict__ partials) {
+    __shared__ double mt[(P + 1) * kMxPStride + 64];
+    double* ct = mt + (P + 1) * kMxPStride;  // c_g of the step's groups
+    const int lane = threadIdx.x;
+    const int f = lane & 15, kq = lane >> 4;
+    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    double sc = 0.0, scy = 0.0, scyy = 0.0, sld = 0.0;
+    const int64_t n_tiles = (n_groups + 63) / 64;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t g = t * 64 + lane;
+        const int64_t ng = g < n_groups ? off[g + 1] - off[g] : 0;
+        const bool live = ng > 0;  // (an empty group contributes nothing)
+        const double nd = (double)ng;
+        const double cg = live ? nd / (1.0 + gamma * nd) : 0.0;
+        if (live) sld += log(1.0 + gamma * nd);
+        PDS_WAVE_LDS_SYNC();  // (the previous step's operand reads are done)
+        double my = 0.0;
+#pragma unroll
+        for (int c = 0; c <= P; ++c) {
+            const double mv = live ? means[(int64_t)c * n_groups + g] : 0.0;
+            mt[c * kMxPStride + lane] = mv;
+            if (c == P) my = mv;
+        }
+        ct[lane] = cg;
+        sc += cg;
+        scy = fma(cg, my, scy);
+        scyy = fma(cg * my, my, scyy);
+        PDS_WAVE_LDS_SYNC();
+        const int steps = (int)((std::min<int64_t>(64, n_groups - t * 64) + 3) >> 2);
+        for (int m = 0; m < steps; ++m) {
+            const int row = 4 * m + kq;
+            const double xv = f < P ? mt[f * kMxPStride + row] : 0.0;
+            const double cv = ct[row];
+            const double bsel = f == 0 ? cv * mt[P * kMxPStride + row] : (f == 1 ? cv : 0.0);  // B columns: 0 = c m_y, 1 = c
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(cv * xv, xv, acc, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, bsel, acc2, 0, 0, 0);
+        }
+    }
+    double* rec = partials + (int64_t)blockIdx.x * kMixedRecStride;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int i = kq + 4 * reg;
+        rec[kMixedRecW + i * 16 + f] = acc[reg];
+        if (f == 0) rec[kMixedRecXY + i] = acc2[reg];
+        if (f == 1) rec[kMixedRecCM + i] = acc2[reg];
+    }
+    sc = mx_wave_sum(sc);
+    scy = mx_wave_sum(scy);
+    scyy = mx_wave_sum(scyy);
+    sld = mx_wave_sum(sld);
+    if (lane == 0) {
+        rec[kMixedRecYY] = scyy;
+        rec[kMixedRecC] = sc;
+        rec[kMixedRecCY] = scy;
+        rec[kMixedRecLD] = sld;
+    }
+    if (lane > kMixedRecLD - kMixedRecYY && lane < kMixedRecStride - kMixedRecYY) rec[kMixedRecYY + lane] = 0.0;  // (padding)
+}
+
+// records [0, n_rec) of `d_rec` -> one record at d_out, in index order: blocks of `per` records, then the block sums
+int sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out) {
+    const int per = 64;
+    const int nb = (n_rec + per - 1) / per;
+    if (nb > 1) {
+        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(nb), dim3(320), 0, ctx->stream, d_rec, n_rec, per, d_stage);
+        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, (const double*)d_stage, nb, nb, d_out);
+    } else {
+        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, d_rec, n_rec, n_rec, d_out);
+    }
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
+}  // namespace
+
+int mixed_stats_blocks(const pds_ctx* ctx, int64_t n_work) { return (int)std::max<int64_t>(1, std::min<int64_t>(n_work, (int64_t)ctx->num_cus * 8)); }
+int mixed_profile_blocks(const pds_ctx* ctx, int64_t n_groups) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + 63) / 64, (int64_t)ctx->num_cus * 4));
+}
+
+#define PDS_MX_CASES(M) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15) M(16)
+
+template <typename T>
+int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                       const MixedChunks& ch, const double* d_beta0, double* d_means, unsigned* d_flags, double* d_partials,
+                       double* d_stage, double* d_w) {
+    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "mixed model: up to 16 feature columns");
+    KernelTimer timer(ctx, kKindGroupedMoments);
+    PDS_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(unsigned), ctx->stream));
+    const int nb = mixed_stats_blocks(ctx, n_groups);
+    const int nbc = ch.n_chunks > 0 ? mixed_stats_blocks(ctx, ch.n_chunks) : 0;
+#define PDS_MX_STATS(PV)                                                                                                                   \
+    case PV:                                                                                                                               \
+        hipLaunchKernelGGL((mixed_stats_kernel<T, PV>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, d_off, n_groups, split_rows, d_beta0,  \
+                           d_means, d_flags, d_partials);                                                                                        \
+        if (nbc > 0) {                                                                                                                     \
+            hipLaunchKernelGGL((mixed_chunk_sums_kernel<T, PV>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0, ch.d_chunk_n, \
+                               ch.d_chunk_first, ch.n_chunks, d_beta0, ch.d_sums, ch.d_varies);                                            \
+            hipLaunchKernelGGL((mixed_chunk_means_kernel<T>), dim3((unsigned)ch.n_long), dim3(64), 0, ctx->stream, d_cols, PV, ch.d_long_g, \
+                               ch.d_long_c0, ch.d_long_nc, ch.d_long_first, ch.d_long_n, (const double*)ch.d_sums,                         \
+                               (const unsigned*)ch.d_varies, d_beta0, n_groups, d_means, d_flags);                                         \
+            hipLaunchKernelGGL((mixed_chunk_scatter_kernel<T, PV>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0,            \
+                               ch.d_chunk_n, ch.d_chunk_g, ch.n_chunks, n_groups, d_beta0, (const double*)d_means,                         \
+                               d_partials + (int64_t)nb * kMixedRecStride);                                                                \
+        }                                                                                                                                  \
+        break;
+    switch (n_feat) { PDS_MX_CASES(PDS_MX_STATS) }
+#undef PDS_MX_STATS
+    PDS_HIP_CHECK(hipGetLastError());
+    return sum_records(ctx, d_partials, nb + nbc, d_stage, d_w);
+}
+
+int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const int64_t* d_off, int64_t n_groups, double gamma,
+                         double* d_partials, double* d_stage, double* d_out) {
+    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "mixed model: up to 16 feature columns");
+    KernelTimer timer(ctx, kKindIter);
+    const int nb = mixed_profile_blocks(ctx, n_groups);
+#define PDS_MX_PROFILE(PV)                                                                                                                  \
+    case PV:                                                                                                                                \
+        hipLaunchKernelGGL((mixed_profile_kernel<PV>), dim3(nb), dim3(64), 0, ctx->stream, d_means, d_off, n_groups, gamma, d_partials);   \
+        break;
+    switch (n_feat) { PDS_MX_CASES(PDS_MX_PROFILE) }
+#undef PDS_MX_PROFILE
+    PDS_HIP_CHECK(hipGetLastError());
+    return sum_records(ctx, d_partials, nb, d_stage, d_out);
+}
+
+template int launch_mixed_stats<double>(pds_ctx*, const double* const*, int, const int64_t*, int64_t, int64_t, const MixedChunks&, const double*,
+                                        double*, unsigned*, double*, double*, double*);
+template int launch_mixed_stats<float>(pds_ctx*, const float* const*, int, const int64_t*, int64_t, int64_t, const MixedChunks&, const double*,
+                                       double*, unsigned*, double*, double*, double*);
+
+}  // namespace pds

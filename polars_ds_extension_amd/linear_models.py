@@ -1,6 +1,6 @@
 """
 Model classes over NumPy / torch data -- the mirror of the reference's pyclass route:
-`LR`, `ElasticNet`, `OnlineLR` of /root/reference/python/polars_ds/linear_models.py:134-700, whose `PyLR` /
+`LR`, `ElasticNet`, `OnlineLR` (and `GLM`, `MixedModel`) of /root/reference/python/polars_ds/linear_models.py:134-1121, whose `PyLR` /
 `PyElasticNet` / `PyOnlineLR` (src/pymodels/py_lr.rs:21-224) call the same solvers as the expressions.  Same
 constructor arguments, method names and error behaviour; the fits run on the MI355X through the C ABI
 (`lstsq.py`): the row-major feature matrix is transposed once on the device into the column buffers the kernels
@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib, config, lstsq
 
-__all__ = ["LR", "ElasticNet", "OnlineLR", "GLM"]
+__all__ = ["LR", "ElasticNet", "OnlineLR", "GLM", "MixedModel"]
 
 
 def _is_torch(a) -> bool:
@@ -513,3 +513,148 @@ class GLM:
             e = np.exp(eta)
             return e / (1.0 + e)
         return {0: lambda e: e, 1: np.exp, 3: lambda e: 1.0 / e}[link](eta)
+
+
+class MixedModel:
+    """
+    A random-intercept linear mixed model, fit via restricted maximum likelihood (linear_models.py:956-1121 of the reference;
+    PyMixedModel, src/pymodels/py_mixed.rs; fit_reml, src/linear/mixed/mod.rs):
+
+        y = X @ beta + Z @ u + e,   u ~ N(0, sigma_g^2 I),   e ~ N(0, sigma_e^2 I)
+
+    X is an intercept column plus the given features, Z the indicator matrix of `group`.  Degrees of freedom are assigned by
+    containment: effects constant within every group level (the intercept included) are tested against the group stratum,
+    everything else against the residual stratum.  On the MI355X the frame is streamed a fixed number of times for the group means
+    and the within-group scatter; the REML search then costs a reduction over the groups per evaluation (`lstsq.mixed_reml`).
+    """
+
+    def __init__(self):
+        self.feature_names_in_: List[str] = []
+        self.group_name_in_: str | None = None
+        self._fit: dict | None = None
+
+    def is_fit(self) -> bool:
+        return self._fit is not None
+
+    def _value(self, name):
+        if self._fit is None:
+            raise ValueError("Model is not fit yet.")
+        return self._fit[name]
+
+    @property
+    def coeffs_(self) -> np.ndarray:
+        return np.asarray(self._value("coeffs"))
+
+    @property
+    def std_errors_(self) -> np.ndarray:
+        return np.asarray(self._value("std_errors"))
+
+    @property
+    def dfs_(self) -> np.ndarray:
+        return np.asarray(self._value("dfs"))
+
+    @property
+    def gamma_(self) -> float:
+        """Variance ratio sigma_g^2 / sigma_e^2 at the REML optimum."""
+        return self._value("gamma")
+
+    @property
+    def resid_variance_(self) -> float:
+        """Residual variance sigma_e^2."""
+        return self._value("resid_variance")
+
+    def __repr__(self) -> str:
+        if not self.is_fit():
+            return "MixedModel (not fitted yet)"
+        return (
+            "MixedModel(Random Intercept, REML)\n"
+            f"Group: {self.group_name_in_}\n"
+            f"Variance ratio (group / residual): {self.gamma_:.6g}\n"
+            f"{self._report_text()}"
+        )
+
+    def _report_text(self) -> str:
+        try:
+            return str(self.report())
+        except ImportError:  # (no polars in this environment: the same columns as plain text)
+            rep = self.report_dict()
+            rows = zip(rep["effect"], rep["estimate"], rep["std_err"], rep["df"], rep["t"], rep["p_value"])
+            return "\n".join(["effect estimate std_err df t p_value"] + [f"{n} {e:.6g} {s:.6g} {d:g} {t:.6g} {pv:.6g}" for n, e, s, d, t, pv in rows])
+
+    def fit(self, X, y, group, null_policy: str = "ignore", max_iter: int = 200, tol: float = 1e-10):
+        """
+        X: n x p features (NumPy or a CUDA tensor; the intercept is added), y: n targets, group: n group labels.  An integer group
+        array is the key column as it is (any row order); any other dtype is coded densely on the host first.
+        """
+        self.feature_names_in_, self.group_name_in_ = [], None  # (fit_df sets them after delegating)
+        X = _as_matrix(X)
+        n = int(X.shape[0])
+        y = _target(y, n)
+        if len(group) != n:
+            raise ValueError("X, y, and group must have the same number of rows.")
+        if _is_torch(group):
+            if group.is_floating_point() or group.dtype.is_complex:
+                group = group.cpu().numpy()
+        else:
+            group = np.asarray(group)
+        if not _is_torch(group) and group.dtype.kind not in "iu":
+            group = np.unique(group, return_inverse=True)[1].reshape(-1).astype(np.int64)
+        if null_policy != "ignore" and not _is_torch(X):
+            keep = ~np.isnan(y) if null_policy != "raise" else np.ones(n, dtype=bool)
+            if null_policy == "skip":
+                keep &= ~np.any(np.isnan(X), axis=1)
+            X, y = _handle_nans_in_np(X, y, null_policy)
+            if not keep.all():
+                if _is_torch(group):
+                    import torch
+
+                    group = group[torch.as_tensor(keep, device=group.device)]
+                else:
+                    group = group[keep]
+        fit = lstsq.mixed_reml(*_columns(X), target=y, key=group, max_iter=max_iter, tol=tol)
+        self._fit = fit
+        return self
+
+    def fit_df(self, df, features: List[str], target: str, group: str, null_policy: str = "skip", max_iter: int = 200, tol: float = 1e-10):
+        """Fit on a dataframe: the columns are extracted, the null policy applied (rows whose group is null are dropped) and `fit` called."""
+        import polars as pl
+
+        lf = df.lazy()
+        if null_policy == "skip":
+            lf = lf.drop_nulls(subset=list(features) + [target])
+        elif null_policy not in ("ignore", "raise"):
+            fill = {"zero": 0.0, "one": 1.0}.get(null_policy)
+            if fill is None:
+                fill = float(null_policy)
+                if not np.isfinite(fill):
+                    raise ValueError("When null_policy is a number, it cannot be nan or infinite.")
+            lf = lf.with_columns(pl.col(features).fill_null(fill)).drop_nulls(subset=target)
+        df2 = lf.drop_nulls(subset=[group]).select(*features, target, group).collect()
+        if null_policy == "raise" and any(df2[c].has_nulls() for c in df2.columns):
+            raise ValueError("Nulls found in Dataframe.")
+        X = np.column_stack([df2.get_column(f).to_numpy().astype(np.float64) for f in features])
+        y = df2.get_column(target).to_numpy().astype(np.float64)
+        self.fit(X, y, df2.get_column(group).to_numpy(), null_policy="ignore", max_iter=max_iter, tol=tol)
+        self.feature_names_in_ = list(features)
+        self.group_name_in_ = group
+        return self
+
+    def report_dict(self) -> dict:
+        """One entry per fixed effect (intercept first): estimate, standard error, containment degrees of freedom, t and the two-sided
+        Student t p-value (`pds_student_t_sf`)."""
+        if not self.is_fit():
+            raise ValueError("Model is not fit yet.")
+        lib = _lib.load()
+        t = self.coeffs_ / self.std_errors_
+        names = self.feature_names_in_ if len(self.feature_names_in_) == len(t) - 1 else [f"x{j + 1}" for j in range(len(t) - 1)]
+        p = [min(1.0, 2.0 * float(lib.pds_student_t_sf(abs(float(ti)), float(dfi)))) for ti, dfi in zip(t, self.dfs_)]
+        return {"effect": ["Intercept"] + list(names), "estimate": self.coeffs_, "std_err": self.std_errors_, "df": self.dfs_, "t": t,
+                "p_value": np.asarray(p)}
+
+    def report(self):
+        """`report_dict` as a Polars dataframe."""
+        if not self.is_fit():
+            raise ValueError("Model is not fit yet.")
+        import polars as pl
+
+        return pl.DataFrame(self.report_dict())

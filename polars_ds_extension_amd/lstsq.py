@@ -21,7 +21,7 @@ from . import _lib, config
 
 __all__ = [
     "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
-    "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "logistic_reg",
+    "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "logistic_reg", "mixed_reml", "mixed_reml_profile",
     "recursive_lin_reg", "lin_reg_w_rcond", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
@@ -110,7 +110,7 @@ class Context:
 
     def set_option(self, name: str, value) -> None:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
-        "glm_split_rows"; the
+        "glm_split_rows", "mixed_split_rows"; the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
 
@@ -1461,3 +1461,78 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
         return torch.sigmoid(eta + b[-1] if add_bias else eta)
     eta = np.stack(cols.keep[1:1 + cols.n_feat], axis=1) @ co[:cols.n_feat] + (co[-1] if add_bias else 0.0)
     return 1.0 / (1.0 + np.exp(-eta))
+
+
+# ---------------------------------------------------------------------------------------------
+# random-intercept mixed model (REML)
+# ---------------------------------------------------------------------------------------------
+def _mixed_check(x, target, groups, what):
+    """Lengths of the columns and of the group argument, before a context exists (fit_reml, mod.rs:184-186)."""
+    if len(x) < 1:
+        raise ValueError(f"{what}: need at least one feature column")
+    n = len(target)
+    if any(len(c) != n for c in x) or (groups is not None and len(groups) != n):
+        raise ValueError("X, y, and group must have the same number of rows.")
+
+
+def _f64_out(n):
+    a = np.empty(n, dtype=np.float64)
+    return a, C.c_void_p(a.ctypes.data)
+
+
+def mixed_reml(*x, target, group_offsets=None, key=None, max_iter: int = 200, tol: float = 1e-10, ctx: Context | None = None):
+    """
+    The reference's `MixedModel` fit (fit_reml, src/linear/mixed/mod.rs:173-272): y = X beta + Z u + e with a random intercept per
+    group, the variance ratio gamma = sigma_g^2 / sigma_e^2 found by the reference's golden section over the profiled REML deviance.
+    X = [1 | x...] (the intercept FIRST), 1 .. 16 feature columns.  The groups are given either as `group_offsets` (group g = rows
+    [group_offsets[g], group_offsets[g+1]), contiguous) or as `key`, an integer column in any row order -- exactly one of the two.
+    The frame is streamed a fixed number of times (group means and the within-group scatter, `pds_mixed_reml_*`); every deviance
+    evaluation is then a reduction over the groups.  Inputs: NumPy arrays or CUDA tensors.  Returns a dict of NumPy values:
+    coeffs [p'], std_errors [p'], dfs [p'] (containment), gamma, resid_variance, n_groups (non-empty groups), n_eval (deviance
+    evaluations).
+    """
+    if (group_offsets is None) == (key is None):
+        raise ValueError("mixed_reml: exactly one of `group_offsets` and `key` must be given")
+    if max_iter < 0:
+        raise ValueError("`max_iter` must not be negative.")
+    if not np.isfinite(tol):
+        raise ValueError("`tol` must be finite.")
+    _mixed_check(x, target, key, "mixed_reml")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + 1
+    (co, co_p), (se, se_p), (df, df_p) = _f64_out(pp), _f64_out(pp), _f64_out(pp)
+    gamma, rv, ng, ne = C.c_double(0.0), C.c_double(0.0), C.c_int64(0), C.c_int32(0)
+    tail = (C.c_int(int(max_iter)), C.c_double(float(tol)), co_p, se_p, df_p, C.byref(gamma), C.byref(rv), C.byref(ng), C.byref(ne))
+    if key is not None:
+        k, k_p = _key_arg(cols, key)
+        _lib.check(ctx.fn("pds_mixed_reml_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(cols.n_rows), cols.space, *tail))
+    else:
+        off, off_p = _offsets_arg(cols, group_offsets)
+        _lib.check(ctx.fn("pds_mixed_reml_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p,
+                                                    C.c_int64(int(off.shape[0]) - 1), cols.space, *tail))
+    return {"coeffs": co, "std_errors": se, "dfs": df, "gamma": float(gamma.value), "resid_variance": float(rv.value),
+            "n_groups": int(ng.value), "n_eval": int(ne.value)}
+
+
+def mixed_reml_profile(*x, target, group_offsets, gammas, ctx: Context | None = None):
+    """
+    The profiled REML deviance of `mixed_reml`'s model at given variance ratios, without the search (`pds_mixed_profile_grouped_*`):
+    returns a dict of NumPy values deviance [k], beta [k, p'] (the GLS coefficients at that gamma, intercept first) and
+    resid_variance [k].  For likelihood-ratio plots and for checking the evaluation on its own.
+    """
+    g = np.ascontiguousarray(np.atleast_1d(np.asarray(gammas, dtype=np.float64)))
+    if g.ndim != 1 or not np.all(np.isfinite(g)) or np.any(g < 0.0):
+        raise ValueError("`gammas` must be finite and not negative")
+    _mixed_check(x, target, None, "mixed_reml_profile")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp, k = cols.n_feat + 1, int(g.shape[0])
+    (dev, dev_p), (beta, beta_p), (rv, rv_p) = _f64_out(k), _f64_out(k * pp), _f64_out(k)
+    off, off_p = _offsets_arg(cols, group_offsets)
+    _lib.check(ctx.fn("pds_mixed_profile_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p,
+                                                   C.c_int64(int(off.shape[0]) - 1), cols.space, C.c_void_p(g.ctypes.data), C.c_int(k), dev_p,
+                                                   beta_p, rv_p))
+    return {"deviance": dev, "beta": beta.reshape(k, pp), "resid_variance": rv}
