@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pds_lstsq.h"
@@ -43,6 +44,19 @@ __device__ __forceinline__ gptr<T> as_global(const T* p) {
 }
 #endif
 
+
+// host side: the kernels templated over a width are instantiated for LO .. HI; f(std::integral_constant<int, N>{}) for the N = n
+// among them.  Returns whether there was one (the fallback, if any, is the caller's).
+template <int LO, int HI, typename F>
+inline bool dispatch_width(int n, F&& f) {
+    if constexpr (LO > HI) {
+        return false;
+    } else {
+        if (n != LO) return dispatch_width<LO + 1, HI>(n, f);
+        f(std::integral_constant<int, LO>{});
+        return true;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // error plumbing: thread-local message, like the plugin ABI's `_polars_plugin_get_last_error_message`

@@ -4,9 +4,9 @@
 // The one-model route (capi_models.hpp, glm_irls_impl) pays per iteration a launch of the full-frame Gram pass, a solve and a
 // blocking copy of the coefficients; for a million groups of 100 rows that is millions of launches.  Here ONE wave owns a group
 // from its first row to its last iteration:
-//   * lane = row, 64 rows per step, as in grouped_report_pass_kernel.  A group of up to kGiCap = 128 rows is RESIDENT: its
-//     feature columns and y are written once into a wave-private LDS tile in the transposed layout the matrix cores read
-//     (feature-major, row stride kGiStride), and every iteration reads them from there -- the frame is read from HBM once,
+//   * lane = row, 64 rows per step: the wave-tile idiom of wave_tile_dev.hpp.  A group of up to kGiCap = 128 rows is RESIDENT: its
+//     feature columns and y are written once into the wave-private LDS tile (feature-major, row stride kGiStride), and every
+//     iteration reads them from there -- the frame is read from HBM once,
 //     not once per iteration.  A longer group re-reads its rows from global memory in every iteration (L2 / Infinity Cache
 //     traffic) through the first 64 row slots of the same tile; the arithmetic and its order are the same, so are the results.
 //   * per iteration (moments.hip WM = 3, orc_glm_irls): eta = x . beta (first iteration: eta0 = g(mu0), mu0 = (y + 0.5) / 2 for the
@@ -25,6 +25,7 @@
 // (capi_glm_grouped.hpp).  Per-row means are written at the end of a group's fit from the rows the wave still holds.
 #include "glm_dev.hpp"
 #include "solve_reg_dev.hpp"
+#include "wave_tile_dev.hpp"
 
 #include <algorithm>
 
@@ -32,17 +33,9 @@ namespace pds {
 
 namespace {
 
-typedef double gi_d4 __attribute__((ext_vector_type(4)));
-
-constexpr int kGiCap = 128;              // resident rows of a group (two 64-row steps)
-constexpr int kGiStride = kGiCap + 2;    // doubles per feature row of the tile: = 2 (mod 32), conflict-free operand reads
-constexpr int kGiG = 18;                 // row stride of the staged Gram matrix (17 x 17: 16 features + bias)
-
-__device__ __forceinline__ double gi_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return __shfl(v, 0, 64);  // (lane 0's order for every lane)
-}
+constexpr int kGiCap = 128;                           // resident rows of a group (two 64-row steps)
+constexpr int kGiStride = wave_tile_stride(kGiCap);  // doubles per feature row of the tile
+constexpr int kGiG = 18;                              // row stride of the staged Gram matrix (17 x 17: 16 features + bias)
 
 template <typename T>
 __device__ __forceinline__ bool gi_finite(T v) {
@@ -67,7 +60,6 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
     double* rh = gm + 17 * kGiG;           // X'Wz, rh[16] = sum w z
     const int lane = threadIdx.x;
     const int pp = P + bias;
-    const int f = lane & 15, kq = lane >> 4;
     const double nanv = __builtin_nan("");
     gptr<T> cx[P];
 #pragma unroll
@@ -119,12 +111,12 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
                 xt[P * kGiStride + r] = yv;
             }
         }
-        const double ymean = gi_wave_sum(sy) / (double)n;
+        const double ymean = wave_sum(sy) / (double)n;
         double bcur = 0.0;  // lane j < p': coefficient j (the bias last)
         int it = 0;
         while (it < max_iter) {
             ++it;
-            gi_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
             double sw = 0.0, swz = 0.0;
             for (int64_t base = 0; base < n; base += 64) {
                 const int slot = resident ? (int)base : 0;
@@ -162,37 +154,32 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
                 wt[lane] = w;
                 zt[lane] = wz;
                 PDS_WAVE_LDS_SYNC();
-                const int steps = (int)((std::min<int64_t>(64, n - base) + 3) >> 2);
-                for (int m = 0; m < steps; ++m) {
-                    const int row = 4 * m + kq;
-                    const double xv = f < P ? xt[f * kGiStride + slot + row] : 0.0;
-                    const double wv = wt[row];
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wv * xv, xv, acc, 0, 0, 0);
-                    const double bsel = f == 0 ? zt[row] : (f == 1 ? wv : 0.0);  // B columns: 0 = w z, 1 = w
-                    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, bsel, acc2, 0, 0, 0);
-                }
+                wave_tile_gram<P>(
+                    xt + slot, kGiStride, (int)std::min<int64_t>(64, n - base), lane, [&](int row) { return wt[row]; },
+                    [&](int c, int row, double wv) { return c == 0 ? zt[row] : (c == 1 ? wv : 0.0); },  // B columns: 0 = w z, 1 = w
+                    acc, acc2);
             }
-            sw = gi_wave_sum(sw);
-            swz = gi_wave_sum(swz);
+            sw = wave_sum(sw);
+            swz = wave_sum(swz);
             PDS_WAVE_LDS_SYNC();  // (bs / gm / rh: the previous iteration's reads are done)
-            // D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 reg
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int i = kq + 4 * reg;
-                gm[i * kGiG + f] = acc[reg];
-                if (f == 0) rh[i] = acc2[reg];
-                if (f == 1) {
-                    gm[i * kGiG + 16] = acc2[reg];
-                    gm[16 * kGiG + i] = acc2[reg];
-                }
-            }
+            wave_tile_for_d(
+                lane,
+                [&](int i, int c, double g, double side) {
+                    gm[i * kGiG + c] = g;
+                    if (c == 0) rh[i] = side;
+                    if (c == 1) {
+                        gm[i * kGiG + 16] = side;
+                        gm[16 * kGiG + i] = side;
+                    }
+                },
+                acc, acc2);
             if (lane == 0) {
                 gm[16 * kGiG + 16] = sw;
                 rh[16] = swz;
             }
             PDS_WAVE_LDS_SYNC();
             // ---- the solve: lane j of every 16-lane row = column j
-            const int j = f;
+            const int j = lane & 15;
             const bool centred = pp > 16;  // 16 features + bias: the bias is eliminated, 16 columns remain
             const int ppq = sp.pp;
             const bool colv = j < ppq;
@@ -282,31 +269,11 @@ int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bi
     if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
     KernelTimer timer(ctx, kKindIter);
     const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
-#define PDS_GI_CASE(PV)                                                                                                           \
-    case PV:                                                                                                                      \
-        hipLaunchKernelGGL((grouped_irls_kernel<T, PV>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows, d_off, n_groups, \
-                           link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter, d_null, d_pred, d_row_null, d_perm,      \
-                           d_long_list, d_long_count, long_cap);                                                                  \
-        break;
-    switch (n_feat) {
-        PDS_GI_CASE(1)
-        PDS_GI_CASE(2)
-        PDS_GI_CASE(3)
-        PDS_GI_CASE(4)
-        PDS_GI_CASE(5)
-        PDS_GI_CASE(6)
-        PDS_GI_CASE(7)
-        PDS_GI_CASE(8)
-        PDS_GI_CASE(9)
-        PDS_GI_CASE(10)
-        PDS_GI_CASE(11)
-        PDS_GI_CASE(12)
-        PDS_GI_CASE(13)
-        PDS_GI_CASE(14)
-        PDS_GI_CASE(15)
-        PDS_GI_CASE(16)
-    }
-#undef PDS_GI_CASE
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((grouped_irls_kernel<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows, d_off,
+                           n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter, d_null, d_pred, d_row_null, d_perm,
+                           d_long_list, d_long_count, long_cap);
+    });
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }

@@ -245,33 +245,11 @@ template <typename T, int MODE>
 void launch_pc(int p, dim3 g, hipStream_t st, const T* const* cols, int bias, int64_t n, const int64_t* off, int64_t ng,
                const T* co, const uint8_t* fl, const uint32_t* perm, T* pred, T* resid, uint8_t* rn, const int64_t* keys = nullptr,
                const int64_t* kmin = nullptr) {
-#define PDS_GP_CASE(PCV)                                                                                                         \
-    case PCV:                                                                                                                    \
-        hipLaunchKernelGGL((grouped_pred_kernel<T, PCV, MODE>), g, dim3(kGpThreads), 0, st, cols, p, bias, n, off, ng, co, fl, perm, \
-                           pred, resid, rn, keys, kmin);                                                                         \
-        break;
-    switch (p) {
-        PDS_GP_CASE(1)
-        PDS_GP_CASE(2)
-        PDS_GP_CASE(3)
-        PDS_GP_CASE(4)
-        PDS_GP_CASE(5)
-        PDS_GP_CASE(6)
-        PDS_GP_CASE(7)
-        PDS_GP_CASE(8)
-        PDS_GP_CASE(9)
-        PDS_GP_CASE(10)
-        PDS_GP_CASE(11)
-        PDS_GP_CASE(12)
-        PDS_GP_CASE(13)
-        PDS_GP_CASE(14)
-        PDS_GP_CASE(15)
-        PDS_GP_CASE(16)
-        default:
-            hipLaunchKernelGGL((grouped_pred_kernel<T, 0, MODE>), g, dim3(kGpThreads), 0, st, cols, p, bias, n, off, ng, co, fl, perm,
-                               pred, resid, rn, keys, kmin);
-    }
-#undef PDS_GP_CASE
+    auto launch = [&](auto pc) {
+        hipLaunchKernelGGL((grouped_pred_kernel<T, decltype(pc)::value, MODE>), g, dim3(kGpThreads), 0, st, cols, p, bias, n, off, ng, co,
+                           fl, perm, pred, resid, rn, keys, kmin);
+    };
+    if (!dispatch_width<1, 16>(p, launch)) launch(std::integral_constant<int, 0>{});  // (wider: the run-time-width kernel)
 }
 
 }  // namespace

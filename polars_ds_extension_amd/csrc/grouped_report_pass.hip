@@ -11,15 +11,16 @@
 // report_item and grouped_report_finish_kernel), 64 rows per step, lane = row.  A lane loads its row (column-major frame:
 // 512 contiguous bytes per column and wave), forms e = y - x.beta_g (beta_g staged in wave-private LDS), the leverage
 // h = z' inv_g z for HC2 / HC3 (inv_g in LDS, broadcast reads) and the row weight s.  The meat's 16 x 16 feature block goes to the
-// matrix cores: the wave writes its 64 rows transposed into LDS and feeds them to v_mfma_f64_16x16x4 (A = s x, B = x, 4 rows per
-// step), as the Gram kernels of moments.hip do; the bias row of the meat (sum s x, sum s) stays in per-lane registers.  Every sum
-// is a per-lane register folded by a fixed butterfly at the end of the group: no atomics, repeated calls are bit-identical.
+// matrix cores by the wave-tile idiom of wave_tile_dev.hpp (A = s x, B = x, no side columns); the bias row of the meat (sum s x,
+// sum s) stays in per-lane registers.  Every sum is a per-lane register folded by a fixed butterfly at the end of the group: no
+// atomics, repeated calls are bit-identical.
 //
 // WEIGHTED (the grouped wls_report, plain standard error only -- pl_wls_report knows no HC estimator, linear_regression.rs:982-1117):
 // cols[p + 1] is the weight column, loaded like one more column of the frame, and the fourth value of an item's sums slot carries
 // sum w e^2 (the mse's numerator); sum e^2 and the y sums stay unweighted, as the reference's r2 has them.
 #include "grouped_report.hpp"
 #include "stats_dev.hpp"
+#include "wave_tile_dev.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -28,17 +29,9 @@ namespace pds {
 
 namespace {
 
-typedef double rp_d4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRpThreads = 256;
 constexpr int kRpStride = 65;  // doubles per feature row of the transposed tile (64 rows + 1: conflict-free column writes)
 constexpr int kRpWaveDoubles = 16 * kRpStride + 64 + 17 + 17 * 17;  // tile, row weights, beta_g, inv_g
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return __shfl(v, 0, 64);  // (lane 0's order for every lane)
-}
 
 // Work item `it` of the pass: items 0 .. n_groups - 1 are the groups themselves (at most `piece_rows` of their rows -- a group's
 // first piece), items n_groups + k the k-th extra piece of a larger group (pieces[3 k ..]: group, first row, end row).  Every item
@@ -81,7 +74,6 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
     const gptr<T> cw = as_global(cols[WEIGHTED ? P + 1 : P]);
-    const int f = lane & 15, kq = lane >> 4;
     const int64_t nwaves = (int64_t)gridDim.x * (kRpThreads / 64);
     for (int64_t it = (int64_t)blockIdx.x * (kRpThreads / 64) + wv; it < n_items; it += nwaves) {
         int64_t g, r0, r1;
@@ -96,7 +88,7 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
         double sb[P];
 #pragma unroll
         for (int c = 0; c < P; ++c) sb[c] = 0.0;
-        rp_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        d4 acc = {0.0, 0.0, 0.0, 0.0};
         for (int64_t base = r0; base < r1; base += 64) {
             const int64_t r = base + lane;
             const bool live = r < r1;
@@ -140,12 +132,8 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
                 for (int c = 0; c < P; ++c) xt[c * kRpStride + lane] = x[c];
                 st[lane] = s;
                 PDS_WAVE_LDS_SYNC();
-                const int steps = (int)((std::min<int64_t>(64, r1 - base) + 3) >> 2);
-                for (int m = 0; m < steps; ++m) {
-                    const int row = 4 * m + kq;
-                    const double xv = xt[f * kRpStride + row];
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(st[row] * xv, xv, acc, 0, 0, 0);
-                }
+                // (all 16 feature rows are read: rows P .. 15 are zero)
+                wave_tile_gram<16>(xt, kRpStride, (int)std::min<int64_t>(64, r1 - base), lane, [&](int row) { return st[row]; }, acc);
             }
         }
         sse = wave_sum(sse);
@@ -160,12 +148,12 @@ __global__ __launch_bounds__(kRpThreads) void grouped_report_pass_kernel(const T
         }
         if (hc) {
             double* mo = meat + it * pp * pp;
-            // D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 reg
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int i = kq + 4 * reg;
-                if (i < P && f < P) mo[i + f * pp] = acc[reg];
-            }
+            wave_tile_for_d(
+                lane,
+                [&](int i, int c, double v) {
+                    if (i < P && c < P) mo[i + c * pp] = v;
+                },
+                acc);
             ss = wave_sum(ss);
 #pragma unroll
             for (int c = 0; c < P; ++c) {
@@ -444,32 +432,11 @@ int launch_grouped_report_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat,
             return;
         }
         const int nb = (int)std::min<int64_t>((n_items + 3) / 4, (int64_t)ctx->num_cus * 8);
-#define PDS_RP_CASE(PV)                                                                                                            \
-    case PV:                                                                                                                       \
-        hipLaunchKernelGGL((grouped_report_pass_kernel<T, PV, W>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,  \
-                           n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);                            \
-        break;
-        switch (n_feat) {
-            PDS_RP_CASE(1)
-            PDS_RP_CASE(2)
-            PDS_RP_CASE(3)
-            PDS_RP_CASE(4)
-            PDS_RP_CASE(5)
-            PDS_RP_CASE(6)
-            PDS_RP_CASE(7)
-            PDS_RP_CASE(8)
-            PDS_RP_CASE(9)
-            PDS_RP_CASE(10)
-            PDS_RP_CASE(11)
-            PDS_RP_CASE(12)
-            PDS_RP_CASE(13)
-            PDS_RP_CASE(14)
-            PDS_RP_CASE(15)
-            default:
-                hipLaunchKernelGGL((grouped_report_pass_kernel<T, 16, W>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols, bias, d_off,
-                                   n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);
-        }
-#undef PDS_RP_CASE
+        auto pass = [&](auto pc) {
+            hipLaunchKernelGGL((grouped_report_pass_kernel<T, decltype(pc)::value, W>), dim3(nb), dim3(kRpThreads), 0, ctx->stream, d_cols,
+                               bias, d_off, n_groups, d_beta, d_inv, hc, d_sums, d_meat, d_pieces, n_items, piece_rows);
+        };
+        if (!dispatch_width<1, 15>(n_feat, pass)) pass(std::integral_constant<int, 16>{});
     };
     if (weighted) launch(std::true_type{});
     else launch(std::false_type{});

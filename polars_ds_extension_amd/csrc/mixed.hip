@@ -7,7 +7,7 @@
 // and never formed).  Every term is positive semi-definite: nothing cancels, whatever the size of the group means.
 //
 //   * mixed_stats_kernel: ONE wave walks groups (grid stride).  A group of up to kMxCap = 128 rows is loaded once into a
-//     wave-private LDS tile (feature-major, row stride kMxStride = 2 mod 32, the layout of grouped_irls.hip), summed and centred
+//     wave-private LDS tile (feature-major, row stride kMxStride: the wave-tile idiom of wave_tile_dev.hpp), summed and centred
 //     there; a longer group reads its rows twice (sums, then centred products through the first 64 row slots of the tile).  The
 //     16 x 16 feature block of W comes from one v_mfma_f64_16x16x4 accumulator with operands (x - m, x - m), W_xy from a second
 //     matrix instruction with B = [y - m_y | 0 ..], W_yy from a per-lane register folded by a fixed butterfly.  The wave keeps its
@@ -27,7 +27,7 @@
 //     y - [1, x] . beta0, formed per row in registers.  The host runs the passes twice (capi_mixed.hpp): on y itself, then on the
 //     residual of a first GLS solution, so that r' H^-1 r comes out of sums of its own size instead of a difference of large ones.
 // Arithmetic is f64 for f64 and f32 frames alike (an f32 frame is converted on load).
-#include "common.hpp"
+#include "wave_tile_dev.hpp"
 
 #include <algorithm>
 
@@ -35,17 +35,9 @@ namespace pds {
 
 namespace {
 
-typedef double mx_d4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMxCap = 128;            // resident rows of a group (two 64-row steps)
-constexpr int kMxStride = kMxCap + 2;  // doubles per feature row of the tile: = 2 (mod 32), conflict-free operand reads
-constexpr int kMxPStride = 64 + 2;     // the profile kernel's tile: 64 groups per step
-
-__device__ __forceinline__ double mx_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return __shfl(v, 0, 64);  // (lane 0's order for every lane)
-}
+constexpr int kMxCap = 128;                           // resident rows of a group (two 64-row steps)
+constexpr int kMxStride = wave_tile_stride(kMxCap);  // doubles per feature row of the tile
+constexpr int kMxPStride = wave_tile_stride(64);     // the profile kernel's tile: 64 groups per step
 
 // the target of a row: y, or y - [1, x] . beta0 (b0: intercept first; x: the row's features)
 template <int P>
@@ -65,12 +57,19 @@ __device__ __forceinline__ bool mx_load_beta0(const double* __restrict__ beta0, 
     return beta0 != nullptr;
 }
 
+// the centred rows of a step (features, then y - m_y at feature row P) -> W block and W_xy
+template <int P>
+__device__ __forceinline__ void mx_centred_gram(const double* xt, int rows, int lane, d4& acc, d4& acc2) {
+    wave_tile_gram<P>(
+        xt, kMxStride, rows, lane, TileNoScale{}, [&](int c, int row) { return c == 0 ? xt[P * kMxStride + row] : 0.0; },  // B column 0 = y - m_y
+        acc, acc2);
+}
+
 // centred products of the rows [r0, r0 + n) with the means `mean` (features, then y), 64 rows per step through the first 64 row
 // slots of the tile
 template <typename T, int P>
 __device__ __forceinline__ void mx_stream_centred(const gptr<T>* cx, gptr<T> cy, int64_t r0, int64_t n, const double* mean, const double* b0,
-                                                  bool has_b0, double* xt, int lane, mx_d4& acc, mx_d4& acc2, double& yy) {
-    const int f = lane & 15, kq = lane >> 4;
+                                                  bool has_b0, double* xt, int lane, d4& acc, d4& acc2, double& yy) {
     for (int64_t base = 0; base < n; base += 64) {
         const int64_t r = base + lane;
         const bool live = r < n;
@@ -85,27 +84,19 @@ __device__ __forceinline__ void mx_stream_centred(const gptr<T>* cx, gptr<T> cy,
         xt[P * kMxStride + lane] = yc;
         yy = fma(yc, yc, yy);
         PDS_WAVE_LDS_SYNC();
-        const int steps = (int)((std::min<int64_t>(64, n - base) + 3) >> 2);
-        for (int m = 0; m < steps; ++m) {
-            const int row = 4 * m + kq;
-            const double xv = f < P ? xt[f * kMxStride + row] : 0.0;
-            const double yv = xt[P * kMxStride + row];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, xv, acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, f == 0 ? yv : 0.0, acc2, 0, 0, 0);  // B column 0 = y - m_y
-        }
+        mx_centred_gram<P>(xt, (int)std::min<int64_t>(64, n - base), lane, acc, acc2);
     }
 }
 
-// D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 reg
-__device__ __forceinline__ void mx_write_record(double* rec, int lane, const mx_d4& acc, const mx_d4& acc2, double yy) {
-    const int f = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-        const int i = kq + 4 * reg;
-        rec[kMixedRecW + i * 16 + f] = acc[reg];
-        if (f == 0) rec[kMixedRecXY + i] = acc2[reg];
-    }
-    yy = mx_wave_sum(yy);
+// entry (i, c) of the 16 x 16 block and of the side block -> a record (a scatter partial or a profile record)
+__device__ __forceinline__ void mx_put_w_xy(double* rec, int i, int c, double w, double side) {
+    rec[kMixedRecW + i * 16 + c] = w;
+    if (c == 0) rec[kMixedRecXY + i] = side;
+}
+
+__device__ __forceinline__ void mx_write_record(double* rec, int lane, const d4& acc, const d4& acc2, double yy) {
+    wave_tile_for_d(lane, [&](int i, int c, double w, double side) { mx_put_w_xy(rec, i, c, w, side); }, acc, acc2);
+    yy = wave_sum(yy);
     if (lane == 0) rec[kMixedRecYY] = yy;
     // the slots only the profile records use: the record sum reads all of them
     if (lane < 16) rec[kMixedRecCM + lane] = 0.0;
@@ -118,14 +109,13 @@ __global__ __launch_bounds__(64) void mixed_stats_kernel(const T* const* __restr
                                                          unsigned* __restrict__ flags, double* __restrict__ partials) {
     __shared__ double xt[(P + 1) * kMxStride];  // features 0 .. P - 1, then y: [c * kMxStride + row]
     const int lane = threadIdx.x;
-    const int f = lane & 15, kq = lane >> 4;
     double b0[P + 1];
     const bool has_b0 = mx_load_beta0<P>(beta0, b0);
     gptr<T> cx[P];
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
     double yy = 0.0;
     unsigned vary_all = 0;
     for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
@@ -159,7 +149,7 @@ __global__ __launch_bounds__(64) void mixed_stats_kernel(const T* const* __restr
         }
 #pragma unroll
         for (int c = 0; c <= P; ++c) {
-            const double sum = mx_wave_sum(s[c]);
+            const double sum = wave_sum(s[c]);
             mean[c] = ((vary >> c) & 1u) ? sum / (double)n : first[c];
             if (lane == c) means[(int64_t)c * n_groups + g] = mean[c];
         }
@@ -175,14 +165,7 @@ __global__ __launch_bounds__(64) void mixed_stats_kernel(const T* const* __restr
                 yy = fma(yc, yc, yy);
             }
             PDS_WAVE_LDS_SYNC();
-            const int steps = (int)((n + 3) >> 2);  // (rows n .. 4 steps - 1 hold zeros)
-            for (int m = 0; m < steps; ++m) {
-                const int row = 4 * m + kq;
-                const double xv = f < P ? xt[f * kMxStride + row] : 0.0;
-                const double yv = xt[P * kMxStride + row];
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, xv, acc, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, f == 0 ? yv : 0.0, acc2, 0, 0, 0);
-            }
+            mx_centred_gram<P>(xt, (int)n, lane, acc, acc2);  // (the rows n .. up to the next multiple of 4 hold zeros)
         } else {
             mx_stream_centred<T, P>(cx, cy, r0, n, mean, b0, has_b0, xt, lane, acc, acc2, yy);
         }
@@ -229,7 +212,7 @@ __global__ __launch_bounds__(64) void mixed_chunk_sums_kernel(const T* const* __
         }
 #pragma unroll
         for (int c = 0; c <= P; ++c) {
-            const double sum = mx_wave_sum(s[c]);
+            const double sum = wave_sum(s[c]);
             if (lane == c) sums[k * (P + 1) + c] = sum;
         }
         if (lane == 0) varies[k] = vary;
@@ -279,7 +262,7 @@ __global__ __launch_bounds__(64) void mixed_chunk_scatter_kernel(const T* const*
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
     double yy = 0.0;
     for (int64_t k = blockIdx.x; k < n_chunks; k += gridDim.x) {
         const int64_t g = chunk_g[k];
@@ -307,8 +290,7 @@ __global__ __launch_bounds__(64) void mixed_profile_kernel(const double* __restr
     __shared__ double mt[(P + 1) * kMxPStride + 64];
     double* ct = mt + (P + 1) * kMxPStride;  // c_g of the step's groups
     const int lane = threadIdx.x;
-    const int f = lane & 15, kq = lane >> 4;
-    mx_d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
     double sc = 0.0, scy = 0.0, scyy = 0.0, sld = 0.0;
     const int64_t n_tiles = (n_groups + 63) / 64;
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
@@ -317,7 +299,6 @@ __global__ __launch_bounds__(64) void mixed_profile_kernel(const double* __restr
         const bool live = ng > 0;  // (an empty group contributes nothing)
         const double nd = (double)ng;
         const double cg = live ? nd / (1.0 + gamma * nd) : 0.0;
-        if (live) sld += log(1.0 + gamma * nd);
         PDS_WAVE_LDS_SYNC();  // (the previous step's operand reads are done)
         double my = 0.0;
 #pragma unroll
@@ -331,28 +312,24 @@ __global__ __launch_bounds__(64) void mixed_profile_kernel(const double* __restr
         scy = fma(cg, my, scy);
         scyy = fma(cg * my, my, scyy);
         PDS_WAVE_LDS_SYNC();
-        const int steps = (int)((std::min<int64_t>(64, n_groups - t * 64) + 3) >> 2);
-        for (int m = 0; m < steps; ++m) {
-            const int row = 4 * m + kq;
-            const double xv = f < P ? mt[f * kMxPStride + row] : 0.0;
-            const double cv = ct[row];
-            const double bsel = f == 0 ? cv * mt[P * kMxPStride + row] : (f == 1 ? cv : 0.0);  // B columns: 0 = c m_y, 1 = c
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(cv * xv, xv, acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, bsel, acc2, 0, 0, 0);
-        }
+        wave_tile_gram<P>(
+            mt, kMxPStride, (int)std::min<int64_t>(64, n_groups - t * 64), lane, [&](int row) { return ct[row]; },
+            [&](int c, int row, double cv) { return c == 0 ? cv * mt[P * kMxPStride + row] : (c == 1 ? cv : 0.0); },  // B columns: 0 = c m_y, 1 = c
+            acc, acc2);
+        if (live) sld += log(1.0 + gamma * nd);  // (behind the matrix loop: in front of it the compiler keeps an accumulator in 8 more VGPRs)
     }
     double* rec = partials + (int64_t)blockIdx.x * kMixedRecStride;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-        const int i = kq + 4 * reg;
-        rec[kMixedRecW + i * 16 + f] = acc[reg];
-        if (f == 0) rec[kMixedRecXY + i] = acc2[reg];
-        if (f == 1) rec[kMixedRecCM + i] = acc2[reg];
-    }
-    sc = mx_wave_sum(sc);
-    scy = mx_wave_sum(scy);
-    scyy = mx_wave_sum(scyy);
-    sld = mx_wave_sum(sld);
+    wave_tile_for_d(
+        lane,
+        [&](int i, int c, double w, double side) {
+            mx_put_w_xy(rec, i, c, w, side);
+            if (c == 1) rec[kMixedRecCM + i] = side;
+        },
+        acc, acc2);
+    sc = wave_sum(sc);
+    scy = wave_sum(scy);
+    scyy = wave_sum(scyy);
+    sld = wave_sum(sld);
     if (lane == 0) {
         rec[kMixedRecYY] = scyy;
         rec[kMixedRecC] = sc;
@@ -383,8 +360,6 @@ int mixed_profile_blocks(const pds_ctx* ctx, int64_t n_groups) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + 63) / 64, (int64_t)ctx->num_cus * 4));
 }
 
-#define PDS_MX_CASES(M) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15) M(16)
-
 template <typename T>
 int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
                        const MixedChunks& ch, const double* d_beta0, double* d_means, unsigned* d_flags, double* d_partials,
@@ -394,23 +369,21 @@ int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const i
     PDS_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(unsigned), ctx->stream));
     const int nb = mixed_stats_blocks(ctx, n_groups);
     const int nbc = ch.n_chunks > 0 ? mixed_stats_blocks(ctx, ch.n_chunks) : 0;
-#define PDS_MX_STATS(PV)                                                                                                                   \
-    case PV:                                                                                                                               \
-        hipLaunchKernelGGL((mixed_stats_kernel<T, PV>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, d_off, n_groups, split_rows, d_beta0,  \
-                           d_means, d_flags, d_partials);                                                                                        \
-        if (nbc > 0) {                                                                                                                     \
-            hipLaunchKernelGGL((mixed_chunk_sums_kernel<T, PV>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0, ch.d_chunk_n, \
-                               ch.d_chunk_first, ch.n_chunks, d_beta0, ch.d_sums, ch.d_varies);                                            \
-            hipLaunchKernelGGL((mixed_chunk_means_kernel<T>), dim3((unsigned)ch.n_long), dim3(64), 0, ctx->stream, d_cols, PV, ch.d_long_g, \
-                               ch.d_long_c0, ch.d_long_nc, ch.d_long_first, ch.d_long_n, (const double*)ch.d_sums,                         \
-                               (const unsigned*)ch.d_varies, d_beta0, n_groups, d_means, d_flags);                                         \
-            hipLaunchKernelGGL((mixed_chunk_scatter_kernel<T, PV>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0,            \
-                               ch.d_chunk_n, ch.d_chunk_g, ch.n_chunks, n_groups, d_beta0, (const double*)d_means,                         \
-                               d_partials + (int64_t)nb * kMixedRecStride);                                                                \
-        }                                                                                                                                  \
-        break;
-    switch (n_feat) { PDS_MX_CASES(PDS_MX_STATS) }
-#undef PDS_MX_STATS
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        constexpr int P = decltype(pc)::value;
+        hipLaunchKernelGGL((mixed_stats_kernel<T, P>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, d_off, n_groups, split_rows, d_beta0,
+                           d_means, d_flags, d_partials);
+        if (nbc > 0) {
+            hipLaunchKernelGGL((mixed_chunk_sums_kernel<T, P>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0, ch.d_chunk_n,
+                               ch.d_chunk_first, ch.n_chunks, d_beta0, ch.d_sums, ch.d_varies);
+            hipLaunchKernelGGL((mixed_chunk_means_kernel<T>), dim3((unsigned)ch.n_long), dim3(64), 0, ctx->stream, d_cols, P, ch.d_long_g,
+                               ch.d_long_c0, ch.d_long_nc, ch.d_long_first, ch.d_long_n, (const double*)ch.d_sums,
+                               (const unsigned*)ch.d_varies, d_beta0, n_groups, d_means, d_flags);
+            hipLaunchKernelGGL((mixed_chunk_scatter_kernel<T, P>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0, ch.d_chunk_n,
+                               ch.d_chunk_g, ch.n_chunks, n_groups, d_beta0, (const double*)d_means,
+                               d_partials + (int64_t)nb * kMixedRecStride);
+        }
+    });
     PDS_HIP_CHECK(hipGetLastError());
     return sum_records(ctx, d_partials, nb + nbc, d_stage, d_w);
 }
@@ -420,12 +393,10 @@ int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const 
     if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "mixed model: up to 16 feature columns");
     KernelTimer timer(ctx, kKindIter);
     const int nb = mixed_profile_blocks(ctx, n_groups);
-#define PDS_MX_PROFILE(PV)                                                                                                                  \
-    case PV:                                                                                                                                \
-        hipLaunchKernelGGL((mixed_profile_kernel<PV>), dim3(nb), dim3(64), 0, ctx->stream, d_means, d_off, n_groups, gamma, d_partials);   \
-        break;
-    switch (n_feat) { PDS_MX_CASES(PDS_MX_PROFILE) }
-#undef PDS_MX_PROFILE
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((mixed_profile_kernel<decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_means, d_off, n_groups, gamma,
+                           d_partials);
+    });
     PDS_HIP_CHECK(hipGetLastError());
     return sum_records(ctx, d_partials, nb, d_stage, d_out);
 }

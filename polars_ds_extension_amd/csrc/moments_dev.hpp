@@ -1,11 +1,10 @@
 // moments_dev.hpp -- device-side building blocks of the Gram build, shared by moments.hip (single system,
 // grouped) and grouped_fused.hip (Gram + solve in one kernel).  See moments.hip for the design notes.
 #pragma once
-#include "common.hpp"
+#include "wave_tile_dev.hpp"  // d4
 
 namespace pds {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
