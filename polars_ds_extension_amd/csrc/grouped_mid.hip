@@ -1,38 +1,17 @@
-// grouped_mid.hip -- grouped regressions with 17 .. 64 f64 features (17 .. 32 also f32) as ONE stream over the frame: the (p+2)^2 moment
-// records of contiguous groups (33 .. 64 features, and the fallback), or -- 17 .. 32 features -- no records at all: a streaming and a
-// solving wave per SIMD, the finished group crossing an LDS slot.  The half-tile layout is moments_mid.hip's
-// (moments_mid_dev.hpp).
+// grouped_mid.hip -- grouped regressions with 17 .. 64 f64 features (17 .. 32 also f32) as ONE stream over the frame
+// (grouped_mid_stream_kernel).  Three forms of the one kernel exist, and the host code below launches nothing else:
+//   record stream  (33 .. 64 f64 features; 17 .. 32 as the fallback of the fused fit): one wave per SIMD writes the (p+2)^2 moment record of
+//                  every group; the record pipeline solves them
+//   paired direct  (17 .. 32 f64 features, 17 .. 30 f32): no records -- a streaming and a solving wave per SIMD, the streaming wave loads
+//                  the frame straight into the matrix instructions' operand registers, a finished group crosses a ring of LDS slots
+//   paired LDS     (31 / 32 f32 features): the same pair of waves with the frame staged in LDS tile images and one slot
+// The half-tile layout of the LDS forms is moments_mid.hip's (moments_mid_dev.hpp).  How the kernel got here, and the forms measured and
+// dropped on the way, is DESIGN_HISTORY.md's subject.
 #include "common.hpp"
 #include "moments_dev.hpp"
 #include "moments_mid_dev.hpp"
 #include "solve_wave_dev.hpp"
 #include "solve_row16_dev.hpp"
-
-#ifndef PDS_MID_DIRECT
-#define PDS_MID_DIRECT 1
-#endif
-// the direct form's loads: two consecutive instructions read the two halves of the same sixteen 128-byte lines -- as non-temporal loads
-// (-DPDS_MID_DIRECT_NT) the second one misses again: 30 features 6.4 -> 7.5 ms (profiles/r06_grouped_mid_direct.txt)
-// (A/B: 1 = the lane terms of the slot / record addresses pass through an empty asm in every direct kernel, not only where registers are short)
-#ifndef PDS_MID_LAUNDER_ALL
-#define PDS_MID_LAUNDER_ALL 0
-#endif
-// the record stream of 33 .. 64 features in the direct form (0: the LDS form of rounds 3 - 5)
-#ifndef PDS_MID_DIRECT_RECORDS
-#define PDS_MID_DIRECT_RECORDS 1
-#endif
-#ifndef PDS_MID_DIRECT_OCTET
-#define PDS_MID_DIRECT_OCTET 1
-#endif
-// a group that crosses a wave boundary is finished by the wave it starts in (0: summed by both waves into a side record, rounds 4 / 5)
-#ifndef PDS_MID_OWNER
-#define PDS_MID_OWNER 1
-#endif
-#ifdef PDS_MID_DIRECT_NT
-#define PDS_MID_DIRECT_LOAD(q) __builtin_nontemporal_load(q)
-#else
-#define PDS_MID_DIRECT_LOAD(q) (*(q))
-#endif
 
 namespace pds {
 
@@ -49,20 +28,18 @@ __device__ unsigned long long g_mid_phase[16];
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Grouped form: the (p+2)^2 moment records of CONTIGUOUS GROUPS (group g = rows [off[g], off[g+1])) from ONE stream over the frame --
-// `group_by(key).agg(pds.lin_reg(...))` with 17 .. 64 f64 features.  The one-wave-per-group kernel of moments.hip loads 32 rows at a
-// time with 8-byte loads and nothing in flight behind them (1.2 - 2.5 TB/s); here the rows are read exactly as above (waves own
-// contiguous, half-tile aligned row ranges; 1 KiB asynchronous loads into wave-private LDS images) and the accumulators are CUT at
-// group boundaries: a half-tile is walked as segments [lo, hi) of one group each, the first and last 4-row step of a segment with the
-// rows outside it zeroed in the operands, and a finished group's tiles go straight from the accumulator registers into its record.
-// Groups that lie inside one wave's rows are written with plain stores; a group cut by a wave boundary (two per wave, or a giant group
-// over many waves) is added to the zero-initialised record with atomics.
-// SPPC > 0 (NBLK = 2, up to 32 features, round 4): NO RECORDS -- a finished group is solved in the wave that streamed it.  Its
-// accumulator tiles go through a 4 KB LDS scratch (16 columns per trip) into one of four pending systems -- one per 16-lane DPP row,
-// lane t = columns t and 16 + t, centred -- and four pending systems are factored side by side (solve_row16_dev.hpp: L D L' with the
-// pivot-ratio gate) and their coefficients written; only what cannot be answered in place leaves as a record: a group cut by a wave
-// boundary (atomics into the side table's slot of the wave it starts in: at most one per wave) and a system next to the gate
-// (appended to the marked list for the pivoted QR; its record is rebuilt from its rows).  The per-group dispatch
+// `group_by(key).agg(pds.lin_reg(...))` with 17 .. 64 features: the moments of CONTIGUOUS GROUPS (group g = rows [off[g], off[g+1])) from
+// ONE stream over the frame.  Waves own contiguous, half-tile aligned row ranges and the accumulators are CUT at group boundaries: a
+// half-tile is walked as segments [lo, hi) of one group each, the rows outside a segment zeroed in the operands of its first and last
+// step.  A group belongs to the wave in whose rows it STARTS; that wave follows it beyond the end of its own range (see `own_limit`), so
+// every group but a giant one is summed by one wave, in one order, and written once.
+// SPPC = 0, the record stream: a finished group's tiles go from the accumulator registers into its (p+2)^2 record with plain stores; a
+// group longer than `own_limit` is added by every wave that meets it to its record, zeroed beforehand (mid_zero_records_kernel).
+// SPPC > 0, the paired forms (NBLK = 2, up to SPPC features): NO RECORDS.  The finished group crosses an LDS slot to the solving wave of
+// the pair, which keeps four pending systems -- one per 16-lane DPP row, lane t = columns t and 16 + t -- centres and factors them side
+// by side (solve_row16_dev.hpp: L D L' with the pivot-ratio gate) and writes coefficients and flags.  Only what cannot be answered in
+// place leaves as a record: a giant group (atomics into the side table's slot of the wave it starts in: at most one per wave) and a
+// system next to the gate (appended to the marked list for the pivoted QR; its record is rebuilt from its rows).  The per-group dispatch
 // of pl_lr under group_by (linear_regression.rs:447-497) at 17 .. 32 features then moves input + coefficients only, as at <= 16.
 template <typename T>
 struct MidSolveArgsT {
@@ -77,7 +54,7 @@ struct MidSolveArgsT {
     unsigned mark_cap = 0;
 };
 using MidSolveArgs = MidSolveArgsT<double>;
-constexpr int kMidSolveScratch = 5120;  // bytes behind the tile images (4 x 40 KB per CU): 24 columns x 26 doubles in one trip, or 16 x 34 per trip
+constexpr int kMidSolveScratch = 5120;  // bytes behind the tile images (4 x 40 KB per CU): the paired LDS form's one slot (MidPacked<32>: 4 760)
 // v summed lane-wise over the four 16-lane rows of the wave (every lane gets its column's total): v_permlane16_swap / v_permlane32_swap
 // of gfx950 -- with both operands the same value the swap leaves [r0 r0 r2 r2] and [r1 r1 r3 r3] (rows), then the two halves -- four
 // vector moves per stage instead of two trips through the LDS crossbar (__shfl_xor)
@@ -124,27 +101,27 @@ __device__ const float g_mid_direct_const_f32[256] = {PDS_R8(1.0f), PDS_R8(1.0f)
                                                       PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f), PDS_R8(1.0f)};
 #undef PDS_R8
 
-// PAIRED (with SPPC): a workgroup is FOUR PAIRS of waves -- waves 0 .. 3 stream (loads, matrix steps, group walk: what a wave of the
-// unpaired form does up to the finished group), waves 4 .. 7 are their solvers: a finished group's moments cross the pair's LDS scratch
-// (a sequence-numbered slot: full / taken / done words behind it, polled with s_sleep -- no workgroup barrier after the first), the
-// solver wave keeps the four pending systems, factors them and writes coefficients, flags and marks.  Waves w and w + 4 of a workgroup
-// share a SIMD (tools/wave_placement.hip), so every SIMD runs one streaming and one solving wave: the hand-over and the solves of one
-// overlap the load waits and matrix instructions of the other (they ran one after the other in a single wave: 2.5 of 7.65 ms).
-// YC (PAIRED, up to 30 features): the ones and the target are columns p and p + 1 of the second operand block -- the column sums, X'y, the
-// row count and sum y come out of the matrix instructions that run anyway (no side sums per step, no cross-row reductions per group),
-// and the accumulator blocks ARE the record [X 1 y]' [X 1 y].
+// The template parameters, and the three forms they spell (the static_asserts below admit exactly the instantiations that are launched):
+// PAIRED (with SPPC > 0): a workgroup is FOUR PAIRS of waves -- waves 0 .. 3 stream (loads, matrix steps, group walk), waves 4 .. 7 are
+// their solvers: a finished group's moments cross the pair's LDS (sequence-numbered slots: published / taken / done words behind them,
+// polled with s_sleep -- no workgroup barrier after the first), the solver wave keeps the four pending systems, factors them and writes
+// coefficients, flags and marks.  Waves w and w + 4 of a workgroup share a SIMD (tools/wave_placement.hip), so every SIMD runs one
+// streaming and one solving wave: the hand-over and the solves of one overlap the load waits and matrix instructions of the other.
+// DIRECT: NO tile images.  The streaming wave loads the half-tile straight into the matrix instructions' operand layout -- lane
+// (feature = lane % 16, slot = lane / 16) reads 16 bytes = rows 8 k + 2 slot, + 1 of its own column for block k of eight rows: sixteen
+// columns x 64 contiguous bytes per 1 KiB load instruction, the order of the rows inside a block does not matter to a sum over rows --
+// into one of two register sets (the half-tile being walked, the next one in flight); a 4-row step multiplies rows {8 k + 2 slot + j}.
+// Without DIRECT the half-tile arrives by 1 KiB asynchronous loads in wave-private LDS images and every step reads its operands there.
+// YC (paired direct, up to 30 features): the ones and the target are columns p and p + 1 of the second operand block -- the column sums,
+// X'y, the row count and sum y come out of the matrix instructions that run anyway (no side sums per step, no cross-row reductions per
+// group), and the accumulator blocks ARE the record [X 1 y]' [X 1 y].  Without YC (31 / 32 features) the target rides beside the blocks.
 // NQ = 1 (YC, up to 18 features: the second operand block holds at most FOUR columns -- x16, x17, the ones, the target): its two
 // 16 x 16 x 4 matrix instructions per step (64 ticks each, a quarter of a block useful) become two v_mfma_f64_4x4x4_4b (20 ticks each; layout
 // and rate: tools/mfma_f64_4x4_probe.hip -- A[i][k] of block b in lane 16 k + 4 b + i, B[k][j] in lane 16 k + 4 b + j, D[i][j] in lane
 // 16 i + 4 b + j): block b of the first multiplies columns 4 b .. 4 b + 3 of the first operand block (its lanes ARE the 16 x 16 operand's)
-// with the quad, the second the quad with itself.
-// T = float (PAIRED only): f32 frames -- 128-row half-tiles of the same 1 KiB instructions and the same LDS bytes, widened to f64 on their
-// way out of LDS; moments, slot, solve and side / marked records are f64 as for f64 frames, the coefficients are written as T.
-// DIRECT (PAIRED; f64 frames of 17 .. 32 features, f32 frames of 17 .. 30; round 6): NO tile images.  The streaming wave loads the half-tile straight into the matrix instructions'
-// operand layout -- lane (feature = lane % 16, slot = lane / 16) reads 16 bytes = rows 8 k + 2 slot, + 1 of its own column for block k of
-// eight rows: sixteen columns x 64 contiguous bytes per 1 KiB load instruction, the order of the rows inside a block does not matter to a
-// sum over rows -- into one of two register sets (the half-tile being walked, the next one in flight); a 4-row step multiplies rows
-// {8 k + 2 slot + j}.  No asynchronous LDS pieces (95 clk of the wave's time each), no operand reads from LDS in front of every step.
+// with the quad, the second the quad with itself.  NQ = 3 (YC, 19 .. 22 features): an octet of columns, described where it is loaded.
+// T = float (paired forms only): f32 frames -- half-tiles of 128 rows in the same bytes, widened to f64 as they are multiplied; moments,
+// slot, solve and side / marked records are f64 as for f64 frames, the coefficients are written as T.
 template <int NBLK, int SPPC = 0, bool PAIRED = false, bool YC = false, int NQ = 0, typename T = double, bool DIRECT = false>
 __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(const T* const* __restrict__ cols, int p, int64_t n_frame,
                                                                 const int64_t* __restrict__ off, int64_t n_groups,
@@ -158,15 +135,23 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
     (void)debug_arg;
 #endif
     constexpr int ES = (int)sizeof(T), EPL = 16 / ES;  // element bytes; elements per 16-byte lane piece
-    static_assert(ES == 8 || PAIRED, "f32 frames: the paired form");
-    static_assert(SPPC == 0 || NBLK == 2, "the in-wave solve serves two tile columns");
-    static_assert(!PAIRED || SPPC > 0, "pairs exist for the in-kernel solve");
+    // the instantiations that exist -- every other combination of the parameters fails here:
+    //   record stream   <2, 0, false, false, 0, double, false>  the LDS form, 17 .. 32 features (the fused fit's fallback)
+    //                   <4, 0, false, false, 0, double, true>   the direct form, 33 .. 64 features
+    //   paired direct   <2, 24, true, true, 1 | 3 | 0, T, true>  up to 18 | 19 .. 22 | 23 .. 24 features
+    //                   <2, 32, true, true, 0, T, true>          25 .. 30 features
+    //                   <2, 32, true, false, 0, double, true>    31 / 32 features, f64 frames
+    //   paired LDS      <2, 32, true, false, 0, float, false>    31 / 32 features, f32 frames
+    static_assert(PAIRED == (SPPC > 0), "pairs of waves exist for the in-kernel solve, and the in-kernel solve only in pairs: the record stream has SPPC = 0");
+    static_assert(PAIRED || (!YC && NQ == 0 && ES == 8 && (DIRECT ? NBLK == 4 : NBLK == 2)),
+                  "the record stream: f64 frames, the target beside the blocks; two tile columns from LDS images or four in the direct form");
+    static_assert(!(PAIRED && DIRECT) || (NBLK == 2 && (YC ? (SPPC == 24 && (NQ == 0 || NQ == 1 || NQ == 3)) || (SPPC == 32 && NQ == 0)
+                                                           : SPPC == 32 && NQ == 0 && ES == 8)),
+                  "the paired direct form: ones and target as columns (24 columns as blocks, a quad or an octet; 32 as blocks), or -- f64 "
+                  "frames of 31 / 32 features -- the target beside 32 columns");
+    static_assert(!(PAIRED && !DIRECT) || (NBLK == 2 && SPPC == 32 && !YC && NQ == 0 && ES == 4),
+                  "the paired LDS form: f32 frames of 31 / 32 features, the target beside the blocks");
     static_assert(!PAIRED || MidPacked<SPPC ? SPPC : 1, YC>::COUNT * 8 <= (DIRECT ? kMidDirectSlotBytes : kMidSolveScratch), "the slot holds one group");
-    static_assert(!YC || PAIRED, "the ones / target columns are the paired form's");
-    static_assert(NQ == 0 || ((NQ == 1 || NQ == 2 || NQ == 3) && YC && NBLK == 2), "the quad form: ones and target inside the quads");
-    static_assert(NQ != 3 || DIRECT, "the octet is the direct form's");
-    static_assert(!DIRECT || (PAIRED && NBLK == 2 && NQ != 2 && (YC || (SPPC == 32 && ES == 8))) || (!PAIRED && NBLK == 4 && SPPC == 0 && !YC && NQ == 0 && ES == 8),
-                  "the direct form: the paired kernels of 17 .. 32 features (the target beside the blocks: f64 frames), or the record stream of 33 .. 64");
     using MD = MidDims<NBLK, ES>;
     constexpr int IMG = DIRECT ? 0 : MD::LDS_BYTES;  // bytes of tile images in front of the pair's slot
     // (the direct form walks eight blocks of eight rows -- sixteen of f32 -- whatever the LDS form's half-tile of this NBLK is)
@@ -205,19 +190,14 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         for (int i = lane * 16; i < IMG; i += 64 * 16) *(__attribute__((address_space(3))) mid_d2*)(sm + i) = mid_d2{0.0, 0.0};
         if constexpr (PAIRED)
             if (lane < 4) FL[lane] = 0u;
-        if constexpr (YC && !DIRECT) {  // the ones column: the (otherwise unused) weight image of both half-tiles, written once
-            PDS_WAVE_LDS_SYNC();
-            for (int b = 0; b < MD::NBUF; ++b)
-                for (int r = lane; r < HR; r += 64) PDS_GM_LDST(sm + b * MD::HALF_BYTES + MD::W_OFF + r * ES) = (T)1;
-        }
         PDS_WAVE_LDS_SYNC();
     }
     if constexpr (PAIRED) __syncthreads();  // (the only workgroup barrier: the flag words are zero before a solver wave polls them)
     if (h0 >= h1) return;
     const int64_t W0 = h0 * HR > row_begin ? h0 * HR : row_begin, W1 = h1 * HR < row_end ? h1 * HR : row_end;  // the wave's rows
     const int q = p + 2;
-    // SPPC: finished groups wait, up to four of them (one per 16-lane DPP row, two columns per lane: solve_row16_dev.hpp), and are
-    // solved side by side.  A system next to the gate is marked; its record is rebuilt from the group's rows (a rare, slow path: the
+    // SPPC: the solving wave takes finished groups FOUR at a time (one per 16-lane DPP row, two columns per lane: solve_row16_dev.hpp) and
+    // solves them side by side.  A system next to the gate is marked; its record is rebuilt from the group's rows (a rare, slow path: the
     // accumulators it came from are gone by then).
     // pending systems: RAW moments (the centring, lambda and the diagonal wait for the solve, where they cost once per four groups)
     //   pa0 / pa1[i] = G[i][t] / G[i][16 + t], [SPPC] = X'y; psj0 / psj1 = column sums; pnn = rows; psy = sum y; pgid = group
@@ -248,7 +228,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         if constexpr (SPPC > 0) {
             if (npend == 0) return;
             const int t = lane & 15, R = lane >> 4, pout = p + sa.sp.bias;
-            const bool live = R < npend && pgid >= 0;  // (pgid < 0: padding of the paired form's last batch)
+            const bool live = R < npend && pgid >= 0;  // (pgid < 0: padding of the stream's last batch -- whatever the slot held: every store below is under `live`)
             // ---- raw moments -> the centred system with lambda on the diagonal (all pending rows at once)
             const bool c0v = t < p, c1v = 16 + t < p;
             pa0[SPPC] = c0v ? pa0[SPPC] : 0.0;
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             const bool pfew = pnn < (double)pout;  // "#Data < #features"
             double w0, w1;
             bool is_null, suspect;
-            row16_ldl_solve<SPPC, (PAIRED && SPPC > 24)>(pa0, pa1, pdj0, pdj1, t, p, pfew, sa.sp, w0, w1, is_null, suspect);
+            row16_ldl_solve<SPPC, (SPPC > 24)>(pa0, pa1, pdj0, pdj1, t, p, pfew, sa.sp, w0, w1, is_null, suspect);
             const double nanv = __builtin_nan("");
             const int64_t gq = live ? pgid : 0;
             T* co = sa.coeffs + gq * (int64_t)pout;
@@ -307,11 +287,9 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             npend = 0;
         }
     };
-    // PAIRED, solving wave: a published slot -> DPP row `npend` of the pending registers (row-masked moves, as route_pending), four
-    // pending -> solve.  The slot holds the UPPER TRIANGLE of G row by row (MidPacked: one trip at any width; the full columns of
-    // route_pending's layout took two from 25 features, and the streaming wave stood still between them while a solve ran): lane t
-    // reads row i of its column at U(i, t) for i <= t and at U(t, i) below the diagonal -- an immediate offset on one of two lane
-    // addresses, chosen per element only inside the two diagonal blocks.
+    // PAIRED, solving wave: four published slots -> the four DPP rows of the pending registers -> solve.  The slot holds the UPPER
+    // TRIANGLE of G row by row (MidPacked): lane t reads row i of its column at U(i, t) for i <= t and at U(t, i) below the diagonal -- an
+    // immediate offset on one of two lane addresses, chosen per element only inside the two diagonal blocks.
     auto solver_wave = [&]() __attribute__((always_inline)) {
         if constexpr (PAIRED) {
             typedef __attribute__((address_space(3))) double* lds_dp;
@@ -520,17 +498,13 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
     // column 16 + fi % 8, so the four lanes of block b hold quad b % 2 of it; rotated by four lanes inside the row (one DPP move per half)
     // they hold the other quad.  Four v_mfma_f64_4x4x4_4b per step -- first block x octet as it is and rotated, octet x octet likewise -- give
     // the first block's products with all eight columns and the 8 x 8 corner: 64 ticks of the matrix pipe where two 16 x 16 x 4 took 128.
-    constexpr int NOP = NQ == 3 ? 2 : (NQ ? 1 + NQ : NBLK);  // operand registers per step: the first block + NQ quads (or the octet), or the NBLK blocks
-    int opo[NOP];  // the lane's operand column inside an image
+    constexpr int NOP = NQ ? 2 : NBLK;  // operand registers per step: the first block + the quad or the octet, or the NBLK blocks
+    auto piece_col = [&](int b) __attribute__((always_inline)) {  // the frame column of operand piece b in this lane
+        return NQ == 3 ? (b == 0 ? fi : 16 + (fi & 7)) : NQ == 1 ? (b == 0 ? fi : 16 + (fi & 3)) : 16 * b + fi;
+    };
+    int opo[NOP];  // the LDS forms (blocks only): the lane's operand column inside an image
 #pragma unroll
-    for (int b = 0; b < NOP; ++b) {
-        const int c = NQ == 3 ? (b == 0 ? fi : 16 + (fi & 7)) : NQ ? (b == 0 ? fi : 12 + 4 * b + (fi & 3)) : 16 * b + fi;  // (quad b - 1: column 16 + 4 (b - 1) + lane % 4)
-        opo[b] = (c & 15) * GS + (c >> 4) * HR * ES;
-        if constexpr (YC) {  // columns p and p + 1: the ones image and the target's image
-            if (b > 0 && c == p) opo[b] = MD::W_OFF;
-            if (b > 0 && c == p + 1) opo[b] = MD::Y_OFF;
-        }
-    }
+    for (int b = 0; b < NOP; ++b) opo[b] = fi * GS + b * HR * ES;
     const int qb = (lane >> 2) & 3, qj = lane & 3;  // quad lanes: D[i = fk][j = qj] of block qb
     // ---- DIRECT: two register sets of NB8 blocks x NOP pieces x 16 bytes; the lane's address per piece moves on by one half-tile per issue
     // (f32 frames: the same 16 bytes per lane are FOUR rows -- blocks of 16 rows, four steps each, the operands widened as they are multiplied)
@@ -543,7 +517,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
     if constexpr (DIRECT) {
 #pragma unroll
         for (int b = 0; b < NOP; ++b) {
-            const int c = NQ == 3 ? (b == 0 ? fi : 16 + (fi & 7)) : NQ ? (b == 0 ? fi : 12 + 4 * b + (fi & 3)) : 16 * b + fi;  // (as opo: the piece's column in this lane)
+            const int c = piece_col(b);
             const bool real = c < p || (YC && c == p + 1);                           // a frame column (YC: p + 1 = the target, p = ones); beyond: zeros
             const char* cst = ES == 8 ? reinterpret_cast<const char*>(g_mid_direct_const) : reinterpret_cast<const char*>(g_mid_direct_const_f32);
             const char* base = real ? reinterpret_cast<const char*>(cols[c < p ? c : p]) + h0 * (int64_t)(HR * ES) : cst + ((YC && c == p) ? 0 : HR * ES);
@@ -573,10 +547,12 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
                 }
             }
             if ((h + 1) * HR <= n_frame) {
+                // (plain loads: two consecutive instructions read the two halves of the same sixteen 128-byte lines, and as non-temporal
+                // loads the second one misses again -- 30 features 6.4 -> 7.5 ms, profiles/r06_grouped_mid_direct.txt)
 #pragma unroll
                 for (int k = 0; k < NB8; ++k)
 #pragma unroll
-                    for (int b = 0; b < NOP; ++b) NXT[k][b] = PDS_MID_DIRECT_LOAD(reinterpret_cast<gptr<VT>>(dcp[b] + 64 * k));
+                    for (int b = 0; b < NOP; ++b) NXT[k][b] = *reinterpret_cast<gptr<VT>>(dcp[b] + 64 * k);
             } else {  // the frame's last, partial half-tile: row by row, rows beyond the frame are zeros (nobody multiplies them)
 #pragma unroll
                 for (int k = 0; k < NB8; ++k)
@@ -624,8 +600,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             const int roff = (4 * s + fk) * ES;
 #pragma unroll
             for (int b = 0; b < NOP; ++b) a[b] = (double)PDS_GM_LDST(base + opo[b] + roff);
-            if constexpr (!YC) yk = (double)PDS_GM_LDST(base + MD::Y_OFF + roff);
-            else yk = 0.0;
+            yk = (double)PDS_GM_LDST(base + MD::Y_OFF + roff);
         };
         auto mult = [&](const double (&a)[NOP], double yk) __attribute__((always_inline)) {
             if constexpr (NQ == 1) {
@@ -641,13 +616,6 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
                 acc[1][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], ar, acc[1][1], 0, 0, 0);    // G[4 qb + fk][16 + 4 (1 - qb % 2) + qj]
                 acc[1][2] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], a[1], acc[1][2], 0, 0, 0);  // G[16 + 4 (qb % 2) + fk][16 + 4 (qb % 2) + qj]
                 acc[1][3] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], ar, acc[1][3], 0, 0, 0);    // G[16 + 4 (qb % 2) + fk][16 + 4 (1 - qb % 2) + qj]
-            } else if constexpr (NQ == 2) {
-                // the 8 x 8 corner in ONE instruction: block 0 = quad 0 with itself, 1 = quad 0 with quad 1, 2 (and 3) = quad 1 with itself
-                const double ca = qb < 2 ? a[1] : a[2], cb = qb == 0 ? a[1] : a[2];
-                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], a[0], acc[0], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], a[1], acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], a[2], acc[1][1], 0, 0, 0);
-                acc[2][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(ca, cb, acc[2][0], 0, 0, 0);
             } else {
                 int t = 0;
 #pragma unroll
@@ -746,9 +714,9 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             yk = in ? yk : 0.0;
             mult(a, yk);
         };
-        // a whole half-tile of one group: the unrolled form of the single-regression kernel (not for f32 frames with the side sums: its 32
-        // steps cost that variant 65 spilled registers -- the column pointers, reloaded behind the loads in flight)
-        if ((ES == 8 || YC) && lo == 0 && hi == HR) {
+        // a whole half-tile of one group: the unrolled form of the single-regression kernel (not for f32 frames: its 32 steps with the side
+        // sums cost that kernel 65 spilled registers -- the column pointers, reloaded behind the loads in flight)
+        if (ES == 8 && lo == 0 && hi == HR) {
             double a[NOP], yk;
             fetch(0, a, yk);
 #pragma unroll
@@ -793,9 +761,10 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
     // register for the whole stream, and the streaming wave's two operand sets leave none: spilled, they were reloaded in front of
     // `s_waitcnt vmcnt(0)` behind the next half-tile's loads.  The 17 / 18-feature f64 kernel has the registers: hoisted there, 3.40 -> 3.32 ms;
     // the octet kernel has them too and is 3 % SLOWER with the addresses hoisted)
+    constexpr bool kLaunder = DIRECT && !(NQ == 1 && ES == 8);
     auto put_record = [&](double* M, bool plain) __attribute__((always_inline)) {
         int l0 = fi, l1 = fk, l2 = qb, l3 = qj;
-        if constexpr (DIRECT && (SPPC == 32 || ES == 4 || NQ != 1 || PDS_MID_LAUNDER_ALL)) asm volatile("" : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3));
+        if constexpr (kLaunder) asm volatile("" : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3));
         const int fi = l0, fk = l1, qb = l2, qj = l3;
         auto put = [&](int64_t idx, double v) __attribute__((always_inline)) {
             if (plain) M[idx] = v;
@@ -825,25 +794,24 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             }
             return;
         }
-        if constexpr (NQ != 0) {
+        if constexpr (NQ == 1) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = fk + 4 * r, j = fi;
                 if (i < pe && j < pe) put(i + (int64_t)j * q, acc[0][r]);
             }
 #pragma unroll
-            for (int u = 0; u < NQ; ++u) {  // first block x quad u: G[4 qb + fk][16 + 4 u + qj]
+            for (int u = 0; u < NQ; ++u) {  // first block x quad u (there is one): G[4 qb + fk][16 + 4 u + qj]
                 const int c = 16 + 4 * u + qj;
                 if (c < pe) {
                     put((4 * qb + fk) + (int64_t)c * q, acc[1][u]);
                     put(c + (int64_t)(4 * qb + fk) * q, acc[1][u]);
                 }
             }
-            {  // the corner: NQ = 1: block 0 = (quad 0, quad 0), both triangles in its lanes; NQ = 2: blocks (0, 0), (0, 1), (1, 1)
-                const int ri = 16 + (NQ == 2 && qb >= 2 ? 4 : 0) + fk, cj = 16 + (NQ == 2 && qb >= 1 ? 4 : 0) + qj;
-                if (qb < (NQ == 2 ? 3 : 1) && ri < pe && cj < pe) {
+            {  // the corner: block 0 = (quad 0, quad 0), both triangles in its lanes
+                const int ri = 16 + fk, cj = 16 + qj;
+                if (qb < 1 && ri < pe && cj < pe) {
                     put(ri + (int64_t)cj * q, acc[2][0]);
-                    if (NQ == 2 && qb == 1) put(cj + (int64_t)ri * q, acc[2][0]);
                 }
             }
             return;
@@ -890,96 +858,10 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             put((p + 1) + (int64_t)(p + 1) * q, vyy);
         }
     };
-    // the finished group's accumulators -> DPP row `npend` of the pending registers, through the LDS scratch behind the tile images
-    // (every lane of every row reads column t / 16 + t; a ROW-MASKED DPP move -- identity permutation, row_mask = the pending row --
-    // drops the values into that row's lanes only: two instructions per value, no select against the old contents, no temporaries)
-    auto route_pending = [&]() __attribute__((always_inline)) {
-        if constexpr (SPPC > 0) {
-            typedef __attribute__((address_space(3))) double* lds_dp;
-            constexpr int SS = SPPC + 2;                                   // doubles per column of the scratch
-            constexpr bool ONE_TRIP = SPPC * SS * 8 <= kMidSolveScratch;   // all SPPC columns at once (up to 24 features)
-            lds_dp S = (lds_dp)(sm + IMG);
-            const int t = lane & 15;
-            double vx0 = xy[0], vx1 = xy[1], vc0 = cs[0], vc1 = cs[1], vys = ys;
-            vx0 += __shfl_xor(vx0, 16); vx0 += __shfl_xor(vx0, 32);
-            vx1 += __shfl_xor(vx1, 16); vx1 += __shfl_xor(vx1, 32);
-            vc0 += __shfl_xor(vc0, 16); vc0 += __shfl_xor(vc0, 32);
-            vc1 += __shfl_xor(vc1, 16); vc1 += __shfl_xor(vc1, 32);
-            vys += __shfl_xor(vys, 16); vys += __shfl_xor(vys, 32);
-            const double nn = (double)rows_in_acc;
-            auto into_row = [&](auto rm) __attribute__((always_inline)) {
-                constexpr int RM = 1 << decltype(rm)::value;
-                auto put = [&](double& dst, double v) __attribute__((always_inline)) {
-                    dst = __builtin_amdgcn_update_dpp(dst, v, 0xE4 /*quad_perm:[0,1,2,3]*/, RM, 0xf, false);
-                };
-                auto put64 = [&](int64_t& dst, int64_t v) __attribute__((always_inline)) {
-                    int lo = (int)(uint32_t)(uint64_t)dst, hi = (int)(uint32_t)((uint64_t)dst >> 32);
-                    lo = __builtin_amdgcn_update_dpp(lo, (int)(uint32_t)(uint64_t)v, 0xE4, RM, 0xf, false);
-                    hi = __builtin_amdgcn_update_dpp(hi, (int)(uint32_t)((uint64_t)v >> 32), 0xE4, RM, 0xf, false);
-                    dst = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-                };
-                PDS_WAVE_LDS_SYNC();
-                // columns 0 .. 15: rows 0 .. 15 from block (0, 0), rows 16 .. from block (0, 1) transposed (G is symmetric)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    S[fi * SS + fk + 4 * r] = acc[0][r];
-                    if (16 + fi < SPPC) S[(fk + 4 * r) * SS + 16 + fi] = acc[1][r];
-                }
-                if constexpr (ONE_TRIP) {
-                    // columns 16 .. SPPC - 1 behind them: rows 0 .. 15 from block (0, 1), rows 16 .. from block (1, 1)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (16 + fi < SPPC) {
-                            S[(16 + fi) * SS + fk + 4 * r] = acc[1][r];
-                            if (16 + fk + 4 * r < SPPC) S[(16 + fi) * SS + 16 + fk + 4 * r] = acc[2][r];
-                        }
-                    }
-                }
-                PDS_WAVE_LDS_SYNC();
-#pragma unroll
-                for (int i = 0; i < SPPC; ++i) put(pa0[i], S[t * SS + i]);
-                if constexpr (ONE_TRIP) {
-                    const int t1 = (16 + t < SPPC) ? 16 + t : 0;  // (lanes without a second column read a valid address, their values are zeroed)
-#pragma unroll
-                    for (int i = 0; i < SPPC; ++i) {
-                        const double v = S[t1 * SS + i];
-                        put(pa1[i], (16 + t < SPPC) ? v : 0.0);
-                    }
-                } else {
-                    PDS_WAVE_LDS_SYNC();
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        S[fi * SS + fk + 4 * r] = acc[1][r];
-                        S[fi * SS + 16 + fk + 4 * r] = acc[2][r];
-                    }
-                    PDS_WAVE_LDS_SYNC();
-#pragma unroll
-                    for (int i = 0; i < SPPC; ++i) put(pa1[i], S[t * SS + i]);
-                }
-                put(pa0[SPPC], vx0);
-                put(pa1[SPPC], vx1);
-                put(psj0, vc0);
-                put(psj1, vc1);
-                put(pnn, nn);
-                put(psy, vys);
-                put64(pgid, g);
-            };
-            switch (npend) {
-                case 0: into_row(std::integral_constant<int, 0>{}); break;
-                case 1: into_row(std::integral_constant<int, 1>{}); break;
-                case 2: into_row(std::integral_constant<int, 2>{}); break;
-                default: into_row(std::integral_constant<int, 3>{}); break;
-            }
-            ++npend;
-            if (npend == 4) {
-                if (debug & 4) npend = 0;  // (timing experiment: routed, never solved)
-                else solve_pending();
-            }
-        }
-    };
-    // PAIRED, streaming wave: the finished group's moments -> the pair's slot (MidPacked), published under a sequence number.  A slot
-    // the solving wave has not taken yet (it is in the middle of a solve) does not stop the stream: the group waits in a spare set of
-    // registers and goes out in front of the next one -- the stream stands still only when the solver is two groups behind.
+    // PAIRED, streaming wave: the finished group's moments -> a slot of the pair (MidPacked), published under a sequence number.  The
+    // direct form's ring of NSLOT slots is the queue.  The LDS form has ONE slot, and a slot the solving wave has not taken yet (it is in
+    // the middle of a solve) does not stop the stream: the group waits in a spare set of registers (st_*) and goes out in front of the
+    // next one -- the stream stands still only when the solver is two groups behind.
     unsigned pseq = 0;
     d4 st_acc[NPAIR];
     double st_x0 = 0.0, st_x1 = 0.0, st_c0 = 0.0, st_c1 = 0.0, st_nn = 0.0, st_ys = 0.0;
@@ -1000,7 +882,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             PDS_MADD(4, tw);
             PDS_MT(tpb);
             int l0 = fi, l1 = fk, l2 = qb, l3 = qj;
-            if constexpr (DIRECT && (SPPC == 32 || ES == 4 || NQ != 1 || PDS_MID_LAUNDER_ALL)) asm volatile("" : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3));
+            if constexpr (kLaunder) asm volatile("" : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3));
             const int fi = l0, fk = l1, qb = l2, qj = l3;
             if constexpr (NQ == 3) {
 #pragma unroll
@@ -1014,19 +896,16 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
                 const int rr = 16 + 4 * par + fk;
                 if (qb < 2 && rr <= c0) S[PK::tri_rt(rr) - rr + c0] = A[1][2];  // the diagonal 4 x 4 blocks of the corner
                 if (qb == 0) S[PK::tri_rt(rr) - rr + c1] = A[1][3];             // rows 16 .. 19 against columns 20 .. 23
-            } else if constexpr (NQ != 0) {
+            } else if constexpr (NQ == 1) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = fk + 4 * r;
                     if (i <= fi) S[PK::tri_rt(i) - i + fi] = A[0][r];
                 }
                 const int qr = 4 * qb + fk;  // quad lanes: D[i = fk][j = qj] of block qb
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) S[PK::tri_rt(qr) - qr + 16 + 4 * u + qj] = A[1][u];
-                {   // the corner: (quad 0, quad 0) [, (quad 0, quad 1), (quad 1, quad 1)]: the upper triangle of it
-                    const int ri = 16 + (NQ == 2 && qb >= 2 ? 4 : 0) + fk, cj = 16 + (NQ == 2 && qb >= 1 ? 4 : 0) + qj;
-                    if (qb < (NQ == 2 ? 3 : 1) && ri <= cj) S[PK::tri_rt(ri) - ri + cj] = A[2][0];
-                }
+                S[PK::tri_rt(qr) - qr + 16 + qj] = A[1][0];
+                const int ri = 16 + fk, cj = 16 + qj;  // the corner (quad, quad): the upper triangle of it
+                if (qb < 1 && ri <= cj) S[PK::tri_rt(ri) - ri + cj] = A[2][0];
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1067,67 +946,12 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
             }
         }
     };
-    // STASH2 (up to 24 features, where the streaming wave has the registers): TWO spare sets -- a solve of four (17 600 ticks at 17 features)
-    // outlasts a group (10 800) and the slot + one set did not always absorb it: the streaming wave stood 9.6 % of its time in front of a
-    // full slot.  A two-deep FIFO in registers: set A / set B, `a_old` says which is the older; drained whenever the slot is free.
-    constexpr bool STASH2 = PAIRED && YC && SPPC == 24 && !DIRECT;  // (the direct form has the registers for one spare set)
-    d4 st_b[STASH2 ? NPAIR : 1];
-    int64_t st_gb = 0;
-    int nst = 0;
-    bool a_old = true;
-    auto drain_one = [&]() __attribute__((always_inline)) {  // (the slot is free, nst > 0)
-        if constexpr (STASH2) {
-            if (a_old) publish_group(st_acc, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, st_g);
-            else publish_group(st_b, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, st_gb);
-            a_old = !a_old;
-            --nst;
-        }
-    };
-    auto drain_free = [&]() __attribute__((always_inline)) {
-        if constexpr (STASH2) {
-            while (nst > 0 && slot_free()) drain_one();
-        }
-    };
-    auto hand_over2 = [&]() __attribute__((always_inline)) {
-        if constexpr (STASH2) {
-            drain_free();
-            if (nst == 0 && slot_free()) {
-                publish_group(acc, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, g);
-                return;
-            }
-            if (nst == 2) drain_one();  // (both sets taken: this one waits for the slot inside publish_group)
-            if (nst == 0) {
-#pragma unroll
-                for (int b = 0; b < NPAIR; ++b) st_acc[b] = acc[b];
-                st_g = g;
-                a_old = true;
-            } else if (a_old) {
-#pragma unroll
-                for (int b = 0; b < NPAIR; ++b) st_b[b] = acc[b];
-                st_gb = g;
-            } else {
-#pragma unroll
-                for (int b = 0; b < NPAIR; ++b) st_acc[b] = acc[b];
-                st_g = g;
-            }
-            ++nst;
-        }
-    };
     auto hand_over = [&]() __attribute__((always_inline)) {
-        if constexpr (STASH2) {
-            hand_over2();
-        } else if constexpr (DIRECT) {  // (the ring is the queue: the stream stands still only in front of NSLOT unsolved groups)
+        if constexpr (DIRECT) {  // (the ring is the queue: the stream stands still only in front of NSLOT unsolved groups)
             if constexpr (YC) publish_group(acc, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, g);
             else publish_group(acc, rows_sum4(xy[0]), rows_sum4(xy[1]), rows_sum4(cs[0]), rows_sum4(cs[1]), (double)rows_in_acc, rows_sum4(ys), g);
         } else if constexpr (PAIRED) {
-            double vx0 = xy[0], vx1 = xy[1], vc0 = cs[0], vc1 = cs[1], vys = ys;
-            if constexpr (!YC) {
-                vx0 = rows_sum4(vx0);
-                vx1 = rows_sum4(vx1);
-                vc0 = rows_sum4(vc0);
-                vc1 = rows_sum4(vc1);
-                vys = rows_sum4(vys);
-            }
+            const double vx0 = rows_sum4(xy[0]), vx1 = rows_sum4(xy[1]), vc0 = rows_sum4(cs[0]), vc1 = rows_sum4(cs[1]), vys = rows_sum4(ys);
             flush_stash();
             if (slot_free()) {
                 publish_group(acc, vx0, vx1, vc0, vc1, (double)rows_in_acc, vys, g);
@@ -1152,8 +976,7 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         }
         if constexpr (SPPC > 0) {
             if (whole) {
-                if constexpr (PAIRED) hand_over();
-                else route_pending();
+                hand_over();
             } else {
                 // the wave the group starts in owns the side-table slot (largest w whose first row is <= gs)
                 int64_t slot = wave;
@@ -1179,13 +1002,12 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         rows_in_acc = 0;
     };
     // ---- stream the half-tiles
-    // OWNER: a group belongs to the wave in whose rows it STARTS.  That wave follows it beyond the end of
-    // its own range -- at most `own_limit` rows, less than the next wave's whole range --, the wave it runs into skips it: no partial sums, no
-    // atomics, no side record, the same bits every run.  Only a group LONGER than `own_limit` (both waves judge by its offsets alone) is
-    // summed by every wave that meets it, into the side table's slot of the wave it starts in, as before.
-    constexpr bool OWNER = PDS_MID_OWNER;  // (the record form too: whole records by plain stores, the caller zeroes only giant and empty groups' records)
+    // A group belongs to the wave in whose rows it STARTS.  That wave follows it beyond the end of its own range -- at most `own_limit`
+    // rows, less than the next wave's whole range --, the wave it runs into skips it: no partial sums, no atomics, no side record, the same
+    // bits every run.  Only a group LONGER than `own_limit` (both waves judge by its offsets alone) is summed by every wave that meets it:
+    // into the side table's slot of the wave it starts in, or -- the record stream -- into its record, which the caller has zeroed.
     const int64_t own_limit = ((H1 - H0) / nwaves) * HR;
-    bool skip = OWNER && !started_here && ge - gs <= own_limit;  // the wave's first group, begun (and finished) by the wave in front
+    bool skip = !started_here && ge - gs <= own_limit;  // the wave's first group, begun (and finished) by the wave in front
     int64_t wend = W1, hend = h1;                                 // the rows this wave walks, the half-tiles it streams: grow with a followed group
     int64_t pos = W0;
     if constexpr (DIRECT) issue_direct(h0);
@@ -1215,14 +1037,12 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         // (a waiting group goes out as soon as the solving wave has emptied the slot, not only when the next group ends: without this look
         // per half-tile the 17-feature kernel is 6 % slower)
         PDS_MT(p11);
-        if constexpr (STASH2) {
-            if (nst > 0) drain_free();
-        } else if constexpr (PAIRED && !DIRECT) {
+        if constexpr (PAIRED && !DIRECT) {
             if (stashed && slot_free()) flush_stash();
         }
         PDS_MADD(11, p11);
         PDS_MT(p1);
-        if (h + 1 < (OWNER ? H1 : h1)) {  // (OWNER: also the half-tile behind the wave's own range -- a group may have to be followed into it)
+        if (h + 1 < H1) {  // (also the half-tile behind the wave's own range: a group may have to be followed into it)
             if constexpr (DIRECT) issue_direct(h + 1);
             else fetch_tile(buf ^ 1, h + 1);  // (the other image was consumed one iteration ago)
         }
@@ -1266,21 +1086,23 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         }
         pos = R0 + posr;
         if (g >= n_groups) break;
-        if constexpr (OWNER) {
-            // the open group at the end of the wave's (possibly extended) rows: its own and not longer than the limit -> one more half-tile
-            if (h + 1 == hend && rows_in_acc != 0 && started_here && ge - gs <= own_limit && h + 1 < H1) {
-                wend = ge < row_end ? ge : row_end;
-                hend = h + 2;
-            }
+        // the open group at the end of the wave's (possibly extended) rows: its own and not longer than the limit -> one more half-tile
+        if (h + 1 == hend && rows_in_acc != 0 && started_here && ge - gs <= own_limit && h + 1 < H1) {
+            wend = ge < row_end ? ge : row_end;
+            hend = h + 2;
         }
         PDS_WAVE_LDS_SYNC();
     }
     if (rows_in_acc != 0 && g < n_groups) flush(false);  // the group that continues in the next wave's rows
     if constexpr (PAIRED) {
         flush_stash();
-        if constexpr (STASH2)
-            while (nst > 0) drain_one();  // (publish_group waits for the slot)
-        while ((pseq & 3u) != 0u && !(debug & 16)) {  // pad the last batch: the slot's contents once more (a valid system), marked as discarded
+        // pad the last batch to four: only the group id of the next slot(s) is written, -1 = discarded.  What the solving wave then reads
+        // from such a slot is NOT a valid system: the one slot of the LDS form still holds the group published last, but a slot of the
+        // direct form's ring of eight may never have been written by this workgroup (a wave that published fewer than eight groups) and
+        // holds whatever a workgroup before it left in LDS -- NaN and Inf included.  The centring and the factorisation run on it all the
+        // same, and every store of the result, the marked list included, is masked by `live` (pgid >= 0).  That is all that keeps a padded
+        // row harmless, so solve_pending and row16_ldl_solve must stay free of control flow that depends on a row's data.
+        while ((pseq & 3u) != 0u && !(debug & 16)) {
             typedef __attribute__((address_space(3))) double* lds_dp;
             while (!slot_free()) __builtin_amdgcn_s_sleep(1);
             if (lane == 0) ((lds_dp)(sm + IMG + (DIRECT ? (int)(pseq % NSLOT) * SLOTB : 0)))[MidPacked<SPPC, YC>::GID] = __longlong_as_double(-1ll);
@@ -1290,8 +1112,6 @@ __global__ __launch_bounds__(PAIRED ? 512 : 64) void grouped_mid_stream_kernel(c
         }
         PDS_WAVE_LDS_SYNC();
         FL[2] = 1u;
-    } else {
-        solve_pending();
     }
 #ifdef PDS_PROFILE_MID
     PDS_MADD(7, t_kernel);
@@ -1322,9 +1142,9 @@ int launch_grouped_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int p, int
                           double* d_records) {
     using MD = MidDims<NBLK>;
     const int q = p + 2;
-    // 33 .. 64 features: the direct form too (round 6) -- a wave alone on its SIMD has the registers for two operand sets of four pieces
-    // beside ten accumulator blocks, and no tile images at all (the target's image: 1 KB)
-    constexpr bool kDirect = NBLK == 4 && PDS_MID_DIRECT_RECORDS;
+    // 33 .. 64 features: the direct form -- a wave alone on its SIMD has the registers for two operand sets of four pieces beside ten
+    // accumulator blocks, and no tile images at all (the target's image: 1 KB); 17 .. 32: the LDS form
+    constexpr bool kDirect = NBLK == 4;
     constexpr int hr = kDirect ? kMidDirectRows<8> : MD::HR, lds_bytes = kDirect ? 2 * kMidDirectYBytes + 64 : MD::LDS_BYTES;
     auto kern = grouped_mid_stream_kernel<NBLK, 0, false, false, 0, double, kDirect>;
     if (lds_bytes > 64 * 1024)
@@ -1333,11 +1153,8 @@ int launch_grouped_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int p, int
     // the sum of two partial records does not depend on their order -- results are reproducible run to run but for such giant groups
     // (the row count of the chunk is not known on the host: the frame's is an upper bound)
     const int64_t waves = std::min<int64_t>((int64_t)ctx->num_cus * kMidWavesPerCu, std::max<int64_t>(1, n_frame / (8 * hr)));
-    if (PDS_MID_OWNER)
-        hipLaunchKernelGGL(mid_zero_records_kernel, dim3((unsigned)((n_groups + 63) / 64)), dim3(256), 0, ctx->stream, d_off, n_groups, q * q, d_records, hr,
-                           waves);
-    else
-        PDS_HIP_CHECK(hipMemsetAsync(d_records, 0, (size_t)n_groups * q * q * sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(mid_zero_records_kernel, dim3((unsigned)((n_groups + 63) / 64)), dim3(256), 0, ctx->stream, d_off, n_groups, q * q, d_records, hr,
+                       waves);
 #ifdef PDS_DEV_SWITCHES  // timing experiments of development builds (EXTRA=-DPDS_DEV_SWITCHES): wrong results with it
     const char* dbg = dev_env("PDS_GMID_DEBUG");
 #else
@@ -1349,7 +1166,7 @@ int launch_grouped_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int p, int
     return PDS_OK;
 }
 
-// ---- the in-wave-solve form (SPPC): host side
+// ---- the paired forms (SPPC > 0): host side
 constexpr unsigned kMidMarkCap = 8192;  // records of marked systems kept for the pivoted QR; more than that: the record pipeline
 inline int64_t mid_fused_waves(const pds_ctx* ctx, int64_t n_frame, int hr = MidDims<2>::HR) {
     const int64_t w = std::min<int64_t>((int64_t)ctx->num_cus * kMidWavesPerCu, std::max<int64_t>(1, n_frame / (8 * hr)));
@@ -1438,8 +1255,8 @@ int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, in
     return fail(PDS_ERR_UNSUPPORTED, "grouped_mid_stream: up to 64 features");
 }
 
-// OLS / ridge fits of n_groups contiguous groups with 17 .. 32 f64 features, rank gate on, as ONE stream with the solves in the
-// streaming waves (grouped_mid_stream_kernel, SPPC): coefficients [n_groups][p + bias] and null flags; no per-group records.
+// OLS / ridge fits of n_groups contiguous groups with 17 .. 32 f64 or f32 features, rank gate on, as ONE stream with the solves in the
+// solving waves beside it (grouped_mid_stream_kernel, the paired forms): coefficients [n_groups][p + bias] and null flags; no per-group records.
 // PDS_ERR_UNSUPPORTED (nothing usable written): not applicable, or more systems next to the gate than the marked list holds -- the
 // caller keeps the record pipeline.  d_ws: grouped_mid_fused_workspace() bytes.
 size_t grouped_mid_fused_workspace(int num_cus, int n_feat, int add_bias) {
@@ -1499,10 +1316,6 @@ int launch_grouped_mid_fused(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, 
     PDS_HIP_CHECK(hipMemsetAsync(d_counts, 0, 256, ctx->stream));
     PDS_HIP_CHECK(hipMemsetAsync(sa.side_rec, 0, (size_t)waves * q * q * 8, ctx->stream));
     PDS_HIP_CHECK(hipMemsetAsync(sa.side_list, 0xFF, (size_t)waves * 4, ctx->stream));
-    constexpr int lds = MD::LDS_BYTES + kMidSolveScratch;
-    const char* pair_env = dev_env("PDS_GROUPED_MID_PAIRED");
-    const bool paired = !(pair_env && pair_env[0] == '0') && waves % 4 == 0;
-    if (!F64 && !paired) return PDS_ERR_UNSUPPORTED;  // (f32 frames: the paired form only)
     {
         KernelTimer timer(ctx, kKindGroupedMoments);
 #ifdef PDS_DEV_SWITCHES  // timing experiments of development builds (EXTRA=-DPDS_DEV_SWITCHES): wrong results with it
@@ -1511,50 +1324,30 @@ int launch_grouped_mid_fused(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, 
         const char* dbg = nullptr;
 #endif
         const int debug = dbg ? std::atoi(dbg) : 0;
-        auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)waves), dim3(64), lds, ctx->stream, dc.d_ptrs, p, n_frame, d_off, n_groups, (double*)nullptr, debug, sa);
-        };
-        bool paired_lds_ok = true;
-        auto launch_paired_c = [&](auto kern, auto direct_c) {
+        // a workgroup of four pairs of waves with the LDS of its form; false: the device does not grant a workgroup that much
+        auto launch_paired = [&](auto kern, auto direct_c) {
             constexpr int plds = 4 * kMidPairLds<2, decltype(direct_c)::value>;
             // (per call, not once per process: the attribute belongs to the function ON THE CURRENT DEVICE, and a process may drive several)
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, plds) != hipSuccess) {
                 (void)hipGetLastError();
-                paired_lds_ok = false;
-                return;
+                return false;
             }
             hipLaunchKernelGGL(kern, dim3((unsigned)(waves / 4)), dim3(512), plds, ctx->stream, dc.d_ptrs, p, n_frame, d_off, n_groups, (double*)nullptr,
                                debug, sa);
+            return true;
         };
-        auto launch_paired = [&](auto kern) { launch_paired_c(kern, std::false_type{}); };
-        if (paired) {
-            const char* yc_env = dev_env("PDS_GROUPED_MID_YC");  // (development: '0' keeps the side sums of the 31 / 32-feature form)
-            const bool yc = !F64 || !(yc_env && yc_env[0] == '0');  // (f32 frames have the ones / target column form only)
-            const char* nq_env = dev_env("PDS_GROUPED_MID_QUAD");  // (development: '0' keeps the 16 x 16 x 4 form of the second block)
-            // the direct form (f64 frames, up to 30 features: PDS_MID_DIRECT, on by default; PDS_GROUPED_MID_DIRECT=0 in development builds)
-            const char* dir_env = dev_env("PDS_GROUPED_MID_DIRECT");
-            const bool direct = PDS_MID_DIRECT && yc && (F64 || p <= 30) && !(dir_env && dir_env[0] == '0');  // (f32 frames of 31 / 32 features: the LDS form)
-            if (direct) {
-                if (p <= 18) launch_paired_c(grouped_mid_stream_kernel<2, 24, true, true, 1, T, true>, std::true_type{});
-                else if (p <= 22 && PDS_MID_DIRECT_OCTET) launch_paired_c(grouped_mid_stream_kernel<2, 24, true, true, 3, T, true>, std::true_type{});
-                else if (p <= 24) launch_paired_c(grouped_mid_stream_kernel<2, 24, true, true, 0, T, true>, std::true_type{});
-                else if (p <= 30) launch_paired_c(grouped_mid_stream_kernel<2, 32, true, true, 0, T, true>, std::true_type{});
-                else if constexpr (F64) launch_paired_c(grouped_mid_stream_kernel<2, 32, true, false, 0, T, true>, std::true_type{});
-            }
-            if (direct) {
-            } else
-            if (p <= 18 && yc && !(nq_env && nq_env[0] == '0')) launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 1, T>);
-            else if (p <= 22 && yc && !(nq_env && nq_env[0] == '0')) launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 2, T>);
-            else if (p <= 24 && (yc || !F64)) launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 0, T>);
-            else if (p <= 24) {
-                if constexpr (F64) launch_paired(grouped_mid_stream_kernel<2, 24, true, false>);
-            } else if (p <= 30 && yc) launch_paired(grouped_mid_stream_kernel<2, 32, true, true, 0, T>);
-            else launch_paired(grouped_mid_stream_kernel<2, 32, true, false, 0, T>);
-        } else if constexpr (F64) {
-            if (p <= 24) launch(grouped_mid_stream_kernel<2, 24>);
-            else launch(grouped_mid_stream_kernel<2, 32>);
-        }
-        if (!paired_lds_ok) return PDS_ERR_UNSUPPORTED;  // (a device that does not grant a workgroup the whole LDS: the record pipeline)
+        constexpr std::true_type direct{};
+        constexpr std::false_type images{};
+        // width -> kernel: the ones and the target as columns of the second block while they fit (a quad to 18 features, an octet to 22,
+        // the block of 24 or 32 columns to 30), beside the blocks at 31 / 32 -- where f32 frames keep the LDS form
+        bool ok;
+        if (p <= 18) ok = launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 1, T, true>, direct);
+        else if (p <= 22) ok = launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 3, T, true>, direct);
+        else if (p <= 24) ok = launch_paired(grouped_mid_stream_kernel<2, 24, true, true, 0, T, true>, direct);
+        else if (p <= 30) ok = launch_paired(grouped_mid_stream_kernel<2, 32, true, true, 0, T, true>, direct);
+        else if constexpr (F64) ok = launch_paired(grouped_mid_stream_kernel<2, 32, true, false, 0, T, true>, direct);
+        else ok = launch_paired(grouped_mid_stream_kernel<2, 32, true, false, 0, T, false>, images);
+        if (!ok) return PDS_ERR_UNSUPPORTED;  // (a device that does not grant a workgroup the whole LDS: the record pipeline)
         PDS_HIP_CHECK(hipGetLastError());
     }
     // the groups cut by wave boundaries: compacted, then the record solver

@@ -1477,6 +1477,60 @@ def test_grouped_mid_fused_f32_frames(pds, orc, f32, p, bias):
     assert np.max(np.linalg.norm(co[ok] - co_t[ok], axis=1) / np.linalg.norm(co_t[ok], axis=1)) < F32_TOL
 
 
+def _dispatch_boundary_frame(p, dtype):
+    """~400 groups of 3 .. 6 rows per coefficient, one group longer than a wave's range, every 89th group empty, four groups with
+    fewer rows than coefficients (the only nulls: ordinary groups are far from the rank gate)."""
+    rng = np.random.default_rng(8300 + p)
+    pp = p + 1
+    sizes = rng.integers(3 * pp, 6 * pp, size=400)
+    sizes[200] = 3000
+    sizes[::89] = 0
+    sizes[3::101] = rng.integers(1, pp, size=len(sizes[3::101]))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    N = int(off[-1])
+    X = (rng.normal(size=(N, p)) + rng.normal(size=p) * 0.3).astype(dtype)
+    y = (X.astype(np.float64) @ rng.normal(size=p) + 0.6 + 0.2 * rng.normal(size=N)).astype(dtype)
+    return X, y, off, sizes
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("p", [18, 19, 23, 25, 31])
+def test_grouped_mid_fused_dispatch_boundaries(pds, orc, p, dtype):
+    """The fused fit picks its kernel by width: a quad of extra columns up to 18 features, an octet up to 22, 24 columns up to 24, 32
+    columns with the ones and the target among them up to 30, and the target beside 32 columns at 31 / 32.  One width on the far side
+    of every boundary (18 | 19, 22 | 23, 24 | 25, 30 | 31), both precisions, bias on: a width sent to its neighbour's kernel has no
+    room for its last columns.  The fused form must answer (route 1), with the oracle's nulls and coefficients."""
+    X, y, off, sizes = _dispatch_boundary_frame(p, dtype)
+    G, pp = len(sizes), p + 1
+    f32 = dtype == np.float32
+    kw = dict(singular_x_tol=1e-10) if f32 else {}
+    pds.config.LIN_REG_EXPR_F64 = not f32
+    try:
+        co, nu = pds.lin_reg_by(*cols_of(X), target=dev(y), group_offsets=off, add_bias=True, **kw)
+    finally:
+        pds.config.LIN_REG_EXPR_F64 = True
+    assert co.element_size() == (4 if f32 else 8)
+    from polars_ds_extension_amd import _lib
+    assert _lib.load().pds_debug_last_grouped_route() == 1
+    co, nu = co.cpu().numpy().astype(np.float64), nu.cpu().numpy().astype(bool)
+    X64, y64 = X.astype(np.float64), y.astype(np.float64)  # (f32 frames: the f64 truth of the same f32 frame)
+    co_o, nu_o = orc.grouped_lr([y64] + [X64[:, j] for j in range(p)], off, add_bias=True, nthreads=4, **(dict(tol=1e-10) if f32 else {}))
+    assert np.array_equal(nu_o, sizes < pp) and nu_o.sum() == 9   # five empty groups, four short ones
+    assert np.array_equal(nu, nu_o), (nu.sum(), nu_o.sum(), np.flatnonzero(nu != nu_o)[:10])
+    ok = ~nu
+    err = np.linalg.norm(co[ok] - co_o[ok], axis=1) / np.linalg.norm(co_o[ok], axis=1)
+    print(f"p {p} {'f32' if f32 else 'f64'}: rows {int(off[-1])}, max err {err.max():.3e}, giant group {err[np.flatnonzero(ok) == 200][0]:.3e}")
+    if f32:
+        assert err.max() < F32_TOL, err.max()
+        return
+    worst = 0.0
+    for g in np.flatnonzero(ok)[np.argsort(err)[-6:]]:  # (as the neighbouring tests: 64 eps cond(X'X) where that exceeds 1e-10)
+        Xb = np.c_[X[off[g]: off[g + 1]], np.ones(int(sizes[g]))]
+        bound = max(F64_TOL, 64 * 2.2e-16 * np.linalg.cond(Xb.T @ Xb))
+        worst = max(worst, float(err[np.flatnonzero(ok) == g][0] / bound))
+    assert worst < 1.0, (worst, err.max())
+
+
 def test_grouped_mid_fused_falls_back_when_the_marked_list_overflows(pds, orc):
     """More suspect systems than the fused form keeps records for (8192): the record pipeline answers the call.  (Suspect since the rule
     of round 4 = one pivot below 1e-5 of its diagonal: every group carries a nearly collinear pair of columns.)"""
