@@ -647,6 +647,34 @@ int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null);
 /*
+ * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
+ * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on
+ * chip by the one-sided Jacobi iteration of the single-system call, singular values below the cut are dropped, the coefficients are
+ * the minimum-norm solution (grouped_rcond.hip: one wave per group, one pass over its rows).
+ * cols = [y, x1..xp], 1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED); f32 frames are fitted in f64 arithmetic.
+ * rcond is the caller's value (kwargs.tol); the floor of pl_lr_w_rcond is applied per group with the group's own row count:
+ * rcond_g = max(rcond, eps_T * max(n_g, p')), eps_T the epsilon of the frame type.
+ * Outputs, `space`-resident: coeffs and singular_values [n_groups][n_feat + add_bias] (bias last; singular values descending),
+ * is_null [n_groups] bytes: 1 (NaN coefficients and singular values) for a group whose offsets leave the frame (nothing is read), a
+ * group with fewer rows than coefficients, a group with a non-finite entry in its moments (the single-system call answers
+ * "SVD failed.") and a group whose final coefficients are not all finite (the all-zero system); a bad group never changes another
+ * group's bits.  Two calls give the same bits, and a group's bits do not depend on its place in the frame.
+ * By key: int64 keys in any row order, groups returned in ascending key order (ordered keys: nothing moves; unordered keys: sort +
+ * gather); *n_groups receives the number of distinct keys, also when it exceeds max_groups (PDS_ERR_INVALID, nothing fitted).
+ */
+int pds_lr_rcond_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, double l2_reg, double rcond, double* coeffs,
+                             double* singular_values, uint8_t* is_null);
+int pds_lr_rcond_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, float l2_reg, float rcond, float* coeffs,
+                             float* singular_values, uint8_t* is_null);
+int pds_lr_rcond_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, double l2_reg, double rcond, int64_t max_groups, int64_t* out_keys, double* coeffs,
+                            double* singular_values, uint8_t* is_null, int64_t* n_groups);
+int pds_lr_rcond_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, float l2_reg, float rcond, int64_t max_groups, int64_t* out_keys, float* coeffs,
+                            float* singular_values, uint8_t* is_null, int64_t* n_groups);
+/*
  * pds_mixed_reml_grouped_* / pds_mixed_reml_by_key_* / pds_mixed_profile_grouped_*: the random-intercept linear mixed model
  * y = X beta + Z u + e, u ~ N(0, sigma_g^2 I), e ~ N(0, sigma_e^2 I), fitted by REML as fit_reml does (src/linear/mixed/mod.rs:173-272):
  * golden section over gamma = sigma_g^2 / sigma_e^2 in [0, 1e6] on the profiled deviance

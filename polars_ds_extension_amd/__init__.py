@@ -34,6 +34,8 @@ from .lstsq import (  # noqa: F401
     lin_reg_from_moments,
     lin_reg_report,
     lin_reg_w_rcond,
+    lin_reg_w_rcond_by,
+    lin_reg_w_rcond_by_key,
     mixed_reml,
     mixed_reml_profile,
     query_ar_coeffs,

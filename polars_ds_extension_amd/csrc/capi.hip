@@ -28,6 +28,7 @@ namespace pds {
 #include "capi_rolling.hpp"
 #include "capi_models.hpp"
 #include "capi_glm_grouped.hpp"
+#include "capi_rcond_grouped.hpp"
 #include "capi_mixed.hpp"
 
 }  // namespace pds
@@ -344,6 +345,31 @@ int pds_lr_rcond_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t
                      int add_bias, float l2_reg, float rcond, float* coeffs, float* singular_values) {
     return pds::lr_rcond_impl<float>(ctx, cols, n_feat, n_rows, space, add_bias, (double)l2_reg, (double)rcond, coeffs,
                                      singular_values);
+}
+
+int pds_lr_rcond_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, double l2_reg, double rcond, double* coeffs,
+                             double* singular_values, uint8_t* is_null) {
+    return pds::rcond_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, l2_reg, rcond, coeffs,
+                                           singular_values, is_null);
+}
+int pds_lr_rcond_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, float l2_reg, float rcond, float* coeffs,
+                             float* singular_values, uint8_t* is_null) {
+    return pds::rcond_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, l2_reg, rcond, coeffs,
+                                          singular_values, is_null);
+}
+int pds_lr_rcond_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, double l2_reg, double rcond, int64_t max_groups, int64_t* out_keys, double* coeffs,
+                            double* singular_values, uint8_t* is_null, int64_t* n_groups) {
+    return pds::rcond_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, l2_reg, rcond, max_groups, out_keys, coeffs,
+                                          singular_values, is_null, n_groups);
+}
+int pds_lr_rcond_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, float l2_reg, float rcond, int64_t max_groups, int64_t* out_keys, float* coeffs,
+                            float* singular_values, uint8_t* is_null, int64_t* n_groups) {
+    return pds::rcond_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, l2_reg, rcond, max_groups, out_keys, coeffs,
+                                         singular_values, is_null, n_groups);
 }
 
 int pds_lin_reg_report_f64(pds_ctx* ctx, const double* const* cols, const double* weights, int n_feat,

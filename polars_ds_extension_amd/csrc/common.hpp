@@ -325,6 +325,12 @@ int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bi
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
                           const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm);
+// ---- grouped_rcond.hip: lin_reg_w_rcond per group, one wave per group: Gram, one-sided Jacobi of X'X (+ l2_reg) and the minimum-norm
+// solve on chip; 1 .. 16 features.  d_coeffs / d_svals [n_groups][p'] (bias last; singular values descending), d_null [n_groups].
+// rcond is the caller's value: the floor eps_T max(n_g, p') is applied per group.
+template <typename T>
+int launch_grouped_rcond(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                         int64_t n_groups, double l2_reg, double rcond, T* d_coeffs, T* d_svals, uint8_t* d_null);
 // ---- mixed.hip: the random-intercept mixed model's passes (capi_mixed.hpp).  One record layout for the scatter partials and the
 // per-gamma sums (doubles): [0,256) the 16 x 16 feature block [i * 16 + j]; [256,272) the y column; [272,288) sum c m_f (profile
 // only); 288 the y diagonal; 289 sum c; 290 sum c m_y; 291 sum ln(1 + gamma n_g)

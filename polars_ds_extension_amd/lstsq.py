@@ -22,7 +22,7 @@ from . import _lib, config
 __all__ = [
     "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
     "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "logistic_reg", "mixed_reml", "mixed_reml_profile",
-    "recursive_lin_reg", "lin_reg_w_rcond", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
+    "recursive_lin_reg", "lin_reg_w_rcond", "lin_reg_w_rcond_by", "lin_reg_w_rcond_by_key", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
 
@@ -415,6 +415,70 @@ def lin_reg_w_rcond(*x, target, add_bias: bool = False, rcond: float = 0.0, l2_r
     _lib.check(fn(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(bool(add_bias)), real(l2_reg), real(rc),
                   C.c_void_p(coeffs.ctypes.data), C.c_void_p(sv.ctypes.data)))
     return coeffs, sv
+
+
+def _rcond_by_check(x, what):
+    if len(x) < 1:
+        raise ValueError(f"{what}: need at least one feature column")
+    if len(x) > 16:
+        raise NotImplementedError("grouped lin_reg_w_rcond: up to 16 feature columns")
+
+
+def _real_args(*values):
+    real = C.c_double if config.LIN_REG_EXPR_F64 else C.c_float
+    return [real(float(v)) for v in values]
+
+
+def lin_reg_w_rcond_by(*x, target, group_offsets, add_bias: bool = False, rcond: float = 0.0, l2_reg: float = 0.0,
+                       ctx: Context | None = None):
+    """
+    `lin_reg_w_rcond` per group in one call: for every group g = rows [group_offsets[g], group_offsets[g+1]) what `lin_reg_w_rcond`
+    computes on g's rows alone -- X'X (+ l2_reg) decomposed on chip, singular values below the cut dropped, the minimum-norm
+    coefficients (`pds_lr_rcond_grouped_*`, one wave per group).  The cut of a group is max(rcond, eps * max(n_g, p')) with the
+    group's own row count.  1 .. 16 feature columns.
+    Returns (coeffs [G, p'] bias last, singular_values [G, p'] descending, is_null [G]) in the memory space of the inputs.  A group
+    with fewer rows than coefficients, with NaN / inf in its rows, or whose coefficients do not end finite (the all-zero system) is
+    null: is_null = 1, NaN coefficients and singular values.
+    """
+    _rcond_by_check(x, "lin_reg_w_rcond_by")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    off, off_p = _offsets_arg(cols, group_offsets)
+    ng = int(off.shape[0]) - 1
+    coeffs, co_p = _out_like(cols, (ng, pp))
+    sv, sv_p = _out_like(cols, (ng, pp))
+    nulls, nu_p = _out_u8(cols, ng)
+    _lib.check(ctx.fn("pds_lr_rcond_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
+                                              int(bool(add_bias)), *_real_args(l2_reg, rcond), co_p, sv_p, nu_p))
+    return coeffs, sv, nulls
+
+
+def lin_reg_w_rcond_by_key(*x, target, key, add_bias: bool = False, rcond: float = 0.0, l2_reg: float = 0.0,
+                           max_groups: int | None = None, ctx: Context | None = None):
+    """
+    `lin_reg_w_rcond_by` for an integer key column in ANY row order (`pds_lr_rcond_by_key_*`): the frame is brought into key order on
+    the device (nothing moves when the keys are already non-decreasing) and every group is fitted.
+    Returns (keys [G] ascending, coeffs, singular_values, is_null).
+    """
+    _rcond_by_check(x, "lin_reg_w_rcond_by_key")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    k, k_p = _key_arg(cols, key)
+
+    def call(cap, ok_p, ng_p):
+        coeffs, co_p = _out_like(cols, (cap, pp))
+        sv, sv_p = _out_like(cols, (cap, pp))
+        nulls, nu_p = _out_u8(cols, cap)
+        rc = ctx.fn("pds_lr_rcond_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(bool(add_bias)),
+                                           *_real_args(l2_reg, rcond), C.c_int64(cap), ok_p, co_p, sv_p, nu_p, ng_p)
+        return rc, (coeffs, sv, nulls)
+
+    keys, (coeffs, sv, nulls), g = _by_key_retry(cols, max_groups, call)
+    return keys, coeffs[:g], sv[:g], nulls[:g]
 
 
 def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = False, tol: float = 1e-5, max_iter: int = 2000,

@@ -2,7 +2,7 @@
 Polars expression builders that route through libpds_lstsq_hip.so's `_polars_plugin_*` symbols.
 
 Same call signatures as /root/reference/python/polars_ds/exprs/expr_linear.py (`lin_reg` :105-274 incl. the multi-target
-form, `lin_reg_w_rcond` :356-410, `lin_reg_report` :561-631, `rolling_lin_reg` :482-558, `recursive_lin_reg` :413-479) plus the key-aware
+form, `lin_reg_w_rcond` :356-410 (+ `by=` / `lin_reg_w_rcond_by_group`), `lin_reg_report` :561-631, `rolling_lin_reg` :482-558, `recursive_lin_reg` :413-479) plus the key-aware
 `lin_reg(..., by=key)` of SURVEY.md 8(b) and `lin_reg_by_group`, the frame-level replacement of `group_by().agg(lin_reg)`,
 `logistic_reg` (:277-353) and the grouped GLM fits `logistic_reg(..., by=key)` / `glm_by_group`.
 Importing this module needs `polars` (>= 1.4), which is NOT installable in the build image: tests/test_polars_exprs.py runs
@@ -157,11 +157,37 @@ def lin_reg_over(df, by, *x, target, **kwargs):
     return _join(df, lin_reg_by_group(df, by, *x, target=target, **kwargs), on=cols)
 
 
-def lin_reg_w_rcond(*x, target, add_bias: bool = False, rcond: float = 0.0, l2_reg: float = 0.0, null_policy: str = "raise"):
-    """expr_linear.py:356-410: SVD solve with a singular-value cut-off; Struct{coeffs, singular_values}."""
+def lin_reg_w_rcond(*x, target, add_bias: bool = False, rcond: float = 0.0, l2_reg: float = 0.0, null_policy: str = "raise", by=None):
+    """
+    expr_linear.py:356-410: SVD solve with a singular-value cut-off; Struct{coeffs, singular_values}.
+    `by` (an integer key column, any row order, nulls = one group): every group's minimum-norm fit from ONE `pl_lr_w_rcond_by` call --
+    Struct{<key>, coeffs, singular_values} per group, keys ascending, null lists for a null group; the cut of a group is
+    max(rcond, eps * max(n_g, p')) with the group's own row count.  Keys of other dtypes or several key columns:
+    `lin_reg_w_rcond_by_group`.
+    """
     cols = [_formula(target).cast(_dtype())] + [_formula(z) for z in x]
     kwargs = {"bias": add_bias, "null_policy": null_policy, "l1_reg": 0.0, "l2_reg": l2_reg, "solver": "", "tol": abs(rcond)}
+    if by is not None:
+        if len(x) > 16:
+            raise NotImplementedError("grouped lin_reg_w_rcond: up to 16 feature columns")
+        return _plugin("pl_lr_w_rcond_by", [_formula(by), *cols], kwargs, changes_length=True).alias("rcond_by")
     return _plugin("pl_lr_w_rcond", cols, kwargs)
+
+
+def lin_reg_w_rcond_by_group(df, by, *x, target, **kwargs):
+    """
+    The replacement for `df.group_by(by).agg(pds.lin_reg_w_rcond(*x, target=...))` on this backend: ONE plugin call over the whole
+    frame (`lin_reg_w_rcond(..., by=)`) instead of one `pl_lr_w_rcond` call per group.  `by`: one key column of any dtype or a list of
+    key columns; null keys form one group (`lin_reg_by_group`'s conventions).  Returns a frame with one row per distinct key:
+    columns *by, `coeffs` and `singular_values` (null lists for a null group); integer keys come back ascending, other keys in order
+    of first appearance.
+    """
+    if _is_integer_key(df, by):
+        res = df.select(lin_reg_w_rcond(*x, target=target, by=by, **kwargs)).unnest("rcond_by")
+        return res.with_columns(_pl().col(by).cast(df.schema[by]))
+    ids, keys = _with_group_ids(df, by)
+    res = ids.select(lin_reg_w_rcond(*x, target=target, by=_GID, **kwargs)).unnest("rcond_by")
+    return _join(keys, res, on=[_GID]).drop(_GID)
 
 
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None):
