@@ -21,6 +21,7 @@ namespace pds {
 #include "capi_staging.hpp"
 #include "capi_lr.hpp"
 #include "capi_report.hpp"
+#include "capi_staged_out.hpp"
 #include "capi_keyed_frame.hpp"
 #include "capi_grouped.hpp"
 #include "capi_report_grouped.hpp"

@@ -21,8 +21,7 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");  // linear_models.py:756-757
     if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int bias = add_bias ? 1 : 0, pp = n_feat + bias, nc = n_feat + 1;
     const bool host_frame = space == PDS_HOST;
@@ -31,10 +30,18 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     const int64_t long_cap = std::min<int64_t>(n_groups, n_rows / split + 1);
     const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
-    size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)long_cap * 8) + 256;
+    T *d_co, *d_pred;
+    int32_t* d_it;
+    uint8_t *d_nu, *d_rn;
+    StagedOuts outs(host_out, (size_t)n_groups), row_outs(host_out, (size_t)n_rows);
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_it, n_iter, 1);
+    outs.add(&d_nu, is_null, 1);
+    row_outs.add(&d_pred, pred, 1);
+    row_outs.add(&d_rn, row_null, 1);
+    size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)long_cap * 8) + 256 + outs.bytes() + row_outs.bytes();
     if (host_frame) need += col_bytes * nc;
-    if (host_out) need += up((size_t)(n_groups + 1) * 8) + up((size_t)n_groups * pp * sizeof(T)) + up((size_t)n_groups * 4) + up((size_t)n_groups) +
-                          (pred ? col_bytes : 0) + (row_null ? up((size_t)n_rows) : 0);
+    if (host_out) need += up((size_t)(n_groups + 1) * 8);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     // ---- the frame: device pointers in the kernels' order x_0 .. x_{p-1}, y
@@ -48,21 +55,13 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     unsigned* d_count = w.take<unsigned>(64);
     PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
     const int64_t* d_off = offsets;
-    T* d_co = coeffs;
-    int32_t* d_it = n_iter;
-    uint8_t* d_nu = is_null;
-    T* d_pred = pred;
-    uint8_t* d_rn = row_null;
     if (host_out) {
         int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
         PDS_HIP_CHECK(hipMemcpyAsync(t, offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         d_off = t;
-        d_co = w.take<T>((size_t)n_groups * pp);
-        d_it = w.take<int32_t>((size_t)n_groups);
-        d_nu = w.take<uint8_t>((size_t)n_groups);
-        if (pred) d_pred = w.take<T>((size_t)n_rows);
-        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
     }
+    outs.place(w);
+    row_outs.place(w);
     if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
                                         d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap))
         return rc;
@@ -106,11 +105,8 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (hb / hi / hn: sources of the copies)
     }
     if (host_out) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_groups * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(n_iter, d_it, (size_t)n_groups * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)n_groups, hipMemcpyDeviceToHost, ctx->stream));
-        if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
+        if (int rc = staged_copy_back(ctx, outs, (size_t)n_groups)) return rc;
+        if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PDS_OK;
@@ -130,48 +126,33 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
-    KeyOrder ko;
-    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
-    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
-    size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap);
-    if (space == PDS_HOST)
-        need += Bump::up((size_t)cap * pp * sizeof(T)) + Bump::up((size_t)cap * 4) + Bump::up((size_t)cap) + Bump::up((size_t)n_rows * sizeof(T)) +
-                Bump::up((size_t)n_rows);
-    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    const int pp = n_feat + (add_bias ? 1 : 0);
+    T *d_co, *d_pred;
+    int32_t* d_it;
+    uint8_t *d_nu, *d_rn;
+    StagedOuts outs(space == PDS_HOST, (size_t)std::min<int64_t>(max_groups, n_rows)), row_outs(space == PDS_HOST, (size_t)n_rows);
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_it, n_iter, 1);
+    outs.add(&d_nu, is_null, 1);
+    row_outs.add(&d_pred, pred, 1, StagedOuts::kOutRoom);
+    row_outs.add(&d_rn, row_null, 1, StagedOuts::kOutRoom);
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
-    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf)) return rc;
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, max_groups, [&](bool) { return outs.bytes() + row_outs.bytes(); }, n_groups, kf, w))
+        return rc;
     const int64_t ng = kf.ng;
-    T* d_co = coeffs;
-    int32_t* d_it = n_iter;
-    uint8_t* d_nu = is_null;
-    T* d_pred = pred;
-    uint8_t* d_rn = row_null;
-    if (space == PDS_HOST) {
-        d_co = w.take<T>((size_t)cap * pp);
-        d_it = w.take<int32_t>((size_t)cap);
-        d_nu = w.take<uint8_t>((size_t)cap);
-        if (pred) d_pred = w.take<T>((size_t)n_rows);
-        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
-    }
+    outs.place(w);
+    row_outs.place(w);
     if (int rc = glm_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, link, variance, tol, max_iter, d_co,
                                      d_it, d_nu, d_pred, d_rn, kf.d_perm))
         return rc;
     const hipMemcpyKind back = space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, back, ctx->stream));
-    if (space == PDS_HOST) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), back, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(n_iter, d_it, (size_t)ng * 4, back, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)ng, back, ctx->stream));
-        if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), back, ctx->stream));
-        if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, back, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)ng)) return rc;
+    if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }

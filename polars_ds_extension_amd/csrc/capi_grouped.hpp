@@ -109,7 +109,13 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     if (n_feat > 16 && n_feat <= 32) need += grouped_mid_fused_workspace(ctx->num_cus, n_feat, bias) + 512;
     if (big) need += (size_t)n_groups * (n_feat + 1) * sizeof(T*) + moments_wide_workspace(ctx->num_cus, n_feat, n_rows) + 8192;
     if (space == PDS_HOST || !coeffs) need += (size_t)(n_groups + 1) * 8 + (size_t)n_groups * (pp * sizeof(T) + 1) + 4096;
-    if (want_pred && space == PDS_HOST) need += 2 * ((size_t)n_rows * sizeof(T) + 256) + (size_t)n_rows + 256;
+    T *d_pred = nullptr, *d_resid = nullptr;
+    uint8_t* d_rn = nullptr;
+    StagedOuts row_outs(space == PDS_HOST, (size_t)n_rows);  // (declared with the caller's row count: the nullable form has no per-row outputs)
+    row_outs.add(&d_pred, pred, 1);
+    row_outs.add(&d_resid, resid, 1);
+    row_outs.add(&d_rn, row_null, 1);
+    need += row_outs.bytes();
     if (nullable) {
         if (policy < PDS_NULL_RAISE || policy > PDS_NULL_IGNORE) return fail(PDS_ERR_INVALID, "Invalid NullPolicy.");
         need += (1 << 20) + null_policy_workspace(n_feat + 1, n_rows, sizeof(T)) + (size_t)(n_groups + 1) * 8 + 4096;
@@ -259,22 +265,11 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         }
     }
     if (want_pred) {
-        T* d_pred = pred;
-        T* d_resid = resid;
-        uint8_t* d_rn = row_null;
-        if (space == PDS_HOST) {
-            if (pred) d_pred = reinterpret_cast<T*>(ws_take(ctx, (size_t)n_rows * sizeof(T)));
-            if (resid) d_resid = reinterpret_cast<T*>(ws_take(ctx, (size_t)n_rows * sizeof(T)));
-            if (row_null) d_rn = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)n_rows));
-        }
+        row_outs.place([&](size_t b) { return ws_take(ctx, b); });
         if (int rc = launch_grouped_pred<T>(ctx, dc.d_ptrs, n_feat, bias, n_rows, d_off, n_groups, d_coeffs, d_null, nullptr, d_pred,
                                             d_resid, d_rn))
             return rc;
-        if (space == PDS_HOST) {
-            if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            if (resid) PDS_HIP_CHECK(hipMemcpyAsync(resid, d_resid, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
     }
     if (small_out) {
         char* pin = static_cast<char*>(ctx->pinned);
@@ -311,17 +306,23 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
     const int bias = prm->add_bias ? 1 : 0, pf = n_feat + bias, nc_in = n_feat + 1;
     const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
-    size_t need = col_bytes * (pf + 1) + up(sizeof(T*) * (size_t)std::max(nc_in, 18)) + up((size_t)n_groups) + 4096;
-    if (space == PDS_HOST || !coeffs) need += up((size_t)n_groups * pf * sizeof(T));
+    T *d_co = nullptr, *d_pred = nullptr, *d_resid = nullptr;
+    uint8_t *d_nu = nullptr, *d_rn = nullptr;
+    StagedOuts outs(space == PDS_HOST, (size_t)n_groups), row_outs(space == PDS_HOST, (size_t)n_rows);
+    outs.add(&d_co, coeffs, pf, StagedOuts::kScratch);
+    outs.add(&d_nu, is_null, 1, StagedOuts::kScratch);
+    if (want_pred) {
+        row_outs.add(&d_pred, pred, 1, StagedOuts::kOutRoom);
+        row_outs.add(&d_resid, resid, 1, StagedOuts::kOutRoom);
+        row_outs.add(&d_rn, row_null, 1, StagedOuts::kOutRoom);
+    }
+    size_t need = col_bytes * (pf + 1) + up(sizeof(T*) * (size_t)std::max(nc_in, 18)) + outs.bytes() + row_outs.bytes() + 4096;
     if (space == PDS_HOST) need += col_bytes * (nc_in + 1) + up((size_t)(n_groups + 1) * 8);
-    if (want_pred && space == PDS_HOST) need += 2 * col_bytes + up((size_t)n_rows);
     // (its own workspace: pds_lr_by_key_* calls this with its sorted frame living in ctx->keyed)
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     std::vector<const T*> src = frame_cols<T>(cols, n_feat, weights);  // [y, x1..xp, w]
     const int64_t* d_off = offsets;
-    T* d_co = coeffs;
-    uint8_t* d_nu = is_null;
     if (space == PDS_HOST) {
         if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
         int64_t* doff = w.take<int64_t>((size_t)n_groups + 1);
@@ -329,8 +330,7 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
         d_off = doff;
     }
     const T* d_w = src[nc_in];
-    if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)n_groups * pf);
-    if (space == PDS_HOST || !d_nu) d_nu = w.take<uint8_t>((size_t)n_groups);
+    outs.place(w);
     // scaled frame in reference order [y, x1..xp, (sqrt w)]
     std::vector<const T*> scaled(pf + 1);
     for (int c = 0; c < nc_in; ++c) {
@@ -356,26 +356,14 @@ static int grouped_weighted_impl(pds_ctx* ctx, const T* const* cols, const T* we
         std::vector<const T*> tbl;
         const T** d_tbl = nullptr;
         if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
-        T* d_pred = pred;
-        T* d_resid = resid;
-        uint8_t* d_rn = row_null;
-        if (space == PDS_HOST) {
-            if (pred) d_pred = w.take<T>((size_t)n_rows);
-            if (resid) d_resid = w.take<T>((size_t)n_rows);
-            if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
-        }
+        row_outs.place(w);
         if (int rc = launch_grouped_pred<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, d_co, d_nu, d_perm, d_pred, d_resid, d_rn))
             return rc;
-        if (space == PDS_HOST) {
-            if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            if (resid) PDS_HIP_CHECK(hipMemcpyAsync(resid, d_resid, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
     }
     if (space == PDS_HOST) {
-        if (coeffs) PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_groups * pf * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        if (is_null) PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        if (int rc = staged_copy_back(ctx, outs, (size_t)n_groups)) return rc;
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PDS_OK;
@@ -458,6 +446,7 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int nc = n_feat + 1 + (weights ? 1 : 0), pp = n_feat + (prm->add_bias ? 1 : 0);
     const size_t col_bytes = Bump::up((size_t)n_rows * sizeof(T));
+    const bool host = space == PDS_HOST;
     StageTrace tr(ctx, "pds_lr_by_key");
     // ---- keys on the device, and are they already in order?
     // dense-key candidates (unweighted, <= 16 features): the order check takes the partition route's bucket histogram along
@@ -476,12 +465,23 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         return fail(PDS_ERR_UNSUPPORTED, "sliced fit: the slice's keys are not in order");
     }
     const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    // output staging, either route (the same predicates as the take() sites below: a device frame with coeffs but no is_null still takes
-    // its flags here)
-    size_t out_need = 0;
-    if (space == PDS_HOST || !coeffs) out_need += Bump::up((size_t)cap * pp * sizeof(T));
-    if (space == PDS_HOST || !is_null) out_need += Bump::up((size_t)cap);
-    if (want_pred) out_need += Bump::up(sizeof(T*) * (size_t)std::max(nc, 18)) + (space == PDS_HOST ? 2 * col_bytes + Bump::up((size_t)n_rows) : 0);
+    // the outputs, either route.  The fit needs coefficients and null flags whether or not the caller asked for them; the flags go back
+    // to a host caller only together with the coefficients.
+    T *d_co = nullptr, *d_pred = nullptr, *d_resid = nullptr;
+    uint8_t *d_nu = nullptr, *d_rn = nullptr;
+    StagedOuts outs(host, (size_t)cap), row_outs(host, (size_t)n_rows);
+    auto declare_group_outs = [&] {  // (again once a ByKeyPlace has said where the results go)
+        outs = StagedOuts(host, (size_t)cap);
+        outs.add(&d_co, coeffs, pp, StagedOuts::kScratch);
+        outs.add(&d_nu, host && !coeffs ? (uint8_t*)nullptr : is_null, 1, StagedOuts::kScratch);
+    };
+    declare_group_outs();
+    if (want_pred) {
+        row_outs.add(&d_pred, pred, 1, StagedOuts::kOutRoom);
+        row_outs.add(&d_resid, resid, 1, StagedOuts::kOutRoom);
+        row_outs.add(&d_rn, row_null, 1, StagedOuts::kOutRoom);
+    }
+    const size_t out_need = outs.bytes() + row_outs.bytes() + (want_pred ? Bump::up(sizeof(T*) * (size_t)std::max(nc, 18)) : 0);
     std::vector<const T*> tbl;  // (source of a table copy: lives until the last synchronisation)
     const T** d_tbl = nullptr;
     // ---- keys in any order: smallest / largest key decide the route.  Dense integer keys (group ids) of an unweighted
@@ -530,21 +530,11 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         if (n_groups) *n_groups = ng;
         if (rc0) return rc0;
         tr.mark("partition + moments");
-        T* d_co = coeffs;
-        uint8_t* d_nu = is_null;
-        if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)cap * pp);
-        if (space == PDS_HOST || !is_null) d_nu = w.take<uint8_t>((size_t)cap);
+        outs.place(w);
         if (int rc = solve_partition_table<T>(ctx, st, n_feat, ng, d_offsets, prm, d_co, d_nu)) return rc;
         tr.mark("solve");
         if (want_pred) {
-            T* d_pred = pred;
-            T* d_resid = resid;
-            uint8_t* d_rn = row_null;
-            if (space == PDS_HOST) {
-                if (pred) d_pred = w.take<T>((size_t)n_rows);
-                if (resid) d_resid = w.take<T>((size_t)n_rows);
-                if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
-            }
+            row_outs.place(w);
             if (pred_table) {
                 T* d_cbi = w.take<T>(cbi_bytes / sizeof(T));
                 if (int rc = launch_grouped_pred_by_id_table<T>(ctx, d_tbl, n_feat, prm->add_bias ? 1 : 0, n_rows, ko.d_keys, d_part_base, st.ids, ng, d_co,
@@ -554,20 +544,11 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
                                                              d_nu, d_pred, d_resid, d_rn)) {
                 return rc;
             }
-            if (space == PDS_HOST) {
-                if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-                if (resid) PDS_HIP_CHECK(hipMemcpyAsync(resid, d_resid, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-                if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-            }
+            if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
             tr.mark("pred");
         }
-        if (space == PDS_HOST) {
-            if (coeffs) PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            if (coeffs && is_null) PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)ng, hipMemcpyDeviceToHost, ctx->stream));
-            if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (out_keys) {
-            PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        }
+        if (int rc = staged_copy_back(ctx, outs, (size_t)ng)) return rc;
+        if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, d_unique, (size_t)ng * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         tr.mark("results D2H");
         return PDS_OK;
@@ -581,20 +562,12 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
     kf.src = frame_cols<T>(cols, n_feat, weights);
     if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf, &tr)) return rc;
     const int64_t ng = kf.ng;
-    if (place)
+    if (place) {
         if (int rc = place->at(ng, &out_keys, &coeffs, &is_null)) return rc;
-    T* d_co = coeffs;
-    uint8_t* d_nu = is_null;
-    if (space == PDS_HOST || !coeffs) d_co = w.take<T>((size_t)cap * pp);
-    if (space == PDS_HOST || !is_null) d_nu = w.take<uint8_t>((size_t)cap);
-    T* d_pred = pred;
-    T* d_resid = resid;
-    uint8_t* d_rn = row_null;
-    if (want_pred && space == PDS_HOST) {
-        if (pred) d_pred = w.take<T>((size_t)n_rows);
-        if (resid) d_resid = w.take<T>((size_t)n_rows);
-        if (row_null) d_rn = w.take<uint8_t>((size_t)n_rows);
+        declare_group_outs();
     }
+    outs.place(w);
+    row_outs.place(w);
     if (weights) {
         if (int rc = grouped_weighted_impl<T>(ctx, kf.src.data(), kf.src[n_feat + 1], n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, prm, d_co, d_nu,
                                               d_pred, d_resid, d_rn, kf.d_perm))
@@ -610,16 +583,9 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         }
     }
     tr.mark("grouped fit");
-    if (space == PDS_HOST) {
-        if (coeffs) PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        if (coeffs && is_null) PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)ng, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (pred) PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pred, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        if (resid) PDS_HIP_CHECK(hipMemcpyAsync(resid, d_resid, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        if (row_null) PDS_HIP_CHECK(hipMemcpyAsync(row_null, d_rn, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    } else if (out_keys) {
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)ng)) return rc;
+    if (out_keys) PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     tr.mark("results D2H");
     return PDS_OK;

@@ -1,5 +1,6 @@
 // capi_keyed_frame.hpp -- an int64 key column in any row order + a frame -> contiguous groups in ascending key order: the stage every
-// by-key entry point starts with (pds_lr_by_key*, pds_*_report_by_key*, pds_{rolling,recursive}_lr_by_key*, pds_glm_irls_by_key*)
+// by-key entry point starts with (pds_lr_by_key*, pds_*_report_by_key*, pds_{rolling,recursive}_lr_by_key*, pds_glm_irls_by_key*,
+// pds_lr_rcond_by_key*, pds_mixed_reml_by_key*), and the host-side pieces the grouped pipelines share
 // Part of the one translation unit capi.hip (included there, inside namespace pds, in dependency order): the entry-point
 // pipelines are templates with internal linkage, split by concern, not by compilation unit.
 //
@@ -7,19 +8,39 @@
 //   A  keyed_order_check: keys on the device, one pass for order flag, key range and the run marks of an ordered column
 //   B  keyed_frame_bytes + keyed_frame_build: the caller adds its own output staging to the bytes, calls ensure_ws(ctx->keyed) ONCE
 //      (it may move the block) and hands the build a Bump over that block, from which it goes on taking its own slices afterwards
+// keyed_frame_open is A and B in one call, for every caller that picks no route between them.
+//
+// Outputs that may live on the host are declared once in a StagedOuts (capi_staged_out.hpp: bytes, device pointers) and come back
+// through staged_copy_back; host_offsets and check_cols are the offsets fetch and the column check of the contiguous-group forms.
 #pragma once
 
-// slices of a workspace block in order, each rounded up to 256 bytes
-struct Bump {
-    char* p;
-    static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
-    template <typename U>
-    U* take(size_t count) {
-        char* r = p;
-        p += up(count * sizeof(U));
-        return reinterpret_cast<U*>(r);
-    }
-};
+// every staged output the caller gave a host buffer for: `units` units of it back to the caller (asynchronous, no synchronisation)
+static int staged_copy_back(pds_ctx* ctx, const StagedOuts& so, size_t units) {
+    for (int i = 0; i < so.n; ++i)
+        if (so.outs[i].back)
+            PDS_HIP_CHECK(hipMemcpyAsync(so.outs[i].user, so.dev(i), units * so.outs[i].unit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return PDS_OK;
+}
+
+// group offsets where the host can read them: device offsets are fetched into `store` (one copy + a synchronisation), host offsets
+// are the caller's own.  Validation is the caller's (the rules and their messages differ).
+static int host_offsets(pds_ctx* ctx, const int64_t* offsets, int64_t n_groups, pds_space space, std::vector<int64_t>& store, const int64_t*& h_off) {
+    h_off = offsets;
+    if (space == PDS_HOST) return PDS_OK;
+    store.resize((size_t)n_groups + 1);
+    PDS_HIP_CHECK(hipMemcpyAsync(store.data(), offsets, store.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    h_off = store.data();
+    return PDS_OK;
+}
+
+// every column [y, x1..xp] of the frame is there
+template <typename T>
+static int check_cols(const T* const* cols, int n_feat) {
+    for (int c = 0; c <= n_feat; ++c)
+        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    return PDS_OK;
+}
 
 // reference order [y, x1..xp (, w)]: a weight column rides through the staging, the sort and the gather as one more column
 template <typename T>
@@ -176,4 +197,21 @@ static int keyed_frame_build(pds_ctx* ctx, const KeyOrder& ko, Bump& w, int64_t 
     if (n_groups) *n_groups = kf.ng;
     if (kf.ng > max_groups) return fail(PDS_ERR_INVALID, "more distinct keys than max_groups");
     return PDS_OK;
+}
+
+// Steps A and B in one call.  kf.src holds the caller's columns (frame_cols).  max_groups: the caller's bound, n_rows for none.
+// extra_bytes(sorted): what the caller's own slices need behind the frame (its staged outputs), asked once the order of the keys is
+// known.  `w` is left behind the frame for those slices.  *n_groups (nullable) is written before the max_groups failure, as in
+// keyed_frame_build.
+template <typename T, typename ExtraBytes>
+static int keyed_frame_open(pds_ctx* ctx, const int64_t* keys, int64_t n_rows, pds_space space, int64_t max_groups, ExtraBytes extra_bytes,
+                            int64_t* n_groups, KeyedFrame<T>& kf, Bump& w) {
+    KeyOrder ko;
+    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
+    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
+    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
+    const size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, (int)kf.src.size(), space, run_cap) + extra_bytes(ko.sorted);
+    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
+    w = Bump{static_cast<char*>(ctx->keyed.ptr)};
+    return keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf);
 }

@@ -130,19 +130,13 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "mixed model: up to 16 feature columns");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int p = n_feat, nc = p + 1, q = p + 2;
     // ---- the offsets on the host: row counts, validation, the chunks of the long groups
     std::vector<int64_t> off_copy;
-    const int64_t* h_off = offsets;
-    if (space != PDS_HOST) {
-        off_copy.resize((size_t)n_groups + 1);
-        PDS_HIP_CHECK(hipMemcpyAsync(off_copy.data(), offsets, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        h_off = off_copy.data();
-    }
+    const int64_t* h_off = nullptr;
+    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_mixed_split_rows > 0 ? ctx->opt_mixed_split_rows : kMixedSplitRowsDefault, 64);
     if (h_off[0] < 0 || h_off[n_groups] > n_rows) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
     int64_t n_obs = 0, n_nonempty = 0;
@@ -403,18 +397,12 @@ static int mixed_reml_by_key_impl(pds_ctx* ctx, const T* const* cols, const int6
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "mixed model: up to 16 feature columns");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (n_rows <= n_feat + 1) return fail(PDS_ERR_TOO_FEW_ROWS, "Not enough rows to fit a mixed model with this many fixed effects.");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nc = n_feat + 1;
-    KeyOrder ko;
-    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
-    const int64_t run_cap = ko.sorted ? ko.n_runs + 1 : n_rows;
-    if (int rc = ensure_ws(ctx, ctx->keyed, keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap))) return rc;
-    Bump w{static_cast<char*>(ctx->keyed.ptr)};
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
-    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, n_rows, nullptr, kf)) return rc;
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, /*max_groups=*/n_rows, [](bool) { return (size_t)0; }, nullptr, kf, w)) return rc;
     return mixed_reml_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, max_iter, tol, coeffs, std_errors, dfs,
                               gamma_out, resid_variance, n_groups_fit, n_eval);
 }

@@ -12,14 +12,19 @@ static int rcond_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, in
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped lin_reg_w_rcond: up to 16 feature columns");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int bias = add_bias ? 1 : 0, pp = n_feat + bias, nc = n_feat + 1;
     const bool host = space == PDS_HOST;
     const auto up = Bump::up;
-    size_t need = 4096 + up(sizeof(T*) * 18);
-    if (host) need += up((size_t)n_rows * sizeof(T)) * nc + up((size_t)(n_groups + 1) * 8) + 2 * up((size_t)n_groups * pp * sizeof(T)) + up((size_t)n_groups);
+    T *d_co, *d_sv;
+    uint8_t* d_nu;
+    StagedOuts outs(host, (size_t)n_groups);
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_sv, singular_values, pp);
+    outs.add(&d_nu, is_null, 1);
+    size_t need = 4096 + up(sizeof(T*) * 18) + outs.bytes();
+    if (host) need += up((size_t)n_rows * sizeof(T)) * nc + up((size_t)(n_groups + 1) * 8);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     // ---- the frame: device pointers in the kernel's order x_0 .. x_{p-1}, y
@@ -30,24 +35,16 @@ static int rcond_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, in
     const T** d_tbl = nullptr;
     if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
     const int64_t* d_off = offsets;
-    T *d_co = coeffs, *d_sv = singular_values;
-    uint8_t* d_nu = is_null;
     if (host) {
         int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
         PDS_HIP_CHECK(hipMemcpyAsync(t, offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         d_off = t;
-        d_co = w.take<T>((size_t)n_groups * pp);
-        d_sv = w.take<T>((size_t)n_groups * pp);
-        d_nu = w.take<uint8_t>((size_t)n_groups);
     }
+    outs.place(w);
     if (int rc = launch_grouped_rcond<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, l2_reg > (T)0 ? (double)l2_reg : 0.0, (double)rcond,
                                          d_co, d_sv, d_nu))
         return rc;
-    if (host) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_groups * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(singular_values, d_sv, (size_t)n_groups * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)n_groups, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)n_groups)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
     return PDS_OK;
 }
@@ -63,38 +60,26 @@ static int rcond_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* 
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped lin_reg_w_rcond: up to 16 feature columns");
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
-    for (int c = 0; c <= n_feat; ++c)
-        if (!cols[c]) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
-    KeyOrder ko;
-    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
-    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
-    size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap);
-    if (space == PDS_HOST) need += 2 * Bump::up((size_t)cap * pp * sizeof(T)) + Bump::up((size_t)cap);
-    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    const int pp = n_feat + (add_bias ? 1 : 0);
+    T *d_co, *d_sv;
+    uint8_t* d_nu;
+    StagedOuts outs(space == PDS_HOST, (size_t)std::min<int64_t>(max_groups, n_rows));
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_sv, singular_values, pp);
+    outs.add(&d_nu, is_null, 1);
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
-    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf)) return rc;
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, max_groups, [&](bool) { return outs.bytes(); }, n_groups, kf, w)) return rc;
     const int64_t ng = kf.ng;
-    T *d_co = coeffs, *d_sv = singular_values;
-    uint8_t* d_nu = is_null;
-    if (space == PDS_HOST) {
-        d_co = w.take<T>((size_t)cap * pp);
-        d_sv = w.take<T>((size_t)cap * pp);
-        d_nu = w.take<uint8_t>((size_t)cap);
-    }
+    outs.place(w);
     if (int rc = rcond_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, l2_reg, rcond, d_co, d_sv, d_nu))
         return rc;
     const hipMemcpyKind back = space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, back, ctx->stream));
-    if (space == PDS_HOST) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)ng * pp * sizeof(T), back, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(singular_values, d_sv, (size_t)ng * pp * sizeof(T), back, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_nu, (size_t)ng, back, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)ng)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }

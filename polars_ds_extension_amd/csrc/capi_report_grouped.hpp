@@ -21,6 +21,22 @@ struct ReportGroupedOut {  // the layout of pds_report_grouped_f64 / _f32
     uint8_t* is_null;
 };
 
+// the nine outputs of a grouped report, `cap` groups of room: `d` receives the device pointers
+template <typename T>
+static StagedOuts report_staged_outs(const ReportGroupedOut<T>& out, ReportGroupedOut<T>& d, pds_space space, int64_t cap, int pp) {
+    StagedOuts so(space == PDS_HOST, (size_t)cap);
+    so.add(&d.beta, out.beta, pp);
+    so.add(&d.std_err, out.std_err, pp);
+    so.add(&d.t, out.t, pp);
+    so.add(&d.p, out.p, pp);
+    so.add(&d.ci_lower, out.ci_lower, pp);
+    so.add(&d.ci_upper, out.ci_upper, pp);
+    so.add(&d.r2, out.r2, 1);
+    so.add(&d.adj_r2, out.adj_r2, 1);
+    so.add(&d.is_null, out.is_null, 1);
+    return so;
+}
+
 // t quantile and ln-gamma term per distinct dof = n_g - p' of the non-null groups (host functions, once each)
 template <typename T>
 static int report_dof_table(pds_ctx* ctx, const int64_t* off, int64_t n_groups, int pp, std::vector<double>& dense,
@@ -93,13 +109,8 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weig
     const int hc = (se_type == PDS_SE) ? 0 : (se_type == PDS_HC2 ? 2 : (se_type == PDS_HC3 ? 3 : 1));
     // the offsets on the host: validated (the kernels index rows with them) and the source of the dof table
     std::vector<int64_t> h_off_store;
-    const int64_t* h_off = offsets;
-    if (space == PDS_DEVICE) {
-        h_off_store.resize((size_t)n_groups + 1);
-        PDS_HIP_CHECK(hipMemcpyAsync(h_off_store.data(), offsets, h_off_store.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        h_off = h_off_store.data();
-    }
+    const int64_t* h_off = nullptr;
+    if (int rc = host_offsets(ctx, offsets, n_groups, space, h_off_store, h_off)) return rc;
     if (h_off[0] < 0 || h_off[n_groups] > n_rows) return fail(PDS_ERR_INVALID, "group offsets outside the frame");
     for (int64_t g = 0; g < n_groups; ++g)
         if (h_off[g + 1] < h_off[g]) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing");
@@ -132,11 +143,10 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weig
     if (hc) need += up((size_t)slots * pp * pp * 8);
     // pass 1 of split groups: one Gram record per piece (virtual groups), summed back per group
     if (max_pieces > 0) need += up(sizeof(T) * (size_t)slots * q * q) + up((size_t)(slots + 1) * 8) + up((size_t)(chunk + 1) * 8);
-    if (space == PDS_HOST) {
-        need += up((size_t)(n_groups + 1) * 8) + 6 * up((size_t)n_groups * pp * sizeof(T)) + 2 * up((size_t)n_groups * sizeof(T)) +
-                up((size_t)n_groups);
-        if (y_var) need += up((size_t)n_groups * sizeof(T));
-    }
+    ReportGroupedOut<T> d;
+    StagedOuts outs = report_staged_outs<T>(*out, d, space, n_groups, pp);
+    need += outs.bytes();
+    if (space == PDS_HOST) need += up((size_t)(n_groups + 1) * 8) + (y_var ? up((size_t)n_groups * sizeof(T)) : 0);
     if (int rc = ws_reserve(ctx, need)) return rc;
     DeviceCols<T> dc;
     if (int rc = make_device_cols<T>(ctx, cols, weights, p, n_rows, space, dc)) return rc;
@@ -145,15 +155,10 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weig
     auto take = [&](size_t b) { void* r = ws_take(ctx, b); if (!r) ws_ok = false; return r; };
     const int64_t* d_off = offsets;
     const T* d_yv = y_var;
-    ReportGroupedOut<T> d = *out;
     if (space == PDS_HOST) {
         int64_t* o = reinterpret_cast<int64_t*>(take((size_t)(n_groups + 1) * 8));
         if (y_var) d_yv = reinterpret_cast<const T*>(take((size_t)n_groups * sizeof(T)));
-        T** vec[6] = {&d.beta, &d.std_err, &d.t, &d.p, &d.ci_lower, &d.ci_upper};
-        for (T** v : vec) *v = reinterpret_cast<T*>(take((size_t)n_groups * pp * sizeof(T)));
-        d.r2 = reinterpret_cast<T*>(take((size_t)n_groups * sizeof(T)));
-        d.adj_r2 = reinterpret_cast<T*>(take((size_t)n_groups * sizeof(T)));
-        d.is_null = reinterpret_cast<uint8_t*>(take((size_t)n_groups));
+        outs.place(take);
         if (!ws_ok) return fail(PDS_ERR_HIP, "workspace allocation failed");
         PDS_HIP_CHECK(hipMemcpyAsync(o, offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         if (y_var) PDS_HIP_CHECK(hipMemcpyAsync(const_cast<T*>(d_yv), y_var, (size_t)n_groups * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
@@ -228,18 +233,7 @@ static int report_grouped_impl(pds_ctx* ctx, const T* const* cols, const T* weig
                                                        d.is_null + g0, weighted))
             return rc;
     }
-    if (space == PDS_HOST) {
-        const size_t cb = (size_t)n_groups * pp * sizeof(T);
-        PDS_HIP_CHECK(hipMemcpyAsync(out->beta, d.beta, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->std_err, d.std_err, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->t, d.t, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->p, d.p, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->ci_lower, d.ci_lower, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->ci_upper, d.ci_upper, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->r2, d.r2, (size_t)n_groups * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->adj_r2, d.adj_r2, (size_t)n_groups * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->is_null, d.is_null, (size_t)n_groups, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)n_groups)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (also: the dof table's host vectors are the sources of async copies)
     return PDS_OK;
 }
@@ -257,46 +251,21 @@ static int report_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* weigh
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (se_type < PDS_SE || se_type > PDS_HC3) return fail(PDS_ERR_INVALID, "unknown standard-error type");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    // (a weight column rides through the staging, the sort and the gather as one more column of the frame: kf.src[nc - 1])
-    const int nc = n_feat + 1 + (weights ? 1 : 0), pp = n_feat + (add_bias ? 1 : 0);
-    KeyOrder ko;
-    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
-    const int64_t cap = std::min<int64_t>(max_groups, n_rows);
-    const int64_t run_cap = ko.sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
-    size_t need = keyed_frame_bytes<T>(ko.sorted, n_rows, nc, space, run_cap);
-    if (space == PDS_HOST) need += 6 * Bump::up((size_t)cap * pp * sizeof(T)) + 2 * Bump::up((size_t)cap * sizeof(T)) + Bump::up((size_t)cap);
-    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    // (a weight column rides through the staging, the sort and the gather as one more column of the frame: kf.src[n_feat + 1])
+    const int pp = n_feat + (add_bias ? 1 : 0);
+    ReportGroupedOut<T> d;
+    StagedOuts outs = report_staged_outs<T>(*out, d, space, std::min<int64_t>(max_groups, n_rows), pp);
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat, weights);
-    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, max_groups, n_groups, kf)) return rc;
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, max_groups, [&](bool) { return outs.bytes(); }, n_groups, kf, w)) return rc;
     const int64_t ng = kf.ng;
-    ReportGroupedOut<T> d = *out;
-    if (space == PDS_HOST) {
-        T** vec[6] = {&d.beta, &d.std_err, &d.t, &d.p, &d.ci_lower, &d.ci_upper};
-        for (T** v : vec) *v = w.take<T>((size_t)cap * pp);
-        d.r2 = w.take<T>((size_t)cap);
-        d.adj_r2 = w.take<T>((size_t)cap);
-        d.is_null = w.take<uint8_t>((size_t)cap);
-    }
+    outs.place(w);
     if (int rc = report_grouped_impl<T>(ctx, kf.src.data(), weights ? kf.src[n_feat + 1] : (const T*)nullptr, n_feat, n_rows, kf.d_offsets, ng,
                                         PDS_DEVICE, add_bias, se_type, (const T*)nullptr, &d))
         return rc;
-    if (space == PDS_HOST) {
-        const size_t cb = (size_t)ng * pp * sizeof(T);
-        PDS_HIP_CHECK(hipMemcpyAsync(out->beta, d.beta, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->std_err, d.std_err, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->t, d.t, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->p, d.p, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->ci_lower, d.ci_lower, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->ci_upper, d.ci_upper, cb, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->r2, d.r2, (size_t)ng * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->adj_r2, d.adj_r2, (size_t)ng * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out->is_null, d.is_null, (size_t)ng, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)ng)) return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }

@@ -26,27 +26,22 @@ static int rolling_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     size_t need = 131072 + ((size_t)(n_rows / 4096) + 2) * 96 * sizeof(double)  // + per-tile totals (expanding)
                   + ((size_t)(n_rows / 4096 / 32) + 2) * 128 * sizeof(double);   // + their chunk sums (tile prefix)
-    if (space == PDS_HOST) need += (size_t)n_rows * ((pp + 1) * sizeof(T) + 1) + 4096;
+    T *d_co, *d_pr;
+    uint8_t* d_va;
+    StagedOuts outs(space == PDS_HOST, (size_t)n_rows);
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_pr, pred, 1);
+    outs.add(&d_va, valid, 1);
+    if (space == PDS_HOST) need += outs.bytes() + 4096;
     if (pp > 12) need += rolling_wide_workspace(n_feat, n_rows, sizeof(T));
     if (int rc = ws_reserve(ctx, need)) return rc;
     DeviceCols<T> dc;
     if (int rc = make_device_cols<T>(ctx, cols, (const T*)nullptr, n_feat, n_rows, space, dc)) return rc;
-    T* d_co = coeffs;
-    T* d_pr = pred;
-    uint8_t* d_va = valid;
-    if (space == PDS_HOST) {
-        d_co = reinterpret_cast<T*>(ws_take(ctx, (size_t)n_rows * pp * sizeof(T)));
-        d_pr = reinterpret_cast<T*>(ws_take(ctx, (size_t)n_rows * sizeof(T)));
-        d_va = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)n_rows));
-    }
+    outs.place([&](size_t b) { return ws_take(ctx, b); });
     if (int rc = launch_rolling<T>(ctx, dc, n_feat, n_rows, add_bias, window, min_size, lambda, expanding,
                                    seed.empty() ? nullptr : seed.data(), d_co, d_pr, d_va))
         return rc;
-    if (space == PDS_HOST) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_rows * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pr, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(valid, d_va, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, outs, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }
@@ -93,13 +88,9 @@ static int rolling_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, 
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int pp = n_feat + (add_bias ? 1 : 0), nc = n_feat + 1;
     // the offsets on the host: validated (the kernels walk rows with them)
-    std::vector<int64_t> h_off((size_t)n_groups + 1);
-    if (space == PDS_DEVICE) {
-        PDS_HIP_CHECK(hipMemcpyAsync(h_off.data(), group_offsets, h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } else {
-        std::copy(group_offsets, group_offsets + n_groups + 1, h_off.begin());
-    }
+    std::vector<int64_t> h_off_store;
+    const int64_t* h_off = nullptr;
+    if (int rc = host_offsets(ctx, group_offsets, n_groups, space, h_off_store, h_off)) return rc;
     if (h_off[0] != 0 || h_off[n_groups] != n_rows) return fail(PDS_ERR_INVALID, "group offsets must start at 0 and end at n_rows");
     for (int64_t g = 0; g < n_groups; ++g)
         if (h_off[g + 1] < h_off[g]) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing");
@@ -113,23 +104,25 @@ static int rolling_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, 
     // host frame: columns, offsets and outputs staged in the keyed workspace (the ws arena belongs to the launch)
     const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
-    const size_t need = col_bytes * nc + up(h_off.size() * 8) + up((size_t)n_rows * pp * sizeof(T)) + col_bytes + up((size_t)n_rows) + 4096;
+    T *d_co, *d_pr;
+    uint8_t* d_va;
+    StagedOuts outs(true, (size_t)n_rows);
+    outs.add(&d_co, coeffs, pp);
+    outs.add(&d_pr, pred, 1);
+    outs.add(&d_va, valid, 1);
+    const size_t need = col_bytes * nc + up((size_t)(n_groups + 1) * 8) + outs.bytes() + 4096;
     if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->keyed.ptr)};
     std::vector<const T*> src = frame_cols<T>(cols, n_feat);
     if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
-    int64_t* d_off = w.take<int64_t>(h_off.size());
-    PDS_HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    T* d_co = w.take<T>((size_t)n_rows * pp);
-    T* d_pr = w.take<T>((size_t)n_rows);
-    uint8_t* d_va = w.take<uint8_t>((size_t)n_rows);
+    int64_t* d_off = w.take<int64_t>((size_t)n_groups + 1);
+    PDS_HIP_CHECK(hipMemcpyAsync(d_off, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    outs.place(w);
     if (int rc = rolling_grouped_device<T>(ctx, src.data(), n_feat, n_rows, d_off, n_groups, add_bias, window, min_size, lambda, expanding,
                                            d_co, d_pr, d_va))
         return rc;
-    PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_rows * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pr, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipMemcpyAsync(valid, d_va, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (h_off: source of an async copy)
+    if (int rc = staged_copy_back(ctx, outs, (size_t)n_rows)) return rc;
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }
 
@@ -143,52 +136,39 @@ static int rolling_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t
     if (!ctx || !cols || !keys || !coeffs || !pred || !valid) return fail(PDS_ERR_INVALID, "null argument");
     if (int rc = check_grouped_window(n_feat, add_bias, n_rows, window, min_size)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nc = n_feat + 1, pp = n_feat + (add_bias ? 1 : 0);
-    KeyOrder ko;
-    if (int rc = keyed_order_check(ctx, keys, n_rows, space, false, -1, ko)) return rc;
-    const bool sorted = ko.sorted;
-    const int64_t run_cap = sorted ? ko.n_runs + 1 : n_rows;  // (no max_groups here)
-    size_t need = keyed_frame_bytes<T>(sorted, n_rows, nc, space, run_cap);
-    const bool stage_out = space == PDS_HOST || !sorted;  // outputs through the workspace (host frame, or scattered back)
-    const size_t out_bytes = Bump::up((size_t)n_rows * pp * sizeof(T)) + Bump::up((size_t)n_rows * sizeof(T)) + Bump::up((size_t)n_rows);
-    if (stage_out) need += out_bytes;
-    if (!sorted && space == PDS_HOST) need += out_bytes;  // the scatter's target
-    if (int rc = ensure_ws(ctx, ctx->keyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->keyed.ptr)};
+    const int pp = n_feat + (add_bias ? 1 : 0);
+    const bool host = space == PDS_HOST;
+    // the fit's outputs go through the workspace on a host frame and whenever the keys are not in order (they are then scattered
+    // back to frame order: into the caller's buffers on the device, else into a second staged set)
+    T *d_co, *d_pr, *o_co = nullptr, *o_pr = nullptr;
+    uint8_t *d_va, *o_va = nullptr;
+    StagedOuts fit(host, (size_t)n_rows), scattered(host, (size_t)n_rows);
+    bool sorted = true;
+    auto declare = [&](bool keys_sorted) {  // (asked once, when the order check has answered)
+        sorted = keys_sorted;
+        fit = StagedOuts(host, (size_t)n_rows, !sorted);
+        fit.add(&d_co, coeffs, pp);
+        fit.add(&d_pr, pred, 1);
+        fit.add(&d_va, valid, 1);
+        if (sorted) return fit.bytes();
+        scattered.add(&o_co, coeffs, pp);
+        scattered.add(&o_pr, pred, 1);
+        scattered.add(&o_va, valid, 1);
+        return fit.bytes() + scattered.bytes();
+    };
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
-    if (int rc = keyed_frame_build<T>(ctx, ko, w, n_rows, space, run_cap, /*max_groups=*/n_rows, nullptr, kf)) return rc;
-    T* d_co = coeffs;
-    T* d_pr = pred;
-    uint8_t* d_va = valid;
-    if (stage_out) {
-        d_co = w.take<T>((size_t)n_rows * pp);
-        d_pr = w.take<T>((size_t)n_rows);
-        d_va = w.take<uint8_t>((size_t)n_rows);
-    }
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, /*max_groups=*/n_rows, declare, nullptr, kf, w)) return rc;
+    fit.place(w);
     if (int rc = rolling_grouped_device<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, add_bias, window, min_size, lambda, expanding,
                                            d_co, d_pr, d_va))
         return rc;
     if (!sorted) {
-        // back to frame order: in place when the caller's buffers are on the device, else into the staged outputs' own slots
-        T* o_co = coeffs;
-        T* o_pr = pred;
-        uint8_t* o_va = valid;
-        if (space == PDS_HOST) {
-            o_co = w.take<T>((size_t)n_rows * pp);
-            o_pr = w.take<T>((size_t)n_rows);
-            o_va = w.take<uint8_t>((size_t)n_rows);
-        }
+        scattered.place(w);
         if (int rc = launch_rolling_scatter<T>(ctx, d_co, d_pr, d_va, kf.d_perm, n_rows, pp, o_co, o_pr, o_va)) return rc;
-        d_co = o_co;
-        d_pr = o_pr;
-        d_va = o_va;
     }
-    if (space == PDS_HOST) {
-        PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_co, (size_t)n_rows * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(pred, d_pr, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(valid, d_va, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (int rc = staged_copy_back(ctx, sorted ? fit : scattered, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;
 }

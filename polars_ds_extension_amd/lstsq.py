@@ -781,15 +781,7 @@ def lin_reg_by(*x, target, group_offsets, add_bias: bool = False, l1_reg: float 
         _follow(ctx, cols)
         prm = _params(add_bias, 0.0, 0.0, tol, solver, False, max_iter, 0.0)
         pp = cols.n_feat + int(bool(add_bias))
-        if cols.space == _lib.PDS_DEVICE:
-            import torch
-
-            off = group_offsets if _is_torch(group_offsets) else torch.as_tensor(np.asarray(group_offsets))
-            off = off.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-            off_p = C.c_void_p(int(off.data_ptr()))
-        else:
-            off = np.ascontiguousarray(np.asarray(group_offsets), dtype=np.int64)
-            off_p = C.c_void_p(off.ctypes.data)
+        off, off_p = _offsets_arg(cols, group_offsets)
         ng = int(off.shape[0]) - 1
         coeffs, co_p = _out_like(cols, (ng, pp))
         nulls, nu_p = _out_u8(cols, ng)
@@ -823,15 +815,7 @@ def lin_reg_by(*x, target, group_offsets, add_bias: bool = False, l1_reg: float 
     _follow(ctx, cols)
     prm = _params(add_bias, l1_reg, l2_reg, tol, solver, positive, max_iter, singular_x_tol)
     pp = cols.n_feat + int(bool(add_bias))
-    if cols.space == _lib.PDS_DEVICE:
-        import torch
-
-        off = group_offsets if _is_torch(group_offsets) else torch.as_tensor(np.asarray(group_offsets))
-        off = off.to(device=cols.keep[0].device, dtype=torch.int64).contiguous()
-        off_p = C.c_void_p(int(off.data_ptr()))
-    else:
-        off = np.ascontiguousarray(np.asarray(group_offsets), dtype=np.int64)
-        off_p = C.c_void_p(off.ctypes.data)
+    off, off_p = _offsets_arg(cols, group_offsets)
     ng = int(off.shape[0]) - 1
     coeffs, co_p = _out_like(cols, (ng, pp))
     nulls, nu_p = _out_u8(cols, ng)
