@@ -8,7 +8,8 @@
  * linear_regression_f32.rs) would bind over `extern "C"` after unwrapping the Arrow column buffers.
  * They replace the calls those functions make into src/linear/lr/lr_solvers.rs and
  * src/linear/online_lr/lr_online_solvers.rs; pds_glm_irls_* and pds_mixed_reml_* stand behind the pyclasses PyGLM and
- * PyMixedModel (src/linear/glm/glm_solvers.rs, src/linear/mixed/mod.rs).  INTEGRATION.md shows the Rust-side binding.
+ * PyMixedModel (src/linear/glm/glm_solvers.rs, src/linear/mixed/mod.rs); pds_glm_enet_* are their elastic-net penalised fits
+ * (l1_reg / l2_reg of the reference's logistic_reg, expr_linear.py:277-353, for every family, per model and per group).  INTEGRATION.md shows the Rust-side binding.
  *
  * Conventions
  *   - plain pointers and sizes only; no torch / HIP types in any signature.
@@ -646,6 +647,40 @@ int pds_glm_irls_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64
 int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                             int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null);
+/*
+ * pds_glm_enet_* / pds_glm_enet_grouped_* / pds_glm_enet_by_key_*: the elastic-net penalised fits -- the argument lists of their
+ * pds_glm_irls_* twins with l1_reg, l2_reg after `variance`; everything said there holds.  For a frame or group of n rows,
+ * coefficients beta with features j < p and an optional unpenalised bias last, the fit minimises
+ *     F(beta) = (1/n) sum_i l(y_i, eta_i) + (l2_reg / 2) sum_{j<p} beta_j^2 + l1_reg sum_{j<p} |beta_j|,    eta = X beta (+ bias),
+ * l the unit-dispersion negative log-likelihood of the family's canonical link (gaussian (y - eta)^2 / 2, poisson e^eta - y eta,
+ * binomial log(1 + e^eta) - y eta, gamma y eta - log eta with eta = 1 / mu); for the binomial family with l1_reg = 0 this is the
+ * cost of the reference's logistic_reg (logistic_solver.rs:44-74).  A penalty <= 0 means none, as there; both <= 0 is the
+ * pds_glm_irls_* fit, bit for bit.  The links are canonical, so an IRLS step is a Newton step and the penalised step minimises
+ * 1/2 beta'Gbeta - c'beta + (n l2_reg / 2) |beta_f|^2 + n l1_reg |beta_f|_1 over the iteration's G = X'WX, c = X'Wz: with l1_reg <= 0
+ * the same pivoted-QR solve with n l2_reg on the feature diagonal; with l1_reg > 0 a covariance-update coordinate descent, warm-started
+ * from the previous iteration (exact zeros; its sweeps end at a largest move of tol / 10 or after 1000).  Start, stopping rule,
+ * n_iter, null rule and pred are those of the unpenalised fit; no line search.  Deliberate deviation: the reference's l1 goes
+ * through OWL-QN and may shrink the bias too.  Grouped: 1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED); one model: any width
+ * pds_glm_irls_* takes.
+ */
+int pds_glm_enet_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
+                     int variance, double l1_reg, double l2_reg, double tol, int max_iter, double* coeffs, int* n_iter);
+int pds_glm_enet_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
+                     int variance, float l1_reg, float l2_reg, float tol, int max_iter, float* coeffs, int* n_iter);
+int pds_glm_enet_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, double l1_reg, double l2_reg, double tol,
+                             int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred, uint8_t* row_null);
+int pds_glm_enet_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, float l1_reg, float l2_reg, float tol,
+                             int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null);
+int pds_glm_enet_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, double l1_reg, double l2_reg, double tol, int max_iter, int64_t max_groups,
+                            int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, double* pred,
+                            uint8_t* row_null);
+int pds_glm_enet_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, float l1_reg, float l2_reg, float tol, int max_iter, int64_t max_groups,
+                            int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred,
+                            uint8_t* row_null);
 /*
  * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
  * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on

@@ -146,26 +146,62 @@ int pds_glm_irls_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t
 int pds_glm_irls_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
                              int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
                              double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred, uint8_t* row_null) {
-    return pds::glm_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol, max_iter,
-                                         coeffs, n_iter, is_null, pred, row_null);
+    return pds::glm_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, 0.0, 0.0, tol,
+                                         max_iter, coeffs, n_iter, is_null, pred, row_null);
 }
 int pds_glm_irls_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
                              int64_t n_groups, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
                              float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null) {
-    return pds::glm_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol, max_iter,
-                                        coeffs, n_iter, is_null, pred, row_null);
+    return pds::glm_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, 0.0f, 0.0f, tol,
+                                        max_iter, coeffs, n_iter, is_null, pred, row_null);
 }
 int pds_glm_irls_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                             int add_bias, int link, int variance, double tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, double* pred, uint8_t* row_null) {
-    return pds::glm_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups, out_keys,
-                                        coeffs, n_iter, is_null, n_groups, pred, row_null);
+    return pds::glm_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, 0.0, 0.0, tol, max_iter, max_groups,
+                                        out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
 }
 int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                             int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null) {
-    return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups, out_keys,
-                                       coeffs, n_iter, is_null, n_groups, pred, row_null);
+    return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, 0.0f, 0.0f, tol, max_iter, max_groups,
+                                       out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
+}
+
+// the elastic-net penalised fits: the argument lists of pds_glm_irls_* with l1_reg, l2_reg after `variance` (<= 0: no penalty)
+int pds_glm_enet_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
+                     int variance, double l1_reg, double l2_reg, double tol, int max_iter, double* coeffs, int* n_iter) {
+    return pds::glm_irls_impl<double>(ctx, cols, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs, n_iter, l1_reg, l2_reg);
+}
+int pds_glm_enet_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
+                     int variance, float l1_reg, float l2_reg, float tol, int max_iter, float* coeffs, int* n_iter) {
+    return pds::glm_irls_impl<float>(ctx, cols, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs, n_iter, l1_reg, l2_reg);
+}
+int pds_glm_enet_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, double l1_reg, double l2_reg, double tol,
+                             int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred, uint8_t* row_null) {
+    return pds::glm_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, l1_reg, l2_reg, tol,
+                                         max_iter, coeffs, n_iter, is_null, pred, row_null);
+}
+int pds_glm_enet_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, int link, int variance, float l1_reg, float l2_reg, float tol,
+                             int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null) {
+    return pds::glm_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, l1_reg, l2_reg, tol,
+                                        max_iter, coeffs, n_iter, is_null, pred, row_null);
+}
+int pds_glm_enet_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, double l1_reg, double l2_reg, double tol, int max_iter, int64_t max_groups,
+                            int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, double* pred,
+                            uint8_t* row_null) {
+    return pds::glm_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, l1_reg, l2_reg, tol, max_iter, max_groups,
+                                        out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
+}
+int pds_glm_enet_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, int link, int variance, float l1_reg, float l2_reg, float tol, int max_iter, int64_t max_groups,
+                            int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred,
+                            uint8_t* row_null) {
+    return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, l1_reg, l2_reg, tol, max_iter, max_groups,
+                                       out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
 }
 
 int pds_mixed_reml_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,

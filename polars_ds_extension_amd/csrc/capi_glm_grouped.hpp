@@ -1,5 +1,6 @@
 // capi_glm_grouped.hpp -- a GLM per group (IRLS): contiguous groups (pds_glm_irls_grouped_*) and int64 keys in any row order
-// (pds_glm_irls_by_key_*) on top of grouped_irls.hip
+// (pds_glm_irls_by_key_*) on top of grouped_irls.hip; with l1_reg / l2_reg the elastic-net penalised fits (pds_glm_enet_grouped_* /
+// pds_glm_enet_by_key_*), a penalty <= 0 meaning none
 // Part of the one translation unit capi.hip (included there, inside namespace pds, in dependency order): the entry-point
 // pipelines are templates with internal linkage, split by concern, not by compilation unit.
 #pragma once
@@ -13,8 +14,8 @@ constexpr int64_t kGlmSplitRowsDefault = 16384;
 // re-reserves ctx->ws, and the by-key form holds its frame in ctx->keyed.
 template <typename T>
 static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups,
-                            pds_space space, int add_bias, int link, int variance, T tol, int max_iter, T* coeffs, int32_t* n_iter,
-                            uint8_t* is_null, T* pred, uint8_t* row_null, const uint32_t* d_perm = nullptr) {
+                            pds_space space, int add_bias, int link, int variance, T l1_reg, T l2_reg, T tol, int max_iter, T* coeffs,
+                            int32_t* n_iter, uint8_t* is_null, T* pred, uint8_t* row_null, const uint32_t* d_perm = nullptr) {
     if (!ctx || !cols || !offsets || !coeffs || !n_iter || !is_null) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -63,7 +64,7 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     outs.place(w);
     row_outs.place(w);
     if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
-                                        d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap))
+                                        d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap, (double)l1_reg, (double)l2_reg))
         return rc;
     unsigned h_count = 0;
     PDS_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
@@ -90,7 +91,7 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
             for (int c = 0; c < nc; ++c) gc[c] = src[c] + rr[0];
             int its = 0;
             if (int rc = glm_irls_impl<T>(ctx, gc.data(), n_feat, rr[1] - rr[0], PDS_DEVICE, add_bias, link, variance, tol, max_iter,
-                                          hb.data() + k * pp, &its))
+                                          hb.data() + k * pp, &its, l1_reg, l2_reg))
                 return rc;
             hi[k] = its;
             bool fin = true;
@@ -117,8 +118,8 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
 // per-row means sent back through the permutation.
 template <typename T>
 static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int add_bias,
-                           int link, int variance, T tol, int max_iter, int64_t max_groups, int64_t* out_keys, T* coeffs, int32_t* n_iter,
-                           uint8_t* is_null, int64_t* n_groups, T* pred, uint8_t* row_null) {
+                           int link, int variance, T l1_reg, T l2_reg, T tol, int max_iter, int64_t max_groups, int64_t* out_keys, T* coeffs,
+                           int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, T* pred, uint8_t* row_null) {
     if (!ctx || !cols || !keys || !out_keys || !coeffs || !n_iter || !is_null || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -146,8 +147,8 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     const int64_t ng = kf.ng;
     outs.place(w);
     row_outs.place(w);
-    if (int rc = glm_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, link, variance, tol, max_iter, d_co,
-                                     d_it, d_nu, d_pred, d_rn, kf.d_perm))
+    if (int rc = glm_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, link, variance, l1_reg, l2_reg, tol, max_iter,
+                                     d_co, d_it, d_nu, d_pred, d_rn, kf.d_perm))
         return rc;
     const hipMemcpyKind back = space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, back, ctx->stream));

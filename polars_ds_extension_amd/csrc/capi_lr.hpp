@@ -222,10 +222,17 @@ static Method pick_method(const pds_lr_params* prm) {
 // Device moments -> coefficients on the host.  The f32 twin's iteration caps apply when T = float: coordinate descent 2000
 // everywhere, NNLS 200 in `pl_lr_f32` (linear_regression_f32.rs:343) but 2000 in `pl_lr_pred_f32` (:620) -- `pred_path`.
 // `force_cd`: ElasticNet::fit_unchecked (lr_solvers.rs:139-164) always runs faer_coordinate_descent, also for l1_reg <= 0.
+// `irls`: the penalised step of an IRLS iteration on a weighted record (`weighted`), whose count slot holds sum w: the penalties
+// scale with irls->rows.  l1 <= 0: rows * l2 on the feature diagonal of the QR solve; l1 > 0: coordinate descent from the
+// coefficients d_coeffs_keep holds (irls->warm) or from 0, sweeps to prm->tol, at most prm->max_iter of them.
+struct IrlsPenalty {
+    double l1, l2, rows;
+    bool warm;
+};
 template <typename T>
 static int lr_from_device_moments(pds_ctx* ctx, const T* d_mom, int p, const pds_lr_params* prm, bool weighted,
                                   T* coeffs, int* is_null, T* d_coeffs_keep /*nullable device copy*/, bool pred_path = false,
-                                  bool force_cd = false) {
+                                  bool force_cd = false, const IrlsPenalty* irls = nullptr) {
     const int bias = prm->add_bias ? 1 : 0, pp = p + bias, q = p + 2;
     if (is_null) *is_null = 0;
     // coefficients and the null flag sit in one block so that they come back in one copy
@@ -236,6 +243,8 @@ static int lr_from_device_moments(pds_ctx* ctx, const T* d_mom, int p, const pds
     int* d_info = reinterpret_cast<int*>(ws_take(ctx, 16));
     if (int rc = ensure_pinned(ctx, 4096 + sizeof(T) * (size_t)(q * q + pp))) return rc;
     Method m = weighted ? Method{Method::OLS, 0.0, 0.0, 0} : pick_method(prm);
+    const double wl2 = (weighted && irls && irls->l2 > 0.0) ? irls->rows * irls->l2 : 0.0;  // (a weighted record's ridge term)
+    if (weighted && irls && irls->l1 > 0.0) m = Method{Method::CD, irls->l1, irls->l2 > 0.0 ? irls->l2 : 0.0, 0};
     if (force_cd) m = Method{Method::CD, prm->l1_reg > 0.0 ? prm->l1_reg : 0.0, prm->l2_reg > 0.0 ? prm->l2_reg : 0.0, prm->positive ? 1 : 0};
     const bool f32 = sizeof(T) == 4;
     if (m.kind == Method::OLS && prm->solver == PDS_SOLVER_SVD) {
@@ -263,10 +272,15 @@ static int lr_from_device_moments(pds_ctx* ctx, const T* d_mom, int p, const pds
         return PDS_OK;
     }
     if (m.kind == Method::OLS) {
-        SolveParams sp{p, bias, prm->solver, weighted ? 0.0 : m.l2, weighted ? 0.0 : prm->singular_x_tol, 0};
+        SolveParams sp{p, bias, prm->solver, weighted ? wl2 : m.l2, weighted ? 0.0 : prm->singular_x_tol, 0};
         if (int rc = launch_solve<T>(ctx, d_mom, 1, sp, d_coeffs, d_flag, nullptr, nullptr)) return rc;
     } else if (m.kind == Method::NNLS) {
         if (int rc = launch_nnls<T>(ctx, d_mom, p, bias, prm->tol, f32 ? (pred_path ? 2000 : 200) : prm->max_iter, d_coeffs)) return rc;
+        PDS_HIP_CHECK(hipMemsetAsync(d_flag, 0, 1, ctx->stream));
+    } else if (weighted) {
+        if (int rc = launch_cd<T>(ctx, d_mom, p, bias, m.l1, m.l2, prm->tol, prm->max_iter, 0, d_coeffs, d_info, 1, nullptr, nullptr,
+                                  irls->rows, irls->warm && d_coeffs_keep ? 1 : 0))
+            return rc;
         PDS_HIP_CHECK(hipMemsetAsync(d_flag, 0, 1, ctx->stream));
     } else {
         if (int rc = launch_cd<T>(ctx, d_mom, p, bias, m.l1, m.l2, prm->tol, (f32 && !force_cd) ? 2000 : prm->max_iter, m.positive,

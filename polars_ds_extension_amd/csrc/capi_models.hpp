@@ -11,7 +11,7 @@
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 static int glm_irls_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, pds_space space, int add_bias, int link,
-                         int variance, T tol, int max_iter, T* coeffs, int* n_iter) {
+                         int variance, T tol, int max_iter, T* coeffs, int* n_iter, T l1_reg = T(0), T l2_reg = T(0)) {
     if (!ctx || !cols || !coeffs) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -61,6 +61,13 @@ static int glm_irls_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     prm.add_bias = bias;
     prm.solver = PDS_SOLVER_QR;  // GLM::fit_unchecked passes LRSolverMethods::QR (:226, :236)
     prm.max_iter = 1;
+    // the penalised step (grouped_irls.hip has the derivation): rows * l2 on the feature diagonal, or coordinate descent when l1 > 0
+    IrlsPenalty pen{l1_reg > T(0) ? (double)l1_reg : 0.0, l2_reg > T(0) ? (double)l2_reg : 0.0, (double)n_rows, false};
+    const bool penalised = pen.l1 > 0.0 || pen.l2 > 0.0;
+    if (pen.l1 > 0.0) {
+        prm.tol = kGiCdInner * (double)tol;
+        prm.max_iter = kGiCdSweeps;
+    }
     std::vector<T> beta(pp, T(0)), bnew(pp, T(0));
     int it = 0;
     while (it < max_iter) {
@@ -73,13 +80,18 @@ static int glm_irls_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
             if (int rc = launch_moments_wide<T>(ctx, dcw, p, n_rows, true, d_mom)) return rc;
         }
         int null_flag = 0;
-        if (int rc = lr_from_device_moments<T>(ctx, d_mom, p, &prm, /*weighted=*/true, bnew.data(), &null_flag, d_beta)) return rc;
+        pen.warm = it > 1;  // (d_beta holds the previous iteration's coefficients)
+        if (int rc = lr_from_device_moments<T>(ctx, d_mom, p, &prm, /*weighted=*/true, bnew.data(), &null_flag, d_beta, false, false,
+                                               penalised ? &pen : nullptr))
+            return rc;
         if (wide) ctx->ws_used = ws_mark;  // the partial tiles of the wide build are per iteration (the solve has synchronised)
         ia.init = 0;
         T max_diff = T(0);
         for (int j = 0; j < pp; ++j) max_diff = std::max(max_diff, (T)std::fabs(beta[j] - bnew[j]));
         beta = bnew;
-        if (max_diff < tol) break;  // (a NaN difference never converges, as in the reference: :339-350)
+        // (a NaN difference never converges, as in the reference: :339-350; a penalised fit does not stop on its first step, whose
+        // system is built at the starting mu and not at beta = 0: grouped_irls.hip)
+        if (max_diff < tol && !(penalised && it == 1)) break;
     }
     for (int j = 0; j < pp; ++j) coeffs[j] = beta[j];
     if (n_iter) *n_iter = it;

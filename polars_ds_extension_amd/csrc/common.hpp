@@ -288,7 +288,10 @@ size_t solve_wave_workspace(int n_feat, int add_bias, int64_t n_sys, size_t elem
 template <typename T>
 int launch_cd(pds_ctx* ctx, const T* d_moments, int p, int add_bias, double l1, double l2, double tol,
               int max_iter, int positive, T* d_coeffs, int* d_info /*per system: [0]=sweeps,[1]=converged; nullable*/,
-              int64_t n_sys = 1, uint8_t* d_flags = nullptr, const int64_t* d_rows_per_sys = nullptr);
+              int64_t n_sys = 1, uint8_t* d_flags = nullptr, const int64_t* d_rows_per_sys = nullptr,
+              double pen_rows = 0.0 /* > 0: the penalties scale with this row count, not with the record's count slot (an IRLS record
+                                       holds sum w there), and the bias move counts towards the sweep's largest move */,
+              int warm_start = 0 /* the sweeps start from the coefficients d_coeffs holds, not from 0 */);
 template <typename T>
 int launch_nnls(pds_ctx* ctx, const T* d_moments, int p, int add_bias, double tol, int max_iter, T* d_coeffs,
                 int64_t n_sys = 1, uint8_t* d_flags = nullptr, const int64_t* d_rows_per_sys = nullptr);
@@ -314,13 +317,19 @@ int launch_grouped_pred_by_id_table(pds_ctx* ctx, const T* const* d_cols, int n_
                                     const int64_t* d_kmin, const uint32_t* d_ids /* dense id of group g */, int64_t n_groups, const T* d_coeffs,
                                     const uint8_t* d_flags, T* d_table /* n_ids x grouped_pred_table_stride(p') workspace */, T* d_pred, T* d_resid, uint8_t* d_row_null);  // grouped_pred.hip
 // ---- grouped_irls.hip: a GLM per group (IRLS), one wave per group, all iterations on chip; 1 .. 16 features.  Groups of more than
-// `split_rows` rows are not fitted: their indices are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it)
+// `split_rows` rows are not fitted: their indices are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it).
+// l1_reg / l2_reg > 0: the elastic-net penalised fit (features only, scaled by the group's row count); both <= 0: the kernel as it
+// was without them.
 template <typename T>
 int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
                         int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
                         int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
                         const uint32_t* d_perm /*nullable: row r of the frame in group order is row d_perm[r] of the outputs*/,
-                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg = 0.0, double l2_reg = 0.0);
+// The penalised IRLS step (l1_reg > 0) is a coordinate descent on the iteration's weighted Gram system: its sweeps end when the
+// largest move of a sweep is below kGiCdInner * tol, or at kGiCdSweeps sweeps (not an error: the outer iteration goes on).
+constexpr double kGiCdInner = 0.1;
+constexpr int kGiCdSweeps = 1000;
 // per-row means g^-1(x . beta) of the rows [r0, r1) from one coefficient vector in device memory
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,

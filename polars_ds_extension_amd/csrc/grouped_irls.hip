@@ -23,11 +23,19 @@
 // Arithmetic is f64 for f64 and f32 frames alike (an f32 frame is converted on load).  Groups above `split_rows` are not
 // walked here: the wave appends them to a list and the host side fits them with the full-device iteration
 // (capi_glm_grouped.hpp).  Per-row means are written at the end of a group's fit from the rows the wave still holds.
+//
+// This file is compiled three times: as it stands it holds the unpenalised kernels (PEN = 0) and the launchers;
+// grouped_irls_ridge.hip and grouped_irls_cd.hip include it with PDS_GROUPED_IRLS_PEN = 1 / 2 and hold the kernels of one penalised
+// mode each -- 32 kernels every time, which one translation unit would compile one after the other.
 #include "glm_dev.hpp"
 #include "solve_reg_dev.hpp"
 #include "wave_tile_dev.hpp"
 
 #include <algorithm>
+
+#ifndef PDS_GROUPED_IRLS_PEN
+#define PDS_GROUPED_IRLS_PEN 0
+#endif
 
 namespace pds {
 
@@ -42,22 +50,91 @@ __device__ __forceinline__ bool gi_finite(T v) {
     return fabs((double)v) <= 1.79769313486231570e308;  // (false for NaN)
 }
 
+// The penalised step (PEN = 1 / 2).  The links are canonical, so the IRLS step is the Newton step of sum_i l(y_i, eta_i), and the step
+// of  F = (1/n) sum l + (l2/2) |beta_f|^2 + l1 |beta_f|_1  (features only, never the bias) is the minimiser of
+//   1/2 beta' G beta - c' beta + (n l2 / 2) |beta_f|^2 + n l1 |beta_f|_1     with G = X'WX, c = X'Wz as staged in gm / rh.
+// The scale is the group's row count n, not sum w.
+//   * l1 <= 0: n l2 goes on the feature diagonal of the staged system and solve_core runs as it does without a penalty (in the
+//     16 + bias form the bias is eliminated first, which is exact because it is unpenalised: the penalty ends up on the centred
+//     16 x 16 diagonal).
+//   * l1 > 0: coordinate descent in the wave (gi_cd_step below) in place of the solve.
+// The two are kernels of their own (PEN = 1 ridge, PEN = 2 coordinate descent): the solve leaves no register to spare at two waves
+// per SIMD, and with both steps in one kernel several widths spilled to scratch.
+// (kGiCdInner, kGiCdSweeps: common.hpp)
+
+// Covariance-update coordinate descent on the staged system, warm-started from the previous outer iteration's coefficients (0 in
+// the first).  Lane k < p' holds beta_k (`bk`) and the running gradient r_k = c_k - sum_j G_kj beta_j; coordinate j's candidate is
+// soft(r_j + G_jj beta_j, n l1) / (G_jj + n l2) for a feature and (r_j + G_jj beta_j) / G_jj for the bias (last, index 16 of gm).
+// Every lane computes the same candidate from broadcasts, so the decision to move is wave-uniform; a coordinate that does not move
+// costs no update.  Lane k reads G_kj as gm[j][k] (the matrix is symmetric up to the rounding of the two matrix-core products):
+// consecutive lanes read consecutive doubles of one row, 17 distinct banks, where column j (row stride kGiG = 18 doubles = 36
+// banks) would put lanes k and k + 16 on one bank.
+template <int P>
+__device__ __forceinline__ double gi_cd_step(const double* gm, const double* rh, int pp, int lane, double bk, double nl1, double nl2,
+                                             double eps) {
+    const int gk = lane < P ? lane : 16;
+    const bool mine = lane < pp;
+    double r = mine ? rh[gk] : 0.0;
+    for (int j = 0; j < pp; ++j) {
+        const double bj = __shfl(bk, j);
+        if (bj != 0.0) r = fma(-bj, mine ? gm[(j < P ? j : 16) * kGiG + gk] : 0.0, r);
+    }
+    for (int sweep = 0; sweep < kGiCdSweeps; ++sweep) {
+        double moved = 0.0;
+        for (int j = 0; j < pp; ++j) {
+            const int gj = j < P ? j : 16;
+            const double gjj = gm[gj * kGiG + gj];
+            const double bj = __shfl(bk, j);
+            const double u = fma(gjj, bj, __shfl(r, j));
+            double nb;
+            if (j < P) {
+                const double mag = fabs(u) - nl1;
+                nb = mag > 0.0 ? copysign(mag, u) / (gjj + nl2) : 0.0;  // (an exact zero inside the threshold)
+            } else {
+                nb = u / gjj;
+            }
+            const double delta = nb - bj;
+            if (delta != 0.0) {  // (wave-uniform; true for a NaN)
+                r = fma(-delta, mine ? gm[gj * kGiG + gk] : 0.0, r);
+                if (lane == j) bk = nb;
+                const double d = fabs(delta);
+                moved = d > moved ? d : moved;
+                if (d != d) moved = d;
+            }
+        }
+        if (!(moved >= eps)) break;  // (converged, or a NaN: the outer loop's NaN rule ends the fit)
+    }
+    return bk;
+}
+
 // (two waves per SIMD: 250 registers, nothing in scratch; a bound of three spilled 111 registers at 8 features)
-template <typename T, int P>
+// PEN = 0 is the unpenalised fit, the code it was before the penalties existed; PEN = 1 / 2 take the penalised step above.
+template <typename T, int P, int PEN>
 __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __restrict__ cols, int bias, int64_t n_rows,
                                                           const int64_t* __restrict__ off, int64_t n_groups, int link, int variance,
                                                           double tol, int max_iter, int64_t split_rows, T* __restrict__ coeffs,
                                                           int32_t* __restrict__ n_iter, uint8_t* __restrict__ is_null,
                                                           T* __restrict__ pred, uint8_t* __restrict__ row_null,
                                                           const uint32_t* __restrict__ perm, int64_t* __restrict__ long_list,
-                                                          unsigned* __restrict__ long_count, int64_t long_cap) {
-    __shared__ double lds[(P + 1) * kGiStride + 64 + 64 + 18 + 17 * kGiG + 18];
+                                                          unsigned* __restrict__ long_count, int64_t long_cap, double l1_reg,
+                                                          double l2_reg) {
+    __shared__ double lds[(P + 1) * kGiStride + 64 + 64 + 18 + 17 * kGiG + 18 + (PEN ? 2 : 0)];
     double* xt = lds;                      // features 0 .. P - 1, then y: [c * kGiStride + row]
     double* wt = xt + (P + 1) * kGiStride;  // w of the step's rows
     double* zt = wt + 64;                  // w z of the step's rows
     double* bs = zt + 64;                  // coefficients: features, bias at bs[P]
     double* gm = bs + 18;                  // X'WX staged for the solve: index 16 is the bias row / column
     double* rh = gm + 17 * kGiG;           // X'Wz, rh[16] = sum w z
+    // PEN: l1_reg, l2_reg, read back where an iteration uses them -- as kernel arguments they would stay in registers across the
+    // solve, which has none to spare
+    [[maybe_unused]] double* pn = rh + (PEN ? 18 : 0);
+    if constexpr (PEN) {
+        if (threadIdx.x == 0) {
+            pn[0] = l1_reg;
+            pn[1] = l2_reg;
+        }
+        PDS_WAVE_LDS_SYNC();
+    }
     const int lane = threadIdx.x;
     const int pp = P + bias;
     const double nanv = __builtin_nan("");
@@ -99,6 +176,9 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
         }
         const bool resident = n <= kGiCap;
         PDS_WAVE_LDS_SYNC();  // (the previous group's reads are done)
+        if constexpr (PEN == 1) {
+            if (lane == 0) pn[0] = (double)n * pn[1];  // (read at the staging of every iteration, many hand-offs from here)
+        }
         double sy = 0.0;
         for (int64_t base = 0; base < n; base += 64) {
             const int64_t r = base + lane;
@@ -162,10 +242,14 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
             sw = wave_sum(sw);
             swz = wave_sum(swz);
             PDS_WAVE_LDS_SYNC();  // (bs / gm / rh: the previous iteration's reads are done)
+            // ridge (PEN = 1): n l2 on the feature diagonal of the staged system, never on index 16 (the bias); the solve below is
+            // the unpenalised one.  In the 16 + bias form the centring then runs on the penalised diagonal: the same matrix.
+            double nl2 = 0.0;
+            if constexpr (PEN == 1) nl2 = pn[0];
             wave_tile_for_d(
                 lane,
                 [&](int i, int c, double g, double side) {
-                    gm[i * kGiG + c] = g;
+                    gm[i * kGiG + c] = (PEN == 1 && i == c) ? g + nl2 : g;
                     if (c == 0) rh[i] = side;
                     if (c == 1) {
                         gm[i * kGiG + 16] = side;
@@ -178,35 +262,42 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
                 rh[16] = swz;
             }
             PDS_WAVE_LDS_SYNC();
-            // ---- the solve: lane j of every 16-lane row = column j
-            const int j = lane & 15;
-            const bool centred = pp > 16;  // 16 features + bias: the bias is eliminated, 16 columns remain
-            const int ppq = sp.pp;
-            const bool colv = j < ppq;
-            const int jm = (j < P) ? j : 16;
-            const double sj = centred ? gm[jm * kGiG + 16] : 0.0;
-            const double mj = centred ? sj / sw : 0.0, mz = centred ? swz / sw : 0.0;
-            double a[16], b[16];
+            if constexpr (PEN == 2) {
+                const double bk = gi_cd_step<P>(gm, rh, pp, lane, bcur, (double)n * pn[0], (double)n * pn[1], kGiCdInner * tol);
+                if (lane < pp) bs[lane] = bk;
+            } else {
+                // ---- the solve: lane j of every 16-lane row = column j
+                const int j = lane & 15;
+                const bool centred = pp > 16;  // 16 features + bias: the bias is eliminated, 16 columns remain
+                const int ppq = sp.pp;
+                const bool colv = j < ppq;
+                const int jm = (j < P) ? j : 16;
+                const double sj = centred ? gm[jm * kGiG + 16] : 0.0;
+                const double mj = centred ? sj / sw : 0.0, mz = centred ? swz / sw : 0.0;
+                double a[16], b[16];
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int im = (i < P) ? i : 16;
-                const double si = centred ? gm[im * kGiG + 16] : 0.0;
-                a[i] = (colv && i < ppq) ? fma(-si, mj, gm[im * kGiG + jm]) : 0.0;
-                b[i] = (i < ppq) ? fma(-si, mz, rh[im]) : 0.0;
-            }
-            const double dj = colv ? gm[jm * kGiG + jm] : 1.0;
-            bool snull = false;
-            int pj = j;
-            double zj = 0.0;
-            solve_core<16>(a, b, dj, j, lane, sp, snull, pj, zj);
-            if (lane < 16 && colv) bs[pj] = zj;
-            if (centred) {
-                const double sb = Grp<16>::sum(colv ? gm[pj * kGiG + 16] * zj : 0.0);
-                if (lane == 0) bs[16] = (swz - sb) / sw;
+                for (int i = 0; i < 16; ++i) {
+                    const int im = (i < P) ? i : 16;
+                    const double si = centred ? gm[im * kGiG + 16] : 0.0;
+                    a[i] = (colv && i < ppq) ? fma(-si, mj, gm[im * kGiG + jm]) : 0.0;
+                    b[i] = (i < ppq) ? fma(-si, mz, rh[im]) : 0.0;
+                }
+                const double dj = colv ? gm[jm * kGiG + jm] : 1.0;
+                bool snull = false;
+                int pj = j;
+                double zj = 0.0;
+                solve_core<16>(a, b, dj, j, lane, sp, snull, pj, zj);
+                if (lane < 16 && colv) bs[pj] = zj;
+                if (centred) {
+                    const double sb = Grp<16>::sum(colv ? gm[pj * kGiG + 16] * zj : 0.0);
+                    if (lane == 0) bs[16] = (swz - sb) / sw;
+                }
             }
             PDS_WAVE_LDS_SYNC();
             const double bnew = lane < pp ? bs[lane] : 0.0;
-            const bool open = lane < pp && !(fabs(bcur - bnew) < tol);
+            // (penalised: the first system is built at the starting mu, not at beta = 0, so an all-zero first step -- every feature
+            // inside the l1 threshold -- says nothing about the point beta = 0 itself: the second iteration decides)
+            const bool open = lane < pp && (!(fabs(bcur - bnew) < tol) || (PEN && it == 1));
             const bool isnan_b = lane < pp && bnew != bnew;
             bcur = bnew;
             if (__any(isnan_b)) {
@@ -258,24 +349,59 @@ __global__ __launch_bounds__(256) void glm_pred_range_kernel(const T* const* __r
     }
 }
 
+template <typename T, int PEN>
+int gi_launch(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off, int64_t n_groups, int link,
+              int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs, int32_t* d_n_iter, uint8_t* d_null, T* d_pred,
+              uint8_t* d_row_null, const uint32_t* d_perm, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg,
+              double l2_reg) {
+    KernelTimer timer(ctx, kKindIter);
+    const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((grouped_irls_kernel<T, decltype(pc)::value, PEN>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows, d_off,
+                           n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter, d_null, d_pred, d_row_null, d_perm,
+                           d_long_list, d_long_count, long_cap, l1_reg, l2_reg);
+    });
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
 }  // namespace
+
+#define PDS_GI_ARGS(T)                                                                                                                   \
+    pds_ctx*, const T* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int, int64_t, T*, int32_t*, uint8_t*, T*, \
+        uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t, double, double
+
+#if PDS_GROUPED_IRLS_PEN
+// the kernels of one penalised mode (grouped_irls_ridge.hip, grouped_irls_cd.hip)
+template <typename T, int PEN>
+int launch_grouped_irls_pen(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                            int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
+                            int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
+                            int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg, double l2_reg) {
+    return gi_launch<T, PEN>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
+                             d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, l1_reg, l2_reg);
+}
+template int launch_grouped_irls_pen<double, PDS_GROUPED_IRLS_PEN>(PDS_GI_ARGS(double));
+template int launch_grouped_irls_pen<float, PDS_GROUPED_IRLS_PEN>(PDS_GI_ARGS(float));
+#else
+template <typename T, int PEN>
+int launch_grouped_irls_pen(PDS_GI_ARGS(T));
 
 template <typename T>
 int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
                         int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
                         int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
-                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
+                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg, double l2_reg) {
     if (n_groups <= 0) return PDS_OK;
     if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
-    KernelTimer timer(ctx, kKindIter);
-    const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
-    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
-        hipLaunchKernelGGL((grouped_irls_kernel<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows, d_off,
-                           n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter, d_null, d_pred, d_row_null, d_perm,
-                           d_long_list, d_long_count, long_cap);
-    });
-    PDS_HIP_CHECK(hipGetLastError());
-    return PDS_OK;
+    if (l1_reg > 0.0 || l2_reg > 0.0) {  // (a penalty <= 0 means none)
+        auto launch = l1_reg > 0.0 ? launch_grouped_irls_pen<T, 2> : launch_grouped_irls_pen<T, 1>;
+        return launch(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
+                      d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, l1_reg > 0.0 ? l1_reg : 0.0,
+                      l2_reg > 0.0 ? l2_reg : 0.0);
+    }
+    return gi_launch<T, 0>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
+                           d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, 0.0, 0.0);
 }
 
 template <typename T>
@@ -290,14 +416,13 @@ int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int 
     return PDS_OK;
 }
 
-template int launch_grouped_irls<double>(pds_ctx*, const double* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
-                                         int64_t, double*, int32_t*, uint8_t*, double*, uint8_t*, const uint32_t*, int64_t*, unsigned*,
-                                         int64_t);
-template int launch_grouped_irls<float>(pds_ctx*, const float* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
-                                        int64_t, float*, int32_t*, uint8_t*, float*, uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t);
+template int launch_grouped_irls<double>(PDS_GI_ARGS(double));
+template int launch_grouped_irls<float>(PDS_GI_ARGS(float));
 template int launch_glm_pred_range<double>(pds_ctx*, const double* const*, int, int, int64_t, int64_t, const double*, const uint8_t*, int,
                                            double*, uint8_t*, const uint32_t*);
 template int launch_glm_pred_range<float>(pds_ctx*, const float* const*, int, int, int64_t, int64_t, const float*, const uint8_t*, int,
                                           float*, uint8_t*, const uint32_t*);
+#endif
+#undef PDS_GI_ARGS
 
 }  // namespace pds

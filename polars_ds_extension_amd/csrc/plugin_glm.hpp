@@ -7,10 +7,14 @@ template <typename T> struct GlmApi;
 template <> struct GlmApi<double> {
     static constexpr auto grouped = pds_glm_irls_grouped_f64;
     static constexpr auto by_key = pds_glm_irls_by_key_f64;
+    static constexpr auto enet_grouped = pds_glm_enet_grouped_f64;
+    static constexpr auto enet_by_key = pds_glm_enet_by_key_f64;
 };
 template <> struct GlmApi<float> {
     static constexpr auto grouped = pds_glm_irls_grouped_f32;
     static constexpr auto by_key = pds_glm_irls_by_key_f32;
+    static constexpr auto enet_grouped = pds_glm_enet_grouped_f32;
+    static constexpr auto enet_by_key = pds_glm_enet_by_key_f32;
 };
 
 // family -> (link, variance) ids of include/pds_lstsq.h, the names of linear_models.GLM_FAMILIES
@@ -31,7 +35,9 @@ inline void glm_family_codes(const std::string& family, int* link, int* variance
 int64_t g_glm_by_first_cap = 0;
 
 // ------------------------------------------------------------------------------------------------- pl_glm_by / pl_glm_by_pred (new)
-// inputs: [key (integer, any row order, nulls = one group), y, x1..xp]; kwargs bias, null_policy, family, tol, max_iter.
+// inputs: [key (integer, any row order, nulls = one group), y, x1..xp]; kwargs bias, null_policy, family, tol, max_iter, and
+// l1_reg / l2_reg (absent or <= 0: none): the elastic-net penalised fits through pds_glm_enet_*, called only when a penalty is
+// positive -- an unpenalised call goes to the pds_glm_irls_* symbols it always went to.
 // pl_glm_by: Struct{<key>, coeffs: List<T>, n_iter: Int32}, one row per group, keys ascending (the null key's group last, with a null
 // key), a null list for a null group (fewer rows than coefficients, or a fit that does not end in finite coefficients).
 // pl_glm_by_pred: the fitted mean of every row, row for row, null where the row's group is null or a null policy dropped the row.
@@ -48,6 +54,8 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
     if (max_iter < 1) raise("`max_iter` must be > 1.");
     const T tol = (T)std::fabs(kw_f64(kw, "tol", 1e-8));
     const int bias = kw_bool(kw, "bias") ? 1 : 0;
+    const T l1_reg = (T)std::max(kw_f64(kw, "l1_reg"), 0.0), l2_reg = (T)std::max(kw_f64(kw, "l2_reg"), 0.0);
+    const bool penalised = l1_reg > T(0) || l2_reg > T(0);
     const int n_feat = (int)n_in - 2;
     if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
     const int pp = n_feat + bias;
@@ -84,9 +92,13 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
             cobuf = raw_buffer<T>((size_t)cap * pp);
             itbuf = raw_buffer<int32_t>((size_t)cap);
             nulls.resize(cap);
-            const int rc = GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
-                                             keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, want_pred ? as<T>(pred_b) : nullptr,
-                                             want_pred ? row_null.data() : nullptr);
+            T* const pr = want_pred ? as<T>(pred_b) : nullptr;
+            uint8_t* const rn = want_pred ? row_null.data() : nullptr;
+            const int rc = penalised ? GlmApi<T>::enet_by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, l1_reg,
+                                                              l2_reg, tol, max_iter, cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf),
+                                                              nulls.data(), &ng, pr, rn)
+                                     : GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter,
+                                                         cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, pr, rn);
             if (rc != 0 && attempt == 0 && ng > cap) {
                 cap = ng;
                 continue;
@@ -142,9 +154,12 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
             pk = raw_buffer<T>((size_t)nk);
             rk.resize(nk);
         }
-        check(GlmApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter,
-                                 as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), want_pred ? as<T>(pk) : nullptr,
-                                 want_pred ? rk.data() : nullptr));
+        T* const pr = want_pred ? as<T>(pk) : nullptr;
+        uint8_t* const rn = want_pred ? rk.data() : nullptr;
+        check(penalised ? GlmApi<T>::enet_grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, l1_reg,
+                                                  l2_reg, tol, max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn)
+                        : GlmApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter,
+                                             as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn));
         if (want_pred) {  // back to the frame's rows: a dropped row is a null row
             pred_b = raw_buffer<T>((size_t)n);
             row_valid.assign((size_t)n, 0);
@@ -194,7 +209,8 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
 // fills the features and drops the rows whose target is null; pred is null where the mask drops a row.
 inline void do_logistic(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
     if (n_in < 2) raise("pl_logistic needs a target and at least one feature");
-    if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0) raise("logistic_reg: l1_reg / l2_reg are not supported on this backend");
+    if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0)
+        raise("logistic_reg: l1_reg / l2_reg are not supported on this backend; use GLM(family='binomial', l2_reg=...) or by=");
     const int max_iter = (int)kw_i64(kw, "max_iter", 200);
     if (max_iter < 1) raise("Input `max_iter` must be a positive.");
     const double tol = std::fabs(kw_f64(kw, "tol", 1e-5));

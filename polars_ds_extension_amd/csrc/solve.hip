@@ -365,7 +365,8 @@ template <typename T>
 __global__ __launch_bounds__(64) void cd_kernel(const T* __restrict__ M, int p, int bias, double l1_reg,
                                                 double l2_reg, double tol, int max_iter, int positive,
                                                 T* __restrict__ coeffs, int* __restrict__ info,
-                                                uint8_t* __restrict__ flags, const int64_t* __restrict__ rows_per_sys) {
+                                                uint8_t* __restrict__ flags, const int64_t* __restrict__ rows_per_sys, double pen_rows,
+                                                int warm_start) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int lane = threadIdx.x;
     const int pp = p + bias, q = p + 2;
@@ -377,13 +378,22 @@ __global__ __launch_bounds__(64) void cd_kernel(const T* __restrict__ M, int p, 
     double* r = sm + (p + 2);    // pp
     double* gd = r + (p + 2);    // p: G[j,j]
     const double m = (double)M[p + p * q];  // n (row count) lives in the bias/bias slot
-    const double lambda_l1 = m * l1_reg, ridge = m * l2_reg;
+    const double pen_m = pen_rows > 0.0 ? pen_rows : m;  // (an IRLS record: m = sum w, the penalties scale with the row count)
+    const double lambda_l1 = pen_m * l1_reg, ridge = pen_m * l2_reg;
     for (int i = lane; i < pp; i += 64) {
-        beta[i] = 0.0;
+        beta[i] = warm_start ? (double)coeffs[i] : 0.0;
         r[i] = (double)M[i + (p + 1) * q];  // X'y, and sum y in the bias slot
         if (i < p) gd[i] = (double)M[i + i * q];
     }
     WSYNC();
+    if (warm_start) {  // r = X'y - G beta
+        for (int i = lane; i < pp; i += 64) {
+            double ri = r[i];
+            for (int k = 0; k < pp; ++k) ri = fma(-beta[k], (double)M[i + (int64_t)k * q], ri);
+            r[i] = ri;
+        }
+        WSYNC();
+    }
     constexpr int kCdPrefetch = 9;  // 64 x 9 >= 514 = the moment columns of config 5; wider systems read each column when it is due
     T pf[kCdPrefetch];
     int pf_col = -1;
@@ -464,6 +474,7 @@ __global__ __launch_bounds__(64) void cd_kernel(const T* __restrict__ M, int p, 
             const T* col = M + (int64_t)p * q;
             for (int k = lane; k < pp; k += 64) r[k] = fma(-delta, (double)col[k], r[k]);
             WSYNC();
+            if (pen_rows > 0.0) max_change = fabs(delta) > max_change ? fabs(delta) : max_change;
         }
         conv = max_change < tol;
         if (conv) {
@@ -519,7 +530,8 @@ __global__ __launch_bounds__(64) void nnls_kernel(const T* __restrict__ M, int p
 
 template <typename T>
 int launch_cd(pds_ctx* ctx, const T* d_moments, int p, int add_bias, double l1, double l2, double tol, int max_iter,
-              int positive, T* d_coeffs, int* d_info, int64_t n_sys, uint8_t* d_flags, const int64_t* d_rows_per_sys) {
+              int positive, T* d_coeffs, int* d_info, int64_t n_sys, uint8_t* d_flags, const int64_t* d_rows_per_sys, double pen_rows,
+              int warm_start) {
     if (n_sys <= 0) return PDS_OK;
     const size_t lds = (size_t)3 * (p + 2) * sizeof(double);
     if (lds > 160 * 1024) return fail(PDS_ERR_INVALID, "coordinate descent: more than 6800 features are not supported");
@@ -528,7 +540,7 @@ int launch_cd(pds_ctx* ctx, const T* d_moments, int p, int add_bias, double l1, 
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     KernelTimer timer(ctx, kKindIter);
     hipLaunchKernelGGL((cd_kernel<T>), dim3((unsigned)n_sys), dim3(64), lds, ctx->stream, d_moments, p, add_bias ? 1 : 0,
-                       l1, l2, tol, max_iter, positive, d_coeffs, d_info, d_flags, d_rows_per_sys);
+                       l1, l2, tol, max_iter, positive, d_coeffs, d_info, d_flags, d_rows_per_sys, pen_rows, warm_start);
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
@@ -550,9 +562,9 @@ template int launch_solve<double>(pds_ctx*, const double*, int64_t, const SolveP
 template int launch_solve<float>(pds_ctx*, const float*, int64_t, const SolveParams&, float*, uint8_t*, float*,
                                  const int64_t*);
 template int launch_cd<double>(pds_ctx*, const double*, int, int, double, double, double, int, int, double*, int*, int64_t,
-                               uint8_t*, const int64_t*);
+                               uint8_t*, const int64_t*, double, int);
 template int launch_cd<float>(pds_ctx*, const float*, int, int, double, double, double, int, int, float*, int*, int64_t,
-                              uint8_t*, const int64_t*);
+                              uint8_t*, const int64_t*, double, int);
 template int launch_nnls<double>(pds_ctx*, const double*, int, int, double, int, double*, int64_t, uint8_t*, const int64_t*);
 template int launch_nnls<float>(pds_ctx*, const float*, int, int, double, int, float*, int64_t, uint8_t*, const int64_t*);
 

@@ -431,10 +431,13 @@ class GLM:
     (inverse).  On the MI355X one IRLS iteration is ONE pass over the frame (`pds_glm_irls_*`): weights and working response
     are formed from the previous coefficients while a row sits in registers (up to 16 features; wider frames write them as two
     columns in front of the weighted wide Gram build).
+    `l1_reg` / `l2_reg` > 0 (`pds_glm_enet_*`; the reference's GLM carries a commented-out `lambda_`): the fit minimises
+    (1/n) sum_i loss(y_i, eta_i) + (l2_reg / 2) sum_j beta_j^2 + l1_reg sum_j |beta_j|, the loss being the family's unit-dispersion
+    negative log-likelihood, the penalties on the features and never on the bias; a penalty <= 0 means none.
     """
 
     def __init__(self, add_bias: bool = False, solver: str = "irls", family: str = "normal", max_iter: int = 100, tol: float = 1e-8,
-                 feature_names_in_: List[str] | None = None):
+                 feature_names_in_: List[str] | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0):
         if solver not in ["irls"]:
             raise NotImplementedError
         if max_iter < 1:
@@ -443,6 +446,7 @@ class GLM:
             raise NotImplementedError
         self.add_bias, self.family, self.solver = bool(add_bias), family, solver
         self.max_iter, self.tol = int(max_iter), abs(float(tol))
+        self.l1_reg, self.l2_reg = max(float(l1_reg), 0.0), max(float(l2_reg), 0.0)
         self.feature_names_in_: List[str] = [] if feature_names_in_ is None else list(feature_names_in_)
         self._coeffs: np.ndarray | None = None
         self._bias = 0.0
@@ -484,9 +488,10 @@ class GLM:
         link, var = GLM_FAMILIES[self.family]
         n_iter = C.c_int(0)
         tol = C.c_double(self.tol) if f64 else C.c_float(self.tol)
-        _lib.check(ctx.fn("pds_glm_irls")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(self.add_bias),
-                                          C.c_int(link), C.c_int(var), tol, C.c_int(self.max_iter), C.c_void_p(co.ctypes.data),
-                                          C.byref(n_iter)))
+        pen = lstsq._pen_args(self.l1_reg, self.l2_reg)
+        fn = ctx.fn("pds_glm_enet" if pen else "pds_glm_irls")
+        _lib.check(fn(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(self.add_bias), C.c_int(link), C.c_int(var),
+                      *pen, tol, C.c_int(self.max_iter), C.c_void_p(co.ctypes.data), C.byref(n_iter)))
         co = co.astype(np.float64)
         self._coeffs, self._bias = (co[:-1].copy(), float(co[-1])) if self.add_bias else (co.copy(), 0.0)
         self.n_iter_ = int(n_iter.value)

@@ -1403,8 +1403,18 @@ def _tol_arg(tol):
     return C.c_double(abs(float(tol))) if config.LIN_REG_EXPR_F64 else C.c_float(abs(float(tol)))
 
 
+def _pen_args(l1_reg, l2_reg):
+    """() for an unpenalised fit (a penalty <= 0 means none, as in the reference), else the two arguments the `pds_glm_enet_*` entry
+    points take after `variance`."""
+    l1, l2 = max(float(l1_reg), 0.0), max(float(l2_reg), 0.0)
+    if l1 == 0.0 and l2 == 0.0:
+        return ()
+    ct = C.c_double if config.LIN_REG_EXPR_F64 else C.c_float
+    return (ct(l1), ct(l2))
+
+
 def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
-           return_pred: bool = False, ctx: Context | None = None):
+           return_pred: bool = False, ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0):
     """
     One GLM per group in one call: for every group g = rows [group_offsets[g], group_offsets[g+1]) what `GLM(family=...).fit` computes
     on g's rows alone (iteratively re-weighted least squares, the reference's faer_irls), every iteration of a group on chip
@@ -1413,6 +1423,11 @@ def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool =
     row_null [n_rows]) with `return_pred`: the fitted mean g^-1(x . beta_group) of every row.  A group with fewer rows than
     coefficients, or whose fit does not end in finite coefficients (a separated binomial group, NaN / inf in its rows), is null:
     is_null = 1 (NaN pred, row_null = 1).
+    `l1_reg` / `l2_reg` > 0 (`pds_glm_enet_grouped_*`): every group minimises
+    (1/n) sum_i loss(y_i, eta_i) + (l2_reg / 2) sum_j beta_j^2 + l1_reg sum_j |beta_j| over its n rows, the loss being the family's
+    unit-dispersion negative log-likelihood and the sums over j running over the features, never the bias.  Same iteration, each step
+    the penalised weighted least squares problem (ridge: one solve; l1: coordinate descent in the wave, exact zeros).  A ridge term
+    gives a separated binomial group a finite fit.
     """
     _glm_check(x, max_iter, "glm_by")
     link, var = _glm_family(family)
@@ -1430,20 +1445,23 @@ def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool =
     if return_pred:
         pred, pr_p = _out_like(cols, cols.n_rows)
         rnull, rn_p = _out_u8(cols, cols.n_rows)
-    _lib.check(ctx.fn("pds_glm_irls_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
-                                              int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)),
-                                              co_p, it_p, nu_p, pr_p, rn_p))
+    pen = _pen_args(l1_reg, l2_reg)
+    fn = ctx.fn("pds_glm_enet_grouped" if pen else "pds_glm_irls_grouped")
+    _lib.check(fn(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space, int(bool(add_bias)),
+                  C.c_int(link), C.c_int(var), *pen, _tol_arg(tol), C.c_int(int(max_iter)), co_p, it_p, nu_p, pr_p, rn_p))
     if return_pred:
         return coeffs, iters, nulls, pred, rnull
     return coeffs, iters, nulls
 
 
 def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
-               return_pred: bool = False, max_groups: int | None = None, ctx: Context | None = None):
+               return_pred: bool = False, max_groups: int | None = None, ctx: Context | None = None, l1_reg: float = 0.0,
+               l2_reg: float = 0.0):
     """
     `glm_by` for an integer key column in ANY row order (`pds_glm_irls_by_key_*`): the frame is brought into key order on the device
     (nothing moves when the keys are already non-decreasing), every group is fitted, per-row means come back at the rows' own
     positions.  Returns (keys [G] ascending, coeffs, n_iter, is_null), plus (pred, row_null) with `return_pred`.
+    `l1_reg` / `l2_reg` > 0: the penalised fits of `glm_by` (`pds_glm_enet_by_key_*`).
     """
     _glm_check(x, max_iter, "glm_by_key")
     link, var = _glm_family(family)
@@ -1453,6 +1471,7 @@ def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
     k, k_p = _key_arg(cols, key)
+    pen = _pen_args(l1_reg, l2_reg)
     pred = rnull = None
     pr_p = rn_p = None
     if return_pred:
@@ -1463,9 +1482,9 @@ def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False
         coeffs, co_p = _out_like(cols, (cap, pp))
         iters, it_p = _out_i32(cols, cap)
         nulls, nu_p = _out_u8(cols, cap)
-        rc = ctx.fn("pds_glm_irls_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
-                                           C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p,
-                                           co_p, it_p, nu_p, ng_p, pr_p, rn_p)
+        fn = ctx.fn("pds_glm_enet_by_key" if pen else "pds_glm_irls_by_key")
+        rc = fn(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)), C.c_int(link), C.c_int(var), *pen,
+                _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p, co_p, it_p, nu_p, ng_p, pr_p, rn_p)
         return rc, (coeffs, iters, nulls)
 
     keys, (coeffs, iters, nulls), g = _by_key_retry(cols, max_groups, call)
@@ -1483,10 +1502,12 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
     Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random start and stops at a gradient
     norm; this backend runs IRLS (binomial family, logit link, `pds_glm_irls_*` on the whole frame) to the same unpenalised
     maximum-likelihood point and stops when no coefficient moves by `tol`.  The two agree to the reference's own test tolerance, not
-    bit for bit.  Penalised fits (`l1_reg` / `l2_reg` > 0) are not supported and raise rather than return an unpenalised fit.
+    bit for bit.  Penalised fits (`l1_reg` / `l2_reg` > 0) are not supported here and raise rather than return an unpenalised fit:
+    `GLM(family="binomial", l1_reg=..., l2_reg=...)` and `glm_by` / `glm_by_key` fit them.
     """
     if l1_reg > 0.0 or l2_reg > 0.0:
-        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend")
+        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend; use GLM(family='binomial', "
+                                  "l2_reg=...) or glm_by / glm_by_key")
     if max_iter <= 0:
         raise ValueError("Input `max_iter` must be a positive.")  # expr_linear.py:231-232
     if len(x) < 1:

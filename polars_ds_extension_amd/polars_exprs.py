@@ -235,17 +235,19 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
     expr_linear.py:277-353: `pl_logistic_coeffs` / `pl_logistic_pred` (Float64 only, as there), aliases `__coeffs__` / `__pred__`.
     Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random start and stops at a gradient
     norm; this backend runs IRLS (binomial family) to the same unpenalised maximum-likelihood point and stops when no coefficient
-    moves by `tol`.  `l1_reg` / `l2_reg` > 0 raise rather than return an unpenalised fit.
+    moves by `tol`.  Without `by`, `l1_reg` / `l2_reg` > 0 raise rather than return an unpenalised fit.
     `by` (an integer key column, any row order, nulls = one group): one logistic model per group from ONE `pl_glm_by` /
     `pl_glm_by_pred` call with family "binomial" -- Struct{<key>, coeffs, n_iter} per group, keys ascending, or the fitted
-    probability of every row.  Keys of other dtypes or several key columns: `glm_by_group`.
+    probability of every row.  Keys of other dtypes or several key columns: `glm_by_group`.  With `by`, `l1_reg` / `l2_reg` > 0
+    fit every group's penalised model (mean log loss + l2_reg / 2 |beta|^2 + l1_reg |beta|_1 over the features, the bias free).
     """
-    if l1_reg > 0.0 or l2_reg > 0.0:
-        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend")
     if max_iter <= 0:
         raise ValueError("Input `max_iter` must be a positive.")
     if by is not None:
-        return _glm_by(x, target, by, "binomial", add_bias, abs(tol), max_iter, null_policy, return_pred)
+        return _glm_by(x, target, by, "binomial", add_bias, abs(tol), max_iter, null_policy, return_pred, l1_reg, l2_reg)
+    if l1_reg > 0.0 or l2_reg > 0.0:
+        raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend; use GLM(family='binomial', "
+                                  "l2_reg=...) or by=")
     from polars.plugins import register_plugin_function
 
     pl = _pl()
@@ -259,7 +261,7 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
                                     pass_name_to_apply=True).alias("__coeffs__")
 
 
-def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_pred):
+def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_pred, l1_reg=0.0, l2_reg=0.0):
     from .linear_models import GLM_FAMILIES
 
     if family not in GLM_FAMILIES:
@@ -267,6 +269,8 @@ def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_
     if max_iter < 1:
         raise ValueError("`max_iter` must be > 1.")
     kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
+    if l1_reg > 0.0 or l2_reg > 0.0:  # (absent = 0 in the plugin: an unpenalised call keeps the kwargs it had)
+        kwargs.update(l1_reg=max(float(l1_reg), 0.0), l2_reg=max(float(l2_reg), 0.0))
     cols = [_formula(by), _formula(target).cast(_dtype())] + [_formula(z) for z in x]
     if return_pred:
         return _plugin("pl_glm_by_pred", cols, kwargs).alias("glm_pred")
@@ -274,7 +278,7 @@ def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_
 
 
 def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool = False, add_bias: bool = False, tol: float = 1e-8,
-                 max_iter: int = 100, null_policy: str = "raise"):
+                 max_iter: int = 100, null_policy: str = "raise", l1_reg: float = 0.0, l2_reg: float = 0.0):
     """
     One GLM per group of a frame (families of `linear_models.GLM_FAMILIES`) from ONE plugin call (`pl_glm_by`: keys in any row
     order, every iteration of a group on chip) -- what fitting `GLM(family=...)` on every group of `df.group_by(by)` computes.
@@ -282,18 +286,20 @@ def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool
     conventions).  Returns a frame with one row per distinct key: columns *by, `coeffs` (bias last; a null list for a group with
     fewer rows than coefficients or a fit that does not end in finite coefficients) and `n_iter`; integer keys come back ascending,
     other keys in order of first appearance.  `return_pred=True`: the input frame with a `glm_pred` column, row for row.
+    `l1_reg` / `l2_reg` > 0: every group's elastic-net penalised fit (`lstsq.glm_by` states the objective).
     """
     args = (family, add_bias, tol, max_iter, null_policy)
+    pen = (l1_reg, l2_reg)
     if return_pred:
         if _is_integer_key(df, by):
-            return df.with_columns(_glm_by(x, target, by, *args, True))
+            return df.with_columns(_glm_by(x, target, by, *args, True, *pen))
         ids, _ = _with_group_ids(df, by)
-        return ids.with_columns(_glm_by(x, target, _GID, *args, True)).drop(_GID)
+        return ids.with_columns(_glm_by(x, target, _GID, *args, True, *pen)).drop(_GID)
     if _is_integer_key(df, by):
-        res = df.select(_glm_by(x, target, by, *args, False)).unnest("glm_by")
+        res = df.select(_glm_by(x, target, by, *args, False, *pen)).unnest("glm_by")
         return res.with_columns(_pl().col(by).cast(df.schema[by]))
     ids, keys = _with_group_ids(df, by)
-    res = ids.select(_glm_by(x, target, _GID, *args, False)).unnest("glm_by")
+    res = ids.select(_glm_by(x, target, _GID, *args, False, *pen)).unnest("glm_by")
     return _join(keys, res, on=[_GID]).drop(_GID)
 
 
