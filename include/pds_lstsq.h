@@ -682,6 +682,56 @@ int pds_glm_enet_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred,
                             uint8_t* row_null);
 /*
+ * pds_glm_report_grouped_* / pds_glm_report_by_key_*: the fit of pds_glm_irls_grouped_* / pds_glm_irls_by_key_* and its report per
+ * group in one call -- the argument lists of those entry points without pred / row_null, and a trailing struct of output pointers.
+ * The groups returned and their coeffs / n_iter / is_null are bit for bit those of the pds_glm_irls_* call on the same frame; the
+ * report is formed afterwards on the device, at the coefficients AS STORED (an f32 frame: the f32 values), in f64 arithmetic
+ * (grouped_glm_report.hip: one wave per group, one more weighted Gram build and one p' x p' inverse; groups longer than the
+ * context option "glm_split_rows" are cut into pieces that stream on many waves and are added in piece order).  No atomics in any
+ * sum: repeated calls are bit-identical.  The unscaled convention of statsmodels' GLM, for a group of n rows, x_i with the
+ * constant 1 last when add_bias is set:
+ *   eta_i = x_i . beta, mu_i = g^-1(eta_i), w_i = 1 / (g'(mu_i)^2 V(mu_i)), I = sum w_i x_i x_i'
+ *   pearson_chi2 = sum (y_i - mu_i)^2 / V(mu_i); df_resid = n - p'
+ *   dispersion = 1 (poisson, binomial), pearson_chi2 / df_resid (gaussian, gamma; NaN when df_resid = 0, and se / z / p / CI / cov too)
+ *   cov = dispersion I^-1, se_j = sqrt(cov_jj), z_j = beta_j / se_j, p_j = erfc(|z_j| / sqrt 2), lo / hi = beta_j -+ 1.959963984540054
+ *   se_j: the normal distribution for every family (statsmodels' use_t = False)
+ *   deviance = sum d_i: gaussian (y - mu)^2, poisson 2 [y ln(y / mu) - (y - mu)], binomial 2 [y ln(y / mu) + (1 - y) ln((1 - y) /
+ *   (1 - mu))], gamma 2 [-ln(y / mu) + (y - mu) / mu], with 0 ln 0 = 0
+ *   null_deviance = the same sum at the constant mean mean_g(y) with a bias, g^-1(0) without (gaussian 0, poisson 1, binomial 0.5;
+ *   gamma: NaN)
+ *   report_null = 1 when is_null = 1 or the factorisation of I meets a pivot that is not a positive finite number: every other
+ *   report field of the group is then NaN except df_resid; the coefficients stay what the fit returned.  A bad group never
+ *   changes another group's bits.
+ * Penalised fits have no report.  1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED).
+ */
+typedef struct {
+    /* each nullable and `space`-resident; the numeric fields are double* for the _f64 entry points, float* for _f32 */
+    void* std_err;       /* [n_groups][p'] */
+    void* z;             /* [n_groups][p'] */
+    void* p;             /* [n_groups][p'] */
+    void* ci_lower;      /* [n_groups][p']  "0.025" */
+    void* ci_upper;      /* [n_groups][p']  "0.975" */
+    void* cov;           /* [n_groups][p'][p'] */
+    void* deviance;      /* [n_groups] */
+    void* null_deviance; /* [n_groups] */
+    void* pearson_chi2;  /* [n_groups] */
+    void* dispersion;    /* [n_groups] */
+    int64_t* df_resid;   /* [n_groups] */
+    uint8_t* report_null; /* [n_groups] */
+} pds_glm_report_out;
+int pds_glm_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                               double* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out);
+int pds_glm_report_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                               float* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out);
+int pds_glm_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int link, int variance, double tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                              double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out);
+int pds_glm_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                              float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out);
+/*
  * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
  * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on
  * chip by the one-sided Jacobi iteration of the single-system call, singular values below the cut are dropped, the coefficients are

@@ -16,6 +16,8 @@ from .lstsq import (  # noqa: F401
     gather,
     glm_by,
     glm_by_key,
+    glm_report_by,
+    glm_report_by_key,
     gram_moments,
     logistic_reg,
     lin_reg,

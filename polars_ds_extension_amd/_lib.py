@@ -22,6 +22,7 @@ EXPORTS = [
     "pds_last_error", "pds_version", "pds_ctx_create", "pds_ctx_destroy", "pds_ctx_set_stream",
     "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_glm_irls_grouped_f64", "pds_glm_irls_grouped_f32", "pds_glm_irls_by_key_f64", "pds_glm_irls_by_key_f32",
     "pds_glm_enet_f64", "pds_glm_enet_f32", "pds_glm_enet_grouped_f64", "pds_glm_enet_grouped_f32", "pds_glm_enet_by_key_f64", "pds_glm_enet_by_key_f32",
+    "pds_glm_report_grouped_f64", "pds_glm_report_grouped_f32", "pds_glm_report_by_key_f64", "pds_glm_report_by_key_f32",
     "pds_lr_rcond_grouped_f64", "pds_lr_rcond_grouped_f32", "pds_lr_rcond_by_key_f64", "pds_lr_rcond_by_key_f32",
     "pds_mixed_reml_grouped_f64", "pds_mixed_reml_grouped_f32", "pds_mixed_reml_by_key_f64", "pds_mixed_reml_by_key_f32",
     "pds_mixed_profile_grouped_f64", "pds_mixed_profile_grouped_f32",
@@ -80,6 +81,12 @@ class ReportF32(C.Structure):
 class ReportGrouped(C.Structure):
     """pds_report_grouped_f64 / _f32: pointers only, so one layout serves both precisions."""
     _fields_ = [(k, C.c_void_p) for k in ("beta", "std_err", "t", "p", "ci_lower", "ci_upper", "r2", "adj_r2", "is_null")]
+
+
+class GlmReportOut(C.Structure):
+    """pds_glm_report_out: nullable output pointers, one layout for both precisions."""
+    _fields_ = [(k, C.c_void_p) for k in ("std_err", "z", "p", "ci_lower", "ci_upper", "cov", "deviance", "null_deviance", "pearson_chi2",
+                                          "dispersion", "df_resid", "report_null")]
 
 
 class PdsError(RuntimeError):

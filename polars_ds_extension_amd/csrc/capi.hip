@@ -29,6 +29,7 @@ namespace pds {
 #include "capi_rolling.hpp"
 #include "capi_models.hpp"
 #include "capi_glm_grouped.hpp"
+#include "capi_glm_report.hpp"
 #include "capi_rcond_grouped.hpp"
 #include "capi_mixed.hpp"
 
@@ -166,6 +167,32 @@ int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null) {
     return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, 0.0f, 0.0f, tol, max_iter, max_groups,
                                        out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
+}
+
+// the grouped GLM report: the fit of pds_glm_irls_grouped_* / _by_key_* and its report per group (capi_glm_report.hpp)
+int pds_glm_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                               double* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out) {
+    return pds::glm_report_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol,
+                                                max_iter, coeffs, n_iter, is_null, out);
+}
+int pds_glm_report_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                               int64_t n_groups, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                               float* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out) {
+    return pds::glm_report_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol,
+                                               max_iter, coeffs, n_iter, is_null, out);
+}
+int pds_glm_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int link, int variance, double tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                              double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out) {
+    return pds::glm_report_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
+                                               out_keys, coeffs, n_iter, is_null, n_groups, out);
+}
+int pds_glm_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                              int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
+                              float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out) {
+    return pds::glm_report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
+                                              out_keys, coeffs, n_iter, is_null, n_groups, out);
 }
 
 // the elastic-net penalised fits: the argument lists of pds_glm_irls_* with l1_reg, l2_reg after `variance` (<= 0: no penalty)

@@ -334,6 +334,27 @@ constexpr int kGiCdSweeps = 1000;
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
                           const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm);
+// ---- grouped_glm_report.hip: the report of a GLM per group at the coefficients in d_coeffs (se, z, p, CI, cov, deviances,
+// dispersion: the definitions stand at the head of that file), one wave per group; 1 .. 16 features.  Every output is nullable.
+// Groups of more than `split_rows` rows are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it) and
+// reported by launch_grouped_glm_report_pieces: d_pieces [n_pieces][3] = (group, first row, end row), d_fin [n_fin][3] = (group,
+// first piece, pieces), d_rec n_pieces records of kGlmReportRec doubles.
+template <typename T>
+struct GlmReportDev {
+    T *se, *z, *p, *lo, *hi, *cov, *deviance, *null_deviance, *pearson, *dispersion;
+    int64_t* df_resid;
+    uint8_t* report_null;
+};
+// a piece's record: [0,256) I [i * 16 + j]; [256,272) X'w; 272 sum w; 273 sum (y - y0); 274 pearson; 275 deviance; 276 the family sum
+constexpr int kGlmReportRec = 280;
+template <typename T>
+int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                              int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
+                              const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+template <typename T>
+int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
+                                     int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
+                                     int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
 // ---- grouped_rcond.hip: lin_reg_w_rcond per group, one wave per group: Gram, one-sided Jacobi of X'X (+ l2_reg) and the minimum-norm
 // solve on chip; 1 .. 16 features.  d_coeffs / d_svals [n_groups][p'] (bias last; singular values descending), d_null [n_groups].
 // rcond is the caller's value: the floor eps_T max(n_g, p') is applied per group.

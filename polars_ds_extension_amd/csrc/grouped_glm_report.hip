@@ -1,0 +1,423 @@
+// grouped_glm_report.hip -- the report of a GLM per group: standard errors, z, p, confidence intervals, deviances and the dispersion
+// of every group of a frame in one kernel, at the coefficients the grouped fit (grouped_irls.hip) left in device memory.  The GLM
+// twin of grouped_report_pass.hip; the definitions are the unscaled convention of statsmodels' GLM:
+//
+//   group of n rows, row i = x_i (the constant 1 last with a bias), beta = the group's coefficients AS STORED (an f32 frame: the f32
+//   values -- the report describes the numbers the caller receives), families / canonical links of glm_dev.hpp:
+//     eta_i = x_i . beta, mu_i = g^-1(eta_i), w_i = 1 / (g'(mu_i)^2 V(mu_i)), I = sum w_i x_i x_i'
+//     pearson_chi2 = sum (y_i - mu_i)^2 / V(mu_i);  df_resid = n - p'
+//     dispersion phi = 1 (poisson, binomial), pearson_chi2 / df_resid (gaussian, gamma; NaN when df_resid = 0, and se / z / p / CI
+//     / cov with it)
+//     cov = phi I^-1, se_j = sqrt(cov_jj), z_j = beta_j / se_j, p_j = erfc(|z_j| / sqrt 2), CI = beta_j -+ 1.959963984540054 se_j
+//     (the normal distribution for every family: statsmodels' use_t = False)
+//     deviance = sum d_i: gaussian (y - mu)^2; poisson 2 [y ln(y / mu) - (y - mu)]; binomial 2 [y ln(y / mu) + (1 - y) ln((1 - y) /
+//     (1 - mu))]; gamma 2 [-ln(y / mu) + (y - mu) / mu]; 0 ln 0 = 0
+//     null_deviance = the same sum at a constant mean mu0: mean_g(y) with a bias; g^-1(0) without (gaussian 0, poisson 1, binomial
+//     0.5, gamma: NaN).  A closed form in (n, sum y, one family sum): gaussian sum (y - y0)^2 (y0 = the group's first y with a
+//     bias -- the shift of grouped_report_pass.hip -- and 0 without), poisson sum y ln y, binomial sum [y ln y + (1 - y) ln(1 - y)],
+//     gamma sum ln y -- no second pass, and the sums of the pieces of a group add up.
+//     report_null = 1 when the fit is null or the factorisation of I meets a pivot that is not a positive finite number: every
+//     report field of the group is then NaN (df_resid = n - p' all the same); the coefficients stay what the fit returned.
+//
+// One wave per group, lane = row, 64 rows per step through a wave-private LDS tile (single pass: no residency), I by
+// v_mfma_f64_16x16x4 with operands (w x, x) and the bias row X'w in the side accumulator (wave_tile_dev.hpp); the scalar sums are
+// per-lane registers folded by wave_sum.  I is staged like the IRLS kernel's gm (index 16 = bias) and inverted in place by a
+// Gauss-Jordan sweep without pivoting (I is symmetric positive definite: every pivot is a Schur complement's diagonal), the 64
+// lanes over the p' x p' entries.  No atomics in any sum: repeated calls are bit-identical.  Arithmetic is f64 for f32 frames too.
+//
+// Groups above `split_rows` are not walked by one wave: the kernel appends them to a list (the one atomic, and the host sorts the
+// list), the host cuts their rows into pieces, grouped_glm_report_piece_kernel streams every piece on a wave of its own into a
+// record (I, X'w and the five sums) and grouped_glm_report_fold_kernel -- one wave per long group -- adds the records in piece order
+// and runs the same epilogue: deterministic whatever the schedule.
+#include "glm_dev.hpp"
+#include "wave_tile_dev.hpp"
+
+#include <algorithm>
+
+namespace pds {
+
+namespace {
+
+constexpr int kGrStride = wave_tile_stride(64);  // doubles per feature row of the tile
+constexpr int kGrG = 18;                         // row stride of the staged matrix (17 x 17: 16 features + bias)
+constexpr int kGrLds = 16 * kGrStride + 64 + 18 + 17 * kGrG + 8;
+constexpr double kGrZ975 = 1.959963984540054;
+
+struct GrSums {
+    double sw, sy, pe, dv, fs;  // sum w, sum (y - y0), pearson, deviance, the family sum of the null deviance
+};
+
+__device__ __forceinline__ double gr_xlogy(double a, double b) { return a > 0.0 ? a * log(b) : 0.0; }  // (0 ln 0 = 0)
+
+// the wave-private carving of a block's LDS
+struct GrLds {
+    double *xt, *wt, *bs, *gm, *sm;
+    __device__ explicit GrLds(double* base) : xt(base), wt(xt + 16 * kGrStride), bs(wt + 64), gm(bs + 18), sm(gm + 17 * kGrG) {}
+};
+
+// rows [r0, r1) of one group at the coefficients in l.bs: I into acc, X'w into column 0 of acc2, the sums (folded) into s
+template <typename T, int P>
+__device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy, int64_t r0, int64_t r1, double y0, int bias, int link,
+                                              int variance, const GrLds& l, int lane, d4& acc, d4& acc2, GrSums& s) {
+    double sw = 0.0, sy = 0.0, pe = 0.0, dv = 0.0, fs = 0.0;
+    for (int64_t base = r0; base < r1; base += 64) {
+        const int64_t r = base + lane;
+        const bool live = r < r1;
+        PDS_WAVE_LDS_SYNC();  // (the previous step's operand reads are done)
+        double eta = bias ? l.bs[P] : 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            const double xv = live ? (double)cx[c][r] : 0.0;
+            l.xt[c * kGrStride + lane] = xv;
+            eta = fma(xv, l.bs[c], eta);
+        }
+        double w = 0.0;
+        if (live) {
+            const double yv = (double)cy[r];
+            const double mu = glm_inv<double>(link, eta);
+            const double d = glm_deriv<double>(link, mu);
+            const double v = glm_var<double>(variance, mu);
+            w = 1.0 / (d * d * v);
+            const double e = yv - mu;
+            pe += e * e / v;
+            const double dy = yv - y0;
+            sy += dy;
+            switch (variance) {
+                case 1:
+                    dv += 2.0 * (gr_xlogy(yv, yv / mu) - e);
+                    fs += gr_xlogy(yv, yv);
+                    break;
+                case 2:
+                    dv += 2.0 * (gr_xlogy(yv, yv / mu) + gr_xlogy(1.0 - yv, (1.0 - yv) / (1.0 - mu)));
+                    fs += gr_xlogy(yv, yv) + gr_xlogy(1.0 - yv, 1.0 - yv);
+                    break;
+                case 3:
+                    dv += 2.0 * (e / mu - log(yv / mu));
+                    fs += log(yv);
+                    break;
+                default:
+                    dv += e * e;
+                    fs += dy * dy;
+                    break;
+            }
+        }
+        sw += w;
+        l.wt[lane] = w;
+        PDS_WAVE_LDS_SYNC();
+        wave_tile_gram<P>(
+            l.xt, kGrStride, (int)std::min<int64_t>(64, r1 - base), lane, [&](int row) { return l.wt[row]; },
+            [&](int c, int row, double wv) { return c == 0 ? wv : 0.0; },  // B column 0 = w: the bias row X'w
+            acc, acc2);
+    }
+    s.sw = wave_sum(sw);
+    s.sy = wave_sum(sy);
+    s.pe = wave_sum(pe);
+    s.dv = wave_sum(dv);
+    s.fs = wave_sum(fs);
+}
+
+// every report field of group g NaN, report_null = 1
+template <typename T>
+__device__ __forceinline__ void gr_write_null(const GlmReportDev<T>& o, int64_t g, int64_t n, int pp, int lane) {
+    const T nanv = (T)__builtin_nan("");
+    if (lane < pp) {
+        const int64_t at = g * pp + lane;
+        if (o.se) o.se[at] = nanv;
+        if (o.z) o.z[at] = nanv;
+        if (o.p) o.p[at] = nanv;
+        if (o.lo) o.lo[at] = nanv;
+        if (o.hi) o.hi[at] = nanv;
+    }
+    if (o.cov)
+        for (int e = lane; e < pp * pp; e += 64) o.cov[g * pp * pp + e] = nanv;
+    if (lane == 0) {
+        if (o.deviance) o.deviance[g] = nanv;
+        if (o.null_deviance) o.null_deviance[g] = nanv;
+        if (o.pearson) o.pearson[g] = nanv;
+        if (o.dispersion) o.dispersion[g] = nanv;
+        if (o.df_resid) o.df_resid[g] = n - pp;
+        if (o.report_null) o.report_null[g] = 1;
+    }
+}
+
+// l.gm holds I (index 16 = bias), l.bs the coefficients, s the group's sums: invert, derive, write
+template <typename T, int P>
+__device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g, int64_t n, int bias, int variance, double y0, const GrLds& l,
+                                            const GrSums& s, int lane) {
+    const int pp = P + bias, ne = pp * pp;
+    auto m = [](int j) { return j < P ? j : 16; };
+    bool bad = false;
+    for (int k = 0; k < pp; ++k) {
+        const int mk = m(k);
+        const double d = l.gm[mk * kGrG + mk];
+        if (!(d > 0.0) || !(d <= 1.79769313486231570e308)) bad = true;  // (wave-uniform: every lane reads the same pivot)
+        const double pv = 1.0 / d;
+        double nv[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int e = lane + 64 * t;
+            nv[t] = 0.0;
+            if (e < ne) {
+                const int i = e / pp, j = e - i * pp;
+                const double aik = l.gm[m(i) * kGrG + mk], akj = l.gm[mk * kGrG + m(j)], aij = l.gm[m(i) * kGrG + m(j)];
+                nv[t] = i == k ? (j == k ? pv : akj * pv) : (j == k ? -(aik * pv) : fma(-aik, akj * pv, aij));
+            }
+        }
+        PDS_WAVE_LDS_SYNC();
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int e = lane + 64 * t;
+            if (e < ne) {
+                const int i = e / pp, j = e - i * pp;
+                l.gm[m(i) * kGrG + m(j)] = nv[t];
+            }
+        }
+        PDS_WAVE_LDS_SYNC();
+    }
+    if (bad) {
+        gr_write_null<T>(o, g, n, pp, lane);
+        return;
+    }
+    const double nanv = __builtin_nan("");
+    const double nn = (double)n;
+    const int64_t df = n - pp;
+    const double phi = (variance == 1 || variance == 2) ? 1.0 : (df > 0 ? s.pe / (double)df : nanv);
+    const double sy = s.sy + nn * y0;  // sum y
+    double nd;
+    if (bias) {
+        const double ym = sy / nn;
+        switch (variance) {
+            case 1: nd = 2.0 * (s.fs - gr_xlogy(sy, ym)); break;
+            case 2: nd = 2.0 * (s.fs - gr_xlogy(sy, ym) - gr_xlogy(nn - sy, 1.0 - ym)); break;
+            case 3: nd = 2.0 * (nn * log(ym) - s.fs); break;
+            default: nd = s.fs - s.sy * s.sy / nn; break;
+        }
+    } else {
+        switch (variance) {
+            case 1: nd = 2.0 * (s.fs - sy + nn); break;
+            case 2: nd = 2.0 * (s.fs + nn * 0.693147180559945309417); break;
+            case 3: nd = nanv; break;
+            default: nd = s.fs; break;  // (y0 = 0 without a bias: sum y^2)
+        }
+    }
+    if (lane < pp) {
+        const int mj = m(lane);
+        const double b = l.bs[lane];  // (the bias sits at bs[P] = bs[lane])
+        const double se = sqrt(phi * l.gm[mj * kGrG + mj]);
+        const double z = b / se;
+        const int64_t at = g * pp + lane;
+        if (o.se) o.se[at] = (T)se;
+        if (o.z) o.z[at] = (T)z;
+        if (o.p) o.p[at] = (T)erfc(fabs(z) * 0.707106781186547524401);
+        if (o.lo) o.lo[at] = (T)(b - kGrZ975 * se);
+        if (o.hi) o.hi[at] = (T)(b + kGrZ975 * se);
+    }
+    if (o.cov)
+        for (int e = lane; e < ne; e += 64) {
+            const int i = e / pp, j = e - i * pp;
+            o.cov[g * ne + e] = (T)(phi * l.gm[m(i) * kGrG + m(j)]);
+        }
+    if (lane == 0) {
+        if (o.deviance) o.deviance[g] = (T)s.dv;
+        if (o.null_deviance) o.null_deviance[g] = (T)nd;
+        if (o.pearson) o.pearson[g] = (T)s.pe;
+        if (o.dispersion) o.dispersion[g] = (T)phi;
+        if (o.df_resid) o.df_resid[g] = df;
+        if (o.report_null) o.report_null[g] = 0;
+    }
+}
+
+template <typename T, int P>
+__device__ __forceinline__ void gr_load_beta(const T* __restrict__ coeffs, int64_t g, int bias, const GrLds& l, int lane) {
+    const int pp = P + bias;
+    PDS_WAVE_LDS_SYNC();  // (the previous group's reads are done)
+    if (lane < pp) l.bs[lane] = (double)coeffs[g * pp + lane];  // (the bias, last, lands at bs[P], where eta reads it)
+    PDS_WAVE_LDS_SYNC();
+}
+
+// the shift of the gaussian sums: the group's first y with a bias (the mean is the null model), nothing otherwise
+template <typename T>
+__device__ __forceinline__ double gr_shift(gptr<T> cy, int64_t first_row, int bias, int variance) {
+    return (variance == 0 && bias) ? (double)cy[first_row] : 0.0;
+}
+
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* __restrict__ cols, int bias, int64_t n_rows,
+                                                                const int64_t* __restrict__ off, int64_t n_groups, int link,
+                                                                int variance, int64_t split_rows, const T* __restrict__ coeffs,
+                                                                const uint8_t* __restrict__ is_null, GlmReportDev<T> o,
+                                                                int64_t* __restrict__ long_list, unsigned* __restrict__ long_count,
+                                                                int64_t long_cap) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    const int pp = P + bias;
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const int64_t r0 = off[g], n = off[g + 1] - r0;
+        const bool bad = r0 < 0 || n < 0 || r0 + n > n_rows;  // (offsets that leave the frame: nothing is read)
+        if (bad || n < pp || is_null[g]) {
+            gr_write_null<T>(o, g, bad ? 0 : n, pp, lane);
+            continue;
+        }
+        if (n > split_rows) {  // the piece route (the order of the list does not matter: the host sorts it)
+            if (lane == 0) {
+                const unsigned k = atomicAdd(long_count, 1u);
+                if ((int64_t)k < long_cap) long_list[k] = g;
+            }
+            continue;
+        }
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        const double y0 = gr_shift<T>(cy, r0, bias, variance);
+        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+        GrSums s;
+        gr_accumulate<T, P>(cx, cy, r0, r0 + n, y0, bias, link, variance, l, lane, acc, acc2, s);
+        PDS_WAVE_LDS_SYNC();
+        wave_tile_for_d(
+            lane,
+            [&](int i, int c, double v, double side) {
+                l.gm[i * kGrG + c] = v;
+                if (c == 0) {
+                    l.gm[i * kGrG + 16] = side;
+                    l.gm[16 * kGrG + i] = side;
+                }
+            },
+            acc, acc2);
+        if (lane == 0) l.gm[16 * kGrG + 16] = s.sw;
+        PDS_WAVE_LDS_SYNC();
+        gr_epilogue<T, P>(o, g, n, bias, variance, y0, l, s, lane);
+    }
+}
+
+// piece k = rows [pieces[3 k + 1], pieces[3 k + 2]) of group pieces[3 k]: its record rec[k * kGlmReportRec ..]
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_piece_kernel(const T* const* __restrict__ cols, int bias,
+                                                                      const int64_t* __restrict__ off, int link, int variance,
+                                                                      const T* __restrict__ coeffs, const int64_t* __restrict__ pieces,
+                                                                      int64_t n_pieces, double* __restrict__ rec) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    for (int64_t k = blockIdx.x; k < n_pieces; k += gridDim.x) {
+        const int64_t g = pieces[3 * k], r0 = pieces[3 * k + 1], r1 = pieces[3 * k + 2];
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        const double y0 = gr_shift<T>(cy, off[g], bias, variance);
+        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+        GrSums s;
+        gr_accumulate<T, P>(cx, cy, r0, r1, y0, bias, link, variance, l, lane, acc, acc2, s);
+        double* out = rec + k * kGlmReportRec;
+        wave_tile_for_d(
+            lane,
+            [&](int i, int c, double v, double side) {
+                out[i * 16 + c] = v;
+                if (c == 0) out[256 + i] = side;
+            },
+            acc, acc2);
+        if (lane == 0) {
+            out[272] = s.sw;
+            out[273] = s.sy;
+            out[274] = s.pe;
+            out[275] = s.dv;
+            out[276] = s.fs;
+        }
+    }
+}
+
+// long group j = fin[3 j]: its records fin[3 j + 1] .. + fin[3 j + 2], added in piece order, then the epilogue of the one-wave route
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_fold_kernel(const T* const* __restrict__ cols, int bias,
+                                                                     const int64_t* __restrict__ off, int variance,
+                                                                     const T* __restrict__ coeffs, const int64_t* __restrict__ fin,
+                                                                     int64_t n_fin, const double* __restrict__ rec, GlmReportDev<T> o) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    const gptr<T> cy = as_global(cols[P]);
+    for (int64_t j = blockIdx.x; j < n_fin; j += gridDim.x) {
+        const int64_t g = fin[3 * j], first = fin[3 * j + 1], cnt = fin[3 * j + 2];
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        for (int e = lane; e < 277; e += 64) {
+            double v = 0.0;
+            for (int64_t k = 0; k < cnt; ++k) v += rec[(first + k) * kGlmReportRec + e];
+            if (e < 256) {
+                l.gm[(e >> 4) * kGrG + (e & 15)] = v;
+            } else if (e < 272) {
+                l.gm[(e - 256) * kGrG + 16] = v;
+                l.gm[16 * kGrG + (e - 256)] = v;
+            } else {
+                if (e == 272) l.gm[16 * kGrG + 16] = v;
+                l.sm[e - 272] = v;
+            }
+        }
+        PDS_WAVE_LDS_SYNC();
+        GrSums s;
+        s.sw = l.sm[0];
+        s.sy = l.sm[1];
+        s.pe = l.sm[2];
+        s.dv = l.sm[3];
+        s.fs = l.sm[4];
+        const int64_t r0 = off[g];
+        gr_epilogue<T, P>(o, g, off[g + 1] - r0, bias, variance, gr_shift<T>(cy, r0, bias, variance), l, s, lane);
+    }
+}
+
+}  // namespace
+
+template <typename T>
+int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                              int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
+                              const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
+    if (n_groups <= 0) return PDS_OK;
+    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+    KernelTimer timer(ctx, kKindPass2);
+    const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((grouped_glm_report_kernel<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows,
+                           d_off, n_groups, link, variance, split_rows, d_coeffs, d_null, out, d_long_list, d_long_count,
+                           long_cap);
+    });
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
+template <typename T>
+int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
+                                     int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
+                                     int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec) {
+    if (n_pieces <= 0 || n_fin <= 0) return PDS_OK;
+    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+    KernelTimer timer(ctx, kKindPass2);
+    const int nbp = (int)std::min<int64_t>(n_pieces, (int64_t)ctx->num_cus * 32);
+    const int nbf = (int)std::min<int64_t>(n_fin, (int64_t)ctx->num_cus * 32);
+    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+        constexpr int P = decltype(pc)::value;
+        hipLaunchKernelGGL((grouped_glm_report_piece_kernel<T, P>), dim3(nbp), dim3(64), 0, ctx->stream, d_cols, bias, d_off, link, variance,
+                           d_coeffs, d_pieces, n_pieces, d_rec);
+        hipLaunchKernelGGL((grouped_glm_report_fold_kernel<T, P>), dim3(nbf), dim3(64), 0, ctx->stream, d_cols, bias, d_off, variance,
+                           d_coeffs, d_fin, n_fin, d_rec, out);
+    });
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
+#define PDS_GR_ARGS(T)                                                                                                                  \
+    pds_ctx*, const T* const*, int, int, int64_t, const int64_t*, int64_t, int, int, int64_t, const T*, const uint8_t*, const GlmReportDev<T>&, \
+        int64_t*, unsigned*, int64_t
+#define PDS_GR_PIECE_ARGS(T)                                                                                                         \
+    pds_ctx*, const T* const*, int, int, const int64_t*, int, int, const T*, const GlmReportDev<T>&, const int64_t*, int64_t, const int64_t*, \
+        int64_t, double*
+template int launch_grouped_glm_report<double>(PDS_GR_ARGS(double));
+template int launch_grouped_glm_report<float>(PDS_GR_ARGS(float));
+template int launch_grouped_glm_report_pieces<double>(PDS_GR_PIECE_ARGS(double));
+template int launch_grouped_glm_report_pieces<float>(PDS_GR_PIECE_ARGS(float));
+#undef PDS_GR_ARGS
+#undef PDS_GR_PIECE_ARGS
+
+}  // namespace pds

@@ -1,5 +1,6 @@
 // plugin_glm.hpp -- pl_logistic_coeffs / pl_logistic_pred (the reference's symbols, src/num_ext/logistic_regression.rs) and the
-// key-aware pl_glm_by / pl_glm_by_pred (+ _f32): GLM fits by IRLS through pds_glm_irls_grouped_* / pds_glm_irls_by_key_*
+// key-aware pl_glm_by / pl_glm_by_pred (+ _f32): GLM fits by IRLS through pds_glm_irls_grouped_* / pds_glm_irls_by_key_*; pl_glm_report_by
+// (+ _f32): the fit and its report per group through pds_glm_report_grouped_* / pds_glm_report_by_key_*
 // Part of the one translation unit plugin.cpp (included there, inside its anonymous namespace, after plugin_exprs.hpp).
 #pragma once
 
@@ -29,6 +30,44 @@ inline void glm_family_codes(const std::string& family, int* link, int* variance
     if (id < 0) raise("unknown GLM family '" + family + "': gaussian / normal, poisson, binomial / logistic, gamma");
     *link = id;
     *variance = id;
+}
+
+// Frames with nulls, prepared on the host for the offsets entry points: rows in key order (a stable sort of the row indices when the
+// keys are not ordered), the policy applied row by row inside every group -- "skip" drops a row with any null, a fill policy fills
+// the features and drops the rows whose target is null, everything else keeps the rows with NaN for the nulls.  keys / off: one
+// entry per group (off: n_groups + 1), kept: the surviving rows column by column, src_row: the frame row of every surviving row.
+template <typename T>
+void glm_prepare_rows(const std::vector<Column<T>>& cols, const int64_t* ikey, int64_t n, const Policy& pol, RawVec<int64_t>& keys,
+                      std::vector<int64_t>& off, std::vector<std::vector<T>>& kept, std::vector<int64_t>& src_row) {
+    std::vector<int64_t> perm(n);
+    for (int64_t i = 0; i < n; ++i) perm[i] = i;
+    bool ordered = true;
+    for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
+    if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
+    const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
+    const size_t nc = cols.size();
+    auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
+    kept.assign(nc, {});
+    for (auto& v : kept) v.reserve((size_t)n);
+    src_row.reserve((size_t)n);
+    const T nanv = std::numeric_limits<T>::quiet_NaN();
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = perm[i];
+        if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
+            off.push_back((int64_t)kept[0].size());
+            keys.push_back(ikey[r]);
+        }
+        bool keep = true;
+        if (skip)
+            for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
+        else if (fill)
+            keep = !is_null(0, r);
+        if (!keep) continue;
+        for (size_t c = 0; c < nc; ++c) kept[c].push_back(is_null(c, r) ? (fill ? (T)pol.fill : nanv) : cols[c].data()[r]);
+        src_row.push_back(r);
+    }
+    off.push_back((int64_t)kept[0].size());
+    if (kept[0].empty()) raise("Empty data");
 }
 
 // test seam: the first capacity guess of pl_glm_by (<= 0: the default rule of do_lr_by), so that the retry can be exercised
@@ -111,38 +150,12 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
             for (int64_t i = 0; i < n; ++i) row_valid[i] = row_null[i] ? 0 : 1;
         }
     } else {
-        std::vector<int64_t> perm(n);
-        for (int64_t i = 0; i < n; ++i) perm[i] = i;
-        bool ordered = true;
-        for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
-        if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
-        const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
-        const size_t nc = cols.size();
-        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
-        std::vector<std::vector<T>> kept(nc);
-        for (auto& v : kept) v.reserve((size_t)n);
+        std::vector<std::vector<T>> kept;
         std::vector<int64_t> off, src_row;
-        src_row.reserve((size_t)n);
         const T nanv = std::numeric_limits<T>::quiet_NaN();
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t r = perm[i];
-            if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
-                off.push_back((int64_t)kept[0].size());
-                keys.push_back(ikey[r]);
-            }
-            bool keep = true;
-            if (skip)
-                for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
-            else if (fill)
-                keep = !is_null(0, r);
-            if (!keep) continue;
-            for (size_t c = 0; c < nc; ++c) kept[c].push_back(is_null(c, r) ? (fill ? (T)pol.fill : nanv) : cols[c].data()[r]);
-            src_row.push_back(r);
-        }
-        off.push_back((int64_t)kept[0].size());
+        glm_prepare_rows<T>(cols, ikey, n, pol, keys, off, kept, src_row);
         ng = (int64_t)keys.size();
         const int64_t nk = (int64_t)kept[0].size();
-        if (nk == 0) raise("Empty data");
         std::vector<const T*> ptrs;
         for (auto& v : kept) ptrs.push_back(v.data());
         cobuf = raw_buffer<T>((size_t)ng * pp);
@@ -197,6 +210,174 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
     sk.push_back(list_schema<T>("coeffs"));
     sk.push_back(make_schema("i", "n_iter"));
     export_series(out, make_schema("+s", "", std::move(sk)), struct_array(ng, std::move(kids)));
+}
+
+// the fields of pl_glm_report_by's Struct behind the key: large-utf8, nine floats, int32
+constexpr const char* kGlmReportFields[11] = {"features", "beta", "std_err", "z", "p>|z|", "0.025", "0.975", "deviance", "null_deviance",
+                                              "dispersion", "n_iter"};
+
+// ------------------------------------------------------------------------------------------------- pl_glm_report_by (new)
+// inputs and kwargs: those of pl_glm_by; a positive l1_reg / l2_reg is an error (penalised fits have no report).  One Struct
+// "glm_report" in long format, built the way do_report_by builds the grouped linear report: n_groups x p' rows {<key>, features,
+// beta, std_err, z, p>|z|, 0.025, 0.975, deviance, null_deviance, dispersion, n_iter}, groups in ascending key order (the null key's
+// group last, with a null key), coefficients in input order with __bias__ last, the per-group fields broadcast over a group's rows.
+// A group with a null report keeps its p' rows with key, features and n_iter set and null numeric fields (beta stays when the fit
+// itself is not null).  z and p come from the normal distribution for every family.  Null-free frames make ONE
+// pds_glm_report_by_key_* call (capacity guess and one retry); frames with nulls are prepared on the host exactly as do_glm_by
+// prepares them (glm_prepare_rows) and go to the offsets entry point.
+template <typename T> struct GlmReportApi;
+template <> struct GlmReportApi<double> {
+    static constexpr auto grouped = pds_glm_report_grouped_f64;
+    static constexpr auto by_key = pds_glm_report_by_key_f64;
+};
+template <> struct GlmReportApi<float> {
+    static constexpr auto grouped = pds_glm_report_grouped_f32;
+    static constexpr auto by_key = pds_glm_report_by_key_f32;
+};
+
+template <typename T>
+void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out) {
+    if (n_in < 3) raise("pl_glm_report_by needs a key, a target and at least one feature");
+    int link = 0, variance = 0;
+    glm_family_codes(kw_str(kw, "family", "gaussian"), &link, &variance);
+    const int max_iter = (int)kw_i64(kw, "max_iter", 100);
+    if (max_iter < 1) raise("`max_iter` must be > 1.");
+    if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0) raise("pl_glm_report_by: penalised fits have no report");
+    const T tol = (T)std::fabs(kw_f64(kw, "tol", 1e-8));
+    const int bias = kw_bool(kw, "bias") ? 1 : 0;
+    const int n_feat = (int)n_in - 2;
+    if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
+    const int pp = n_feat + bias;
+    auto key = import_series<int64_t>(in[0]);
+    std::vector<Column<T>> cols;  // [y, x1..xp]
+    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
+    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
+    bool any_null = false;
+    for (auto& c : cols) any_null |= c.null_count > 0;
+    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
+    const int64_t n = key.size();
+    for (auto& c : cols)
+        if (c.size() != n) raise("input columns differ in length");
+    if (n == 0) raise("Empty data");
+    int64_t null_stand_in = 0;
+    const bool null_group = null_key_stand_in(key, n, "pl_glm_report_by", &null_stand_in);
+    const int64_t* ikey = key.data();
+    RawVec<int64_t> keys;
+    ByteVec vb[6], gb[3], itbuf;  // beta, se, z, p, lo, hi [ng][p']; deviance, null_deviance, dispersion [ng]; n_iter [ng]
+    RawVec<uint8_t> nulls, rnulls;
+    int64_t ng = 0;
+    pds_glm_report_out rep{};  // (cov, pearson_chi2, df_resid: not asked for)
+    auto size_outputs = [&](int64_t cap) {
+        keys.resize(cap);
+        for (auto& b : vb) b = raw_buffer<T>((size_t)cap * pp);
+        for (auto& b : gb) b = raw_buffer<T>((size_t)cap);
+        itbuf = raw_buffer<int32_t>((size_t)cap);
+        nulls.resize(cap);
+        rnulls.resize(cap);
+        rep.std_err = as<T>(vb[1]); rep.z = as<T>(vb[2]); rep.p = as<T>(vb[3]); rep.ci_lower = as<T>(vb[4]); rep.ci_upper = as<T>(vb[5]);
+        rep.deviance = as<T>(gb[0]); rep.null_deviance = as<T>(gb[1]); rep.dispersion = as<T>(gb[2]);
+        rep.report_null = rnulls.data();
+    };
+    if (!any_null) {
+        std::vector<const T*> ptrs;
+        for (auto& c : cols) ptrs.push_back(c.data());
+        int64_t cap = g_glm_by_first_cap > 0 ? std::min<int64_t>(g_glm_by_first_cap, n)
+                                             : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
+        for (int attempt = 0;; ++attempt) {
+            size_outputs(cap);
+            const int rc = GlmReportApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
+                                                   keys.data(), as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &ng, &rep);
+            if (rc != 0 && attempt == 0 && ng > cap) {
+                cap = ng;
+                continue;
+            }
+            check(rc);
+            break;
+        }
+    } else {
+        std::vector<std::vector<T>> kept;
+        std::vector<int64_t> off, src_row;
+        glm_prepare_rows<T>(cols, ikey, n, pol, keys, off, kept, src_row);
+        ng = (int64_t)keys.size();
+        std::vector<const T*> ptrs;
+        for (auto& v : kept) ptrs.push_back(v.data());
+        size_outputs(ng);  // (keys already holds its ng values)
+        check(GlmReportApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, (int64_t)kept[0].size(), off.data(), ng, PDS_HOST, bias, link, variance,
+                                       tol, max_iter, as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep));
+    }
+    // ---- the long frame
+    const int64_t rows = ng * pp;
+    std::vector<std::string> names;
+    for (size_t i = 1; i < cols.size(); ++i) names.push_back(cols[i].name);
+    if (bias) names.push_back("__bias__");
+    std::vector<std::unique_ptr<ArrowArray>> kids;
+    {
+        ByteVec kb = raw_buffer<int64_t>((size_t)rows);
+        int64_t* kd = as<int64_t>(kb);
+        std::vector<uint8_t> kvalid;
+        if (null_group) kvalid.assign((size_t)rows, 1);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int i = 0; i < pp; ++i) {
+                kd[g * pp + i] = keys[g];
+                if (null_group && keys[g] == null_stand_in) kvalid[g * pp + i] = 0;
+            }
+        kids.push_back(prim_array_take<int64_t>(std::move(kb), rows, null_group ? kvalid.data() : nullptr));
+    }
+    {   // features: the p' names, once per group (large-utf8: int64 offsets)
+        std::string one;
+        std::vector<int64_t> o1 = {0};
+        for (auto& s : names) {
+            one += s;
+            o1.push_back((int64_t)one.size());
+        }
+        ByteVec ob = raw_buffer<int64_t>((size_t)rows + 1), db = raw_buffer<char>((size_t)ng * one.size());
+        int64_t* od = as<int64_t>(ob);
+        for (int64_t g = 0; g < ng; ++g) {
+            for (int i = 0; i < pp; ++i) od[g * pp + i] = g * (int64_t)one.size() + o1[i];
+            if (!one.empty()) std::memcpy(db.data() + g * one.size(), one.data(), one.size());
+        }
+        od[rows] = ng * (int64_t)one.size();
+        std::vector<ByteVec> bufs;
+        bufs.emplace_back();
+        bufs.push_back(std::move(ob));
+        bufs.push_back(std::move(db));
+        kids.push_back(make_array(rows, 0, std::move(bufs), {false, true, true}));
+    }
+    std::vector<uint8_t> fit_valid((size_t)rows, 1), rep_valid((size_t)rows, 1);
+    bool any_fit_null = false, any_rep_null = false;
+    for (int64_t g = 0; g < ng; ++g) {
+        if (nulls[g]) any_fit_null = true;
+        if (rnulls[g]) any_rep_null = true;
+        for (int i = 0; i < pp; ++i) {
+            fit_valid[g * pp + i] = nulls[g] ? 0 : 1;
+            rep_valid[g * pp + i] = rnulls[g] ? 0 : 1;
+        }
+    }
+    const uint8_t* vr = any_rep_null ? rep_valid.data() : nullptr;
+    kids.push_back(prim_array_take<T>(std::move(vb[0]), rows, any_fit_null ? fit_valid.data() : nullptr));
+    for (int k = 1; k < 6; ++k) kids.push_back(prim_array_take<T>(std::move(vb[k]), rows, vr));
+    for (auto& b : gb) {
+        ByteVec wide = raw_buffer<T>((size_t)rows);
+        const T* sv = as<T>(b);
+        T* dv = as<T>(wide);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
+        kids.push_back(prim_array_take<T>(std::move(wide), rows, vr));
+    }
+    {
+        ByteVec wide = raw_buffer<int32_t>((size_t)rows);
+        const int32_t* sv = as<int32_t>(itbuf);
+        int32_t* dv = as<int32_t>(wide);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
+        kids.push_back(prim_array_take<int32_t>(std::move(wide), rows, nullptr));
+    }
+    std::vector<std::unique_ptr<ArrowSchema>> sk;
+    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(make_schema("U", kGlmReportFields[0]));
+    for (int i = 1; i < 10; ++i) sk.push_back(make_schema(fmt_of<T>(), kGlmReportFields[i]));
+    sk.push_back(make_schema("i", kGlmReportFields[10]));
+    export_series(out, make_schema("+s", "glm_report", std::move(sk)), struct_array(rows, std::move(kids)));
 }
 
 // ------------------------------------------------------------------------------------------------- pl_logistic_coeffs / pl_logistic_pred

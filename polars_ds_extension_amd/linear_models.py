@@ -472,13 +472,20 @@ class GLM:
     def bias(self) -> float:
         return float(self._bias)
 
-    def fit(self, X, y, null_policy: str = "ignore"):
+    def fit(self, X, y, null_policy: str = "ignore", report: bool = False):
+        """`report=True`: the fit goes through the grouped entry point with ONE group covering the frame (`lstsq.glm_report_by`, up to
+        16 features, no penalty) and fills `std_errors_`, `z_`, `p_values_`, `deviance_`, `null_deviance_`, `dispersion_`, `df_resid_`
+        (the bias last; z and p from the normal distribution for every family); `report()` returns them.  The default path is the
+        one-model iteration, untouched."""
         X = _as_matrix(X)
         y = _target(y, int(X.shape[0]))
         X, y = _handle_nans_in_np(X, y, null_policy)
         n, p = int(X.shape[0]), int(X.shape[1])
         if n < p or n == 0:
             raise ValueError("Not enough data.")  # LinearModel::fit, src/linear/lr/mod.rs:114-125
+        self._report = None
+        if report:
+            return self._fit_report(X, y, n)
         ctx = lstsq.default_context()
         cols = lstsq._Cols(y, _columns(X))
         lstsq._follow(ctx, cols)
@@ -496,6 +503,42 @@ class GLM:
         self._coeffs, self._bias = (co[:-1].copy(), float(co[-1])) if self.add_bias else (co.copy(), 0.0)
         self.n_iter_ = int(n_iter.value)
         return self
+
+    def _fit_report(self, X, y, n: int):
+        rep = lstsq.glm_report_by(*_columns(X), target=y, group_offsets=[0, n], family=self.family, add_bias=self.add_bias, tol=self.tol,
+                                  max_iter=self.max_iter, l1_reg=self.l1_reg, l2_reg=self.l2_reg)
+        host = {k: (v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)) for k, v in rep.items() if k != "features"}
+        if int(host["is_null"][0]):
+            raise ValueError("The fit did not end in finite coefficients.")
+        co = host["beta"][0].astype(np.float64)
+        self._coeffs, self._bias = (co[:-1].copy(), float(co[-1])) if self.add_bias else (co.copy(), 0.0)
+        self.n_iter_ = int(host["n_iter"][0])
+        self.std_errors_, self.z_, self.p_values_ = (host[k][0].astype(np.float64) for k in ("std_err", "z", "p>|z|"))
+        self.ci_lower_, self.ci_upper_ = host["0.025"][0].astype(np.float64), host["0.975"][0].astype(np.float64)
+        self.deviance_, self.null_deviance_, self.dispersion_ = (float(host[k][0]) for k in ("deviance", "null_deviance", "dispersion"))
+        self.df_resid_ = int(host["df_resid"][0])
+        self._report = True
+        return self
+
+    def report_dict(self) -> dict:
+        """One entry per coefficient (the bias last): estimate, standard error, z, the two-sided normal p-value and the 95 % interval,
+        with the model's deviance, null deviance and dispersion repeated on every row."""
+        if not self.is_fit() or not getattr(self, "_report", None):
+            raise ValueError("Fit the model with `report=True` first.")
+        p = len(self._coeffs)
+        names = list(self.feature_names_in_) if len(self.feature_names_in_) == p else [f"x{j + 1}" for j in range(p)]
+        beta = np.append(self._coeffs, self._bias) if self.add_bias else self._coeffs.copy()
+        k = len(beta)
+        return {"features": names + (["__bias__"] if self.add_bias else []), "beta": beta, "std_err": self.std_errors_, "z": self.z_,
+                "p>|z|": self.p_values_, "0.025": self.ci_lower_, "0.975": self.ci_upper_, "deviance": np.full(k, self.deviance_),
+                "null_deviance": np.full(k, self.null_deviance_), "dispersion": np.full(k, self.dispersion_)}
+
+    def report(self):
+        """`report_dict` as a Polars dataframe; raises when the model was fitted without `report=True`."""
+        d = self.report_dict()
+        import polars as pl
+
+        return pl.DataFrame(d)
 
     def fit_df(self, df, features: List[str], target: str, null_policy: str = "skip", show_report: bool = False):
         X, y = _Fitted._frame_to_numpy(self, df, features, target, null_policy)

@@ -21,7 +21,7 @@ from . import _lib, config
 
 __all__ = [
     "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
-    "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "logistic_reg", "mixed_reml", "mixed_reml_profile",
+    "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "glm_report_by", "glm_report_by_key", "logistic_reg", "mixed_reml", "mixed_reml_profile",
     "recursive_lin_reg", "lin_reg_w_rcond", "lin_reg_w_rcond_by", "lin_reg_w_rcond_by_key", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
@@ -1491,6 +1491,106 @@ def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False
     if return_pred:
         return keys, coeffs[:g], iters[:g], nulls[:g], pred, rnull
     return keys, coeffs[:g], iters[:g], nulls[:g]
+
+
+_GLM_REPORT_COEF = ("std_err", "z", "p", "ci_lower", "ci_upper")
+_GLM_REPORT_GROUP = ("deviance", "null_deviance", "pearson_chi2", "dispersion")
+
+
+def _glm_report_outs(cols: _Cols, ng: int, pp: int, return_cov: bool):
+    outs = {"beta": _out_like(cols, (ng, pp)), "n_iter": _out_i32(cols, ng), "is_null": _out_u8(cols, ng)}
+    for k in _GLM_REPORT_COEF:
+        outs[k] = _out_like(cols, (ng, pp))
+    outs["cov"] = _out_like(cols, (ng, pp, pp)) if return_cov else (None, C.c_void_p(None))
+    for k in _GLM_REPORT_GROUP:
+        outs[k] = _out_like(cols, (ng,))
+    outs["df_resid"] = _out_int(cols, ng, "int64")
+    outs["report_null"] = _out_u8(cols, ng)
+    rep = _lib.GlmReportOut(*[outs[k][1] for k in (*_GLM_REPORT_COEF, "cov", *_GLM_REPORT_GROUP, "df_resid", "report_null")])
+    return outs, rep
+
+
+def _glm_report_dict(outs, n_feat, add_bias, feature_names, return_cov, g=None):
+    names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(n_feat)]
+    if add_bias:
+        names.append("__bias__")
+    cut = (lambda a: a[:g]) if g is not None else (lambda a: a)
+    d = {"features": names, "beta": cut(outs["beta"][0]), "std_err": cut(outs["std_err"][0]), "z": cut(outs["z"][0]),
+         "p>|z|": cut(outs["p"][0]), "0.025": cut(outs["ci_lower"][0]), "0.975": cut(outs["ci_upper"][0])}
+    for k in (*_GLM_REPORT_GROUP, "df_resid", "n_iter", "is_null", "report_null"):
+        d[k] = cut(outs[k][0])
+    if return_cov:
+        d["cov"] = cut(outs["cov"][0])
+    return d
+
+
+def _glm_report_check(x, max_iter, what, penalties):
+    _glm_check(x, max_iter, what)
+    if any(float(v) > 0.0 for v in penalties):
+        raise NotImplementedError(f"{what}: penalised fits have no report")
+
+
+def glm_report_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+                  feature_names: Sequence[str] | None = None, return_cov: bool = False, ctx: Context | None = None, l1_reg: float = 0.0,
+                  l2_reg: float = 0.0) -> dict:
+    """
+    The fit of `glm_by` and its report per group in one call (`pds_glm_report_grouped_*`): the GLM twin of `lin_reg_report_by`.
+    "beta", "n_iter" and "is_null" are bit for bit what `glm_by` returns on the same frame; the report is formed on the device at
+    those coefficients (for an f32 frame: the f32 values), in the unscaled convention of statsmodels' `GLM`: with mu = g^-1(x . beta),
+    w = 1 / (g'(mu)^2 V(mu)) and I = sum w x x', cov = dispersion * I^-1, std_err = sqrt(diag cov), z = beta / std_err,
+    p = erfc(|z| / sqrt 2) and the interval beta -+ 1.959963984540054 std_err -- the NORMAL distribution for every family
+    (statsmodels' `use_t=False`), never Student's t.  dispersion is 1 for poisson / binomial and pearson_chi2 / df_resid for
+    gaussian / gamma (NaN when df_resid = n - p' is 0, and the standard errors with it); deviance and null_deviance (the deviance at
+    the group's mean with a bias, at g^-1(0) without: NaN for gamma) are the families' unit deviances summed over the group.
+    Returns a dict in the memory space of the inputs: "beta", "std_err", "z", "p>|z|", "0.025", "0.975" [G, p'] (bias last);
+    "deviance", "null_deviance", "pearson_chi2", "dispersion", "df_resid" (int64), "n_iter", "is_null", "report_null" [G];
+    "features"; "cov" [G, p', p'] with `return_cov`.  report_null = 1 for a null fit and for a group whose I has no positive
+    finite pivots (an all-zero column): its report fields are NaN, its coefficients stay what the fit returned.
+    Penalised fits have no report: `l1_reg` / `l2_reg` > 0 raise NotImplementedError.
+    """
+    _glm_report_check(x, max_iter, "glm_report_by", (l1_reg, l2_reg))
+    link, var = _glm_family(family)
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    off, off_p = _offsets_arg(cols, group_offsets)
+    ng = int(off.shape[0]) - 1
+    outs, rep = _glm_report_outs(cols, ng, pp, return_cov)
+    _lib.check(ctx.fn("pds_glm_report_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
+                                                int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)),
+                                                outs["beta"][1], outs["n_iter"][1], outs["is_null"][1], C.byref(rep)))
+    return _glm_report_dict(outs, cols.n_feat, add_bias, feature_names, return_cov)
+
+
+def glm_report_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+                      feature_names: Sequence[str] | None = None, return_cov: bool = False, max_groups: int | None = None,
+                      ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0) -> dict:
+    """
+    `glm_report_by` for an integer key column in ANY row order (`pds_glm_report_by_key_*`): the frame is brought into key order on the
+    device as `glm_by_key` does (nothing moves when the keys are already non-decreasing) and reported where it lies.  Returns the
+    dict of `glm_report_by` plus "keys" (ascending).  The normal distribution is used for every family.
+    """
+    _glm_report_check(x, max_iter, "glm_report_by_key", (l1_reg, l2_reg))
+    link, var = _glm_family(family)
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    n_rows = cols.n_rows
+    k, k_p = _key_arg(cols, key)
+
+    def call(cap, ok_p, ng_p):
+        outs, rep = _glm_report_outs(cols, cap, pp, return_cov)
+        rc = ctx.fn("pds_glm_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
+                                             C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p,
+                                             outs["beta"][1], outs["n_iter"][1], outs["is_null"][1], ng_p, C.byref(rep))
+        return rc, outs
+
+    keys, outs, g = _by_key_retry(cols, max_groups, call)
+    d = _glm_report_dict(outs, cols.n_feat, add_bias, feature_names, return_cov, g)
+    d["keys"] = keys
+    return d
 
 
 def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,

@@ -303,6 +303,41 @@ def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool
     return _join(keys, res, on=[_GID]).drop(_GID)
 
 
+def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+               null_policy: str = "raise"):
+    """
+    The report of one GLM per group from ONE `pl_glm_report_by` call (the GLM twin of `lin_reg_report(..., by=)`): `by` is an
+    integer key column in any row order, nulls = one group.  Long format -- a Struct "glm_report" {<key>, features, beta, std_err, z,
+    p>|z|, 0.025, 0.975, deviance, null_deviance, dispersion, n_iter} with p' rows per group, groups in ascending key order, the
+    per-group fields repeated on a group's rows.  z, p and the interval use the normal distribution for every family (statsmodels'
+    `use_t=False`; `lstsq.glm_report_by` states the definitions).  A group with a null report keeps its rows with null numeric
+    fields.  Penalised fits have no report.  Keys of other dtypes or several key columns: `glm_report_by_group`.
+    """
+    from .linear_models import GLM_FAMILIES
+
+    if family not in GLM_FAMILIES:
+        raise NotImplementedError(f"GLM family {family!r}: one of {sorted(GLM_FAMILIES)}")
+    if max_iter < 1:
+        raise ValueError("`max_iter` must be > 1.")
+    kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
+    cols = [_formula(by), _formula(target).cast(_dtype())] + [_formula(z) for z in x]
+    return _plugin("pl_glm_report_by", cols, kwargs, changes_length=True).alias("glm_report")
+
+
+def glm_report_by_group(df, by, *x, target, **kwargs):
+    """
+    `glm_report(..., by=)` over the whole frame for a key column of any dtype or a list of key columns (null keys form one group):
+    the long frame [*by, features, beta, std_err, z, p>|z|, 0.025, 0.975, deviance, null_deviance, dispersion, n_iter] with p' rows per
+    group; integer keys come back ascending, other keys in order of first appearance (`lin_reg_report_by_group`'s conventions).
+    """
+    if _is_integer_key(df, by):
+        res = df.select(glm_report(*x, target=target, by=by, **kwargs)).unnest("glm_report")
+        return res.with_columns(_pl().col(by).cast(df.schema[by]))
+    ids, keys = _with_group_ids(df, by)
+    res = ids.select(glm_report(*x, target=target, by=_GID, **kwargs)).unnest("glm_report")
+    return _join(res, keys, on=[_GID]).select([*keys.columns[1:], *res.columns[1:]])
+
+
 def rolling_lin_reg(*x, target, window_size: int, add_bias: bool = False, l2_reg: float = 0.0, min_valid_rows: int | None = None,
                     null_policy: str = "raise", by=None):
     """
