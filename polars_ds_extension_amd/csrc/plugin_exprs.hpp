@@ -192,31 +192,7 @@ void do_report(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
 // (pds_*_lr_by_key_*).  The null policies act per row as in the plain symbols; the recursive compaction carries the key along, so
 // group membership and order survive.  PDS_REFERENCE_QUIRKS' compacted-row pred is not applied to keyed calls (pred is
 // x_row . coeffs_row).
-// Polars' group_by / over make the null keys ONE group.  They take a key value no valid row uses -- max + 1, so that group comes
-// last (min - 1 when the maximum is INT64_MAX); returns whether there were null keys (and the stand-in)
-inline bool null_key_stand_in(Column<int64_t>& key, int64_t n, const char* who, int64_t* stand_in) {
-    if (key.null_count <= 0) return false;
-    const int64_t* k = key.data();
-    int64_t mx = std::numeric_limits<int64_t>::min(), mn = std::numeric_limits<int64_t>::max();
-    bool any_valid = false;
-    for (int64_t i = 0; i < n; ++i)
-        if (bit_get(key.validity.data(), i)) {
-            mx = std::max(mx, k[i]);
-            mn = std::min(mn, k[i]);
-            any_valid = true;
-        }
-    int64_t v = 0;
-    if (!any_valid) v = 0;
-    else if (mx < std::numeric_limits<int64_t>::max()) v = mx + 1;
-    else if (mn > std::numeric_limits<int64_t>::min()) v = mn - 1;
-    else raise(std::string(who) + ": the keys span the whole int64 range, no value is left for the null group");
-    auto& kv = key.own();
-    for (int64_t i = 0; i < n; ++i)
-        if (!bit_get(key.validity.data(), i)) kv[i] = v;
-    *stand_in = v;
-    return true;
-}
-
+// (null keys: null_key_stand_in, plugin_keyed.hpp)
 template <typename T>
 void do_windowed(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool rolling, bool keyed = false) {
     Column<int64_t> key;
@@ -361,18 +337,18 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
     const bool weighted = kw_bool(kw, "weighted");
     if (n_in < (weighted ? 4u : 3u)) raise("pl_lr_by needs a key, a target and at least one feature");
     const pds_lr_params prm = lr_params(kw);
-    auto key = import_series<int64_t>(in[0]);  // an Int64 key column is borrowed as it is; other integer widths are widened
-    std::vector<Column<T>> cols;
-    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
-    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
-    bool any_null = false;
-    for (auto& c : cols) any_null |= c.null_count > 0;
-    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
+    // the three steps of keyed_inputs apart: the weights' check comes before the lengths', the pred compaction before the stand-in.
+    // The references below are written through: from the compaction on, ki.key / ki.cols / ki.n / ki.any_null describe the COMPACTED
+    // frame (what keyed_settle and key_array must see), and the local `ikey` -- not ki.ikey -- follows the sorted copy of the keys.
+    KeyedInputs<T> ki = keyed_import<T>(in, n_in, kw);
+    auto& key = ki.key;
+    auto& cols = ki.cols;
+    const Policy& pol = ki.pol;
+    bool& any_null = ki.any_null;
+    int64_t& n = ki.n;
     // pl_lr never compacts its weights (:436-446): a weighted fit on a frame that loses rows fails in the reference too
     if (any_null && weighted) raise("Shape of weights is not the same as the data.");
-    int64_t n = key.size();
-    for (auto& c : cols)
-        if (c.size() != n) raise("input columns differ in length");
+    keyed_check_lengths(ki);
     // per-row predictions of a frame with nulls: what every group's pl_lr_pred does with them (linear_regression.rs:151-267,
     // 790-812) -- "skip" fits on the rows without a null, a fill policy fills the features and drops the rows whose target is
     // null; the dropped rows come back as null rows.  The frame is compacted on the host, fitted, and re-expanded below.
@@ -452,17 +428,11 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
         any_null = false;
         if (n == 0) raise("Empty data");
     }
-    // Polars' group_by makes the null keys ONE group.  They take a key value no valid row uses -- max + 1, so that group comes
-    // last (min - 1 when the maximum is INT64_MAX) -- and the group that carries it is reported with a null key.
-    int64_t null_stand_in = 0;
-    const bool null_group = null_key_stand_in(key, n, "pl_lr_by", &null_stand_in);
+    keyed_settle(ki, "pl_lr_by");
     const int n_feat = (int)n_in - 2 - (weighted ? 1 : 0);
     const int pp = n_feat + prm.add_bias;
-    const int64_t* ikey = key.data();
-    if (n == 0) raise("Empty data");
-    // result storage is sized for a guessed capacity but never zeroed: pages the device-to-host copies do not write are
-    // never touched (a zeroed 1M-group guess cost 16 ms of page faults per call)
-    RawVec<int64_t> keys;
+    const int64_t* ikey = ki.ikey;
+    RawVec<int64_t> keys;  // (result storage: never zeroed, by_key_with_retry)
     ByteVec cobuf;
     RawVec<uint8_t> nulls;
     ByteVec pred_b, resid_b;
@@ -491,14 +461,12 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
                                           nullptr, as<T>(pred_b), as<T>(resid_b), row_null.data()));
             }
         } else {
-            // output capacity: the number of distinct keys is unknown until the device has counted the runs -- start from a
-            // guess (every row its own group is always enough but costs n x p' of host memory) and repeat with the count once
-            int64_t cap = n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16);
-            for (int attempt = 0;; ++attempt) {
+            auto size_outputs = [&](int64_t cap) {
                 keys.resize(cap);
                 cobuf = raw_buffer<T>((size_t)cap * pp);
                 nulls.resize(cap);
-                int rc;
+            };
+            auto call = [&](int64_t cap) {
                 // large unweighted frames: the sliced route -- several contexts (devices: PDS_DEVICES; per device:
                 // PDS_BY_KEY_CONTEXTS), every slice over its context's stream / its device's PCIe link (capi_multi.hpp); it
                 // falls back to the single-context entry point by itself when the keys are not in order
@@ -506,36 +474,24 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
                 const int64_t multi_min = settings().by_key_multi_min_rows;
                 const int slices = settings().by_key_slices;
                 std::unique_lock<std::mutex> multi(MultiContexts::get().busy, std::defer_lock);
-                if (weighted) {
-                    rc = Api<T>::by_key_pred(thread_ctx(), ptrs.data(), wts, ikey, n_feat, n, PDS_HOST, &prm, cap, keys.data(), as<T>(cobuf),
-                                             nulls.data(), &ng, nullptr, nullptr, nullptr);
-                } else if (n >= multi_min && multi_min > 0 && multi.try_lock() && MultiContexts::get().contexts().size() > 1) {
+                if (weighted)
+                    return Api<T>::by_key_pred(thread_ctx(), ptrs.data(), wts, ikey, n_feat, n, PDS_HOST, &prm, cap, keys.data(), as<T>(cobuf),
+                                               nulls.data(), &ng, nullptr, nullptr, nullptr);
+                if (n >= multi_min && multi_min > 0 && multi.try_lock() && MultiContexts::get().contexts().size() > 1) {
                     const auto& cx = MultiContexts::get().contexts();
-                    rc = Api<T>::by_key_multi(cx.data(), (int)cx.size(), slices, ptrs.data(), ikey, n_feat, n, &prm, cap, keys.data(),
-                                              as<T>(cobuf), nulls.data(), &ng);
-                } else {
-                    rc = Api<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, &prm, cap, keys.data(), as<T>(cobuf),
-                                        nulls.data(), &ng);
+                    return Api<T>::by_key_multi(cx.data(), (int)cx.size(), slices, ptrs.data(), ikey, n_feat, n, &prm, cap, keys.data(),
+                                                as<T>(cobuf), nulls.data(), &ng);
                 }
-                if (rc != 0 && attempt == 0 && ng > cap) {
-                    cap = ng;
-                    continue;
-                }
-                check(rc);
-                break;
-            }
-            keys.resize(ng);
-            nulls.resize(ng);
+                return Api<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, &prm, cap, keys.data(), as<T>(cobuf),
+                                      nulls.data(), &ng);
+            };
+            by_key_with_retry(first_group_capacity(n, 0), size_outputs, call, ng);
         }
     } else {
-        // rows with nulls: the rows are put into key order on the host (a stable sort of the row indices; the validity bitmaps
-        // travel with their rows), then the bitmap-aware grouped entry point applies the policy inside every group
-        bool ordered = true;
-        for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
-        if (!ordered) {
-            std::vector<int64_t> perm(n);
-            for (int64_t i = 0; i < n; ++i) perm[i] = i;
-            std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
+        // rows with nulls: the rows are put into key order on the host (key_order; here the values move and their validity bitmaps
+        // travel with them), then the bitmap-aware grouped entry point applies the policy inside every group
+        const std::vector<int64_t> perm = key_order(ikey, n);
+        if (!perm.empty()) {
             std::vector<int64_t> k2(n);
             for (int64_t i = 0; i < n; ++i) k2[i] = ikey[perm[i]];
             key.view = nullptr;
@@ -642,21 +598,13 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
         export_series(out, make_schema("+s", "", std::move(sk)), struct_array(n, std::move(kids)));
         return;
     }
-    std::vector<uint8_t> ok(ng);
-    for (int64_t g = 0; g < ng; ++g) ok[g] = nulls[g] ? 0 : 1;
+    std::vector<uint8_t> ok;
+    group_flags_to_row_valid(nulls.data(), ng, 1, ok);
     std::vector<std::unique_ptr<ArrowArray>> kids;
-    {
-        std::vector<uint8_t> kvalid;
-        if (null_group) {
-            kvalid.assign(ng, 1);
-            for (int64_t g = 0; g < ng; ++g)
-                if (keys[g] == null_stand_in) kvalid[g] = 0;
-        }
-        kids.push_back(prim_array_take<int64_t>(bytes_of(keys.data(), keys.size()), ng, null_group ? kvalid.data() : nullptr));
-    }
+    kids.push_back(key_array(ki, keys, ng, 1));
     kids.push_back(list_array_take_rows<T>(std::move(cobuf), ng, pp, ok.data()));
     std::vector<std::unique_ptr<ArrowSchema>> sk;
-    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(key_schema(ki));
     sk.push_back(list_schema<T>("coeffs"));
     export_series(out, make_schema("+s", "", std::move(sk)), struct_array(ng, std::move(kids)));
 }
@@ -671,35 +619,28 @@ void do_lr_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out
 // features set and every numeric field null (the reference's per-group call would raise and abort the query; the deviation the C
 // ABI documents).  Nulls in y / x: "raise" fails on the first one; the other policies act on every group as pl_lin_reg_report acts
 // on that group's rows alone, var(y) being the variance of the group's ORIGINAL non-null target values (what Polars hands a
-// per-group call): the rows are prepared on the host in key order and go to the offsets entry with y_var.  pl_wls_report_by with
-// nulls raises, as pl_wls_report does (linear_regression.rs:1013-1020: the weights are never compacted).
-// (test seam: the capacity guess of the by-key call; <= 0 = the default rule of do_lr_by)
+// per-group call): the rows are prepared on the host (prepare_keyed_rows) and go to the offsets entry with y_var.  pl_wls_report_by
+// with nulls raises, as pl_wls_report does (linear_regression.rs:1013-1020: the weights are never compacted).
+// (test seam: the first capacity guess of the by-key call; <= 0: first_group_capacity's rule)
 int64_t g_report_by_first_cap = 0;
 template <typename T>
 void do_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool wls) {
-    const size_t iy = wls ? 2 : 1;  // cols: [key, weights?, y, x1..xp]
+    const size_t iy = wls ? 2 : 1;  // in: [key, weights?, y, x1..xp]
     if (n_in < iy + 2) raise("need a key, a target and at least one feature");
-    auto key = import_series<int64_t>(in[0]);
-    std::vector<Column<T>> cols;  // [weights?, y, x1..xp]
-    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
-    const size_t cy = iy - 1;  // index of y in cols
+    const size_t cy = iy - 1;  // index of y in ki.cols = [weights?, y, x1..xp]
     const bool bias = kw_bool(kw, "bias");
     const std::string se = kw_str(kw, "std_err", "se");
     const int se_type = wls ? PDS_SE : se == "hc0" ? PDS_HC0 : se == "hc1" ? PDS_HC1 : se == "hc2" ? PDS_HC2 : se == "hc3" ? PDS_HC3 : PDS_SE;
-    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
-    bool any_null = false;
-    for (size_t i = cy; i < cols.size(); ++i) any_null |= cols[i].null_count > 0;
-    if (wls && cols[0].null_count > 0) any_null = true;
-    if (any_null && (wls || pol.kind == Policy::RAISE)) raise("Nulls found in data");
-    const int64_t n = key.size();
-    for (auto& c : cols)
-        if (c.size() != n) raise("input columns differ in length");
-    if (n == 0) raise("Empty data");
+    // the three steps of keyed_inputs apart: pl_wls_report_by raises on a null (weights included) whatever the policy, and before
+    // the lengths are compared
+    KeyedInputs<T> ki = keyed_import<T>(in, n_in, kw);
+    if (ki.any_null && wls) raise("Nulls found in data");
+    keyed_check_lengths(ki);
+    keyed_settle(ki, wls ? "pl_wls_report_by" : "pl_lin_reg_report_by");
+    const auto& cols = ki.cols;
+    const int64_t n = ki.n;
     const int n_feat = (int)(n_in - iy - 1);
     const int pp = n_feat + (bias ? 1 : 0);
-    int64_t null_stand_in = 0;
-    const bool null_group = null_key_stand_in(key, n, wls ? "pl_wls_report_by" : "pl_lin_reg_report_by", &null_stand_in);
-    const int64_t* ikey = key.data();
     RawVec<int64_t> keys;
     ByteVec vb[6], r2b, ar2b;  // beta, se, t, p, lo, hi [ng][p'], r2 / adj_r2 [ng]
     RawVec<uint8_t> nulls;
@@ -715,152 +656,55 @@ void do_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport*
         rep.ci_lower = as<T>(vb[4]); rep.ci_upper = as<T>(vb[5]); rep.r2 = as<T>(r2b); rep.adj_r2 = as<T>(ar2b);
         rep.is_null = nulls.data();
     };
-    if (!any_null) {
+    if (!ki.any_null) {
         std::vector<const T*> ptrs;
         for (size_t c = cy; c < cols.size(); ++c) ptrs.push_back(cols[c].data());
-        // the group count is unknown until the device has counted the runs: guess, then repeat once with the count (do_lr_by)
-        int64_t cap = g_report_by_first_cap > 0 ? std::min<int64_t>(g_report_by_first_cap, n)
-                                                : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
-        for (int attempt = 0;; ++attempt) {
-            size_outputs(cap);
-            const int rc = wls ? Api<T>::wls_report_by_key(thread_ctx(), ptrs.data(), cols[0].data(), ikey, n_feat, n, PDS_HOST, bias, cap,
-                                                           keys.data(), &rep, &ng)
-                               : Api<T>::report_by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, se_type, cap, keys.data(),
-                                                       &rep, &ng);
-            if (rc != 0 && attempt == 0 && ng > cap) {
-                cap = ng;
-                continue;
-            }
-            check(rc);
-            break;
-        }
+        by_key_with_retry(first_group_capacity(n, g_report_by_first_cap), size_outputs, [&](int64_t cap) {
+            return wls ? Api<T>::wls_report_by_key(thread_ctx(), ptrs.data(), cols[0].data(), ki.ikey, n_feat, n, PDS_HOST, bias, cap, keys.data(),
+                                                   &rep, &ng)
+                       : Api<T>::report_by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, n, PDS_HOST, bias, se_type, cap, keys.data(), &rep,
+                                               &ng);
+        }, ng);
     } else {
-        // rows with nulls: a stable sort of the row indices by key, the policy applied row by row (series_to_mat_for_lr,
-        // linear_regression.rs:187-248, per group: "skip" drops a row with any null, a fill policy fills the features and drops the
-        // rows whose target is null, everything else keeps the rows with NaN for the nulls), the surviving rows written in key order
-        std::vector<int64_t> perm(n);
-        for (int64_t i = 0; i < n; ++i) perm[i] = i;
-        bool ordered = true;
-        for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
-        if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
-        const int code = pol.kind == Policy::FILL ? PDS_NULL_FILL : pol.kind == Policy::SKIP ? PDS_NULL_SKIP : PDS_NULL_IGNORE;
-        const size_t nc = cols.size();
-        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
-        std::vector<std::vector<T>> kept(nc);
-        for (auto& v : kept) v.reserve((size_t)n);
-        std::vector<int64_t> off;
+        // (never pl_wls_report_by: cols = [y, x1..xp])
+        const PreparedRows<T> pr = prepare_keyed_rows(ki, keys);
+        ng = (int64_t)keys.size();
+        // var(y) of a group: the sample variance (ddof = 1) of its ORIGINAL non-null target values, dropped rows included, two passes in f64
         std::vector<T> yvar;
-        const T nanv = std::numeric_limits<T>::quiet_NaN();
-        // var(y) of a group: the sample variance (ddof = 1) of its non-null target values, two passes in f64
-        auto close_group = [&](int64_t a, int64_t b) {
-            double sum = 0.0;
+        for (int64_t g = 0; g < ng; ++g) {
+            double sum = 0.0, ss = 0.0;
             int64_t m = 0;
-            for (int64_t i = a; i < b; ++i)
-                if (!is_null(0, perm[i])) {
-                    sum += (double)cols[0].data()[perm[i]];
+            for (int64_t i = pr.first[g]; i < pr.first[g + 1]; ++i)
+                if (!is_null_at(cols[0], pr.row(i))) {
+                    sum += (double)cols[0].data()[pr.row(i)];
                     ++m;
                 }
-            if (m < 2) {
-                yvar.push_back(nanv);
-                return;
-            }
             const double mean = sum / (double)m;
-            double ss = 0.0;
-            for (int64_t i = a; i < b; ++i)
-                if (!is_null(0, perm[i])) {
-                    const double d = (double)cols[0].data()[perm[i]] - mean;
+            for (int64_t i = pr.first[g]; i < pr.first[g + 1]; ++i)
+                if (!is_null_at(cols[0], pr.row(i))) {
+                    const double d = (double)cols[0].data()[pr.row(i)] - mean;
                     ss += d * d;
                 }
-            yvar.push_back((T)(ss / (double)(m - 1)));
-        };
-        int64_t g_first = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t r = perm[i];
-            if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
-                if (i) close_group(g_first, i);
-                g_first = i;
-                off.push_back((int64_t)kept[0].size());
-                keys.push_back(ikey[r]);
-            }
-            bool keep = true;
-            if (code == PDS_NULL_SKIP)
-                for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
-            else if (code == PDS_NULL_FILL)
-                keep = !is_null(0, r);
-            if (!keep) continue;
-            for (size_t c = 0; c < nc; ++c)
-                kept[c].push_back(is_null(c, r) ? (code == PDS_NULL_FILL ? (T)pol.fill : nanv) : cols[c].data()[r]);
+            yvar.push_back(m < 2 ? std::numeric_limits<T>::quiet_NaN() : (T)(ss / (double)(m - 1)));
         }
-        close_group(g_first, n);
-        off.push_back((int64_t)kept[0].size());
-        ng = (int64_t)keys.size();
-        const int64_t nk = (int64_t)kept[0].size();
-        if (nk == 0) raise("Empty data");
-        std::vector<const T*> ptrs;
-        for (auto& v : kept) ptrs.push_back(v.data());
         size_outputs(ng);  // (keys already holds its ng values)
-        check(Api<T>::report_grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, se_type, yvar.data(), &rep));
+        check(Api<T>::report_grouped(thread_ctx(), pr.ptrs.data(), n_feat, pr.rows(), pr.off.data(), ng, PDS_HOST, bias, se_type, yvar.data(),
+                                     &rep));
     }
     // ---- the long frame
     const int64_t rows = ng * pp;
-    std::vector<std::string> names;
-    for (size_t i = cy + 1; i < cols.size(); ++i) names.push_back(cols[i].name);
-    if (bias) names.push_back("__bias__");
     std::vector<std::unique_ptr<ArrowArray>> kids;
-    {
-        ByteVec kb = raw_buffer<int64_t>((size_t)rows);
-        int64_t* kd = as<int64_t>(kb);
-        std::vector<uint8_t> kvalid;
-        if (null_group) kvalid.assign((size_t)rows, 1);
-        for (int64_t g = 0; g < ng; ++g)
-            for (int i = 0; i < pp; ++i) {
-                kd[g * pp + i] = keys[g];
-                if (null_group && keys[g] == null_stand_in) kvalid[g * pp + i] = 0;
-            }
-        kids.push_back(prim_array_take<int64_t>(std::move(kb), rows, null_group ? kvalid.data() : nullptr));
-    }
-    {   // features: the p' names, once per group (large-utf8: int64 offsets)
-        std::string one;
-        std::vector<int64_t> o1 = {0};
-        for (auto& s : names) {
-            one += s;
-            o1.push_back((int64_t)one.size());
-        }
-        ByteVec ob = raw_buffer<int64_t>((size_t)rows + 1), db = raw_buffer<char>((size_t)ng * one.size());
-        int64_t* od = as<int64_t>(ob);
-        for (int64_t g = 0; g < ng; ++g) {
-            for (int i = 0; i < pp; ++i) od[g * pp + i] = g * (int64_t)one.size() + o1[i];
-            if (!one.empty()) std::memcpy(db.data() + g * one.size(), one.data(), one.size());
-        }
-        od[rows] = ng * (int64_t)one.size();
-        std::vector<ByteVec> bufs;
-        bufs.emplace_back();
-        bufs.push_back(std::move(ob));
-        bufs.push_back(std::move(db));
-        kids.push_back(make_array(rows, 0, std::move(bufs), {false, true, true}));
-    }
-    std::vector<uint8_t> valid((size_t)rows, 1);
-    bool any_group_null = false;
-    for (int64_t g = 0; g < ng; ++g)
-        if (nulls[g]) {
-            any_group_null = true;
-            for (int i = 0; i < pp; ++i) valid[g * pp + i] = 0;
-        }
-    const uint8_t* vf = any_group_null ? valid.data() : nullptr;
+    kids.push_back(key_array(ki, keys, ng, pp));
+    kids.push_back(features_array(cols, cy + 1, bias, ng));
+    std::vector<uint8_t> valid;
+    const uint8_t* vf = group_flags_to_row_valid(nulls.data(), ng, pp, valid) ? nullptr : valid.data();
     for (auto& b : vb) kids.push_back(prim_array_take<T>(std::move(b), rows, vf));
-    for (ByteVec* b : {&r2b, &ar2b}) {
-        ByteVec wide = raw_buffer<T>((size_t)rows);
-        const T* sv = as<T>(*b);
-        T* dv = as<T>(wide);
-        for (int64_t g = 0; g < ng; ++g)
-            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
-        kids.push_back(prim_array_take<T>(std::move(wide), rows, vf));
-    }
+    for (ByteVec* b : {&r2b, &ar2b}) kids.push_back(prim_array_take<T>(broadcast_rows<T>(*b, ng, pp), rows, vf));
     const char* se_name = se_type == PDS_HC0 ? "hc0_se" : se_type == PDS_HC1 ? "hc1_se" : se_type == PDS_HC2 ? "hc2_se"
                           : se_type == PDS_HC3 ? "hc3_se" : "std_err";
     const char* fnames[9] = {"features", "beta", se_name, "t", "p>|t|", "0.025", "0.975", "r2", "adj_r2"};
     std::vector<std::unique_ptr<ArrowSchema>> sk;
-    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(key_schema(ki));
     sk.push_back(make_schema("U", fnames[0]));
     for (int i = 1; i < 9; ++i) sk.push_back(make_schema(fmt_of<T>(), fnames[i]));
     export_series(out, make_schema("+s", "lin_reg_report", std::move(sk)), struct_array(rows, std::move(kids)));

@@ -32,45 +32,7 @@ inline void glm_family_codes(const std::string& family, int* link, int* variance
     *variance = id;
 }
 
-// Frames with nulls, prepared on the host for the offsets entry points: rows in key order (a stable sort of the row indices when the
-// keys are not ordered), the policy applied row by row inside every group -- "skip" drops a row with any null, a fill policy fills
-// the features and drops the rows whose target is null, everything else keeps the rows with NaN for the nulls.  keys / off: one
-// entry per group (off: n_groups + 1), kept: the surviving rows column by column, src_row: the frame row of every surviving row.
-template <typename T>
-void glm_prepare_rows(const std::vector<Column<T>>& cols, const int64_t* ikey, int64_t n, const Policy& pol, RawVec<int64_t>& keys,
-                      std::vector<int64_t>& off, std::vector<std::vector<T>>& kept, std::vector<int64_t>& src_row) {
-    std::vector<int64_t> perm(n);
-    for (int64_t i = 0; i < n; ++i) perm[i] = i;
-    bool ordered = true;
-    for (int64_t i = 1; i < n && ordered; ++i) ordered = ikey[i] >= ikey[i - 1];
-    if (!ordered) std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return ikey[a] < ikey[b]; });
-    const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
-    const size_t nc = cols.size();
-    auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
-    kept.assign(nc, {});
-    for (auto& v : kept) v.reserve((size_t)n);
-    src_row.reserve((size_t)n);
-    const T nanv = std::numeric_limits<T>::quiet_NaN();
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = perm[i];
-        if (i == 0 || ikey[r] != ikey[perm[i - 1]]) {
-            off.push_back((int64_t)kept[0].size());
-            keys.push_back(ikey[r]);
-        }
-        bool keep = true;
-        if (skip)
-            for (size_t c = 0; c < nc && keep; ++c) keep = !is_null(c, r);
-        else if (fill)
-            keep = !is_null(0, r);
-        if (!keep) continue;
-        for (size_t c = 0; c < nc; ++c) kept[c].push_back(is_null(c, r) ? (fill ? (T)pol.fill : nanv) : cols[c].data()[r]);
-        src_row.push_back(r);
-    }
-    off.push_back((int64_t)kept[0].size());
-    if (kept[0].empty()) raise("Empty data");
-}
-
-// test seam: the first capacity guess of pl_glm_by (<= 0: the default rule of do_lr_by), so that the retry can be exercised
+// test seam: the first capacity guess of pl_glm_by / pl_glm_report_by (<= 0: first_group_capacity's rule), so that the retry can be exercised
 int64_t g_glm_by_first_cap = 0;
 
 // ------------------------------------------------------------------------------------------------- pl_glm_by / pl_glm_by_pred (new)
@@ -80,10 +42,9 @@ int64_t g_glm_by_first_cap = 0;
 // pl_glm_by: Struct{<key>, coeffs: List<T>, n_iter: Int32}, one row per group, keys ascending (the null key's group last, with a null
 // key), a null list for a null group (fewer rows than coefficients, or a fit that does not end in finite coefficients).
 // pl_glm_by_pred: the fitted mean of every row, row for row, null where the row's group is null or a null policy dropped the row.
-// Null-free frames make ONE pds_glm_irls_by_key_* call (capacity guess and one retry as do_lr_by); frames with nulls are prepared on
-// the host as do_report_by prepares them -- rows in key order, the policy applied row by row inside every group ("skip" drops a row
-// with any null, a fill policy fills the features and drops the rows whose target is null, "ignore" keeps the rows with NaN for the
-// nulls: that group's fit is not finite, so it is a null group) -- and go to the offsets entry point.
+// Null-free frames make ONE pds_glm_irls_by_key_* call (by_key_with_retry); frames with nulls are prepared on the host
+// (prepare_keyed_rows; "ignore" keeps the rows with NaN for the nulls: that group's fit is not finite, so it is a null group) and go
+// to the offsets entry point.
 template <typename T>
 void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
     if (n_in < 3) raise("pl_glm_by needs a key, a target and at least one feature");
@@ -98,69 +59,43 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
     const int n_feat = (int)n_in - 2;
     if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
     const int pp = n_feat + bias;
-    auto key = import_series<int64_t>(in[0]);
-    std::vector<Column<T>> cols;  // [y, x1..xp]
-    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
-    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
-    bool any_null = false;
-    for (auto& c : cols) any_null |= c.null_count > 0;
-    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
-    const int64_t n = key.size();
-    for (auto& c : cols)
-        if (c.size() != n) raise("input columns differ in length");
-    if (n == 0) raise("Empty data");
-    int64_t null_stand_in = 0;
-    const bool null_group = null_key_stand_in(key, n, "pl_glm_by", &null_stand_in);
-    const int64_t* ikey = key.data();
+    const KeyedInputs<T> ki = keyed_inputs<T>(in, n_in, kw, "pl_glm_by");  // cols: [y, x1..xp]
+    const int64_t n = ki.n;
     RawVec<int64_t> keys;
     ByteVec cobuf, itbuf, pred_b;
     RawVec<uint8_t> nulls, row_null;
     std::vector<uint8_t> row_valid;  // pred: one validity byte per row of the frame
     int64_t ng = 0;
-    if (!any_null) {
+    auto size_outputs = [&](int64_t cap) {
+        keys.resize(cap);
+        cobuf = raw_buffer<T>((size_t)cap * pp);
+        itbuf = raw_buffer<int32_t>((size_t)cap);
+        nulls.resize(cap);
+    };
+    if (!ki.any_null) {
         std::vector<const T*> ptrs;
-        for (auto& c : cols) ptrs.push_back(c.data());
+        for (auto& c : ki.cols) ptrs.push_back(c.data());
         if (want_pred) {
             pred_b = raw_buffer<T>((size_t)n);
             row_null.resize(n);
         }
-        int64_t cap = g_glm_by_first_cap > 0 ? std::min<int64_t>(g_glm_by_first_cap, n)
-                                             : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
-        for (int attempt = 0;; ++attempt) {
-            keys.resize(cap);
-            cobuf = raw_buffer<T>((size_t)cap * pp);
-            itbuf = raw_buffer<int32_t>((size_t)cap);
-            nulls.resize(cap);
-            T* const pr = want_pred ? as<T>(pred_b) : nullptr;
-            uint8_t* const rn = want_pred ? row_null.data() : nullptr;
-            const int rc = penalised ? GlmApi<T>::enet_by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, l1_reg,
-                                                              l2_reg, tol, max_iter, cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf),
-                                                              nulls.data(), &ng, pr, rn)
-                                     : GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter,
-                                                         cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, pr, rn);
-            if (rc != 0 && attempt == 0 && ng > cap) {
-                cap = ng;
-                continue;
-            }
-            check(rc);
-            break;
-        }
+        T* const pr = want_pred ? as<T>(pred_b) : nullptr;
+        uint8_t* const rn = want_pred ? row_null.data() : nullptr;
+        by_key_with_retry(first_group_capacity(n, g_glm_by_first_cap), size_outputs, [&](int64_t cap) {
+            return penalised ? GlmApi<T>::enet_by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, n, PDS_HOST, bias, link, variance, l1_reg, l2_reg,
+                                                      tol, max_iter, cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, pr, rn)
+                             : GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
+                                                 keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, pr, rn);
+        }, ng);
         if (want_pred) {
             row_valid.resize((size_t)n);
             for (int64_t i = 0; i < n; ++i) row_valid[i] = row_null[i] ? 0 : 1;
         }
     } else {
-        std::vector<std::vector<T>> kept;
-        std::vector<int64_t> off, src_row;
-        const T nanv = std::numeric_limits<T>::quiet_NaN();
-        glm_prepare_rows<T>(cols, ikey, n, pol, keys, off, kept, src_row);
+        const PreparedRows<T> rows = prepare_keyed_rows(ki, keys);
         ng = (int64_t)keys.size();
-        const int64_t nk = (int64_t)kept[0].size();
-        std::vector<const T*> ptrs;
-        for (auto& v : kept) ptrs.push_back(v.data());
-        cobuf = raw_buffer<T>((size_t)ng * pp);
-        itbuf = raw_buffer<int32_t>((size_t)ng);
-        nulls.resize(ng);
+        const int64_t nk = rows.rows();
+        size_outputs(ng);  // (keys already holds its ng values)
         ByteVec pk;
         RawVec<uint8_t> rk;
         if (want_pred) {
@@ -169,19 +104,19 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
         }
         T* const pr = want_pred ? as<T>(pk) : nullptr;
         uint8_t* const rn = want_pred ? rk.data() : nullptr;
-        check(penalised ? GlmApi<T>::enet_grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, l1_reg,
-                                                  l2_reg, tol, max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn)
-                        : GlmApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, nk, off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter,
-                                             as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn));
+        check(penalised ? GlmApi<T>::enet_grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance,
+                                                  l1_reg, l2_reg, tol, max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn)
+                        : GlmApi<T>::grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance, tol,
+                                             max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn));
         if (want_pred) {  // back to the frame's rows: a dropped row is a null row
             pred_b = raw_buffer<T>((size_t)n);
             row_valid.assign((size_t)n, 0);
             T* pd = as<T>(pred_b);
-            for (int64_t i = 0; i < n; ++i) pd[i] = nanv;
+            for (int64_t i = 0; i < n; ++i) pd[i] = std::numeric_limits<T>::quiet_NaN();
             const T* ps = as<T>(pk);
             for (int64_t k = 0; k < nk; ++k) {
-                pd[src_row[k]] = ps[k];
-                row_valid[src_row[k]] = rk[k] ? 0 : 1;
+                pd[rows.src_row[k]] = ps[k];
+                row_valid[rows.src_row[k]] = rk[k] ? 0 : 1;
             }
         }
     }
@@ -191,22 +126,14 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
         export_series(out, make_schema(fmt_of<T>(), "pred"), prim_array_take<T>(std::move(pred_b), n, all_valid ? nullptr : row_valid.data()));
         return;
     }
-    std::vector<uint8_t> ok(ng);
-    for (int64_t g = 0; g < ng; ++g) ok[g] = nulls[g] ? 0 : 1;
+    std::vector<uint8_t> ok;
+    group_flags_to_row_valid(nulls.data(), ng, 1, ok);
     std::vector<std::unique_ptr<ArrowArray>> kids;
-    {
-        std::vector<uint8_t> kvalid;
-        if (null_group) {
-            kvalid.assign(ng, 1);
-            for (int64_t g = 0; g < ng; ++g)
-                if (keys[g] == null_stand_in) kvalid[g] = 0;
-        }
-        kids.push_back(prim_array_take<int64_t>(bytes_of(keys.data(), (size_t)ng), ng, null_group ? kvalid.data() : nullptr));
-    }
+    kids.push_back(key_array(ki, keys, ng, 1));
     kids.push_back(list_array_take_rows<T>(std::move(cobuf), ng, pp, ok.data()));
     kids.push_back(prim_array_take<int32_t>(std::move(itbuf), ng, nullptr));
     std::vector<std::unique_ptr<ArrowSchema>> sk;
-    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(key_schema(ki));
     sk.push_back(list_schema<T>("coeffs"));
     sk.push_back(make_schema("i", "n_iter"));
     export_series(out, make_schema("+s", "", std::move(sk)), struct_array(ng, std::move(kids)));
@@ -218,13 +145,13 @@ constexpr const char* kGlmReportFields[11] = {"features", "beta", "std_err", "z"
 
 // ------------------------------------------------------------------------------------------------- pl_glm_report_by (new)
 // inputs and kwargs: those of pl_glm_by; a positive l1_reg / l2_reg is an error (penalised fits have no report).  One Struct
-// "glm_report" in long format, built the way do_report_by builds the grouped linear report: n_groups x p' rows {<key>, features,
+// "glm_report" in long format (key_array, features_array, broadcast_rows): n_groups x p' rows {<key>, features,
 // beta, std_err, z, p>|z|, 0.025, 0.975, deviance, null_deviance, dispersion, n_iter}, groups in ascending key order (the null key's
 // group last, with a null key), coefficients in input order with __bias__ last, the per-group fields broadcast over a group's rows.
 // A group with a null report keeps its p' rows with key, features and n_iter set and null numeric fields (beta stays when the fit
 // itself is not null).  z and p come from the normal distribution for every family.  Null-free frames make ONE
-// pds_glm_report_by_key_* call (capacity guess and one retry); frames with nulls are prepared on the host exactly as do_glm_by
-// prepares them (glm_prepare_rows) and go to the offsets entry point.
+// pds_glm_report_by_key_* call (by_key_with_retry); frames with nulls are prepared on the host (prepare_keyed_rows) and go to the
+// offsets entry point.
 template <typename T> struct GlmReportApi;
 template <> struct GlmReportApi<double> {
     static constexpr auto grouped = pds_glm_report_grouped_f64;
@@ -248,20 +175,7 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     const int n_feat = (int)n_in - 2;
     if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
     const int pp = n_feat + bias;
-    auto key = import_series<int64_t>(in[0]);
-    std::vector<Column<T>> cols;  // [y, x1..xp]
-    for (size_t i = 1; i < n_in; ++i) cols.push_back(import_series<T>(in[i]));
-    const Policy pol = parse_policy(kw_str(kw, "null_policy", "raise"));
-    bool any_null = false;
-    for (auto& c : cols) any_null |= c.null_count > 0;
-    if (any_null && pol.kind == Policy::RAISE) raise("Nulls found in data");
-    const int64_t n = key.size();
-    for (auto& c : cols)
-        if (c.size() != n) raise("input columns differ in length");
-    if (n == 0) raise("Empty data");
-    int64_t null_stand_in = 0;
-    const bool null_group = null_key_stand_in(key, n, "pl_glm_report_by", &null_stand_in);
-    const int64_t* ikey = key.data();
+    const KeyedInputs<T> ki = keyed_inputs<T>(in, n_in, kw, "pl_glm_report_by");  // cols: [y, x1..xp]
     RawVec<int64_t> keys;
     ByteVec vb[6], gb[3], itbuf;  // beta, se, z, p, lo, hi [ng][p']; deviance, null_deviance, dispersion [ng]; n_iter [ng]
     RawVec<uint8_t> nulls, rnulls;
@@ -278,102 +192,34 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
         rep.deviance = as<T>(gb[0]); rep.null_deviance = as<T>(gb[1]); rep.dispersion = as<T>(gb[2]);
         rep.report_null = rnulls.data();
     };
-    if (!any_null) {
+    if (!ki.any_null) {
         std::vector<const T*> ptrs;
-        for (auto& c : cols) ptrs.push_back(c.data());
-        int64_t cap = g_glm_by_first_cap > 0 ? std::min<int64_t>(g_glm_by_first_cap, n)
-                                             : (n <= ((int64_t)1 << 20) ? n : std::max<int64_t>((int64_t)1 << 20, n / 16));
-        for (int attempt = 0;; ++attempt) {
-            size_outputs(cap);
-            const int rc = GlmReportApi<T>::by_key(thread_ctx(), ptrs.data(), ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
-                                                   keys.data(), as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &ng, &rep);
-            if (rc != 0 && attempt == 0 && ng > cap) {
-                cap = ng;
-                continue;
-            }
-            check(rc);
-            break;
-        }
+        for (auto& c : ki.cols) ptrs.push_back(c.data());
+        by_key_with_retry(first_group_capacity(ki.n, g_glm_by_first_cap), size_outputs, [&](int64_t cap) {
+            return GlmReportApi<T>::by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, ki.n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
+                                           keys.data(), as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &ng, &rep);
+        }, ng);
     } else {
-        std::vector<std::vector<T>> kept;
-        std::vector<int64_t> off, src_row;
-        glm_prepare_rows<T>(cols, ikey, n, pol, keys, off, kept, src_row);
+        const PreparedRows<T> pr = prepare_keyed_rows(ki, keys);
         ng = (int64_t)keys.size();
-        std::vector<const T*> ptrs;
-        for (auto& v : kept) ptrs.push_back(v.data());
         size_outputs(ng);  // (keys already holds its ng values)
-        check(GlmReportApi<T>::grouped(thread_ctx(), ptrs.data(), n_feat, (int64_t)kept[0].size(), off.data(), ng, PDS_HOST, bias, link, variance,
-                                       tol, max_iter, as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep));
+        check(GlmReportApi<T>::grouped(thread_ctx(), pr.ptrs.data(), n_feat, pr.rows(), pr.off.data(), ng, PDS_HOST, bias, link, variance, tol,
+                                       max_iter, as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep));
     }
     // ---- the long frame
     const int64_t rows = ng * pp;
-    std::vector<std::string> names;
-    for (size_t i = 1; i < cols.size(); ++i) names.push_back(cols[i].name);
-    if (bias) names.push_back("__bias__");
     std::vector<std::unique_ptr<ArrowArray>> kids;
-    {
-        ByteVec kb = raw_buffer<int64_t>((size_t)rows);
-        int64_t* kd = as<int64_t>(kb);
-        std::vector<uint8_t> kvalid;
-        if (null_group) kvalid.assign((size_t)rows, 1);
-        for (int64_t g = 0; g < ng; ++g)
-            for (int i = 0; i < pp; ++i) {
-                kd[g * pp + i] = keys[g];
-                if (null_group && keys[g] == null_stand_in) kvalid[g * pp + i] = 0;
-            }
-        kids.push_back(prim_array_take<int64_t>(std::move(kb), rows, null_group ? kvalid.data() : nullptr));
-    }
-    {   // features: the p' names, once per group (large-utf8: int64 offsets)
-        std::string one;
-        std::vector<int64_t> o1 = {0};
-        for (auto& s : names) {
-            one += s;
-            o1.push_back((int64_t)one.size());
-        }
-        ByteVec ob = raw_buffer<int64_t>((size_t)rows + 1), db = raw_buffer<char>((size_t)ng * one.size());
-        int64_t* od = as<int64_t>(ob);
-        for (int64_t g = 0; g < ng; ++g) {
-            for (int i = 0; i < pp; ++i) od[g * pp + i] = g * (int64_t)one.size() + o1[i];
-            if (!one.empty()) std::memcpy(db.data() + g * one.size(), one.data(), one.size());
-        }
-        od[rows] = ng * (int64_t)one.size();
-        std::vector<ByteVec> bufs;
-        bufs.emplace_back();
-        bufs.push_back(std::move(ob));
-        bufs.push_back(std::move(db));
-        kids.push_back(make_array(rows, 0, std::move(bufs), {false, true, true}));
-    }
-    std::vector<uint8_t> fit_valid((size_t)rows, 1), rep_valid((size_t)rows, 1);
-    bool any_fit_null = false, any_rep_null = false;
-    for (int64_t g = 0; g < ng; ++g) {
-        if (nulls[g]) any_fit_null = true;
-        if (rnulls[g]) any_rep_null = true;
-        for (int i = 0; i < pp; ++i) {
-            fit_valid[g * pp + i] = nulls[g] ? 0 : 1;
-            rep_valid[g * pp + i] = rnulls[g] ? 0 : 1;
-        }
-    }
-    const uint8_t* vr = any_rep_null ? rep_valid.data() : nullptr;
-    kids.push_back(prim_array_take<T>(std::move(vb[0]), rows, any_fit_null ? fit_valid.data() : nullptr));
+    kids.push_back(key_array(ki, keys, ng, pp));
+    kids.push_back(features_array(ki.cols, 1, bias != 0, ng));
+    std::vector<uint8_t> fit_valid, rep_valid;
+    const uint8_t* vfit = group_flags_to_row_valid(nulls.data(), ng, pp, fit_valid) ? nullptr : fit_valid.data();
+    const uint8_t* vr = group_flags_to_row_valid(rnulls.data(), ng, pp, rep_valid) ? nullptr : rep_valid.data();
+    kids.push_back(prim_array_take<T>(std::move(vb[0]), rows, vfit));
     for (int k = 1; k < 6; ++k) kids.push_back(prim_array_take<T>(std::move(vb[k]), rows, vr));
-    for (auto& b : gb) {
-        ByteVec wide = raw_buffer<T>((size_t)rows);
-        const T* sv = as<T>(b);
-        T* dv = as<T>(wide);
-        for (int64_t g = 0; g < ng; ++g)
-            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
-        kids.push_back(prim_array_take<T>(std::move(wide), rows, vr));
-    }
-    {
-        ByteVec wide = raw_buffer<int32_t>((size_t)rows);
-        const int32_t* sv = as<int32_t>(itbuf);
-        int32_t* dv = as<int32_t>(wide);
-        for (int64_t g = 0; g < ng; ++g)
-            for (int i = 0; i < pp; ++i) dv[g * pp + i] = sv[g];
-        kids.push_back(prim_array_take<int32_t>(std::move(wide), rows, nullptr));
-    }
+    for (auto& b : gb) kids.push_back(prim_array_take<T>(broadcast_rows<T>(b, ng, pp), rows, vr));
+    kids.push_back(prim_array_take<int32_t>(broadcast_rows<int32_t>(itbuf, ng, pp), rows, nullptr));
     std::vector<std::unique_ptr<ArrowSchema>> sk;
-    sk.push_back(make_schema("l", key.name.empty() ? "key" : key.name));
+    sk.push_back(key_schema(ki));
     sk.push_back(make_schema("U", kGlmReportFields[0]));
     for (int i = 1; i < 10; ++i) sk.push_back(make_schema(fmt_of<T>(), kGlmReportFields[i]));
     sk.push_back(make_schema("i", kGlmReportFields[10]));
@@ -386,8 +232,7 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
 // start; this backend runs IRLS (binomial family, logit link) to the same unpenalised maximum-likelihood point through
 // pds_glm_irls_grouped_f64 with ONE group (offsets [0, n]): a frame above the context's glm_split_rows takes the full-device
 // iteration, a shorter one the one-wave kernel.  A positive l1_reg / l2_reg is an error, not an unpenalised fit.
-// Nulls as series_to_mat_for_lr's mask has them (logistic_regression.rs:76-94): "skip" fits on the rows without a null, a fill policy
-// fills the features and drops the rows whose target is null; pred is null where the mask drops a row.
+// Nulls as series_to_mat_for_lr's mask has them (logistic_regression.rs:76-94; push_kept_row); pred is null where the mask drops a row.
 inline void do_logistic(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
     if (n_in < 2) raise("pl_logistic needs a target and at least one feature");
     if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0)
@@ -411,20 +256,9 @@ inline void do_logistic(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesE
     std::vector<const double*> ptrs;
     int64_t nk = n;
     if (any_null) {
-        const bool fill = pol.kind == Policy::FILL, skip = pol.kind == Policy::SKIP;
-        auto is_null = [&](size_t c, int64_t r) { return cols[c].null_count > 0 && !bit_get(cols[c].validity.data(), r); };
         kept.resize(cols.size());
-        const double nanv = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t r = 0; r < n; ++r) {
-            bool keep = true;
-            if (skip)
-                for (size_t c = 0; c < cols.size() && keep; ++c) keep = !is_null(c, r);
-            else if (fill)
-                keep = !is_null(0, r);
-            if (!keep) continue;
-            for (size_t c = 0; c < cols.size(); ++c) kept[c].push_back(is_null(c, r) ? (fill ? pol.fill : nanv) : cols[c].data()[r]);
-            src_row.push_back(r);
-        }
+        for (int64_t r = 0; r < n; ++r)
+            if (push_kept_row(cols, r, pol, kept)) src_row.push_back(r);
         nk = (int64_t)src_row.size();
         for (auto& v : kept) ptrs.push_back(v.data());
     } else {
