@@ -872,4 +872,9 @@ int pds_gather_f32(pds_ctx* const* ctxs, int n_ctx, const float* const* src, con
 }
 int pds_debug_last_multi_route(void) { return pds::g_multi_route; }
 int pds_debug_last_grouped_route(void) { return pds::g_grouped_route; }
+int pds_debug_last_by_key_route(int* info /* 4 ints, nullable */) {
+    if (info)
+        for (int i = 0; i < 4; ++i) info[i] = pds::g_by_key_info[i];
+    return pds::g_by_key_route;
+}
 }  // extern "C"

@@ -9,6 +9,12 @@
 // which way the last grouped call of this thread with 17 .. 32 f64 features went (tests): 0 neither, 1 the fused stream, 2 the record
 // pipeline after the fused form gave the call back (marked list overflow)
 static thread_local int g_grouped_route = 0;
+// which way the last pds_lr_by_key* call of this thread went (tests; pds_debug_last_by_key_route): -1 none yet / the call failed before
+// it chose, 0 keys already in order, 1 the partition route (keyed_partition.hip), 2 sort + gather; info = {part_shift, n_buckets,
+// histogram taken from the order check's slots (1 / 0), per-row prediction mode of the partition route (0 none, 2 rank lookup, 3 id
+// table)} -- zeros off the partition route
+static thread_local int g_by_key_route = -1;
+static thread_local int g_by_key_info[4] = {0, 0, 0, 0};
 // Groups with more than 64 features (coverage path): every group's Gram matrix comes from the tiled matrix-core SYRK of the
 // single-regression path (moments_wide.hip) on that group's row range, the records of a chunk of groups are then solved
 // together (solve_big.hip: Cholesky on an L2-resident workspace, one workgroup per system; CD / NNLS: one wavefront each).
@@ -435,6 +441,8 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
                           ByKeyPlace<T>* place = nullptr) {
     const bool want_pred = pred || resid || row_null;
     const bool want_coef = out_keys || coeffs || place;
+    g_by_key_route = -1;  // (development hook: pds_debug_last_by_key_route never reports an earlier call)
+    g_by_key_info[0] = g_by_key_info[1] = g_by_key_info[2] = g_by_key_info[3] = 0;
     if (!ctx || !cols || !keys || !prm) return fail(PDS_ERR_INVALID, "null argument");
     if (!want_pred && !place && (!out_keys || !coeffs || !n_groups)) return fail(PDS_ERR_INVALID, "null argument");
     if (place && space != PDS_HOST) return fail(PDS_ERR_INVALID, "sliced fits take host frames");
@@ -525,6 +533,11 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         int64_t ng = 0;
         const bool use_slots = ko.hist_taken && part_buckets <= kKeySlots;
         const unsigned first_slot = (unsigned)((part_base >> part_shift) & (int64_t)(kKeySlots - 1));
+        g_by_key_route = 1;
+        g_by_key_info[0] = part_shift;
+        g_by_key_info[1] = (int)part_buckets;
+        g_by_key_info[2] = use_slots ? 1 : 0;
+        g_by_key_info[3] = !want_pred ? 0 : (pred_table ? 3 : 2);
         const int rc0 = keyed_partition_build<T>(ctx, d_tbl, ko.d_keys, d_part_base, part_range, n_feat, n_rows, part_buckets, pws, cap, d_unique,
                                                  d_offsets, &ng, st, use_slots ? ko.d_slots : nullptr, first_slot);
         if (n_groups) *n_groups = ng;
@@ -554,6 +567,7 @@ static int lr_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* key
         return PDS_OK;
     }
     // ---- the frame in key order (capi_keyed_frame.hpp), then the fit on contiguous groups
+    g_by_key_route = sorted ? 0 : 2;
     const int64_t run_cap = sorted ? std::min<int64_t>(ko.n_runs + 1, cap) : n_rows;
     if (int rc = ensure_ws(ctx, ctx->keyed, keyed_frame_bytes<T>(sorted, n_rows, nc, space, run_cap) + out_need)) return rc;
     tr.mark("workspace");

@@ -7,6 +7,7 @@ the oracle against; nothing in it follows either one's operation order.
     report(X, y, std_err="se", y_var=None, digits=None) -> dict
         X: [n, p'] with the bias column already appended (as the oracle takes it); y: [n]
         beta, std_err (the requested type), se_all (all five types), t, p, ci_lo, ci_hi, r2, adj_r2, dof, h (leverages)
+    beta(X, y, digits=None) -> the coefficients alone, formed the same way (tests/partition_cases.py)
 
 Gram X'X and X'y in extended precision, the inverse by Gauss-Jordan elimination with complete pivoting, beta = inv X'y plus one
 step of iterative refinement, residuals, leverages h_i = x_i' inv x_i, the sandwich inv (X' diag(s) X) inv, and var(y)
@@ -130,6 +131,19 @@ def report(X, y, std_err="se", y_var=None, digits=None) -> dict:
         tc = st.t.ppf(0.975, dof) if dof > 0 else np.nan
     return {"beta": b, "std_err": se_v, "se_all": se_all, "t": t, "p": p, "ci_lo": b - tc * se_v, "ci_hi": b + tc * se_v,
             "r2": r2, "adj_r2": adj, "dof": dof, "h": h}
+
+
+def beta(X, y, digits=None) -> np.ndarray:
+    """The coefficients alone, the way report() forms them: extended-precision normal equations, `inverse`, one refinement step."""
+    ops = _Ld() if digits is None and EXTENDED else _Mp(digits or 40)
+    with ops.ctx():
+        Xl, yl = ops.arr(X), ops.arr(y)
+        G = Xl.T @ Xl
+        xty = Xl.T @ yl
+        inv = inverse(G, ops)
+        b = inv @ xty
+        b = b + inv @ (xty - G @ b)
+        return _f64(b)
 
 
 def nrel(a, truth) -> float:

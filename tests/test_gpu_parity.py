@@ -49,6 +49,20 @@ def nrel(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
+def by_key_route():
+    """Which way this thread's last pds_lr_by_key* call went (pds_debug_last_by_key_route): (route, info) -- route 0 keys already in
+    order, 1 the partition route, 2 sort + gather; info = [part_shift, n_buckets, histogram from the order check's slots, per-row
+    prediction mode (0 none, 2 rank lookup, 3 id table)]"""
+    import ctypes as C
+
+    from polars_ds_extension_amd import _lib
+
+    fn = _lib.load().pds_debug_last_by_key_route
+    fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_int)]
+    info = (C.c_int * 4)()
+    return int(fn(info)), [int(v) for v in info]
+
+
 def frel(a, b, floor):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
@@ -666,9 +680,12 @@ def test_context_options(pds):
     perm = rng.permutation(N)
     cols, yt, kt = cols_of(X[perm]), dev(y[perm]), dev(key[perm])
     k0, c0, n0 = pds.lin_reg_by_key(*cols, target=yt, key=kt, ctx=ctx)           # partition route
+    assert by_key_route()[0] == 1
     ctx.set_option("keyed_sort", 1)
     k1, c1, n1 = pds.lin_reg_by_key(*cols, target=yt, key=kt, ctx=ctx)
+    assert by_key_route()[0] == 2
     k2, c2, n2 = pds.lin_reg_by_key(*cols, target=yt, key=kt, ctx=ctx)
+    assert by_key_route()[0] == 2
     ctx.set_option("keyed_sort", 0)
     assert torch.equal(c1, c2) and torch.equal(n1, n2) and torch.equal(k1, k2)
     assert torch.equal(k0, k1) and torch.equal(n0, n1)
@@ -691,11 +708,13 @@ def test_partition_route_does_not_reserve_the_sort_routes_workspace(pds):
     frame_bytes = N * (p + 1) * 8
     ctx = pds.Context(0)
     pds.lin_reg_by_key(*cols, target=yt, key=kt, ctx=ctx, max_groups=G)
+    assert by_key_route()[0] == 1
     part = ctx.workspace_bytes("keyed")
     ctx.close()
     ctx = pds.Context(0)
     ctx.set_option("keyed_sort", 1)
     pds.lin_reg_by_key(*cols, target=yt, key=kt, ctx=ctx, max_groups=G)
+    assert by_key_route()[0] == 2
     srt = ctx.workspace_bytes("keyed")
     ctx.close()
     # sort route: 2 key copies + 2 rank arrays + a gathered copy of the frame twice over (columns + packed rows) > 2 frames;
@@ -730,8 +749,11 @@ def test_by_key_pred_partition_route(pds, orc, p, bias, f32):
     pds.config.LIN_REG_EXPR_F64 = not f32
     try:
         pred, resid, rn = pds.lin_reg_by_key_pred(*cols_of(Xp.astype(dt)), target=dev(yp.astype(dt)), key=dev(kp), add_bias=bias)
+        route, info = by_key_route()
+        assert route == 1 and info[3] == 3, (route, info)
         order = np.argsort(kp, kind="stable")
         ps, rs, ns = pds.lin_reg_by_key_pred(*cols_of(Xp[order].astype(dt)), target=dev(yp[order].astype(dt)), key=dev(kp[order]), add_bias=bias)
+        assert by_key_route()[0] == 0
     finally:
         pds.config.LIN_REG_EXPR_F64 = True
     pred, resid, rn = pred.cpu().numpy().astype(np.float64), resid.cpu().numpy().astype(np.float64), rn.cpu().numpy().astype(bool)
@@ -944,6 +966,7 @@ def test_by_key_shuffled_rows_beyond_16_features(pds, orc, p, bias, l2):
         X[off0[g]: off0[g + 1], 3] = X[off0[g]: off0[g + 1], 0] - X[off0[g]: off0[g + 1], 2]
     perm = rng.permutation(N)
     k1, c1, n1 = pds.lin_reg_by_key(*cols_of(X[perm]), target=dev(y[perm]), key=dev(key[perm]), add_bias=bias, l2_reg=l2)
+    assert by_key_route()[0] == 2
     k1, c1, n1 = k1.cpu().numpy(), c1.cpu().numpy(), n1.cpu().numpy().astype(bool)
     order = np.argsort(key, kind="stable")
     uk, cnt = np.unique(key[order], return_counts=True)
@@ -986,6 +1009,7 @@ def test_by_key_partition_route_against_oracle(pds, orc, p, bias, kw):
     perm = rng.permutation(N)
     kp, Xp, yp = key[perm], X[perm], y[perm]
     k1, c1, n1 = pds.lin_reg_by_key(*cols_of(Xp), target=dev(yp), key=dev(kp), add_bias=bias, tol=1e-9, max_iter=2000, **kw)
+    assert by_key_route()[0] == 1
     k1, c1, n1 = k1.cpu().numpy(), c1.cpu().numpy(), n1.cpu().numpy().astype(bool)
     order = np.argsort(key, kind="stable")
     ks, Xs, ys = key[order], X[order], y[order]
@@ -1010,6 +1034,7 @@ def test_by_key_partition_route_against_oracle(pds, orc, p, bias, kw):
     assert worst < (1e-8 if kw.get("l1_reg") or kw.get("positive") else F64_TOL), worst
     # the frame in key order (nothing moves, fused streaming kernel): same groups, same nulls, same fits
     k2, c2, n2 = pds.lin_reg_by_key(*cols_of(Xs), target=dev(ys), key=dev(ks), add_bias=bias, tol=1e-9, max_iter=2000, **kw)
+    assert by_key_route()[0] == 0
     assert np.array_equal(k2.cpu().numpy(), k1) and np.array_equal(n2.cpu().numpy().astype(bool), n1)
     ok = ~n1 & (cnt >= 2 * pp + 8)
     d = np.linalg.norm(c2.cpu().numpy()[ok] - c1[ok], axis=1) / np.linalg.norm(c1[ok], axis=1)
@@ -1017,12 +1042,16 @@ def test_by_key_partition_route_against_oracle(pds, orc, p, bias, kw):
     # host frame through the same route
     k3, c3, n3 = pds.lin_reg_by_key(*[np.ascontiguousarray(Xp[:, j]) for j in range(p)], target=yp, key=kp, add_bias=bias, tol=1e-9,
                                     max_iter=2000, **kw)
+    assert by_key_route()[0] == 1
     assert np.array_equal(k3, k1) and np.array_equal(n3.astype(bool), n1)
     assert np.max(np.linalg.norm(c3[ok] - c1[ok], axis=1) / np.linalg.norm(c1[ok], axis=1)) < 1e-9
     if not kw:
-        # per-row predictions of the shuffled frame (grouped_pred.hip MODE 2: the row's group looked up from its key, nothing
-        # permuted): the route's own coefficients applied to every row where it lies; rows of null groups are null
+        # per-row predictions of the shuffled frame (grouped_pred.hip MODE 3: the row's dense id, key - base, indexes an id-indexed
+        # copy of the coefficient block, nothing permuted): the route's own coefficients applied to every row where it lies; rows of
+        # null groups are null
         pr, rs, rn = pds.lin_reg_by_key_pred(*cols_of(Xp), target=dev(yp), key=dev(kp), add_bias=bias)
+        route, info = by_key_route()
+        assert route == 1 and info[3] == 3, (route, info)
         pr, rs, rn = pr.cpu().numpy(), rs.cpu().numpy(), rn.cpu().numpy().astype(bool)
         gi = np.searchsorted(uk, kp)
         assert np.array_equal(rn, n1[gi])
@@ -1034,6 +1063,7 @@ def test_by_key_partition_route_against_oracle(pds, orc, p, bias, kw):
         assert np.max(np.abs(rs[live] - (yp[live] - own)) / np.maximum(scale, np.abs(yp[live]))) < 1e-12
         assert np.all(np.isnan(pr[rn])) and np.all(np.isnan(rs[rn]))
         ph, rh, nh = pds.lin_reg_by_key_pred(*[np.ascontiguousarray(Xp[:, j]) for j in range(p)], target=yp, key=kp, add_bias=bias)
+        assert by_key_route()[0] == 1
         # (not bit for bit: the records of a bucket arrive in the order of the scatter's atomics, so the sums round differently per call)
         assert np.array_equal(nh.astype(bool), rn)
         assert np.max(np.abs(ph[live] - pr[live]) / scale) < 1e-9 and np.max(np.abs(rh[live] - rs[live]) / np.maximum(scale, np.abs(yp[live]))) < 1e-9
@@ -1060,7 +1090,11 @@ def test_by_key_partition_route_unaligned_keys_and_negative_base(pds, orc):
     k_al = torch.from_numpy(kp).cuda()
     assert kbuf[1:].data_ptr() % 16 == 8 and k_al.data_ptr() % 16 == 0
     k1, c1, n1 = pds.lin_reg_by_key(*cols_of(Xp), target=dev(yp), key=k_al, add_bias=True)
+    route, info = by_key_route()
+    assert route == 1 and info[2] == 1, (route, info)   # the histogram came from the order check's slots
     k2, c2, n2 = pds.lin_reg_by_key(*cols_of(Xp), target=dev(yp), key=kbuf[1:], add_bias=True)
+    route, info = by_key_route()
+    assert route == 1 and info[2] == 0, (route, info)   # the separate histogram pass
     assert torch.equal(k1, k2) and torch.equal(n1, n2) and np.array_equal(k1.cpu().numpy(), np.sort(keys_g))
     assert float(torch.max(torch.linalg.norm(c1 - c2, dim=1) / torch.linalg.norm(c1, dim=1))) < 1e-10
     order = np.argsort(key, kind="stable")
@@ -1083,6 +1117,7 @@ def test_by_key_partition_route_f32_and_giant_group(pds, orc, f32):
     y = (X @ rng.normal(size=p) + 0.1 * rng.normal(size=N) + 0.25).astype(np.float32)
     perm = rng.permutation(N)
     k1, c1, n1 = pds.lin_reg_by_key(*cols_of(X[perm]), target=dev(y[perm]), key=dev(key[perm]), add_bias=True)
+    assert by_key_route()[0] == 1
     assert c1.dtype.is_floating_point and c1.element_size() == 4 and not n1.any().item()
     c1 = c1.cpu().numpy().astype(np.float64)
     off = np.concatenate([[0], np.cumsum(sizes)])
@@ -1186,6 +1221,7 @@ def test_grouped_by_key_any_row_order(pds, orc, p, bias):
             k_out, co, nu = k_out.cpu().numpy(), co.cpu().numpy(), nu.cpu().numpy()
         else:
             k_out, co, nu = pds.lin_reg_by_key(*[np.ascontiguousarray(Xs[:, j]) for j in range(p)], target=ys, key=ks, add_bias=bias)
+        assert by_key_route()[0] == 2  # (fewer than 2^16 rows: sort + gather)
         assert np.array_equal(k_out, ko) and np.array_equal(nu.astype(bool), nu_o)
         assert np.max(np.linalg.norm(co - co_o, axis=1) / np.linalg.norm(co_o, axis=1)) < 1e-9
     # keys already in order: no data movement, identical results
@@ -1585,6 +1621,7 @@ def test_grouped_solver_svd_gate(pds, orc, p):
         key = np.repeat(np.arange(G, dtype=np.int64), sizes)
         perm = rng.permutation(N)
         k2, co2, nu2 = pds.lin_reg_by_key(*cols_of(X[perm]), target=dev(y[perm]), key=dev(key[perm]), add_bias=True, solver="svd")
+        assert by_key_route()[0] == 2
         assert np.array_equal(nu2.cpu().numpy().astype(bool), nu_o)
         co2 = co2.cpu().numpy()
         assert np.median(np.linalg.norm(co2[ok] - co_o[ok], axis=1) / np.linalg.norm(co_o[ok], axis=1)) < 1e-10
