@@ -648,6 +648,49 @@ int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                             float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, float* pred, uint8_t* row_null);
 /*
+ * pds_glm_irls_wo_grouped_* / pds_glm_irls_wo_by_key_*: the grouped fits with a prior weight pw_i and an offset o_i per row (R's
+ * glm(weights=, offset=), statsmodels' var_weights=, offset=) -- the argument lists of their twins above with `weights`, `offset`
+ * after `cols`: both nullable (pw = 1, o = 0), `space`-resident, n_rows long.  With both null the twin's implementation is called:
+ * the same bits.  Per group, everything else as in the twins:
+ *     eta_i = x_i . beta + o_i,  mu_i = g^-1(eta_i),  working weight w_i = pw_i / (g'(mu_i)^2 V(mu_i)),
+ *     working response z_i = (eta_i - o_i) + g'(mu_i) (y_i - mu_i);
+ *     start: mu = (y + 0.5) / 2 (binomial), mu = (y + ybar) / 2 otherwise with ybar = sum pw_i y_i / sum pw_i, then eta = g(mu) --
+ *     the offset enters the first iteration only through z;
+ *     the same pivoted-QR solve (16 features + bias: weighted centring), stopping rule, n_iter and NaN rule.
+ * A row with pw_i = 0 contributes nothing and does not count as a row.  A group is null (NaN coefficients, n_iter = 0, NaN pred and
+ * row_null = 1 on its rows) when fewer than n_feat + add_bias of its rows have pw_i > 0 or when any pw_i is negative or not
+ * finite; a non-finite offset makes the coefficients non-finite, so the group is null by the twins' rule.  A bad group never changes
+ * another group's bits.  pred = g^-1(x_i . beta_group + o_i) for every row of a non-null group, rows of weight 0 included.
+ * By key the two columns travel with the frame: ordered keys move nothing, unordered keys take the same sort + gather; a host frame
+ * stages them with the other columns.  1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED).
+ * Groups longer than "glm_split_rows" are fitted one by one with the full-device iteration of pds_glm_irls_wo_* on their row range of
+ * the two columns; such a group that fails the weight rule is null like any other.
+ * pds_glm_irls_wo_*: the one-model form, the argument list of pds_glm_irls_* with `weights`, `offset` after `cols`, any width that
+ * pds_glm_irls_* takes.  Each iteration writes the weight and the working response as two columns and runs the weighted Gram build
+ * on them (what pds_glm_irls_* does above 16 features).  A negative or non-finite weight, or fewer rows of positive weight than
+ * coefficients, is PDS_ERR_INVALID with a message.
+ * Not built: a penalty together with either column (the pds_glm_enet_* forms take neither).  The report: pds_glm_report_wo_*.
+ */
+int pds_glm_irls_wo_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                        pds_space space, int add_bias, int link, int variance, double tol, int max_iter, double* coeffs, int* n_iter);
+int pds_glm_irls_wo_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                        pds_space space, int add_bias, int link, int variance, float tol, int max_iter, float* coeffs, int* n_iter);
+int pds_glm_irls_wo_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat,
+                                int64_t n_rows, const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link,
+                                int variance, double tol, int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred,
+                                uint8_t* row_null);
+int pds_glm_irls_wo_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                                const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                float tol, int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null);
+int pds_glm_irls_wo_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                               int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                               int64_t max_groups, int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                               double* pred, uint8_t* row_null);
+int pds_glm_irls_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                               int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                               int64_t max_groups, int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                               float* pred, uint8_t* row_null);
+/*
  * pds_glm_enet_* / pds_glm_enet_grouped_* / pds_glm_enet_by_key_*: the elastic-net penalised fits -- the argument lists of their
  * pds_glm_irls_* twins with l1_reg, l2_reg after `variance`; everything said there holds.  For a frame or group of n rows,
  * coefficients beta with features j < p and an optional unpenalised bias last, the fit minimises
@@ -731,6 +774,29 @@ int pds_glm_report_by_key_f64(pds_ctx* ctx, const double* const* cols, const int
 int pds_glm_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                               int add_bias, int link, int variance, float tol, int max_iter, int64_t max_groups, int64_t* out_keys,
                               float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out);
+/*
+ * pds_glm_report_wo_grouped_* / pds_glm_report_wo_by_key_*: the fit of pds_glm_irls_wo_grouped_* / _by_key_* and its report per group --
+ * the argument lists of pds_glm_report_grouped_* / _by_key_* with `weights`, `offset` after `cols` (both nullable; both null: the
+ * twin's call).  The unscaled convention extended: I = sum pw_i w~_i x_i x_i' with w~ = 1 / (g'^2 V) at mu_i = g^-1(x_i . beta + o_i);
+ * pearson_chi2 = sum pw_i (y_i - mu_i)^2 / V(mu_i); deviance = sum pw_i d_i; df_resid = n+ - p' (n+: the rows of positive weight);
+ * dispersion, cov, se, z, p and the interval from those as in the twins; null_deviance without an offset: the twins' closed form with
+ * weighted sums (at ybar = sum pw y / sum pw under a bias, at g^-1(0) without); with an offset: NaN (the intercept-only model under an
+ * offset needs an iteration of its own).  A group that is null by the weight rule has a null report.
+ */
+int pds_glm_report_wo_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                                  const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                  double tol, int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out);
+int pds_glm_report_wo_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys, int n_feat,
+                                 int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                                 int64_t max_groups, int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                                 const pds_glm_report_out* out);
+int pds_glm_report_wo_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                                  const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                  float tol, int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out);
+int pds_glm_report_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys, int n_feat,
+                                 int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                                 int64_t max_groups, int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                                 const pds_glm_report_out* out);
 /*
  * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
  * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on

@@ -169,6 +169,46 @@ int pds_glm_irls_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                                        out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null);
 }
 
+// prior weights and an offset per row: the argument lists of pds_glm_irls_* / _grouped_* / _by_key_* with `weights`, `offset` after
+// `cols` (both nullable; both null: the twin's call)
+int pds_glm_irls_wo_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                        pds_space space, int add_bias, int link, int variance, double tol, int max_iter, double* coeffs, int* n_iter) {
+    return pds::glm_irls_wo_impl<double>(ctx, cols, weights, offset, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs,
+                                         n_iter);
+}
+int pds_glm_irls_wo_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                        pds_space space, int add_bias, int link, int variance, float tol, int max_iter, float* coeffs, int* n_iter) {
+    return pds::glm_irls_wo_impl<float>(ctx, cols, weights, offset, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs,
+                                        n_iter);
+}
+int pds_glm_irls_wo_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat,
+                                int64_t n_rows, const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link,
+                                int variance, double tol, int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, double* pred,
+                                uint8_t* row_null) {
+    return pds::glm_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, 0.0, 0.0, tol,
+                                         max_iter, coeffs, n_iter, is_null, pred, row_null, nullptr, weights, offset);
+}
+int pds_glm_irls_wo_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                                const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                float tol, int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, float* pred, uint8_t* row_null) {
+    return pds::glm_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, 0.0f, 0.0f, tol,
+                                        max_iter, coeffs, n_iter, is_null, pred, row_null, nullptr, weights, offset);
+}
+int pds_glm_irls_wo_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                               int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                               int64_t max_groups, int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                               double* pred, uint8_t* row_null) {
+    return pds::glm_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, 0.0, 0.0, tol, max_iter, max_groups,
+                                        out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null, weights, offset);
+}
+int pds_glm_irls_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                               int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                               int64_t max_groups, int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                               float* pred, uint8_t* row_null) {
+    return pds::glm_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, 0.0f, 0.0f, tol, max_iter, max_groups,
+                                       out_keys, coeffs, n_iter, is_null, n_groups, pred, row_null, weights, offset);
+}
+
 // the grouped GLM report: the fit of pds_glm_irls_grouped_* / _by_key_* and its report per group (capi_glm_report.hpp)
 int pds_glm_report_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
                                int64_t n_groups, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
@@ -193,6 +233,34 @@ int pds_glm_report_by_key_f32(pds_ctx* ctx, const float* const* cols, const int6
                               float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out) {
     return pds::glm_report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
                                               out_keys, coeffs, n_iter, is_null, n_groups, out);
+}
+
+// the report with prior weights and an offset per row: the argument lists of pds_glm_report_* with `weights`, `offset` after `cols`
+int pds_glm_report_wo_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                                  const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                  double tol, int max_iter, double* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out) {
+    return pds::glm_report_grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol,
+                                                max_iter, coeffs, n_iter, is_null, out, weights, offset);
+}
+int pds_glm_report_wo_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys, int n_feat,
+                                 int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol, int max_iter,
+                                 int64_t max_groups, int64_t* out_keys, double* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                                 const pds_glm_report_out* out) {
+    return pds::glm_report_by_key_impl<double>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
+                                               out_keys, coeffs, n_iter, is_null, n_groups, out, weights, offset);
+}
+int pds_glm_report_wo_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                                  const int64_t* group_offsets, int64_t n_groups, pds_space space, int add_bias, int link, int variance,
+                                  float tol, int max_iter, float* coeffs, int32_t* n_iter, uint8_t* is_null, const pds_glm_report_out* out) {
+    return pds::glm_report_grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, add_bias, link, variance, tol,
+                                                max_iter, coeffs, n_iter, is_null, out, weights, offset);
+}
+int pds_glm_report_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys, int n_feat,
+                                 int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol, int max_iter,
+                                 int64_t max_groups, int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
+                                 const pds_glm_report_out* out) {
+    return pds::glm_report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
+                                               out_keys, coeffs, n_iter, is_null, n_groups, out, weights, offset);
 }
 
 // the elastic-net penalised fits: the argument lists of pds_glm_irls_* with l1_reg, l2_reg after `variance` (<= 0: no penalty)

@@ -1,6 +1,7 @@
 // capi_glm_grouped.hpp -- a GLM per group (IRLS): contiguous groups (pds_glm_irls_grouped_*) and int64 keys in any row order
 // (pds_glm_irls_by_key_*) on top of grouped_irls.hip; with l1_reg / l2_reg the elastic-net penalised fits (pds_glm_enet_grouped_* /
-// pds_glm_enet_by_key_*), a penalty <= 0 meaning none
+// pds_glm_enet_by_key_*), a penalty <= 0 meaning none; with a prior-weight and / or an offset column the weighted / offset fits
+// (pds_glm_irls_wo_grouped_* / pds_glm_irls_wo_by_key_*)
 // Part of the one translation unit capi.hip (included there, inside namespace pds, in dependency order): the entry-point
 // pipelines are templates with internal linkage, split by concern, not by compilation unit.
 #pragma once
@@ -12,10 +13,13 @@ constexpr int64_t kGlmSplitRowsDefault = 16384;
 // d_perm (device, nullable): row r of the frame in
 // group order is row d_perm[r] of pred / row_null.  Its buffers come out of ctx->wkeyed: the full-device iteration of a long group
 // re-reserves ctx->ws, and the by-key form holds its frame in ctx->keyed.
+// weights / offset (nullable, in `space`, n_rows long): with either one the weighted / offset kernels of grouped_irls.hip fit the
+// groups and glm_irls_wo_impl the long ones, on their row range of the two columns; with neither the call is the one it was.
 template <typename T>
 static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups,
                             pds_space space, int add_bias, int link, int variance, T l1_reg, T l2_reg, T tol, int max_iter, T* coeffs,
-                            int32_t* n_iter, uint8_t* is_null, T* pred, uint8_t* row_null, const uint32_t* d_perm = nullptr) {
+                            int32_t* n_iter, uint8_t* is_null, T* pred, uint8_t* row_null, const uint32_t* d_perm = nullptr,
+                            const T* weights = nullptr, const T* offset = nullptr) {
     if (!ctx || !cols || !offsets || !coeffs || !n_iter || !is_null) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -23,8 +27,11 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    const bool wo = weights || offset;
+    if (wo && (l1_reg > 0 || l2_reg > 0))
+        return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): l1_reg / l2_reg together with weights / offset is not built");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int bias = add_bias ? 1 : 0, pp = n_feat + bias, nc = n_feat + 1;
+    const int bias = add_bias ? 1 : 0, pp = n_feat + bias, nc = n_feat + 1 + (weights ? 1 : 0) + (offset ? 1 : 0);
     const bool host_frame = space == PDS_HOST;
     const bool host_out = space == PDS_HOST;
     const int64_t split = std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
@@ -40,18 +47,21 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     outs.add(&d_nu, is_null, 1);
     row_outs.add(&d_pred, pred, 1);
     row_outs.add(&d_rn, row_null, 1);
-    size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)long_cap * 8) + 256 + outs.bytes() + row_outs.bytes();
+    size_t need = 4096 + up(sizeof(T*) * (wo ? 20 : 18)) + up((size_t)long_cap * 8) + 256 + outs.bytes() + row_outs.bytes();
     if (host_frame) need += col_bytes * nc;
     if (host_out) need += up((size_t)(n_groups + 1) * 8);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     // ---- the frame: device pointers in the kernels' order x_0 .. x_{p-1}, y
-    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp (, weights) (, offset)], device resident
+    if (weights) src.push_back(weights);
+    if (offset) src.push_back(offset);
     if (host_frame)
         if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
     std::vector<const T*> tbl;
     const T** d_tbl = nullptr;
-    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+    const T* const d_wo[2] = {weights ? src[n_feat + 1] : nullptr, offset ? src[nc - 1] : nullptr};  // (device resident by now)
+    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl, wo ? d_wo : nullptr)) return rc;
     int64_t* d_long = w.take<int64_t>((size_t)long_cap);
     unsigned* d_count = w.take<unsigned>(64);
     PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
@@ -63,9 +73,15 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     }
     outs.place(w);
     row_outs.place(w);
-    if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
-                                        d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap, (double)l1_reg, (double)l2_reg))
+    if (wo) {
+        if (int rc = launch_grouped_irls_wo<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
+                                               d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap))
+            return rc;
+    } else if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter,
+                                               split, d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap, (double)l1_reg,
+                                               (double)l2_reg)) {
         return rc;
+    }
     unsigned h_count = 0;
     PDS_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
@@ -87,12 +103,18 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
             } else {
                 PDS_HIP_CHECK(hipMemcpy(rr, d_off + g, 16, hipMemcpyDeviceToHost));
             }
-            std::vector<const T*> gc(nc);
-            for (int c = 0; c < nc; ++c) gc[c] = src[c] + rr[0];
-            int its = 0;
-            if (int rc = glm_irls_impl<T>(ctx, gc.data(), n_feat, rr[1] - rr[0], PDS_DEVICE, add_bias, link, variance, tol, max_iter,
-                                          hb.data() + k * pp, &its, l1_reg, l2_reg))
+            std::vector<const T*> gc(n_feat + 1);
+            for (int c = 0; c <= n_feat; ++c) gc[c] = src[c] + rr[0];
+            int its = 0, wnull = 0;  // (a long group that fails the weight rule is null, like a short one)
+            if (wo) {
+                if (int rc = glm_irls_wo_impl<T>(ctx, gc.data(), d_wo[0] ? d_wo[0] + rr[0] : nullptr, d_wo[1] ? d_wo[1] + rr[0] : nullptr, n_feat,
+                                                 rr[1] - rr[0], PDS_DEVICE, add_bias, link, variance, tol, max_iter, hb.data() + k * pp, &its,
+                                                 &wnull))
+                    return rc;
+            } else if (int rc = glm_irls_impl<T>(ctx, gc.data(), n_feat, rr[1] - rr[0], PDS_DEVICE, add_bias, link, variance, tol, max_iter,
+                                                 hb.data() + k * pp, &its, l1_reg, l2_reg)) {
                 return rc;
+            }
             hi[k] = its;
             bool fin = true;
             for (int j = 0; j < pp; ++j) fin = fin && std::isfinite(hb[k * pp + j]);
@@ -100,7 +122,8 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
             PDS_HIP_CHECK(hipMemcpyAsync(d_co + g * pp, hb.data() + k * pp, sizeof(T) * pp, hipMemcpyHostToDevice, ctx->stream));
             PDS_HIP_CHECK(hipMemcpyAsync(d_it + g, &hi[k], 4, hipMemcpyHostToDevice, ctx->stream));
             PDS_HIP_CHECK(hipMemcpyAsync(d_nu + g, &hn[k], 1, hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = launch_glm_pred_range<T>(ctx, d_tbl, n_feat, bias, rr[0], rr[1], d_co + g * pp, d_nu + g, link, d_pred, d_rn, d_perm))
+            if (int rc = launch_glm_pred_range<T>(ctx, d_tbl, n_feat, bias, rr[0], rr[1], d_co + g * pp, d_nu + g, link, d_pred, d_rn, d_perm,
+                                                  d_wo[1]))
                 return rc;
         }
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (hb / hi / hn: sources of the copies)
@@ -119,7 +142,8 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
 template <typename T>
 static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int add_bias,
                            int link, int variance, T l1_reg, T l2_reg, T tol, int max_iter, int64_t max_groups, int64_t* out_keys, T* coeffs,
-                           int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, T* pred, uint8_t* row_null) {
+                           int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, T* pred, uint8_t* row_null, const T* weights = nullptr,
+                           const T* offset = nullptr) {
     if (!ctx || !cols || !keys || !out_keys || !coeffs || !n_iter || !is_null || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -128,6 +152,8 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    if ((weights || offset) && (l1_reg > 0 || l2_reg > 0))
+        return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): l1_reg / l2_reg together with weights / offset is not built");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int pp = n_feat + (add_bias ? 1 : 0);
     T *d_co, *d_pred;
@@ -140,7 +166,9 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     row_outs.add(&d_pred, pred, 1, StagedOuts::kOutRoom);
     row_outs.add(&d_rn, row_null, 1, StagedOuts::kOutRoom);
     KeyedFrame<T> kf;
-    kf.src = frame_cols<T>(cols, n_feat);
+    kf.src = frame_cols<T>(cols, n_feat);  // the two columns ride through the staging, the sort and the gather with the frame
+    if (weights) kf.src.push_back(weights);
+    if (offset) kf.src.push_back(offset);
     Bump w{};
     if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, max_groups, [&](bool) { return outs.bytes() + row_outs.bytes(); }, n_groups, kf, w))
         return rc;
@@ -148,7 +176,8 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     outs.place(w);
     row_outs.place(w);
     if (int rc = glm_grouped_impl<T>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, ng, PDS_DEVICE, add_bias, link, variance, l1_reg, l2_reg, tol, max_iter,
-                                     d_co, d_it, d_nu, d_pred, d_rn, kf.d_perm))
+                                     d_co, d_it, d_nu, d_pred, d_rn, kf.d_perm, weights ? kf.src[n_feat + 1] : nullptr,
+                                     offset ? kf.src.back() : nullptr))
         return rc;
     const hipMemcpyKind back = space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, back, ctx->stream));

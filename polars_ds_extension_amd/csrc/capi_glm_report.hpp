@@ -31,12 +31,15 @@ static StagedOuts glm_report_staged_outs(const pds_glm_report_out& out, GlmRepor
 // Fit and report of a DEVICE-resident frame (src: reference order [y, x1..xp]; every pointer a device pointer).  The fit is
 // glm_grouped_impl as the pds_glm_irls_* entry points call it; the report's own arrays come out of ctx->ws, which the fit has
 // finished with (its full-device iteration of long groups re-reserves it).
+// d_pw / d_o (device, nullable): prior weights and offsets -- the weighted / offset fit and the weighted / offset report kernels
+// (grouped_glm_report_wo.hip); with neither, the calls they always were.
 template <typename T>
 static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int n_feat, int64_t n_rows, const int64_t* d_off, int64_t n_groups,
                              int add_bias, int link, int variance, T tol, int max_iter, T* d_co, int32_t* d_it, uint8_t* d_nu,
-                             const GlmReportDev<T>& d) {
+                             const GlmReportDev<T>& d, const T* d_pw = nullptr, const T* d_o = nullptr) {
+    const bool wo = d_pw || d_o;
     if (int rc = glm_grouped_impl<T>(ctx, src.data(), n_feat, n_rows, d_off, n_groups, PDS_DEVICE, add_bias, link, variance, (T)0, (T)0, tol,
-                                     max_iter, d_co, d_it, d_nu, (T*)nullptr, (uint8_t*)nullptr))
+                                     max_iter, d_co, d_it, d_nu, (T*)nullptr, (uint8_t*)nullptr, nullptr, d_pw, d_o))
         return rc;
     const int bias = add_bias ? 1 : 0;
     const int64_t split = std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
@@ -44,21 +47,23 @@ static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int
     const int64_t long_cap = std::min<int64_t>(n_groups, n_rows / split + 1);
     const int64_t piece_cap = n_rows / piece_rows + long_cap + 1;
     const auto up = Bump::up;
-    const size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)long_cap * 8) + 256 + 2 * up((size_t)piece_cap * 24) +
+    const size_t need = 4096 + up(sizeof(T*) * (wo ? 20 : 18)) + up((size_t)long_cap * 8) + 256 + 2 * up((size_t)piece_cap * 24) +
                         up((size_t)piece_cap * kGlmReportRec * 8);
     if (int rc = ws_reserve(ctx, need)) return rc;
     Bump w{static_cast<char*>(ctx->ws.ptr)};
     std::vector<const T*> tbl;
     const T** d_tbl = nullptr;
-    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+    const T* const d_wo[2] = {d_pw, d_o};
+    std::vector<const T*> frame(src.begin(), src.begin() + n_feat + 1);  // (src may carry the two columns behind the frame)
+    if (int rc = kernel_order_table<T>(ctx, w, frame, n_feat, tbl, d_tbl, wo ? d_wo : nullptr)) return rc;
     int64_t* d_long = w.take<int64_t>((size_t)long_cap);
     unsigned* d_count = w.take<unsigned>(64);
     int64_t* d_pieces = w.take<int64_t>((size_t)piece_cap * 3);
     int64_t* d_fin = w.take<int64_t>((size_t)piece_cap * 3);
     double* d_rec = w.take<double>((size_t)piece_cap * kGlmReportRec);
     PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
-    if (int rc = launch_grouped_glm_report<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, split, d_co, d_nu, d, d_long,
-                                              d_count, long_cap))
+    const auto report = wo ? launch_grouped_glm_report_wo<T> : launch_grouped_glm_report<T>;
+    if (int rc = report(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, split, d_co, d_nu, d, d_long, d_count, long_cap))
         return rc;
     unsigned h_count = 0;
     PDS_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
@@ -87,9 +92,8 @@ static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int
     if (n_pieces > piece_cap) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
     PDS_HIP_CHECK(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(d_fin, fin.data(), fin.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = launch_grouped_glm_report_pieces<T>(ctx, d_tbl, n_feat, bias, d_off, link, variance, d_co, d, d_pieces, n_pieces, d_fin, n_fin,
-                                                     d_rec))
-        return rc;
+    const auto pieced = wo ? launch_grouped_glm_report_wo_pieces<T> : launch_grouped_glm_report_pieces<T>;
+    if (int rc = pieced(ctx, d_tbl, n_feat, bias, d_off, link, variance, d_co, d, d_pieces, n_pieces, d_fin, n_fin, d_rec)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (pieces / fin: sources of the copies)
     return PDS_OK;
 }
@@ -109,7 +113,7 @@ static int glm_report_check(const void* ctx, const void* cols, const void* coeff
 template <typename T>
 static int glm_report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups,
                                    pds_space space, int add_bias, int link, int variance, T tol, int max_iter, T* coeffs, int32_t* n_iter,
-                                   uint8_t* is_null, const pds_glm_report_out* out) {
+                                   uint8_t* is_null, const pds_glm_report_out* out, const T* weights = nullptr, const T* offset = nullptr) {
     if (int rc = glm_report_check(ctx, cols, coeffs, n_iter, is_null, out, n_feat, max_iter, link, variance)) return rc;
     if (!offsets) return fail(PDS_ERR_INVALID, "null argument");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -126,10 +130,12 @@ static int glm_report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_fea
     fit.add(&d_it, n_iter, 1);
     fit.add(&d_nu, is_null, 1);
     StagedOuts rep = glm_report_staged_outs<T>(*out, d, host, n_groups, pp);
-    std::vector<const T*> src = frame_cols<T>(cols, n_feat);
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // [y, x1..xp (, weights) (, offset)]: a host frame stages them together
+    if (weights) src.push_back(weights);
+    if (offset) src.push_back(offset);
     const int64_t* d_off = offsets;
     if (host) {
-        const size_t need = 4096 + Bump::up((size_t)n_rows * sizeof(T)) * (n_feat + 1) + Bump::up((size_t)(n_groups + 1) * 8) + fit.bytes() + rep.bytes();
+        const size_t need = 4096 + Bump::up((size_t)n_rows * sizeof(T)) * src.size() + Bump::up((size_t)(n_groups + 1) * 8) + fit.bytes() + rep.bytes();
         if (int rc = ensure_ws(ctx, ctx->stage, need)) return rc;
         Bump w{static_cast<char*>(ctx->stage.ptr)};
         if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
@@ -139,7 +145,8 @@ static int glm_report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_fea
         fit.place(w);
         rep.place(w);
     }
-    if (int rc = glm_report_device<T>(ctx, src, n_feat, n_rows, d_off, n_groups, add_bias, link, variance, tol, max_iter, d_co, d_it, d_nu, d))
+    if (int rc = glm_report_device<T>(ctx, src, n_feat, n_rows, d_off, n_groups, add_bias, link, variance, tol, max_iter, d_co, d_it, d_nu, d,
+                                      weights ? src[n_feat + 1] : nullptr, offset ? src.back() : nullptr))
         return rc;
     if (host) {
         if (int rc = staged_copy_back(ctx, fit, (size_t)n_groups)) return rc;
@@ -153,7 +160,8 @@ static int glm_report_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_fea
 template <typename T>
 static int glm_report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                                   int add_bias, int link, int variance, T tol, int max_iter, int64_t max_groups, int64_t* out_keys, T* coeffs,
-                                  int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out) {
+                                  int32_t* n_iter, uint8_t* is_null, int64_t* n_groups, const pds_glm_report_out* out,
+                                  const T* weights = nullptr, const T* offset = nullptr) {
     if (int rc = glm_report_check(ctx, cols, coeffs, n_iter, is_null, out, n_feat, max_iter, link, variance)) return rc;
     if (!keys || !out_keys || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
@@ -173,14 +181,17 @@ static int glm_report_by_key_impl(pds_ctx* ctx, const T* const* cols, const int6
     fit.add(&d_nu, is_null, 1);
     StagedOuts rep = glm_report_staged_outs<T>(*out, d, host, cap, pp);
     KeyedFrame<T> kf;
-    kf.src = frame_cols<T>(cols, n_feat);
+    kf.src = frame_cols<T>(cols, n_feat);  // (the two columns ride through the staging, the sort and the gather with the frame)
+    if (weights) kf.src.push_back(weights);
+    if (offset) kf.src.push_back(offset);
     Bump w{};
     if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, max_groups, [&](bool) { return fit.bytes() + rep.bytes(); }, n_groups, kf, w))
         return rc;
     const int64_t ng = kf.ng;
     fit.place(w);
     rep.place(w);
-    if (int rc = glm_report_device<T>(ctx, kf.src, n_feat, n_rows, kf.d_offsets, ng, add_bias, link, variance, tol, max_iter, d_co, d_it, d_nu, d))
+    if (int rc = glm_report_device<T>(ctx, kf.src, n_feat, n_rows, kf.d_offsets, ng, add_bias, link, variance, tol, max_iter, d_co, d_it, d_nu, d,
+                                      weights ? kf.src[n_feat + 1] : nullptr, offset ? kf.src.back() : nullptr))
         return rc;
     PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)ng * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
     if (int rc = staged_copy_back(ctx, fit, (size_t)ng)) return rc;

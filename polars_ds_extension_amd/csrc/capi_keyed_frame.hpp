@@ -62,13 +62,18 @@ static int cols_to_device(pds_ctx* ctx, Bump& w, std::vector<const T*>& src, int
 }
 
 // device pointer table of a frame in the kernels' order x_0 .. x_{p-1}, y, padded to 18 entries.  `tbl` is the source of an
-// asynchronous copy: the caller keeps it alive until it has synchronised the stream.
+// asynchronous copy: the caller keeps it alive until it has synchronised the stream.  `trailing` (nullable): two more entries behind
+// y, each of which may be null -- the prior weights and the offsets of the weighted / offset GLM kernels; the table then has 20.
 template <typename T>
 static int kernel_order_table(pds_ctx* ctx, Bump& w, const std::vector<const T*>& src, int n_feat, std::vector<const T*>& tbl,
-                              const T**& d_tbl) {
-    tbl.assign(std::max<size_t>(src.size(), 18), src[0]);
+                              const T**& d_tbl, const T* const* trailing = nullptr) {
+    tbl.assign(trailing ? 20 : std::max<size_t>(src.size(), 18), src[0]);
     for (int c = 0; c < n_feat; ++c) tbl[c] = src[c + 1];
     tbl[n_feat] = src[0];
+    if (trailing) {
+        tbl[n_feat + 1] = trailing[0];
+        tbl[n_feat + 2] = trailing[1];
+    }
     d_tbl = w.take<const T*>(tbl.size());
     PDS_HIP_CHECK(hipMemcpyAsync(d_tbl, tbl.data(), sizeof(T*) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
     return PDS_OK;

@@ -99,6 +99,103 @@ static int glm_irls_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     return PDS_OK;
 }
 
+// The one-model fit with prior weights and an offset per row (pds_glm_irls_wo_*; the groups of a weighted / offset grouped call above
+// glm_split_rows): the iteration above with eta = x . beta + o, w = pw / (g'^2 V), z = (eta - o) + g' (y - mu) and the start from
+// ybar = sum pw y / sum pw.  The weight and the working response are written as two columns (glm_wo_model.hip) and the weighted Gram
+// build reads them, at every width -- the route frames of more than 16 features always took; the fused WM = 3 pass is untouched.
+// The first pass returns the side sums: n+ (rows of positive weight) and the count of weights that are negative or not finite.
+// weight_null (nullable): where given, a frame that fails the weight rule (n+ < p', a bad weight) is a null fit -- NaN coefficients,
+// 0 iterations, *weight_null = 1, PDS_OK; without it the same frame is PDS_ERR_INVALID with a message.
+template <typename T>
+static int glm_irls_wo_impl(pds_ctx* ctx, const T* const* cols, const T* weights, const T* offset, int n_feat, int64_t n_rows,
+                            pds_space space, int add_bias, int link, int variance, T tol, int max_iter, T* coeffs, int* n_iter,
+                            int* weight_null = nullptr) {
+    if (!weights && !offset)
+        return glm_irls_impl<T>(ctx, cols, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, coeffs, n_iter);
+    if (!ctx || !cols || !coeffs) return fail(PDS_ERR_INVALID, "null argument");
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");
+    if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int p = n_feat, bias = add_bias ? 1 : 0, pp = p + bias, q = p + 2, ne = (weights ? 1 : 0) + (offset ? 1 : 0);
+    const bool wide = p > kMaxFeatSmall;
+    const size_t row_bytes = ((size_t)n_rows * sizeof(T) + 255) & ~(size_t)255;
+    if (int rc = ws_reserve(ctx, 262144 + (size_t)max_iter * 1024 + sizeof(T) * (size_t)(2 * q * q + 2 * pp + 16) + sizeof(T*) * (4 * (size_t)p + 128) +
+                                     2 * row_bytes + (wide ? moments_wide_workspace(ctx->num_cus, p, n_rows, true) : 0)))
+        return rc;
+    // one staging of [y, x1..xp, pw?, o?] (a host frame's columns share the staging block), then the frame's own table
+    std::vector<const T*> all(cols, cols + p + 1);
+    if (weights) all.push_back(weights);
+    if (offset) all.push_back(offset);
+    DeviceCols<T> dall, dc;
+    if (int rc = make_device_cols<T>(ctx, all.data(), (const T*)nullptr, p + ne, n_rows, space, dall)) return rc;
+    const T* d_pw = weights ? dall.h_ptrs[p] : nullptr;
+    const T* d_o = offset ? dall.h_ptrs[p + (weights ? 1 : 0)] : nullptr;
+    std::vector<const T*> fr(p + 1);
+    fr[0] = dall.h_ptrs[p + ne];
+    for (int c = 0; c < p; ++c) fr[c + 1] = dall.h_ptrs[c];
+    if (int rc = make_device_cols<T>(ctx, fr.data(), (const T*)nullptr, p, n_rows, PDS_DEVICE, dc)) return rc;
+    T* d_mom = reinterpret_cast<T*>(ws_take(ctx, sizeof(T) * q * q));
+    T* d_beta = reinterpret_cast<T*>(ws_take(ctx, sizeof(T) * (pp + 2)));
+    double* d_sums = reinterpret_cast<double*>(ws_take(ctx, 4 * sizeof(double)));
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
+    if (int rc = launch_glm_wo_sums<T>(ctx, fr[0], d_pw, n_rows, d_sums)) return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (sums[1] > 0.0 || sums[0] < (double)pp) {
+        if (!weight_null)
+            return fail(PDS_ERR_INVALID, sums[1] > 0.0 ? "GLM (IRLS): weights must be finite and not negative"
+                                                       : "GLM (IRLS): fewer rows of positive weight than coefficients");
+        *weight_null = 1;
+        for (int j = 0; j < pp; ++j) coeffs[j] = std::numeric_limits<T>::quiet_NaN();
+        if (n_iter) *n_iter = 0;
+        return PDS_OK;
+    }
+    if (weight_null) *weight_null = 0;
+    IrlsArgs ia;
+    ia.link = link;
+    ia.variance = variance;
+    ia.init = 1;
+    ia.y_mean = sums[3] / sums[2];
+    T* d_w = reinterpret_cast<T*>(ws_take(ctx, row_bytes));
+    T* d_z = reinterpret_cast<T*>(ws_take(ctx, row_bytes));
+    std::vector<const T*> cw(p + 1);
+    cw[0] = d_z;
+    for (int c = 0; c < p; ++c) cw[c + 1] = dc.h_ptrs[c];
+    DeviceCols<T> dcw;  // [z | x1..xp] with the weight column w
+    if (int rc = make_device_cols<T>(ctx, cw.data(), d_w, p, n_rows, PDS_DEVICE, dcw)) return rc;
+    pds_lr_params prm{};
+    prm.add_bias = bias;
+    prm.solver = PDS_SOLVER_QR;
+    prm.max_iter = 1;
+    std::vector<T> beta(pp, T(0)), bnew(pp, T(0));
+    int it = 0;
+    while (it < max_iter) {
+        ++it;
+        const size_t ws_mark = ctx->ws_used;
+        if (int rc = launch_irls_working_wo<T>(ctx, dc, p, n_rows, bias, d_beta, ia, d_pw, d_o, d_w, d_z)) return rc;
+        if (!wide) {
+            if (int rc = launch_moments<T>(ctx, dcw, p, n_rows, true, d_mom)) return rc;
+        } else if (int rc = launch_moments_wide<T>(ctx, dcw, p, n_rows, true, d_mom)) {
+            return rc;
+        }
+        int null_flag = 0;
+        if (int rc = lr_from_device_moments<T>(ctx, d_mom, p, &prm, /*weighted=*/true, bnew.data(), &null_flag, d_beta, false, false, nullptr))
+            return rc;
+        if (wide) ctx->ws_used = ws_mark;
+        ia.init = 0;
+        T max_diff = T(0);
+        for (int j = 0; j < pp; ++j) max_diff = std::max(max_diff, (T)std::fabs(beta[j] - bnew[j]));
+        beta = bnew;
+        if (max_diff < tol) break;
+    }
+    for (int j = 0; j < pp; ++j) coeffs[j] = beta[j];
+    if (n_iter) *n_iter = it;
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return PDS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Fits straight from a row-major matrix (the pyclass route, src/pymodels/py_lr.rs over numpy_faer.rs:10-66).
 // mode 0: LR::fit (faer_solve_lr through the pl_lr dispatch of `prm`), 1: ElasticNet::fit (always coordinate descent),

@@ -326,6 +326,21 @@ int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bi
                         int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
                         const uint32_t* d_perm /*nullable: row r of the frame in group order is row d_perm[r] of the outputs*/,
                         int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg = 0.0, double l2_reg = 0.0);
+// The weighted / offset form (grouped_irls_wo.hip): d_cols holds n_feat + 3 entries, x_0 .. x_{p-1}, y, prior weights, offsets, of
+// which the last two may be null (weights 1, offsets 0).  Unpenalised; groups of more than `split_rows` rows go to d_long_list, as above.
+template <typename T>
+int launch_grouped_irls_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                           int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
+                           int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
+                           const uint32_t* d_perm /*nullable*/, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+// glm_wo_model.hip: the one-model iteration with prior weights d_pw and offsets d_off (device, each nullable).  The side sums of the
+// first pass, d_out4 = {rows of positive weight, weights that are negative or not finite, sum pw, sum pw y}; and the weight and the
+// working response of one IRLS step as two columns, which the weighted Gram build then reads (every width).
+template <typename T>
+int launch_glm_wo_sums(pds_ctx* ctx, const T* d_y, const T* d_pw, int64_t n_rows, double* d_out4);
+template <typename T>
+int launch_irls_working_wo(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, int bias, const T* d_beta, const IrlsArgs& ia,
+                           const T* d_pw, const T* d_off, T* d_w, T* d_z);
 // The penalised IRLS step (l1_reg > 0) is a coordinate descent on the iteration's weighted Gram system: its sweeps end when the
 // largest move of a sweep is below kGiCdInner * tol, or at kGiCdSweeps sweeps (not an error: the outer iteration goes on).
 constexpr double kGiCdInner = 0.1;
@@ -333,7 +348,8 @@ constexpr int kGiCdSweeps = 1000;
 // per-row means g^-1(x . beta) of the rows [r0, r1) from one coefficient vector in device memory
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
-                          const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm);
+                          const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
+                          const T* d_offset = nullptr /*an offset per row of the frame, added to x . beta*/);
 // ---- grouped_glm_report.hip: the report of a GLM per group at the coefficients in d_coeffs (se, z, p, CI, cov, deviances,
 // dispersion: the definitions stand at the head of that file), one wave per group; 1 .. 16 features.  Every output is nullable.
 // Groups of more than `split_rows` rows are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it) and
@@ -346,6 +362,7 @@ struct GlmReportDev {
     uint8_t* report_null;
 };
 // a piece's record: [0,256) I [i * 16 + j]; [256,272) X'w; 272 sum w; 273 sum (y - y0); 274 pearson; 275 deviance; 276 the family sum
+// (the weighted / offset form: 273 .. 276 weighted by pw; 277 sum pw; 278 rows of positive weight)
 constexpr int kGlmReportRec = 280;
 template <typename T>
 int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
@@ -355,6 +372,16 @@ template <typename T>
 int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
                                      int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
                                      int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
+// grouped_glm_report_wo.hip: the same two with prior weights and offsets: d_cols holds n_feat + 3 entries, x_0 .. x_{p-1}, y, pw, o,
+// of which the last two may be null
+template <typename T>
+int launch_grouped_glm_report_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                                 int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
+                                 const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+template <typename T>
+int launch_grouped_glm_report_wo_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
+                                        int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
+                                        int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
 // ---- grouped_rcond.hip: lin_reg_w_rcond per group, one wave per group: Gram, one-sided Jacobi of X'X (+ l2_reg) and the minimum-norm
 // solve on chip; 1 .. 16 features.  d_coeffs / d_svals [n_groups][p'] (bias last; singular values descending), d_null [n_groups].
 // rcond is the caller's value: the floor eps_T max(n_g, p') is applied per group.

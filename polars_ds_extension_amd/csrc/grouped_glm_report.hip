@@ -29,10 +29,21 @@
 // list), the host cuts their rows into pieces, grouped_glm_report_piece_kernel streams every piece on a wave of its own into a
 // record (I, X'w and the five sums) and grouped_glm_report_fold_kernel -- one wave per long group -- adds the records in piece order
 // and runs the same epilogue: deterministic whatever the schedule.
+//
+// The weighted / offset form (WO: grouped_glm_report_wo.hip compiles this file with PDS_GLM_REPORT_WO and holds its kernels, the
+// kernels above keep their names and objects): a prior weight pw_i and an offset o_i per row, entries P + 1 and P + 2 of the column
+// table, each nullable.  eta_i = x_i . beta + o_i; I = sum pw_i w~_i x_i x_i' with w~ = 1 / (g'^2 V); pearson_chi2 =
+// sum pw_i (y_i - mu_i)^2 / V; deviance = sum pw_i d_i; df_resid = n+ - p' with n+ the rows of positive weight; null_deviance: the
+// closed form above with weighted sums (n -> sum pw, sum y -> sum pw y, the family sum weighted; the gaussian shift is the group's
+// first y of positive weight), NaN when an offset is given.  A piece's record gains sum pw (277) and n+ (278).
 #include "glm_dev.hpp"
 #include "wave_tile_dev.hpp"
 
 #include <algorithm>
+
+#ifndef PDS_GLM_REPORT_WO
+#define PDS_GLM_REPORT_WO 0
+#endif
 
 namespace pds {
 
@@ -45,6 +56,7 @@ constexpr double kGrZ975 = 1.959963984540054;
 
 struct GrSums {
     double sw, sy, pe, dv, fs;  // sum w, sum (y - y0), pearson, deviance, the family sum of the null deviance
+    double spw, npos;           // WO: sum pw, rows of positive weight (sy, pe, dv, fs are then weighted by pw)
 };
 
 __device__ __forceinline__ double gr_xlogy(double a, double b) { return a > 0.0 ? a * log(b) : 0.0; }  // (0 ln 0 = 0)
@@ -56,10 +68,12 @@ struct GrLds {
 };
 
 // rows [r0, r1) of one group at the coefficients in l.bs: I into acc, X'w into column 0 of acc2, the sums (folded) into s
-template <typename T, int P>
+template <typename T, int P, bool WO = false>
 __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy, int64_t r0, int64_t r1, double y0, int bias, int link,
-                                              int variance, const GrLds& l, int lane, d4& acc, d4& acc2, GrSums& s) {
+                                              int variance, const GrLds& l, int lane, d4& acc, d4& acc2, GrSums& s,
+                                              const T* pwp = nullptr, const T* ofp = nullptr) {
     double sw = 0.0, sy = 0.0, pe = 0.0, dv = 0.0, fs = 0.0;
+    [[maybe_unused]] double spw = 0.0, npos = 0.0;
     for (int64_t base = r0; base < r1; base += 64) {
         const int64_t r = base + lane;
         const bool live = r < r1;
@@ -72,7 +86,41 @@ __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy
             eta = fma(xv, l.bs[c], eta);
         }
         double w = 0.0;
-        if (live) {
+        if constexpr (WO) {
+            const double pwv = live ? (pwp ? (double)as_global(pwp)[r] : 1.0) : 0.0;
+            if (live && ofp) eta += (double)as_global(ofp)[r];
+            if (pwv > 0.0) {  // (a row of weight 0 contributes nothing whatever its y holds)
+                const double yv = (double)cy[r];
+                const double mu = glm_inv<double>(link, eta);
+                const double d = glm_deriv<double>(link, mu);
+                const double v = glm_var<double>(variance, mu);
+                w = pwv / (d * d * v);
+                const double e = yv - mu;
+                pe += pwv * (e * e / v);
+                const double dy = yv - y0;
+                sy += pwv * dy;
+                spw += pwv;
+                npos += 1.0;
+                switch (variance) {
+                    case 1:
+                        dv += pwv * (2.0 * (gr_xlogy(yv, yv / mu) - e));
+                        fs += pwv * gr_xlogy(yv, yv);
+                        break;
+                    case 2:
+                        dv += pwv * (2.0 * (gr_xlogy(yv, yv / mu) + gr_xlogy(1.0 - yv, (1.0 - yv) / (1.0 - mu))));
+                        fs += pwv * (gr_xlogy(yv, yv) + gr_xlogy(1.0 - yv, 1.0 - yv));
+                        break;
+                    case 3:
+                        dv += pwv * (2.0 * (e / mu - log(yv / mu)));
+                        fs += pwv * log(yv);
+                        break;
+                    default:
+                        dv += pwv * (e * e);
+                        fs += pwv * (dy * dy);
+                        break;
+                }
+            }
+        } else if (live) {
             const double yv = (double)cy[r];
             const double mu = glm_inv<double>(link, eta);
             const double d = glm_deriv<double>(link, mu);
@@ -114,6 +162,10 @@ __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy
     s.pe = wave_sum(pe);
     s.dv = wave_sum(dv);
     s.fs = wave_sum(fs);
+    if constexpr (WO) {
+        s.spw = wave_sum(spw);
+        s.npos = wave_sum(npos);
+    }
 }
 
 // every report field of group g NaN, report_null = 1
@@ -141,9 +193,9 @@ __device__ __forceinline__ void gr_write_null(const GlmReportDev<T>& o, int64_t 
 }
 
 // l.gm holds I (index 16 = bias), l.bs the coefficients, s the group's sums: invert, derive, write
-template <typename T, int P>
+template <typename T, int P, bool WO = false>
 __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g, int64_t n, int bias, int variance, double y0, const GrLds& l,
-                                            const GrSums& s, int lane) {
+                                            const GrSums& s, int lane, bool has_offset = false) {
     const int pp = P + bias, ne = pp * pp;
     auto m = [](int j) { return j < P ? j : 16; };
     bool bad = false;
@@ -179,8 +231,8 @@ __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g,
         return;
     }
     const double nanv = __builtin_nan("");
-    const double nn = (double)n;
-    const int64_t df = n - pp;
+    const double nn = WO ? s.spw : (double)n;  // (WO: sum pw stands where the row count stood; s.sy, s.fs are weighted)
+    const int64_t df = (WO ? (int64_t)s.npos : n) - pp;
     const double phi = (variance == 1 || variance == 2) ? 1.0 : (df > 0 ? s.pe / (double)df : nanv);
     const double sy = s.sy + nn * y0;  // sum y
     double nd;
@@ -200,6 +252,7 @@ __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g,
             default: nd = s.fs; break;  // (y0 = 0 without a bias: sum y^2)
         }
     }
+    if (WO && has_offset) nd = nanv;  // (the intercept-only model under an offset needs an iteration of its own)
     if (lane < pp) {
         const int mj = m(lane);
         const double b = l.bs[lane];  // (the bias sits at bs[P] = bs[lane])
@@ -235,10 +288,31 @@ __device__ __forceinline__ void gr_load_beta(const T* __restrict__ coeffs, int64
     PDS_WAVE_LDS_SYNC();
 }
 
+// a group for the piece route: appended to the list (the order does not matter: the host sorts it)
+__device__ __forceinline__ void gr_append_long(int64_t* long_list, unsigned* long_count, int64_t long_cap, int64_t g, int lane) {
+    if (lane == 0) {
+        const unsigned k = atomicAdd(long_count, 1u);
+        if ((int64_t)k < long_cap) long_list[k] = g;
+    }
+}
+
 // the shift of the gaussian sums: the group's first y with a bias (the mean is the null model), nothing otherwise
 template <typename T>
 __device__ __forceinline__ double gr_shift(gptr<T> cy, int64_t first_row, int bias, int variance) {
     return (variance == 0 && bias) ? (double)cy[first_row] : 0.0;
+}
+
+// WO: ... the group's first y of positive weight (the same row for every piece of a group: the scan starts at the group's first row)
+template <typename T>
+__device__ __forceinline__ double gr_shift_wo(gptr<T> cy, const T* pwp, int64_t r0, int64_t r1, int bias, int variance, int lane) {
+    if (!(variance == 0 && bias)) return 0.0;
+    if (!pwp) return (double)cy[r0];
+    for (int64_t base = r0; base < r1; base += 64) {
+        const int64_t r = base + lane;
+        const unsigned long long m = __ballot(r < r1 && (double)as_global(pwp)[r] > 0.0);
+        if (m) return (double)cy[base + (__ffsll((long long)m) - 1)];
+    }
+    return 0.0;
 }
 
 template <typename T, int P>
@@ -264,10 +338,7 @@ __global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* 
             continue;
         }
         if (n > split_rows) {  // the piece route (the order of the list does not matter: the host sorts it)
-            if (lane == 0) {
-                const unsigned k = atomicAdd(long_count, 1u);
-                if ((int64_t)k < long_cap) long_list[k] = g;
-            }
+            gr_append_long(long_list, long_count, long_cap, g, lane);
             continue;
         }
         gr_load_beta<T, P>(coeffs, g, bias, l, lane);
@@ -368,10 +439,153 @@ __global__ __launch_bounds__(64) void grouped_glm_report_fold_kernel(const T* co
     }
 }
 
+
+// ---- the weighted / offset form of the three kernels: cols[P + 1] = pw, cols[P + 2] = o (each nullable)
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_wo_kernel(const T* const* __restrict__ cols, int bias, int64_t n_rows,
+                                                                   const int64_t* __restrict__ off, int64_t n_groups, int link,
+                                                                   int variance, int64_t split_rows, const T* __restrict__ coeffs,
+                                                                   const uint8_t* __restrict__ is_null, GlmReportDev<T> o,
+                                                                   int64_t* __restrict__ long_list, unsigned* __restrict__ long_count,
+                                                                   int64_t long_cap) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    const int pp = P + bias;
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    const T* const pwp = cols[P + 1];
+    const T* const ofp = cols[P + 2];
+    for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const int64_t r0 = off[g], n = off[g + 1] - r0;
+        const bool bad = r0 < 0 || n < 0 || r0 + n > n_rows;
+        if (bad || n < pp || is_null[g]) {  // (a group that fails the weight rule is a null fit)
+            gr_write_null<T>(o, g, bad ? 0 : n, pp, lane);
+            continue;
+        }
+        if (n > split_rows) {
+            gr_append_long(long_list, long_count, long_cap, g, lane);
+            continue;
+        }
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        const double y0 = gr_shift_wo<T>(cy, pwp, r0, r0 + n, bias, variance, lane);
+        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+        GrSums s;
+        gr_accumulate<T, P, true>(cx, cy, r0, r0 + n, y0, bias, link, variance, l, lane, acc, acc2, s, pwp, ofp);
+        PDS_WAVE_LDS_SYNC();
+        wave_tile_for_d(
+            lane,
+            [&](int i, int c, double v, double side) {
+                l.gm[i * kGrG + c] = v;
+                if (c == 0) {
+                    l.gm[i * kGrG + 16] = side;
+                    l.gm[16 * kGrG + i] = side;
+                }
+            },
+            acc, acc2);
+        if (lane == 0) l.gm[16 * kGrG + 16] = s.sw;
+        PDS_WAVE_LDS_SYNC();
+        gr_epilogue<T, P, true>(o, g, n, bias, variance, y0, l, s, lane, ofp != nullptr);
+    }
+}
+
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_wo_piece_kernel(const T* const* __restrict__ cols, int bias,
+                                                                         const int64_t* __restrict__ off, int link, int variance,
+                                                                         const T* __restrict__ coeffs, const int64_t* __restrict__ pieces,
+                                                                         int64_t n_pieces, double* __restrict__ rec) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    gptr<T> cx[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
+    const gptr<T> cy = as_global(cols[P]);
+    const T* const pwp = cols[P + 1];
+    const T* const ofp = cols[P + 2];
+    for (int64_t k = blockIdx.x; k < n_pieces; k += gridDim.x) {
+        const int64_t g = pieces[3 * k], r0 = pieces[3 * k + 1], r1 = pieces[3 * k + 2];
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        const double y0 = gr_shift_wo<T>(cy, pwp, off[g], off[g + 1], bias, variance, lane);
+        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+        GrSums s;
+        gr_accumulate<T, P, true>(cx, cy, r0, r1, y0, bias, link, variance, l, lane, acc, acc2, s, pwp, ofp);
+        double* out = rec + k * kGlmReportRec;
+        wave_tile_for_d(
+            lane,
+            [&](int i, int c, double v, double side) {
+                out[i * 16 + c] = v;
+                if (c == 0) out[256 + i] = side;
+            },
+            acc, acc2);
+        if (lane == 0) {
+            out[272] = s.sw;
+            out[273] = s.sy;
+            out[274] = s.pe;
+            out[275] = s.dv;
+            out[276] = s.fs;
+            out[277] = s.spw;
+            out[278] = s.npos;
+        }
+    }
+}
+
+template <typename T, int P>
+__global__ __launch_bounds__(64) void grouped_glm_report_wo_fold_kernel(const T* const* __restrict__ cols, int bias,
+                                                                        const int64_t* __restrict__ off, int variance,
+                                                                        const T* __restrict__ coeffs, const int64_t* __restrict__ fin,
+                                                                        int64_t n_fin, const double* __restrict__ rec, GlmReportDev<T> o) {
+    __shared__ double lds[kGrLds];
+    const GrLds l(lds);
+    const int lane = threadIdx.x;
+    const gptr<T> cy = as_global(cols[P]);
+    const T* const pwp = cols[P + 1];
+    const T* const ofp = cols[P + 2];
+    for (int64_t j = blockIdx.x; j < n_fin; j += gridDim.x) {
+        const int64_t g = fin[3 * j], first = fin[3 * j + 1], cnt = fin[3 * j + 2];
+        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
+        for (int e = lane; e < 279; e += 64) {
+            double v = 0.0;
+            for (int64_t k = 0; k < cnt; ++k) v += rec[(first + k) * kGlmReportRec + e];
+            if (e < 256) {
+                l.gm[(e >> 4) * kGrG + (e & 15)] = v;
+            } else if (e < 272) {
+                l.gm[(e - 256) * kGrG + 16] = v;
+                l.gm[16 * kGrG + (e - 256)] = v;
+            } else {
+                if (e == 272) l.gm[16 * kGrG + 16] = v;
+                l.sm[e - 272] = v;
+            }
+        }
+        PDS_WAVE_LDS_SYNC();
+        GrSums s;
+        s.sw = l.sm[0];
+        s.sy = l.sm[1];
+        s.pe = l.sm[2];
+        s.dv = l.sm[3];
+        s.fs = l.sm[4];
+        s.spw = l.sm[5];
+        s.npos = l.sm[6];
+        const int64_t r0 = off[g], r1 = off[g + 1];
+        gr_epilogue<T, P, true>(o, g, r1 - r0, bias, variance, gr_shift_wo<T>(cy, pwp, r0, r1, bias, variance, lane), l, s, lane,
+                                ofp != nullptr);
+    }
+}
+
 }  // namespace
 
+#if PDS_GLM_REPORT_WO
+#define PDS_GR_K(name) grouped_glm_report_wo_##name
+#define PDS_GR_L(name) launch_grouped_glm_report_wo##name
+#else
+#define PDS_GR_K(name) grouped_glm_report_##name
+#define PDS_GR_L(name) launch_grouped_glm_report##name
+#endif
+
 template <typename T>
-int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+int PDS_GR_L()(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
                               int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
                               const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
     if (n_groups <= 0) return PDS_OK;
@@ -379,7 +593,7 @@ int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, 
     KernelTimer timer(ctx, kKindPass2);
     const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
     dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
-        hipLaunchKernelGGL((grouped_glm_report_kernel<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows,
+        hipLaunchKernelGGL((PDS_GR_K(kernel)<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows,
                            d_off, n_groups, link, variance, split_rows, d_coeffs, d_null, out, d_long_list, d_long_count,
                            long_cap);
     });
@@ -388,7 +602,7 @@ int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, 
 }
 
 template <typename T>
-int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
+int PDS_GR_L(_pieces)(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
                                      int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
                                      int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec) {
     if (n_pieces <= 0 || n_fin <= 0) return PDS_OK;
@@ -398,9 +612,9 @@ int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n
     const int nbf = (int)std::min<int64_t>(n_fin, (int64_t)ctx->num_cus * 32);
     dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        hipLaunchKernelGGL((grouped_glm_report_piece_kernel<T, P>), dim3(nbp), dim3(64), 0, ctx->stream, d_cols, bias, d_off, link, variance,
+        hipLaunchKernelGGL((PDS_GR_K(piece_kernel)<T, P>), dim3(nbp), dim3(64), 0, ctx->stream, d_cols, bias, d_off, link, variance,
                            d_coeffs, d_pieces, n_pieces, d_rec);
-        hipLaunchKernelGGL((grouped_glm_report_fold_kernel<T, P>), dim3(nbf), dim3(64), 0, ctx->stream, d_cols, bias, d_off, variance,
+        hipLaunchKernelGGL((PDS_GR_K(fold_kernel)<T, P>), dim3(nbf), dim3(64), 0, ctx->stream, d_cols, bias, d_off, variance,
                            d_coeffs, d_fin, n_fin, d_rec, out);
     });
     PDS_HIP_CHECK(hipGetLastError());
@@ -413,11 +627,13 @@ int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n
 #define PDS_GR_PIECE_ARGS(T)                                                                                                         \
     pds_ctx*, const T* const*, int, int, const int64_t*, int, int, const T*, const GlmReportDev<T>&, const int64_t*, int64_t, const int64_t*, \
         int64_t, double*
-template int launch_grouped_glm_report<double>(PDS_GR_ARGS(double));
-template int launch_grouped_glm_report<float>(PDS_GR_ARGS(float));
-template int launch_grouped_glm_report_pieces<double>(PDS_GR_PIECE_ARGS(double));
-template int launch_grouped_glm_report_pieces<float>(PDS_GR_PIECE_ARGS(float));
+template int PDS_GR_L()<double>(PDS_GR_ARGS(double));
+template int PDS_GR_L()<float>(PDS_GR_ARGS(float));
+template int PDS_GR_L(_pieces)<double>(PDS_GR_PIECE_ARGS(double));
+template int PDS_GR_L(_pieces)<float>(PDS_GR_PIECE_ARGS(float));
 #undef PDS_GR_ARGS
 #undef PDS_GR_PIECE_ARGS
+#undef PDS_GR_K
+#undef PDS_GR_L
 
 }  // namespace pds

@@ -24,9 +24,10 @@
 // walked here: the wave appends them to a list and the host side fits them with the full-device iteration
 // (capi_glm_grouped.hpp).  Per-row means are written at the end of a group's fit from the rows the wave still holds.
 //
-// This file is compiled three times: as it stands it holds the unpenalised kernels (PEN = 0) and the launchers;
+// This file is compiled four times: as it stands it holds the unpenalised kernels (PEN = 0) and the launchers;
 // grouped_irls_ridge.hip and grouped_irls_cd.hip include it with PDS_GROUPED_IRLS_PEN = 1 / 2 and hold the kernels of one penalised
-// mode each -- 32 kernels every time, which one translation unit would compile one after the other.
+// mode each; grouped_irls_wo.hip includes it with PDS_GROUPED_IRLS_PEN = 3 and holds the weighted / offset form (kGiWo, below) --
+// 32 kernels every time, which one translation unit would compile one after the other.
 #include "glm_dev.hpp"
 #include "solve_reg_dev.hpp"
 #include "wave_tile_dev.hpp"
@@ -107,6 +108,19 @@ __device__ __forceinline__ double gi_cd_step(const double* gm, const double* rh,
     return bk;
 }
 
+// The weighted / offset form (PEN = kGiWo = 3: unpenalised, a prior weight pw_i and an offset o_i per row; R's glm(weights=, offset=)).
+// The two columns are entries P + 1 and P + 2 of the column table, either may be null (pw = 1, o = 0):
+//   eta = x . beta + o,  w = pw / (g'(mu)^2 V(mu)),  z = (eta - o) + g'(mu) (y - mu): x . beta itself from the second iteration on, so
+//   the offset is read where eta is formed and nowhere else and does not live across the solve;
+//   the start is mu0 = (y + ybar) / 2 with ybar = sum pw y / sum pw (binomial: (y + 0.5) / 2 as ever), eta0 = g(mu0), z's linear
+//   part eta0 - o;
+//   a row with pw = 0 contributes nothing and is not counted: the group is null with fewer than p' rows of positive weight, or with
+//   any weight that is negative or not finite (counted / flagged in the load loop by ballots: wave-uniform, no register per lane).
+// A resident group keeps pw and o as two more rows of the tile ((P + 3) x kGiStride doubles: 23 520 bytes per wave at 16 features
+// where the other forms take 21 440, six workgroups per CU where they have seven); a streamed group re-reads them with its rows.
+// With pw = 1 and o = 0 every operation below is the unweighted one or an exact one (x 1, + 0): the same bits.
+constexpr int kGiWo = 3;
+
 // (two waves per SIMD: 250 registers, nothing in scratch; a bound of three spilled 111 registers at 8 features)
 // PEN = 0 is the unpenalised fit, the code it was before the penalties existed; PEN = 1 / 2 take the penalised step above.
 template <typename T, int P, int PEN>
@@ -118,17 +132,20 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
                                                           const uint32_t* __restrict__ perm, int64_t* __restrict__ long_list,
                                                           unsigned* __restrict__ long_count, int64_t long_cap, double l1_reg,
                                                           double l2_reg) {
-    __shared__ double lds[(P + 1) * kGiStride + 64 + 64 + 18 + 17 * kGiG + 18 + (PEN ? 2 : 0)];
-    double* xt = lds;                      // features 0 .. P - 1, then y: [c * kGiStride + row]
-    double* wt = xt + (P + 1) * kGiStride;  // w of the step's rows
+    constexpr bool WO = PEN == kGiWo;
+    constexpr bool kPen = PEN == 1 || PEN == 2;
+    constexpr int kTileRows = P + 1 + (WO ? 2 : 0);
+    __shared__ double lds[kTileRows * kGiStride + 64 + 64 + 18 + 17 * kGiG + 18 + (kPen ? 2 : 0)];
+    double* xt = lds;                      // features 0 .. P - 1, then y (WO: then pw, then o): [c * kGiStride + row]
+    double* wt = xt + kTileRows * kGiStride;  // w of the step's rows
     double* zt = wt + 64;                  // w z of the step's rows
     double* bs = zt + 64;                  // coefficients: features, bias at bs[P]
     double* gm = bs + 18;                  // X'WX staged for the solve: index 16 is the bias row / column
     double* rh = gm + 17 * kGiG;           // X'Wz, rh[16] = sum w z
     // PEN: l1_reg, l2_reg, read back where an iteration uses them -- as kernel arguments they would stay in registers across the
     // solve, which has none to spare
-    [[maybe_unused]] double* pn = rh + (PEN ? 18 : 0);
-    if constexpr (PEN) {
+    [[maybe_unused]] double* pn = rh + (kPen ? 18 : 0);
+    if constexpr (kPen) {
         if (threadIdx.x == 0) {
             pn[0] = l1_reg;
             pn[1] = l2_reg;
@@ -142,6 +159,8 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
+    [[maybe_unused]] const T* const pwp = WO ? cols[P + 1] : nullptr;  // (null: every weight 1)
+    [[maybe_unused]] const T* const ofp = WO ? cols[P + 2] : nullptr;  // (null: every offset 0)
     SolveRegDev sp;
     sp.p = P;
     sp.bias = bias;
@@ -180,18 +199,58 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
             if (lane == 0) pn[0] = (double)n * pn[1];  // (read at the staging of every iteration, many hand-offs from here)
         }
         double sy = 0.0;
+        [[maybe_unused]] double spw = 0.0;
+        [[maybe_unused]] int64_t n_pos = 0;   // rows of positive weight
+        [[maybe_unused]] bool bad_w = false;  // a weight that is negative or not finite
         for (int64_t base = 0; base < n; base += 64) {
             const int64_t r = base + lane;
             const bool live = r < n;
             const double yv = live ? (double)cy[r0 + r] : 0.0;
-            sy += yv;
+            if constexpr (WO) {
+                const double pwv = live ? (pwp ? (double)as_global(pwp)[r0 + r] : 1.0) : 0.0;
+                n_pos += __popcll(__ballot(pwv > 0.0));
+                bad_w = bad_w || __any(!(pwv >= 0.0 && gi_finite<double>(pwv)));
+                // (a weight of 0 takes its y out of the mean whatever y holds)
+                if (pwv > 0.0) {
+                    sy += pwv * yv;
+                    spw += pwv;
+                }
+                if (resident) {
+                    xt[(P + 1) * kGiStride + r] = pwv;
+                    xt[(P + 2) * kGiStride + r] = (live && ofp) ? (double)as_global(ofp)[r0 + r] : 0.0;
+                }
+            } else {
+                sy += yv;
+            }
             if (resident) {
 #pragma unroll
                 for (int c = 0; c < P; ++c) xt[c * kGiStride + r] = live ? (double)cx[c][r0 + r] : 0.0;
                 xt[P * kGiStride + r] = yv;
             }
         }
-        const double ymean = wave_sum(sy) / (double)n;
+        if constexpr (WO) {
+            if (bad_w || n_pos < pp) {  // null by the weight rule: nothing computed
+                if (lane < pp) coeffs[g * pp + lane] = (T)nanv;
+                if (lane == 0) {
+                    n_iter[g] = 0;
+                    is_null[g] = 1;
+                }
+                if (pred || row_null) {
+                    for (int64_t r = lane; r < n; r += 64) {
+                        const int64_t o = perm ? (int64_t)perm[r0 + r] : r0 + r;
+                        if (pred) pred[o] = (T)nanv;
+                        if (row_null) row_null[o] = 1;
+                    }
+                }
+                continue;
+            }
+        }
+        double ymean;
+        if constexpr (WO) {
+            ymean = wave_sum(sy) / wave_sum(spw);
+        } else {
+            ymean = wave_sum(sy) / (double)n;
+        }
         double bcur = 0.0;  // lane j < p': coefficient j (the bias last)
         int it = 0;
         while (it < max_iter) {
@@ -216,19 +275,43 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
                     }
                     yv = live ? (double)cy[r0 + r] : 0.0;
                 }
-                double eta, mu;
+                [[maybe_unused]] double pwv = 1.0, ov = 0.0;
+                if constexpr (WO) {
+                    if (resident) {
+                        pwv = xt[(P + 1) * kGiStride + slot + lane];
+                        ov = xt[(P + 2) * kGiStride + slot + lane];
+                    } else {
+                        pwv = live ? (pwp ? (double)as_global(pwp)[r0 + r] : 1.0) : 0.0;
+                        ov = (live && ofp) ? (double)as_global(ofp)[r0 + r] : 0.0;
+                    }
+                }
+                double eta, mu;  // eta: the linear part of z, x . beta (the first iteration: g(mu0) - o)
                 if (it == 1) {
                     mu = (variance == 2) ? (yv + 0.5) * 0.5 : (yv + ymean) * 0.5;
                     eta = glm_link<double>(link, mu);
+                    if constexpr (WO) eta -= ov;
                 } else {
                     eta = bias ? bs[P] : 0.0;
 #pragma unroll
                     for (int c = 0; c < P; ++c) eta = fma(x[c], bs[c], eta);
-                    mu = glm_inv<double>(link, eta);
+                    if constexpr (WO) {
+                        mu = glm_inv<double>(link, eta + ov);
+                    } else {
+                        mu = glm_inv<double>(link, eta);
+                    }
                 }
                 const double d = glm_deriv<double>(link, mu);
-                const double w = live ? 1.0 / (d * d * glm_var<double>(variance, mu)) : 0.0;
-                const double wz = live ? w * (eta + d * (yv - mu)) : 0.0;
+                double w, wz;
+                if constexpr (WO) {
+                    // (a row of weight 0 contributes nothing whatever its y holds; its features stay in the tile for pred and meet
+                    // w = 0 in the matrix instructions, so they have to be finite)
+                    const bool on = live && pwv > 0.0;
+                    w = on ? pwv / (d * d * glm_var<double>(variance, mu)) : 0.0;
+                    wz = on ? w * (eta + d * (yv - mu)) : 0.0;
+                } else {
+                    w = live ? 1.0 / (d * d * glm_var<double>(variance, mu)) : 0.0;
+                    wz = live ? w * (eta + d * (yv - mu)) : 0.0;
+                }
                 sw += w;
                 swz += wz;
                 wt[lane] = w;
@@ -297,7 +380,7 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
             const double bnew = lane < pp ? bs[lane] : 0.0;
             // (penalised: the first system is built at the starting mu, not at beta = 0, so an all-zero first step -- every feature
             // inside the l1 threshold -- says nothing about the point beta = 0 itself: the second iteration decides)
-            const bool open = lane < pp && (!(fabs(bcur - bnew) < tol) || (PEN && it == 1));
+            const bool open = lane < pp && (!(fabs(bcur - bnew) < tol) || (kPen && it == 1));
             const bool isnan_b = lane < pp && bnew != bnew;
             bcur = bnew;
             if (__any(isnan_b)) {
@@ -325,6 +408,13 @@ __global__ __launch_bounds__(64, 2) void grouped_irls_kernel(const T* const* __r
 #pragma unroll
                     for (int c = 0; c < P; ++c) eta = fma((double)cx[c][r0 + r], bs[c], eta);
                 }
+                if constexpr (WO) {
+                    if (resident) {
+                        eta += xt[(P + 2) * kGiStride + r];
+                    } else if (ofp) {
+                        eta += (double)as_global(ofp)[r0 + r];
+                    }
+                }
                 const int64_t o = perm ? (int64_t)perm[r0 + r] : r0 + r;
                 if (pred) pred[o] = gnull ? (T)nanv : (T)glm_inv<double>(link, eta);
                 if (row_null) row_null[o] = gnull ? 1 : 0;
@@ -338,11 +428,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void glm_pred_range_kernel(const T* const* __restrict__ cols, int p, int bias, int64_t r0, int64_t r1,
                                                              const T* __restrict__ beta, const uint8_t* __restrict__ null_flag, int link,
                                                              T* __restrict__ pred, uint8_t* __restrict__ row_null,
-                                                             const uint32_t* __restrict__ perm) {
+                                                             const uint32_t* __restrict__ perm, const T* __restrict__ offset) {
     const bool gnull = null_flag[0] != 0;
     for (int64_t r = r0 + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r1; r += (int64_t)gridDim.x * 256) {
         double eta = bias ? (double)beta[p] : 0.0;
         for (int c = 0; c < p; ++c) eta = fma((double)as_global(cols[c])[r], (double)beta[c], eta);
+        if (offset) eta += (double)as_global(offset)[r];
         const int64_t o = perm ? (int64_t)perm[r] : r;
         if (pred) pred[o] = gnull ? (T)__builtin_nan("") : (T)glm_inv<double>(link, eta);
         if (row_null) row_null[o] = gnull ? 1 : 0;
@@ -371,7 +462,23 @@ int gi_launch(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_
     pds_ctx*, const T* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int, int64_t, T*, int32_t*, uint8_t*, T*, \
         uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t, double, double
 
-#if PDS_GROUPED_IRLS_PEN
+#if PDS_GROUPED_IRLS_PEN == 3
+// the weighted / offset kernels (grouped_irls_wo.hip): d_cols holds P + 3 entries, x_0 .. x_{p-1}, y, pw (nullable), o (nullable)
+template <typename T>
+int launch_grouped_irls_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
+                           int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
+                           int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
+                           int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
+    if (n_groups <= 0) return PDS_OK;
+    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
+    return gi_launch<T, kGiWo>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs,
+                               d_n_iter, d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, 0.0, 0.0);
+}
+template int launch_grouped_irls_wo<double>(pds_ctx*, const double* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
+                                            int64_t, double*, int32_t*, uint8_t*, double*, uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t);
+template int launch_grouped_irls_wo<float>(pds_ctx*, const float* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
+                                           int64_t, float*, int32_t*, uint8_t*, float*, uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t);
+#elif PDS_GROUPED_IRLS_PEN
 // the kernels of one penalised mode (grouped_irls_ridge.hip, grouped_irls_cd.hip)
 template <typename T, int PEN>
 int launch_grouped_irls_pen(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
@@ -406,12 +513,12 @@ int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bi
 
 template <typename T>
 int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t r0, int64_t r1, const T* d_beta,
-                          const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm) {
+                          const uint8_t* d_null_flag, int link, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm, const T* d_offset) {
     if (r1 <= r0 || (!d_pred && !d_row_null)) return PDS_OK;
     KernelTimer timer(ctx, kKindPass2);
     const int nb = (int)std::min<int64_t>((r1 - r0 + 255) / 256, (int64_t)ctx->num_cus * 16);
     hipLaunchKernelGGL((glm_pred_range_kernel<T>), dim3(nb), dim3(256), 0, ctx->stream, d_cols, n_feat, bias, r0, r1, d_beta, d_null_flag,
-                       link, d_pred, d_row_null, d_perm);
+                       link, d_pred, d_row_null, d_perm, d_offset);
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
@@ -419,9 +526,9 @@ int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int 
 template int launch_grouped_irls<double>(PDS_GI_ARGS(double));
 template int launch_grouped_irls<float>(PDS_GI_ARGS(float));
 template int launch_glm_pred_range<double>(pds_ctx*, const double* const*, int, int, int64_t, int64_t, const double*, const uint8_t*, int,
-                                           double*, uint8_t*, const uint32_t*);
+                                           double*, uint8_t*, const uint32_t*, const double*);
 template int launch_glm_pred_range<float>(pds_ctx*, const float* const*, int, int, int64_t, int64_t, const float*, const uint8_t*, int,
-                                          float*, uint8_t*, const uint32_t*);
+                                          float*, uint8_t*, const uint32_t*, const float*);
 #endif
 #undef PDS_GI_ARGS
 

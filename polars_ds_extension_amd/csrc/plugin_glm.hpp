@@ -1,5 +1,6 @@
 // plugin_glm.hpp -- pl_logistic_coeffs / pl_logistic_pred (the reference's symbols, src/num_ext/logistic_regression.rs) and the
-// key-aware pl_glm_by / pl_glm_by_pred (+ _f32): GLM fits by IRLS through pds_glm_irls_grouped_* / pds_glm_irls_by_key_*; pl_glm_report_by
+// key-aware pl_glm_by / pl_glm_by_pred (+ _f32): GLM fits by IRLS through pds_glm_irls_grouped_* / pds_glm_irls_by_key_* (with prior
+// weights / an offset: pds_glm_irls_wo_grouped_* / pds_glm_irls_wo_by_key_*); pl_glm_report_by
 // (+ _f32): the fit and its report per group through pds_glm_report_grouped_* / pds_glm_report_by_key_*
 // Part of the one translation unit plugin.cpp (included there, inside its anonymous namespace, after plugin_exprs.hpp).
 #pragma once
@@ -10,12 +11,16 @@ template <> struct GlmApi<double> {
     static constexpr auto by_key = pds_glm_irls_by_key_f64;
     static constexpr auto enet_grouped = pds_glm_enet_grouped_f64;
     static constexpr auto enet_by_key = pds_glm_enet_by_key_f64;
+    static constexpr auto wo_grouped = pds_glm_irls_wo_grouped_f64;
+    static constexpr auto wo_by_key = pds_glm_irls_wo_by_key_f64;
 };
 template <> struct GlmApi<float> {
     static constexpr auto grouped = pds_glm_irls_grouped_f32;
     static constexpr auto by_key = pds_glm_irls_by_key_f32;
     static constexpr auto enet_grouped = pds_glm_enet_grouped_f32;
     static constexpr auto enet_by_key = pds_glm_enet_by_key_f32;
+    static constexpr auto wo_grouped = pds_glm_irls_wo_grouped_f32;
+    static constexpr auto wo_by_key = pds_glm_irls_wo_by_key_f32;
 };
 
 // family -> (link, variance) ids of include/pds_lstsq.h, the names of linear_models.GLM_FAMILIES
@@ -45,9 +50,15 @@ int64_t g_glm_by_first_cap = 0;
 // Null-free frames make ONE pds_glm_irls_by_key_* call (by_key_with_retry); frames with nulls are prepared on the host
 // (prepare_keyed_rows; "ignore" keeps the rows with NaN for the nulls: that group's fit is not finite, so it is a null group) and go
 // to the offsets entry point.
+// kwargs has_weights / has_offset (absent: false, the call it always was): the inputs are then [key, weights?, offset?, y, x1..xp]
+// -- the place pl_lr_by gives its weights -- and the fit goes through pds_glm_irls_wo_by_key_* / _wo_grouped_* (prior weights and an
+// offset per row).  A null in the weights or the offset is an error whatever the null policy; nulls elsewhere follow the host
+// preparation above, the two columns going through the same row rule.  Not together with a penalty.
 template <typename T>
 void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool want_pred) {
-    if (n_in < 3) raise("pl_glm_by needs a key, a target and at least one feature");
+    const bool has_w = kw_bool(kw, "has_weights"), has_o = kw_bool(kw, "has_offset");
+    const size_t n_extra = (has_w ? 1 : 0) + (has_o ? 1 : 0);
+    if (n_in < 3 + n_extra) raise("pl_glm_by needs a key, a target and at least one feature");
     int link = 0, variance = 0;
     glm_family_codes(kw_str(kw, "family", "gaussian"), &link, &variance);
     const int max_iter = (int)kw_i64(kw, "max_iter", 100);
@@ -56,11 +67,19 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
     const int bias = kw_bool(kw, "bias") ? 1 : 0;
     const T l1_reg = (T)std::max(kw_f64(kw, "l1_reg"), 0.0), l2_reg = (T)std::max(kw_f64(kw, "l2_reg"), 0.0);
     const bool penalised = l1_reg > T(0) || l2_reg > T(0);
-    const int n_feat = (int)n_in - 2;
+    if (n_extra && penalised) raise("pl_glm_by: l1_reg / l2_reg together with weights / offset is not built");
+    const int n_feat = (int)(n_in - 2 - n_extra);
     if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
     const int pp = n_feat + bias;
-    const KeyedInputs<T> ki = keyed_inputs<T>(in, n_in, kw, "pl_glm_by");  // cols: [y, x1..xp]
+    // the three steps of keyed_inputs apart: the check of the two columns comes before the lengths', and they move behind the frame
+    KeyedInputs<T> ki = keyed_import<T>(in, n_in, kw);  // cols: [weights?, offset?, y, x1..xp]
+    for (size_t k = 0; k < n_extra; ++k)
+        if (ki.cols[k].null_count > 0) raise("pl_glm_by: nulls in the weights or the offset are an error whatever the null policy");
+    keyed_check_lengths(ki);
+    std::rotate(ki.cols.begin(), ki.cols.begin() + n_extra, ki.cols.end());  // cols: [y, x1..xp, weights?, offset?]
+    keyed_settle(ki, "pl_glm_by");
     const int64_t n = ki.n;
+    const size_t iw = (size_t)n_feat + 1, io = iw + (has_w ? 1 : 0);  // where the two columns stand behind the frame
     RawVec<int64_t> keys;
     ByteVec cobuf, itbuf, pred_b;
     RawVec<uint8_t> nulls, row_null;
@@ -82,6 +101,10 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
         T* const pr = want_pred ? as<T>(pred_b) : nullptr;
         uint8_t* const rn = want_pred ? row_null.data() : nullptr;
         by_key_with_retry(first_group_capacity(n, g_glm_by_first_cap), size_outputs, [&](int64_t cap) {
+            if (n_extra)
+                return GlmApi<T>::wo_by_key(thread_ctx(), ptrs.data(), has_w ? ptrs[iw] : nullptr, has_o ? ptrs[io] : nullptr, ki.ikey, n_feat, n,
+                                            PDS_HOST, bias, link, variance, tol, max_iter, cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf),
+                                            nulls.data(), &ng, pr, rn);
             return penalised ? GlmApi<T>::enet_by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, n, PDS_HOST, bias, link, variance, l1_reg, l2_reg,
                                                       tol, max_iter, cap, keys.data(), as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), &ng, pr, rn)
                              : GlmApi<T>::by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
@@ -104,10 +127,13 @@ void do_glm_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* ou
         }
         T* const pr = want_pred ? as<T>(pk) : nullptr;
         uint8_t* const rn = want_pred ? rk.data() : nullptr;
-        check(penalised ? GlmApi<T>::enet_grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance,
-                                                  l1_reg, l2_reg, tol, max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn)
-                        : GlmApi<T>::grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance, tol,
-                                             max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn));
+        check(n_extra ? GlmApi<T>::wo_grouped(thread_ctx(), rows.ptrs.data(), has_w ? rows.ptrs[iw] : nullptr, has_o ? rows.ptrs[io] : nullptr,
+                                              n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter, as<T>(cobuf),
+                                              as<int32_t>(itbuf), nulls.data(), pr, rn)
+              : penalised ? GlmApi<T>::enet_grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance,
+                                                    l1_reg, l2_reg, tol, max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn)
+                          : GlmApi<T>::grouped(thread_ctx(), rows.ptrs.data(), n_feat, nk, rows.off.data(), ng, PDS_HOST, bias, link, variance, tol,
+                                               max_iter, as<T>(cobuf), as<int32_t>(itbuf), nulls.data(), pr, rn));
         if (want_pred) {  // back to the frame's rows: a dropped row is a null row
             pred_b = raw_buffer<T>((size_t)n);
             row_valid.assign((size_t)n, 0);
@@ -156,15 +182,22 @@ template <typename T> struct GlmReportApi;
 template <> struct GlmReportApi<double> {
     static constexpr auto grouped = pds_glm_report_grouped_f64;
     static constexpr auto by_key = pds_glm_report_by_key_f64;
+    static constexpr auto wo_grouped = pds_glm_report_wo_grouped_f64;
+    static constexpr auto wo_by_key = pds_glm_report_wo_by_key_f64;
 };
 template <> struct GlmReportApi<float> {
     static constexpr auto grouped = pds_glm_report_grouped_f32;
     static constexpr auto by_key = pds_glm_report_by_key_f32;
+    static constexpr auto wo_grouped = pds_glm_report_wo_grouped_f32;
+    static constexpr auto wo_by_key = pds_glm_report_wo_by_key_f32;
 };
 
 template <typename T>
 void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out) {
-    if (n_in < 3) raise("pl_glm_report_by needs a key, a target and at least one feature");
+    // has_weights / has_offset: as in pl_glm_by -- inputs [key, weights?, offset?, y, x1..xp], pds_glm_report_wo_*
+    const bool has_w = kw_bool(kw, "has_weights"), has_o = kw_bool(kw, "has_offset");
+    const size_t n_extra = (has_w ? 1 : 0) + (has_o ? 1 : 0);
+    if (n_in < 3 + n_extra) raise("pl_glm_report_by needs a key, a target and at least one feature");
     int link = 0, variance = 0;
     glm_family_codes(kw_str(kw, "family", "gaussian"), &link, &variance);
     const int max_iter = (int)kw_i64(kw, "max_iter", 100);
@@ -172,10 +205,16 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     if (kw_f64(kw, "l1_reg") > 0.0 || kw_f64(kw, "l2_reg") > 0.0) raise("pl_glm_report_by: penalised fits have no report");
     const T tol = (T)std::fabs(kw_f64(kw, "tol", 1e-8));
     const int bias = kw_bool(kw, "bias") ? 1 : 0;
-    const int n_feat = (int)n_in - 2;
+    const int n_feat = (int)(n_in - 2 - n_extra);
     if (n_feat > 16) raise("grouped GLM (IRLS): up to 16 feature columns");
     const int pp = n_feat + bias;
-    const KeyedInputs<T> ki = keyed_inputs<T>(in, n_in, kw, "pl_glm_report_by");  // cols: [y, x1..xp]
+    KeyedInputs<T> ki = keyed_import<T>(in, n_in, kw);  // cols: [weights?, offset?, y, x1..xp]
+    for (size_t k = 0; k < n_extra; ++k)
+        if (ki.cols[k].null_count > 0) raise("pl_glm_report_by: nulls in the weights or the offset are an error whatever the null policy");
+    keyed_check_lengths(ki);
+    std::rotate(ki.cols.begin(), ki.cols.begin() + n_extra, ki.cols.end());  // cols: [y, x1..xp, weights?, offset?]
+    keyed_settle(ki, "pl_glm_report_by");
+    const size_t iw = (size_t)n_feat + 1, io = iw + (has_w ? 1 : 0);
     RawVec<int64_t> keys;
     ByteVec vb[6], gb[3], itbuf;  // beta, se, z, p, lo, hi [ng][p']; deviance, null_deviance, dispersion [ng]; n_iter [ng]
     RawVec<uint8_t> nulls, rnulls;
@@ -196,6 +235,10 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
         std::vector<const T*> ptrs;
         for (auto& c : ki.cols) ptrs.push_back(c.data());
         by_key_with_retry(first_group_capacity(ki.n, g_glm_by_first_cap), size_outputs, [&](int64_t cap) {
+            if (n_extra)
+                return GlmReportApi<T>::wo_by_key(thread_ctx(), ptrs.data(), has_w ? ptrs[iw] : nullptr, has_o ? ptrs[io] : nullptr, ki.ikey,
+                                                  n_feat, ki.n, PDS_HOST, bias, link, variance, tol, max_iter, cap, keys.data(), as<T>(vb[0]),
+                                                  as<int32_t>(itbuf), nulls.data(), &ng, &rep);
             return GlmReportApi<T>::by_key(thread_ctx(), ptrs.data(), ki.ikey, n_feat, ki.n, PDS_HOST, bias, link, variance, tol, max_iter, cap,
                                            keys.data(), as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &ng, &rep);
         }, ng);
@@ -203,9 +246,13 @@ void do_glm_report_by(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
         const PreparedRows<T> pr = prepare_keyed_rows(ki, keys);
         ng = (int64_t)keys.size();
         size_outputs(ng);  // (keys already holds its ng values)
-        check(GlmReportApi<T>::grouped(thread_ctx(), pr.ptrs.data(), n_feat, pr.rows(), pr.off.data(), ng, PDS_HOST, bias, link, variance, tol,
-                                       max_iter, as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep));
+        check(n_extra ? GlmReportApi<T>::wo_grouped(thread_ctx(), pr.ptrs.data(), has_w ? pr.ptrs[iw] : nullptr, has_o ? pr.ptrs[io] : nullptr,
+                                                    n_feat, pr.rows(), pr.off.data(), ng, PDS_HOST, bias, link, variance, tol, max_iter,
+                                                    as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep)
+                      : GlmReportApi<T>::grouped(thread_ctx(), pr.ptrs.data(), n_feat, pr.rows(), pr.off.data(), ng, PDS_HOST, bias, link, variance,
+                                                 tol, max_iter, as<T>(vb[0]), as<int32_t>(itbuf), nulls.data(), &rep));
     }
+    ki.cols.erase(ki.cols.begin() + n_feat + 1, ki.cols.end());  // (the two columns are no features: the names below are [y, x1..xp]'s)
     // ---- the long frame
     const int64_t rows = ng * pp;
     std::vector<std::unique_ptr<ArrowArray>> kids;

@@ -472,22 +472,48 @@ class GLM:
     def bias(self) -> float:
         return float(self._bias)
 
-    def fit(self, X, y, null_policy: str = "ignore", report: bool = False):
-        """`report=True`: the fit goes through the grouped entry point with ONE group covering the frame (`lstsq.glm_report_by`, up to
+    def fit(self, X, y, null_policy: str = "ignore", report: bool = False, sample_weight=None, offset=None):
+        """`sample_weight` / `offset` (one entry per row each): prior weights and an offset per row, R's `glm(weights=, offset=)`
+        (`pds_glm_irls_wo_*`; `lstsq.glm_by` states the semantics).  A negative or non-finite weight, or fewer rows of positive weight
+        than coefficients, raises.  Not together with a penalty; a null policy that drops rows drops them from the two columns too.
+        `report=True`: the fit goes through the grouped entry point with ONE group covering the frame (`lstsq.glm_report_by`, up to
         16 features, no penalty) and fills `std_errors_`, `z_`, `p_values_`, `deviance_`, `null_deviance_`, `dispersion_`, `df_resid_`
         (the bias last; z and p from the normal distribution for every family); `report()` returns them.  The default path is the
         one-model iteration, untouched."""
         X = _as_matrix(X)
         y = _target(y, int(X.shape[0]))
-        X, y = _handle_nans_in_np(X, y, null_policy)
+        wo = sample_weight is not None or offset is not None
+        if wo:  # the two columns ride through the null policy as two more feature columns: the rows it drops go from them too
+            n_in, p_in = int(X.shape[0]), int(X.shape[1])
+            side = []
+            for name, c in (("sample_weight", sample_weight), ("offset", offset)):
+                if c is not None:
+                    c = c.detach().cpu().numpy() if _is_torch(c) else np.asarray(c)
+                    if c.shape != (n_in,):
+                        raise ValueError(f"`{name}` must have one entry per row")
+                    if not np.isfinite(c).all() and null_policy not in ("ignore", "raise"):
+                        raise ValueError(f"`{name}` holds NaN / inf: an error whatever the null policy")
+                    side.append(c)
+            if null_policy not in ("ignore", "raise") and not _is_torch(X):
+                Xs, y = _handle_nans_in_np(np.column_stack([X, *side]), y, null_policy)
+                X, side = Xs[:, :p_in], [Xs[:, p_in + k] for k in range(len(side))]
+                sample_weight = side.pop(0) if sample_weight is not None else None
+                offset = side.pop(0) if offset is not None else None
+            else:
+                X, y = _handle_nans_in_np(X, y, null_policy)
+                if int(X.shape[0]) != n_in:
+                    raise ValueError("GLM.fit: sample_weight= / offset= with a null policy that drops rows need a NumPy frame")
+        else:
+            X, y = _handle_nans_in_np(X, y, null_policy)
         n, p = int(X.shape[0]), int(X.shape[1])
         if n < p or n == 0:
             raise ValueError("Not enough data.")  # LinearModel::fit, src/linear/lr/mod.rs:114-125
         self._report = None
         if report:
-            return self._fit_report(X, y, n)
+            return self._fit_report(X, y, n, sample_weight, offset)
+        pen = lstsq._pen_args(self.l1_reg, self.l2_reg)
+        cols, w_p, o_p = lstsq._glm_wo_cols("GLM.fit", _columns(X), y, sample_weight, offset, pen)
         ctx = lstsq.default_context()
-        cols = lstsq._Cols(y, _columns(X))
         lstsq._follow(ctx, cols)
         pp = p + int(self.add_bias)
         f64 = bool(config.LIN_REG_EXPR_F64)
@@ -495,18 +521,19 @@ class GLM:
         link, var = GLM_FAMILIES[self.family]
         n_iter = C.c_int(0)
         tol = C.c_double(self.tol) if f64 else C.c_float(self.tol)
-        pen = lstsq._pen_args(self.l1_reg, self.l2_reg)
-        fn = ctx.fn("pds_glm_enet" if pen else "pds_glm_irls")
-        _lib.check(fn(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(self.add_bias), C.c_int(link), C.c_int(var),
+        fn = ctx.fn("pds_glm_irls_wo" if wo else ("pds_glm_enet" if pen else "pds_glm_irls"))
+        _lib.check(fn(ctx._h, cols.cols, *((w_p, o_p) if wo else ()), cols.n_feat, C.c_int64(cols.n_rows), cols.space, int(self.add_bias), C.c_int(link), C.c_int(var),
                       *pen, tol, C.c_int(self.max_iter), C.c_void_p(co.ctypes.data), C.byref(n_iter)))
         co = co.astype(np.float64)
         self._coeffs, self._bias = (co[:-1].copy(), float(co[-1])) if self.add_bias else (co.copy(), 0.0)
         self.n_iter_ = int(n_iter.value)
         return self
 
-    def _fit_report(self, X, y, n: int):
+    def _fit_report(self, X, y, n: int, sample_weight=None, offset=None):
+        if (sample_weight is not None or offset is not None) and lstsq._pen_args(self.l1_reg, self.l2_reg):
+            raise NotImplementedError("GLM.fit: l1_reg / l2_reg together with sample_weight= / offset= is not built")
         rep = lstsq.glm_report_by(*_columns(X), target=y, group_offsets=[0, n], family=self.family, add_bias=self.add_bias, tol=self.tol,
-                                  max_iter=self.max_iter, l1_reg=self.l1_reg, l2_reg=self.l2_reg)
+                                  max_iter=self.max_iter, l1_reg=self.l1_reg, l2_reg=self.l2_reg, weights=sample_weight, offset=offset)
         host = {k: (v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)) for k, v in rep.items() if k != "features"}
         if int(host["is_null"][0]):
             raise ValueError("The fit did not end in finite coefficients.")
@@ -545,11 +572,19 @@ class GLM:
         self.feature_names_in_ = list(features)
         return self.fit(X, y, null_policy="ignore")
 
-    def predict(self, X, linear: bool = False):
-        """E[Y | X] = g^-1(X beta + bias), or the linear predictor eta when `linear` (glm_predict, glm_solvers.rs:243-250)."""
+    def predict(self, X, linear: bool = False, offset=None):
+        """E[Y | X] = g^-1(X beta + bias), or the linear predictor eta when `linear` (glm_predict, glm_solvers.rs:243-250).
+        `offset` (one entry per row): added to the linear predictor, as the fit with `offset=` had it."""
         if not self.is_fit():
             raise ValueError("Matrix is not learned yet.")
         eta = _predict(X, self._coeffs, self._bias)
+        if offset is not None:
+            if _is_torch(eta):
+                import torch
+
+                eta = eta + torch.as_tensor(offset, dtype=eta.dtype, device=eta.device).reshape(eta.shape)
+            else:
+                eta = eta + np.asarray(offset, dtype=np.float64).reshape(eta.shape)
         if linear:
             return eta
         link = GLM_FAMILIES[self.family][0]

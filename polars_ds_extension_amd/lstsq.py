@@ -1413,8 +1413,34 @@ def _pen_args(l1_reg, l2_reg):
     return (ct(l1), ct(l2))
 
 
+def _glm_wo_cols(what, x, target, weights, offset, pen):
+    """The frame of a GLM call with a prior-weight and / or an offset column: (cols, weights pointer, offset pointer).  The two
+    columns are cast and placed like the frame's own (`_Cols`) and must have one entry per row; together with a penalty they are
+    refused before a device is touched."""
+    extra = [c for c in (weights, offset) if c is not None]
+    if extra and pen:
+        raise NotImplementedError(f"{what}: l1_reg / l2_reg together with weights= / offset= is not built")
+    n = int(target.shape[0]) if hasattr(target, "shape") else len(target)
+    for name, c in (("weights", weights), ("offset", offset)):
+        if c is not None and (int(c.shape[0]) if hasattr(c, "shape") else len(c)) != n:
+            raise ValueError(f"`{name}` must have one entry per row")
+    cols = _Cols(target, x)
+    if not extra:
+        return cols, C.c_void_p(None), C.c_void_p(None)
+    # the two columns: cast and placed like the frame's (a second _Cols whose "target" is the frame's, so that a device frame pulls
+    # host columns onto the device and the reverse never happens), kept alive with it
+    side = _Cols(cols.keep[0], extra)
+    if side.space != cols.space:
+        raise ValueError(f"{what}: weights / offset must live where the frame lives")
+    cols.keep.extend(side.keep[1:])
+    ptrs = [C.c_void_p(side.cols[1 + k]) for k in range(len(extra))]
+    w_p = ptrs.pop(0) if weights is not None else C.c_void_p(None)
+    o_p = ptrs.pop(0) if offset is not None else C.c_void_p(None)
+    return cols, w_p, o_p
+
+
 def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
-           return_pred: bool = False, ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0):
+           return_pred: bool = False, ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0, weights=None, offset=None):
     """
     One GLM per group in one call: for every group g = rows [group_offsets[g], group_offsets[g+1]) what `GLM(family=...).fit` computes
     on g's rows alone (iteratively re-weighted least squares, the reference's faer_irls), every iteration of a group on chip
@@ -1428,11 +1454,20 @@ def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool =
     unit-dispersion negative log-likelihood and the sums over j running over the features, never the bias.  Same iteration, each step
     the penalised weighted least squares problem (ridge: one solve; l1: coordinate descent in the wave, exact zeros).  A ridge term
     gives a separated binomial group a finite fit.
+    `weights` / `offset` (one entry per row each, either alone or both; `pds_glm_irls_wo_grouped_*`): prior weights pw and an offset
+    o per row, R's `glm(weights=, offset=)` -- eta = x . beta + o, working weight pw / (g'(mu)^2 V(mu)), start from the weighted mean
+    of y.  A row of weight 0 contributes nothing and does not count as a row (its target may hold anything, its features and offset must be
+    finite: they give the row's `pred`): a group with fewer rows of positive weight than
+    coefficients, or with a weight that is negative or not finite, is null.  `pred` is g^-1(x . beta_group + o), rows of weight 0
+    included.  Not together with `l1_reg` / `l2_reg` (NotImplementedError).  Without the two the call is the one it was.  Groups above the
+    context option "glm_split_rows" take the full-device iteration (`pds_glm_irls_wo_*`) on their rows of the two columns.
     """
     _glm_check(x, max_iter, "glm_by")
     link, var = _glm_family(family)
+    pen = _pen_args(l1_reg, l2_reg)
+    wo = weights is not None or offset is not None
+    cols, w_p, o_p = _glm_wo_cols("glm_by", x, target, weights, offset, pen)
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     off, off_p = _offsets_arg(cols, group_offsets)
@@ -1445,10 +1480,10 @@ def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool =
     if return_pred:
         pred, pr_p = _out_like(cols, cols.n_rows)
         rnull, rn_p = _out_u8(cols, cols.n_rows)
-    pen = _pen_args(l1_reg, l2_reg)
-    fn = ctx.fn("pds_glm_enet_grouped" if pen else "pds_glm_irls_grouped")
-    _lib.check(fn(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space, int(bool(add_bias)),
-                  C.c_int(link), C.c_int(var), *pen, _tol_arg(tol), C.c_int(int(max_iter)), co_p, it_p, nu_p, pr_p, rn_p))
+    fn = ctx.fn("pds_glm_irls_wo_grouped" if wo else ("pds_glm_enet_grouped" if pen else "pds_glm_irls_grouped"))
+    _lib.check(fn(ctx._h, cols.cols, *((w_p, o_p) if wo else ()), cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
+                  int(bool(add_bias)), C.c_int(link), C.c_int(var), *pen, _tol_arg(tol), C.c_int(int(max_iter)), co_p, it_p, nu_p, pr_p,
+                  rn_p))
     if return_pred:
         return coeffs, iters, nulls, pred, rnull
     return coeffs, iters, nulls
@@ -1456,22 +1491,24 @@ def glm_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool =
 
 def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
                return_pred: bool = False, max_groups: int | None = None, ctx: Context | None = None, l1_reg: float = 0.0,
-               l2_reg: float = 0.0):
+               l2_reg: float = 0.0, weights=None, offset=None):
     """
     `glm_by` for an integer key column in ANY row order (`pds_glm_irls_by_key_*`): the frame is brought into key order on the device
     (nothing moves when the keys are already non-decreasing), every group is fitted, per-row means come back at the rows' own
     positions.  Returns (keys [G] ascending, coeffs, n_iter, is_null), plus (pred, row_null) with `return_pred`.
     `l1_reg` / `l2_reg` > 0: the penalised fits of `glm_by` (`pds_glm_enet_by_key_*`).
+    `weights` / `offset`: as in `glm_by` (`pds_glm_irls_wo_by_key_*`); the two columns travel with the frame into key order.
     """
     _glm_check(x, max_iter, "glm_by_key")
     link, var = _glm_family(family)
+    pen = _pen_args(l1_reg, l2_reg)
+    wo = weights is not None or offset is not None
+    cols, w_p, o_p = _glm_wo_cols("glm_by_key", x, target, weights, offset, pen)
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
     k, k_p = _key_arg(cols, key)
-    pen = _pen_args(l1_reg, l2_reg)
     pred = rnull = None
     pr_p = rn_p = None
     if return_pred:
@@ -1482,9 +1519,10 @@ def glm_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False
         coeffs, co_p = _out_like(cols, (cap, pp))
         iters, it_p = _out_i32(cols, cap)
         nulls, nu_p = _out_u8(cols, cap)
-        fn = ctx.fn("pds_glm_enet_by_key" if pen else "pds_glm_irls_by_key")
-        rc = fn(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)), C.c_int(link), C.c_int(var), *pen,
-                _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p, co_p, it_p, nu_p, ng_p, pr_p, rn_p)
+        fn = ctx.fn("pds_glm_irls_wo_by_key" if wo else ("pds_glm_enet_by_key" if pen else "pds_glm_irls_by_key"))
+        rc = fn(ctx._h, cols.cols, *((w_p, o_p) if wo else ()), k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
+                C.c_int(link), C.c_int(var), *pen, _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p, co_p, it_p, nu_p, ng_p,
+                pr_p, rn_p)
         return rc, (coeffs, iters, nulls)
 
     keys, (coeffs, iters, nulls), g = _by_key_retry(cols, max_groups, call)
@@ -1532,7 +1570,7 @@ def _glm_report_check(x, max_iter, what, penalties):
 
 def glm_report_by(*x, target, group_offsets, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
                   feature_names: Sequence[str] | None = None, return_cov: bool = False, ctx: Context | None = None, l1_reg: float = 0.0,
-                  l2_reg: float = 0.0) -> dict:
+                  l2_reg: float = 0.0, weights=None, offset=None) -> dict:
     """
     The fit of `glm_by` and its report per group in one call (`pds_glm_report_grouped_*`): the GLM twin of `lin_reg_report_by`.
     "beta", "n_iter" and "is_null" are bit for bit what `glm_by` returns on the same frame; the report is formed on the device at
@@ -1547,34 +1585,42 @@ def glm_report_by(*x, target, group_offsets, family: str = "gaussian", add_bias:
     "features"; "cov" [G, p', p'] with `return_cov`.  report_null = 1 for a null fit and for a group whose I has no positive
     finite pivots (an all-zero column): its report fields are NaN, its coefficients stay what the fit returned.
     Penalised fits have no report: `l1_reg` / `l2_reg` > 0 raise NotImplementedError.
+    `weights` / `offset` (`pds_glm_report_wo_grouped_*`): the fit of `glm_by(weights=, offset=)` and its report with prior weights pw
+    and an offset o: mu = g^-1(x . beta + o), I = sum pw w x x', pearson_chi2 = sum pw (y - mu)^2 / V, deviance = sum pw d_i,
+    df_resid = n+ - p' (n+: the rows of positive weight); null_deviance is the closed form with weighted sums, and NaN whenever an
+    offset is given (the intercept-only model under an offset needs an iteration of its own).
     """
     _glm_report_check(x, max_iter, "glm_report_by", (l1_reg, l2_reg))
     link, var = _glm_family(family)
+    wo = weights is not None or offset is not None
+    cols, w_p, o_p = _glm_wo_cols("glm_report_by", x, target, weights, offset, ())
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     off, off_p = _offsets_arg(cols, group_offsets)
     ng = int(off.shape[0]) - 1
     outs, rep = _glm_report_outs(cols, ng, pp, return_cov)
-    _lib.check(ctx.fn("pds_glm_report_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
-                                                int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)),
-                                                outs["beta"][1], outs["n_iter"][1], outs["is_null"][1], C.byref(rep)))
+    fn = ctx.fn("pds_glm_report_wo_grouped" if wo else "pds_glm_report_grouped")
+    _lib.check(fn(ctx._h, cols.cols, *((w_p, o_p) if wo else ()), cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space,
+                  int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), outs["beta"][1],
+                  outs["n_iter"][1], outs["is_null"][1], C.byref(rep)))
     return _glm_report_dict(outs, cols.n_feat, add_bias, feature_names, return_cov)
 
 
 def glm_report_by_key(*x, target, key, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
                       feature_names: Sequence[str] | None = None, return_cov: bool = False, max_groups: int | None = None,
-                      ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0) -> dict:
+                      ctx: Context | None = None, l1_reg: float = 0.0, l2_reg: float = 0.0, weights=None, offset=None) -> dict:
     """
     `glm_report_by` for an integer key column in ANY row order (`pds_glm_report_by_key_*`): the frame is brought into key order on the
     device as `glm_by_key` does (nothing moves when the keys are already non-decreasing) and reported where it lies.  Returns the
     dict of `glm_report_by` plus "keys" (ascending).  The normal distribution is used for every family.
+    `weights` / `offset`: as in `glm_report_by` (`pds_glm_report_wo_by_key_*`); the two columns travel with the frame into key order.
     """
     _glm_report_check(x, max_iter, "glm_report_by_key", (l1_reg, l2_reg))
     link, var = _glm_family(family)
+    wo = weights is not None or offset is not None
+    cols, w_p, o_p = _glm_wo_cols("glm_report_by_key", x, target, weights, offset, ())
     ctx = ctx or default_context()
-    cols = _Cols(target, x)
     _follow(ctx, cols)
     pp = cols.n_feat + int(bool(add_bias))
     n_rows = cols.n_rows
@@ -1582,9 +1628,10 @@ def glm_report_by_key(*x, target, key, family: str = "gaussian", add_bias: bool 
 
     def call(cap, ok_p, ng_p):
         outs, rep = _glm_report_outs(cols, cap, pp, return_cov)
-        rc = ctx.fn("pds_glm_report_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
-                                             C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p,
-                                             outs["beta"][1], outs["n_iter"][1], outs["is_null"][1], ng_p, C.byref(rep))
+        fn = ctx.fn("pds_glm_report_wo_by_key" if wo else "pds_glm_report_by_key")
+        rc = fn(ctx._h, cols.cols, *((w_p, o_p) if wo else ()), k_p, cols.n_feat, C.c_int64(n_rows), cols.space, int(bool(add_bias)),
+                C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), C.c_int64(cap), ok_p, outs["beta"][1],
+                outs["n_iter"][1], outs["is_null"][1], ng_p, C.byref(rep))
         return rc, outs
 
     keys, outs, g = _by_key_retry(cols, max_groups, call)

@@ -230,7 +230,7 @@ def lin_reg_report_by_group(df, by, *x, target, **kwargs):
 
 
 def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,
-                 null_policy: str = "skip", return_pred: bool = False, by=None):
+                 null_policy: str = "skip", return_pred: bool = False, by=None, weights=None, offset=None):
     """
     expr_linear.py:277-353: `pl_logistic_coeffs` / `pl_logistic_pred` (Float64 only, as there), aliases `__coeffs__` / `__pred__`.
     Deliberate deviation: the reference minimises the mean log loss with L-BFGS from a seeded random start and stops at a gradient
@@ -240,11 +240,16 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
     `pl_glm_by_pred` call with family "binomial" -- Struct{<key>, coeffs, n_iter} per group, keys ascending, or the fitted
     probability of every row.  Keys of other dtypes or several key columns: `glm_by_group`.  With `by`, `l1_reg` / `l2_reg` > 0
     fit every group's penalised model (mean log loss + l2_reg / 2 |beta|^2 + l1_reg |beta|_1 over the features, the bias free).
+    `weights` / `offset` (column names or expressions, with `by` only): prior weights and an offset per row, as in `glm_by_group` --
+    with the target a success proportion and `weights` its trial count, the fit of the expanded Bernoulli frame.  Without `by` the
+    reference's signature stands: the two are refused.
     """
     if max_iter <= 0:
         raise ValueError("Input `max_iter` must be a positive.")
     if by is not None:
-        return _glm_by(x, target, by, "binomial", add_bias, abs(tol), max_iter, null_policy, return_pred, l1_reg, l2_reg)
+        return _glm_by(x, target, by, "binomial", add_bias, abs(tol), max_iter, null_policy, return_pred, l1_reg, l2_reg, weights, offset)
+    if weights is not None or offset is not None:
+        raise NotImplementedError("logistic_reg: weights= / offset= need by= (one model per group); without by they are not built")
     if l1_reg > 0.0 or l2_reg > 0.0:
         raise NotImplementedError("logistic_reg: l1_reg / l2_reg are not supported on this backend; use GLM(family='binomial', "
                                   "l2_reg=...) or by=")
@@ -261,7 +266,7 @@ def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg:
                                     pass_name_to_apply=True).alias("__coeffs__")
 
 
-def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_pred, l1_reg=0.0, l2_reg=0.0):
+def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_pred, l1_reg=0.0, l2_reg=0.0, weights=None, offset=None):
     from .linear_models import GLM_FAMILIES
 
     if family not in GLM_FAMILIES:
@@ -271,14 +276,24 @@ def _glm_by(x, target, by, family, add_bias, tol, max_iter, null_policy, return_
     kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
     if l1_reg > 0.0 or l2_reg > 0.0:  # (absent = 0 in the plugin: an unpenalised call keeps the kwargs it had)
         kwargs.update(l1_reg=max(float(l1_reg), 0.0), l2_reg=max(float(l2_reg), 0.0))
-    cols = [_formula(by), _formula(target).cast(_dtype())] + [_formula(z) for z in x]
+        if weights is not None or offset is not None:
+            raise NotImplementedError("grouped GLM: l1_reg / l2_reg together with weights= / offset= is not built")
+    # (absent = false in the plugin: a call without the two columns keeps the kwargs and the inputs it had)
+    extra = []
+    if weights is not None:
+        kwargs["has_weights"] = True
+        extra.append(_formula(weights).cast(_dtype()))
+    if offset is not None:
+        kwargs["has_offset"] = True
+        extra.append(_formula(offset).cast(_dtype()))
+    cols = [_formula(by), *extra, _formula(target).cast(_dtype())] + [_formula(z) for z in x]
     if return_pred:
         return _plugin("pl_glm_by_pred", cols, kwargs).alias("glm_pred")
     return _plugin("pl_glm_by", cols, kwargs, changes_length=True).alias("glm_by")
 
 
 def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool = False, add_bias: bool = False, tol: float = 1e-8,
-                 max_iter: int = 100, null_policy: str = "raise", l1_reg: float = 0.0, l2_reg: float = 0.0):
+                 max_iter: int = 100, null_policy: str = "raise", l1_reg: float = 0.0, l2_reg: float = 0.0, weights=None, offset=None):
     """
     One GLM per group of a frame (families of `linear_models.GLM_FAMILIES`) from ONE plugin call (`pl_glm_by`: keys in any row
     order, every iteration of a group on chip) -- what fitting `GLM(family=...)` on every group of `df.group_by(by)` computes.
@@ -287,9 +302,12 @@ def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool
     fewer rows than coefficients or a fit that does not end in finite coefficients) and `n_iter`; integer keys come back ascending,
     other keys in order of first appearance.  `return_pred=True`: the input frame with a `glm_pred` column, row for row.
     `l1_reg` / `l2_reg` > 0: every group's elastic-net penalised fit (`lstsq.glm_by` states the objective).
+    `weights` / `offset` (column names or expressions): prior weights and an offset per row, R's `glm(weights=, offset=)`
+    (`lstsq.glm_by` states the semantics) -- a Poisson rate is `offset=pl.col("exposure").log()`.  A null in either is an error
+    whatever `null_policy`; not together with a penalty.  `glm_pred` is then g^-1(x . beta_group + offset).
     """
     args = (family, add_bias, tol, max_iter, null_policy)
-    pen = (l1_reg, l2_reg)
+    pen = (l1_reg, l2_reg, weights, offset)
     if return_pred:
         if _is_integer_key(df, by):
             return df.with_columns(_glm_by(x, target, by, *args, True, *pen))
@@ -304,7 +322,7 @@ def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool
 
 
 def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
-               null_policy: str = "raise"):
+               null_policy: str = "raise", weights=None, offset=None):
     """
     The report of one GLM per group from ONE `pl_glm_report_by` call (the GLM twin of `lin_reg_report(..., by=)`): `by` is an
     integer key column in any row order, nulls = one group.  Long format -- a Struct "glm_report" {<key>, features, beta, std_err, z,
@@ -312,6 +330,8 @@ def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False,
     per-group fields repeated on a group's rows.  z, p and the interval use the normal distribution for every family (statsmodels'
     `use_t=False`; `lstsq.glm_report_by` states the definitions).  A group with a null report keeps its rows with null numeric
     fields.  Penalised fits have no report.  Keys of other dtypes or several key columns: `glm_report_by_group`.
+    `weights` / `offset` (column names or expressions): prior weights and an offset per row (`lstsq.glm_report_by` states the
+    weighted definitions; `null_deviance` is null-valued NaN under an offset).  A null in either is an error whatever `null_policy`.
     """
     from .linear_models import GLM_FAMILIES
 
@@ -320,7 +340,14 @@ def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False,
     if max_iter < 1:
         raise ValueError("`max_iter` must be > 1.")
     kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
-    cols = [_formula(by), _formula(target).cast(_dtype())] + [_formula(z) for z in x]
+    extra = []
+    if weights is not None:
+        kwargs["has_weights"] = True
+        extra.append(_formula(weights).cast(_dtype()))
+    if offset is not None:
+        kwargs["has_offset"] = True
+        extra.append(_formula(offset).cast(_dtype()))
+    cols = [_formula(by), *extra, _formula(target).cast(_dtype())] + [_formula(z) for z in x]
     return _plugin("pl_glm_report_by", cols, kwargs, changes_length=True).alias("glm_report")
 
 

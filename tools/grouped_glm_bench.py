@@ -11,6 +11,10 @@ long = 1e4 groups x 1e4 rows (beyond the 128 resident rows); skewed = one 1e7-ro
 route).  `--split a,b,..` repeats the long and skewed shapes with the context option glm_split_rows set to each value.
 `--sample K`: the parent's only way, `GLM.fit` per group, on the first K groups of the headline frame, alternating with the grouped
 call on those K groups; the factor between the two.
+`--weighted`: on the headline and wide frames, `glm_by` with prior weights (headline) / with weights and an offset (wide) against
+`glm_by` without, the two calls alternating in one process: medians of `--reps` warmed calls each, their ratio, the mean iteration
+counts (weights U(0.25, 4), offsets U(-0.1, 0.1): the target is not redrawn, so the counts may differ a little); and
+`glm_report_by` with the columns against `glm_report_by` without, the same way.
 A per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/grouped_glm_bench.py ...`.
 """
 import argparse
@@ -93,6 +97,56 @@ def run_shape(name, ctx, gen, dev, sizes_desc, off, p, family, reps, split=None)
     return X, y
 
 
+def run_weighted(name, ctx, gen, dev, X, y, off, p, family, reps, with_offset):
+    """`glm_by(weights= (, offset=))` against `glm_by` on the same frame, the two calls alternating."""
+    n = int(y.numel())
+    pw = 0.25 + 3.75 * torch.rand(n, generator=gen, device=dev, dtype=torch.float64)
+    o = (0.2 * torch.rand(n, generator=gen, device=dev, dtype=torch.float64) - 0.1) if with_offset else None
+    kw = dict(target=y, group_offsets=off, family=family, add_bias=True, tol=1e-8, max_iter=100, ctx=ctx)
+    plain = lambda: pds.glm_by(*X, **kw)  # noqa: E731
+    weighted = lambda: pds.glm_by(*X, weights=pw, offset=o, **kw)  # noqa: E731
+    for _ in range(2):
+        plain()
+        weighted()
+    s = torch.cuda.current_stream()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = {"plain": [], "weighted": []}
+    for _ in range(reps):
+        for k, fn in (("plain", plain), ("weighted", weighted)):
+            a.record(s)
+            fn()
+            b.record(s)
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    it0, itw = plain()[1], weighted()[1]
+    # the report likewise: glm_report_by with the columns against glm_report_by without, alternating
+    rplain = lambda: pds.glm_report_by(*X, **kw)  # noqa: E731
+    rweighted = lambda: pds.glm_report_by(*X, weights=pw, offset=o, **kw)  # noqa: E731
+    for _ in range(2):
+        rplain()
+        rweighted()
+    rms = {"plain": [], "weighted": []}
+    for _ in range(reps):
+        for k, fn in (("plain", rplain), ("weighted", rweighted)):
+            a.record(s)
+            fn()
+            b.record(s)
+            b.synchronize()
+            rms[k].append(a.elapsed_time(b))
+    rmed = {k: sorted(v)[len(v) // 2] for k, v in rms.items()}
+    print(json.dumps({"bench": "grouped_glm_weighted", "shape": name, "groups": int(off.numel()) - 1, "rows": n, "p": p, "family": family,
+                      "columns": "weights + offset" if with_offset else "weights", "plain_ms": round(med["plain"], 3),
+                      "plain_ms_best": round(min(ms["plain"]), 3), "plain_ms_worst": round(max(ms["plain"]), 3),
+                      "weighted_ms": round(med["weighted"], 3), "weighted_ms_best": round(min(ms["weighted"]), 3),
+                      "weighted_ms_worst": round(max(ms["weighted"]), 3), "ratio": round(med["weighted"] / med["plain"], 4),
+                      "mean_n_iter_plain": round(float(it0.float().mean().item()), 2),
+                      "mean_n_iter_weighted": round(float(itw.float().mean().item()), 2),
+                      "report_plain_ms": round(rmed["plain"], 3), "report_weighted_ms": round(rmed["weighted"], 3),
+                      "report_ratio": round(rmed["weighted"] / rmed["plain"], 4),
+                      "report_weighted_over_fit_weighted": round(rmed["weighted"] / med["weighted"], 4)}), flush=True)
+
+
 def sample_against_glm_fit(ctx, X, y, m, p, family, k):
     """`GLM(family).fit` per group on the first k groups (m rows each), alternating with the grouped call on those k groups."""
     from polars_ds_extension_amd.linear_models import GLM
@@ -127,6 +181,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--split", default="")
     ap.add_argument("--sample", type=int, default=1000)
+    ap.add_argument("--weighted", action="store_true", help="headline / wide: the weighted (/ offset) call against the plain one")
     ap.add_argument("--scale", type=float, default=1.0, help="scales the group counts (a smaller rehearsal)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -143,11 +198,15 @@ def main():
         X, y = run_shape("headline", ctx, gen, dev, None, off, 8, "binomial", a.reps)
         if a.sample > 0:
             sample_against_glm_fit(ctx, X, y, m, 8, "binomial", min(a.sample, G))
+        if a.weighted:
+            run_weighted("headline", ctx, gen, dev, X, y, off, 8, "binomial", a.reps, with_offset=False)
         del X, y
     if "wide" in shapes:
         G, m = int(1_000_000 * sc), 100
         off = torch.arange(0, G * m + 1, m, dtype=torch.int64, device=dev)
         X, y = run_shape("wide", ctx, gen, dev, None, off, 16, "poisson", a.reps)
+        if a.weighted:
+            run_weighted("wide", ctx, gen, dev, X, y, off, 16, "poisson", a.reps, with_offset=True)
         del X, y
     if "long" in shapes:
         G, m = int(10_000 * sc), 10_000
