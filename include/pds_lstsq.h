@@ -89,8 +89,21 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             iteration, one by one (<= 0: the default, 16384; at least 64).
  *   "mixed_split_rows"                        pds_mixed_*: groups of more rows are cut into row chunks that are separate work items
  *                                             (<= 0: the default, 16384; at least 64).
- * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows: a count).  Unknown names are PDS_ERR_INVALID. */
+ *   "grouped_fused_waves"                     pds_lr_grouped_* / pds_lr_by_key_* up to 16 features: cap on the number of waves the fused
+ *                                             kernel starts (<= 0: the default, every wave slot of the device).
+ *   "grouped_fused_late_permille"             the same kernel: share of the frame's rows, in 1/1000, dealt to the second half of its
+ *                                             waves (1 .. 999; 0: the default -- equal shares unless the grid fills the device, see
+ *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
+ *                                             does not enter the group's arithmetic.
+ * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
+/* Host restatement of how the fused grouped kernel deals groups to its waves (no device needed): wave w of `waves` fits the groups
+ * [first_group[w], end_group[w]) -- those whose first row lies in the wave's share of the row range [group_offsets[0],
+ * group_offsets[n_groups]).  late_permille = 0: equal shares of the rows; 1 .. 999: that share of the rows goes to the second half of
+ * the waves (a device-filling launch uses an unequal share because the second wave of a SIMD advances more slowly beside the first).
+ * The ranges are in order and partition [0, n_groups) for every setting.  first_group / end_group: `waves` values each, host memory. */
+int pds_grouped_fused_split(const int64_t* group_offsets, int64_t n_groups, int waves, int late_permille, int64_t* first_group,
+                            int64_t* end_group);
 /* Host-frame staging (process wide): chunk_mb = bytes of one row chunk of a PDS_HOST frame (default 256, env
  * PDS_HOST_CHUNK_MB); resident_max_mb = largest host frame that pds_lr_pred_* still stages whole (one PCIe trip; larger
  * frames make two chunked trips; default 98304, env PDS_HOST_RESIDENT_MAX_MB).  A value <= 0 leaves the setting as is.

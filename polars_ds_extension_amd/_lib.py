@@ -20,7 +20,7 @@ PDS_REPORT_DERIVE_YVAR = 0x100  # include/pds_lstsq.h
 
 EXPORTS = [
     "pds_last_error", "pds_version", "pds_ctx_create", "pds_ctx_destroy", "pds_ctx_set_stream",
-    "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_glm_irls_grouped_f64", "pds_glm_irls_grouped_f32", "pds_glm_irls_by_key_f64", "pds_glm_irls_by_key_f32",
+    "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_grouped_fused_split", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_glm_irls_grouped_f64", "pds_glm_irls_grouped_f32", "pds_glm_irls_by_key_f64", "pds_glm_irls_by_key_f32",
     "pds_glm_irls_wo_f64", "pds_glm_irls_wo_f32", "pds_glm_irls_wo_grouped_f64", "pds_glm_irls_wo_grouped_f32", "pds_glm_irls_wo_by_key_f64", "pds_glm_irls_wo_by_key_f32",
     "pds_glm_enet_f64", "pds_glm_enet_f32", "pds_glm_enet_grouped_f64", "pds_glm_enet_grouped_f32", "pds_glm_enet_by_key_f64", "pds_glm_enet_by_key_f32",
     "pds_glm_report_wo_grouped_f64", "pds_glm_report_wo_grouped_f32", "pds_glm_report_wo_by_key_f64", "pds_glm_report_wo_by_key_f32",

@@ -14,6 +14,7 @@
 
 #include "common.hpp"
 #include "grouped_report.hpp"
+#include "grouped_split_dev.hpp"
 
 namespace pds {
 
@@ -131,7 +132,29 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     else if (n == "glm_split_rows") ctx->opt_glm_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "mixed_split_rows") ctx->opt_mixed_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
-    else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
+    else if (n == "grouped_fused_waves") ctx->opt_fused_waves = value > 0 ? (int64_t)value : 0;
+    else if (n == "grouped_fused_late_permille") {
+        if (value < 0 || value > 999) return fail(PDS_ERR_INVALID, "grouped_fused_late_permille: 0 (the default rule) or 1 .. 999");
+        ctx->opt_fused_late_permille = (int64_t)value;
+    } else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
+    return PDS_OK;
+}
+
+int pds_grouped_fused_split(const int64_t* group_offsets, int64_t n_groups, int waves, int late_permille, int64_t* first_group,
+                            int64_t* end_group) {
+    if (!group_offsets || !first_group || !end_group) return fail(PDS_ERR_INVALID, "null argument");
+    if (n_groups < 0 || waves < 1 || late_permille < 0 || late_permille > 999) return fail(PDS_ERR_INVALID, "pds_grouped_fused_split: bad argument");
+    // the kernel's own rule, on the host: first group whose start row is >= the wave's first row (lower bound over offsets[0 .. n_groups))
+    const int64_t base = group_offsets[0], total = group_offsets[n_groups] - base;
+    auto bound = [&](int64_t w) -> int64_t {
+        if (w == 0) return 0;
+        if (w == waves) return n_groups;
+        return std::lower_bound(group_offsets, group_offsets + n_groups, base + pds::fused_split_row(w, waves, total, late_permille)) - group_offsets;
+    };
+    for (int w = 0; w < waves; ++w) {
+        first_group[w] = bound(w);
+        end_group[w] = std::max(bound(w + 1), first_group[w]);
+    }
     return PDS_OK;
 }
 

@@ -131,6 +131,8 @@ struct pds_ctx {
     int64_t opt_glm_split_rows = 0;       // "glm_split_rows": groups above this many rows leave the grouped IRLS kernel (0: the default)
     int64_t opt_report_chunk_groups = 0;  // "report_chunk_groups": groups per pass of the grouped report (0: from its record budget)
     int64_t opt_mixed_split_rows = 0;     // "mixed_split_rows": groups above this many rows are cut into row chunks (0: the default)
+    int64_t opt_fused_waves = 0;          // "grouped_fused_waves": cap on the grid of the fused grouped kernel (0: every wave slot)
+    int64_t opt_fused_late_permille = 0;  // "grouped_fused_late_permille": rows, in 1/1000, of the grid's second half (0: grouped_split_dev.hpp)
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<float> kind_samples[8];  // the individual bracketed durations (ms), newest kept up to 4096 per class

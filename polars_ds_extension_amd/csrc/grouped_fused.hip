@@ -8,8 +8,11 @@
 // p = 16) never exist, HBM traffic is input + coefficients only, and memory-bound tile streaming of some waves
 // overlaps the VALU-bound solves of others on the same CU.
 //
-// Work split: wave w owns the groups whose first row lies in [w N / W, (w+1) N / W) -- balanced in ROWS
-// (binary search in the offsets), so skewed group sizes do not unbalance the stream.
+// Work split: wave w owns the groups whose first row lies in [row(w), row(w + 1)) -- shares of the ROWS (binary search in the
+// offsets), so skewed group sizes do not unbalance the stream.  row(w) = w N / W on a grid that leaves wave slots free.  On a grid
+// that fills the device the second half of the blocks are the younger of the two waves on every SIMD and advance more slowly
+// beside the older one, so they get a smaller share of the rows (grouped_split_dev.hpp: fused_split_row, kFusedLatePermille;
+// measured with `tools/phase_profile.py tail`, profiles/fused_tail_parent.txt and fused_tail_ab.txt).
 //
 // Solver: with the rank gate on (the default of pds.lin_reg) the systems are factored by Cholesky in registers
 // (breakdown or rel. determinant <= tol => null, exactly the reference's `choleskey` rule, lr_solvers.rs:369-380);
@@ -18,6 +21,7 @@
 // reference's finite answers on rank-deficient groups.  PDS_GROUPED_PIVOTED=1 forces QR everywhere.
 #include <type_traits>
 
+#include "grouped_split_dev.hpp"
 #include "moments_dev.hpp"
 #include "solve_reg_dev.hpp"
 
@@ -31,6 +35,38 @@ __device__ unsigned long long g_phase_cycles[8];
 #else
 #define PDS_T0() do {} while (0)
 #define PDS_T1(k) do {} while (0)
+#endif
+// -DPDS_PROFILE_TAIL (implied by PDS_PROFILE_PHASES): every wave leaves when it started and ended on the constant 100 MHz clock
+// all XCDs share, its residency in shader clocks and the XCD it ran on -- two stamps per wave and nothing inside the loop, so the
+// launch runs as the product kernel does (development; `python tools/phase_profile.py tail` reads them).  The stamps go to a buffer
+// of their own that nothing else reads.
+#if defined(PDS_PROFILE_PHASES) || defined(PDS_PROFILE_TAIL)
+#define PDS_WAVE_STAMPS 1
+constexpr int kStampWaves = 4096;
+__device__ unsigned long long g_wave_stamps[4 * kStampWaves];  // per wave: start, end (100 MHz), shader clocks, valid << 63 | HW_ID << 8 | XCD id
+static int g_stamp_grid = 0;                                  // grid of the last launch
+#define PDS_STAMP_BEGIN()                                                             \
+    const unsigned long long _st_rt = __builtin_amdgcn_s_memrealtime();               \
+    const unsigned long long _st_mt = __builtin_amdgcn_s_memtime()
+#define PDS_STAMP_END()                                                                                                     \
+    do {                                                                                                                    \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kStampWaves) {                                                \
+            unsigned long long* _s = g_wave_stamps + 4 * (size_t)blockIdx.x;                                                \
+            _s[0] = _st_rt;                                                                                                 \
+            _s[1] = __builtin_amdgcn_s_memrealtime();                                                                       \
+            _s[2] = __builtin_amdgcn_s_memtime() - _st_mt;                                                                  \
+            _s[3] = (1ull << 63) | ((unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) << 8) /* HW_REG_HW_ID */     \
+                    | (unsigned long long)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 0xFu);          /* HW_REG_XCC_ID */     \
+        }                                                                                                                   \
+    } while (0)
+#define PDS_STAMP_SKIP()                                                                                  \
+    do {                                                                                                  \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kStampWaves) g_wave_stamps[4 * (size_t)blockIdx.x + 3] = 0ull; \
+    } while (0)
+#else
+#define PDS_STAMP_BEGIN() do {} while (0)
+#define PDS_STAMP_END() do {} while (0)
+#define PDS_STAMP_SKIP() do {} while (0)
 #endif
 
 constexpr int kFQ = 18;                  // LDS scratch moment matrix: indices 0..15 features, 16 bias, 17 y
@@ -224,7 +260,8 @@ __global__ __launch_bounds__(64) void grouped_stream_kernel(const T* const* __re
                                                             const int64_t* __restrict__ offsets, int64_t n_groups,
                                                             int64_t n_rows, SolveRegDev sp, T* __restrict__ coeffs,
                                                             uint8_t* __restrict__ flags, int32_t* __restrict__ mark_list,
-                                                            unsigned* __restrict__ mark_count, unsigned* __restrict__ mark_host_flag) {
+                                                            unsigned* __restrict__ mark_count, unsigned* __restrict__ mark_host_flag,
+                                                            int late_permille) {
     constexpr int SPW = 64 / LPS;
     constexpr int RPL = Tile<T>::RPL;
     constexpr int TR = 64 * RPL;
@@ -247,13 +284,17 @@ __global__ __launch_bounds__(64) void grouped_stream_kernel(const T* const* __re
     const int pout = p + (BIAS ? 1 : 0);
     const int sub = lane / LPS, j_in = lane % LPS;
 
-    // ---- this wave's groups: balanced in rows
+    PDS_STAMP_BEGIN();
+    // ---- this wave's groups: its share of the rows (fused_split_row)
     const int64_t W = gridDim.x, w = blockIdx.x;
     const int64_t base_row = offsets[0];
     const int64_t total = offsets[n_groups] - base_row;
-    const int64_t gl = (w == 0) ? 0 : lower_bound_i64(offsets, n_groups, base_row + (total * w) / W);
-    const int64_t gh = (w == W - 1) ? n_groups : lower_bound_i64(offsets, n_groups, base_row + (total * (w + 1)) / W);
-    if (gl >= gh) return;
+    const int64_t gl = (w == 0) ? 0 : lower_bound_i64(offsets, n_groups, base_row + fused_split_row(w, W, total, late_permille));
+    const int64_t gh = (w == W - 1) ? n_groups : lower_bound_i64(offsets, n_groups, base_row + fused_split_row(w + 1, W, total, late_permille));
+    if (gl >= gh) {
+        PDS_STAMP_SKIP();
+        return;
+    }
     const int64_t rlo = offsets[gl], rhi = offsets[gh];
 
     // zero the unused feature slots of the tile once
@@ -550,6 +591,7 @@ __global__ __launch_bounds__(64) void grouped_stream_kernel(const T* const* __re
     if (lane == 0)
         for (int k = 0; k < 8; ++k) atomicAdd(&g_phase_cycles[k], prof[k]);
 #endif
+    PDS_STAMP_END();
 }
 
 template <typename T, int LPS>
@@ -558,7 +600,10 @@ static int launch_stream_lps(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, 
                              uint8_t* d_flags, int32_t* d_mark_list, unsigned* d_mark_count, unsigned* d_mark_host) {
     const size_t lds = (size_t)kFWaveLds;
     const int per_cu = std::max(1, (int)((160 * 1024) / lds));
-    int64_t nb = std::min<int64_t>(std::max<int64_t>(n_groups / (64 / LPS), 1), (int64_t)ctx->num_cus * per_cu);
+    const int64_t slots = (int64_t)ctx->num_cus * per_cu;
+    int64_t nb = std::min<int64_t>(std::max<int64_t>(n_groups / (64 / LPS), 1), slots);
+    if (ctx->opt_fused_waves > 0) nb = std::min<int64_t>(nb, ctx->opt_fused_waves);  // "grouped_fused_waves": a cap (tests, A/B runs)
+    const int late_pm = fused_late_permille(nb, slots, ctx->opt_fused_late_permille);
     KernelTimer timer(ctx, kKindGroupedMoments);
     // (the pivoted-QR variant of this kernel measured slower than the two-kernel pipeline and is not instantiated;
     //  callers route the ungated case to grouped_moments_kernel + solve_reg_kernel)
@@ -569,7 +614,7 @@ static int launch_stream_lps(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, 
     auto go = [&](auto bias_c, auto pc_c) {
         hipLaunchKernelGGL((grouped_stream_kernel<T, LPS, true, decltype(bias_c)::value, decltype(pc_c)::value>), dim3((unsigned)nb),
                            dim3(64), lds, ctx->stream, dc.d_ptrs, n_feat, d_offsets, n_groups, n_rows, sd, d_coeffs, d_flags, d_mark_list,
-                           d_mark_count, d_mark_host);
+                           d_mark_count, d_mark_host, late_pm);
     };
     auto by_pc = [&](auto bias_c) {
         using std::integral_constant;
@@ -593,6 +638,9 @@ static int launch_stream_lps(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, 
     if (sd.bias) by_pc(std::true_type{});
     else by_pc(std::false_type{});
     PDS_HIP_CHECK(hipGetLastError());
+#ifdef PDS_WAVE_STAMPS
+    g_stamp_grid = (int)nb;
+#endif
     return PDS_OK;
 }
 
@@ -703,6 +751,17 @@ extern "C" int pds_debug_phase_cycles(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_cycles), sizeof(z)) != hipSuccess) return -1;
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)) != hipSuccess) return -1;
     return 0;
+}
+#endif
+
+#ifdef PDS_WAVE_STAMPS
+// the stamps of the last fused launch (four words per wave, see g_wave_stamps); returns the number of waves copied.  The caller has
+// synchronised: the grouped entry points do before they return.
+extern "C" int pds_debug_wave_stamps(unsigned long long* out, int max_waves) {
+    const int n = std::min(std::min(g_stamp_grid, kStampWaves), max_waves);
+    if (n <= 0) return 0;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_stamps), (size_t)n * 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    return n;
 }
 #endif
 
