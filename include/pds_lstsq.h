@@ -95,6 +95,7 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             waves (1 .. 999; 0: the default -- equal shares unless the grid fills the device, see
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
+ *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
  * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host restatement of how the fused grouped kernel deals groups to its waves (no device needed): wave w of `waves` fits the groups
@@ -838,6 +839,44 @@ int pds_lr_rcond_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64
 int pds_lr_rcond_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
                             int add_bias, float l2_reg, float rcond, int64_t max_groups, int64_t* out_keys, float* coeffs,
                             float* singular_values, uint8_t* is_null, int64_t* n_groups);
+/*
+ * pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: `lin_reg(target=[t_0 .. t_{k-1}], by=key)` -- for every group g what pds_lr_multi_*
+ * computes on g's rows alone (pl_lr_multi under group_by / over): k targets share the group's design matrix.  The frame is staged
+ * once and the keys are ordered once for all k targets.
+ * cols = [t_0 .. t_{k-1}, x_1 .. x_p], the order of pds_lr_multi_*.  1 .. 16 feature columns, 1 .. 15 targets; anything beyond is
+ * PDS_ERR_UNSUPPORTED ("grouped multi-target lin_reg: up to 16 feature columns and 15 targets"), never an approximate answer.
+ * OLS / ridge (l2_reg on the feature diagonals, never on the intercept); f32 frames are fitted in f64 arithmetic.
+ * The gate and the null rule are pds_lr_grouped_*'s, group for group: null (is_null = 1, NaN coefficients) are a group whose offsets
+ * leave the frame (nothing is read), a group with fewer rows than coefficients, a group with a non-finite moment, and a group the
+ * rank gate rejects (singular_x_tol; <= 0: no gate; solver as in pds_lr_params, PDS_SOLVER_SVD runs the pivoted QR as in
+ * pds_lr_multi_*).  The gate depends on X alone: a group is null for every target or for none, so a NaN in ONE target nulls the group
+ * (route 2 finds such a group by its coefficients: a gated group with a coefficient that is not finite is null).
+ * Context option "grouped_multi_route": 1 = one kernel (grouped_multi.hip: one wave per group, X'X and all X't_c from one pass over
+ * the group's rows, one L D L' factorisation, k substitutions; groups next to the gate go through the pivoted QR unless the solver
+ * is PDS_SOLVER_CHOLESKEY), 2 = the fused kernel of pds_lr_grouped_* once per target on the one staged frame, 0 (default) = whichever
+ * measured faster for the shape.  With singular_x_tol <= 0 every route runs the grouped Gram records and the pivoted QR per target.
+ * Routes 0 / 2, the ungated form and the per-row outputs need offsets that are non-decreasing and inside the frame (a gated call
+ * without per-row outputs falls back to route 1, which reads nothing of a bad group; otherwise PDS_ERR_INVALID).
+ * "grouped_multi_waves": cap on the number of waves route 1 starts (<= 0: every wave slot); it changes no result bit.
+ * Outputs, `space`-resident: coeffs [n_groups][n_targets][n_feat + add_bias] (bias last), is_null [n_groups]; optional pred / resid
+ * [n_targets][n_rows] (target-major) and row_null [n_rows] (1 on the rows of null groups, whose pred / resid are NaN), in the frame's
+ * own row order.
+ * By key: int64 keys in any row order, groups returned in ascending key order; *n_groups receives the number of distinct keys, also
+ * when it exceeds max_groups (PDS_ERR_INVALID, nothing fitted).  A caller that only wants the per-row outputs passes NULL for
+ * out_keys, coeffs, is_null and n_groups (max_groups is then not looked at), as with pds_lr_by_key_pred_*.
+ */
+int pds_lr_multi_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_targets, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, double l2_reg, int solver, double singular_x_tol, double* coeffs,
+                             uint8_t* is_null, double* pred, double* resid, uint8_t* row_null);
+int pds_lr_multi_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_targets, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, float l2_reg, int solver, float singular_x_tol, float* coeffs,
+                             uint8_t* is_null, float* pred, float* resid, uint8_t* row_null);
+int pds_lr_multi_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_targets, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, double l2_reg, int solver, double singular_x_tol, int64_t max_groups, int64_t* out_keys, double* coeffs,
+                            uint8_t* is_null, int64_t* n_groups, double* pred, double* resid, uint8_t* row_null);
+int pds_lr_multi_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_targets, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, float l2_reg, int solver, float singular_x_tol, int64_t max_groups, int64_t* out_keys, float* coeffs,
+                            uint8_t* is_null, int64_t* n_groups, float* pred, float* resid, uint8_t* row_null);
 /*
  * pds_mixed_reml_grouped_* / pds_mixed_reml_by_key_* / pds_mixed_profile_grouped_*: the random-intercept linear mixed model
  * y = X beta + Z u + e, u ~ N(0, sigma_g^2 I), e ~ N(0, sigma_e^2 I), fitted by REML as fit_reml does (src/linear/mixed/mod.rs:173-272):

@@ -34,6 +34,8 @@ from .lstsq import (  # noqa: F401
     lin_reg_by_key_pred,
     lin_reg_by_pred,
     lin_reg_from_moments,
+    lin_reg_multi_by,
+    lin_reg_multi_by_key,
     lin_reg_report,
     lin_reg_w_rcond,
     lin_reg_w_rcond_by,

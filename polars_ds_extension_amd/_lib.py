@@ -26,6 +26,7 @@ EXPORTS = [
     "pds_glm_report_wo_grouped_f64", "pds_glm_report_wo_grouped_f32", "pds_glm_report_wo_by_key_f64", "pds_glm_report_wo_by_key_f32",
     "pds_glm_report_grouped_f64", "pds_glm_report_grouped_f32", "pds_glm_report_by_key_f64", "pds_glm_report_by_key_f32",
     "pds_lr_rcond_grouped_f64", "pds_lr_rcond_grouped_f32", "pds_lr_rcond_by_key_f64", "pds_lr_rcond_by_key_f32",
+    "pds_lr_multi_grouped_f64", "pds_lr_multi_grouped_f32", "pds_lr_multi_by_key_f64", "pds_lr_multi_by_key_f32",
     "pds_mixed_reml_grouped_f64", "pds_mixed_reml_grouped_f32", "pds_mixed_reml_by_key_f64", "pds_mixed_reml_by_key_f32",
     "pds_mixed_profile_grouped_f64", "pds_mixed_profile_grouped_f32",
     "pds_lr_rowmajor_f64", "pds_lr_rowmajor_f32", "pds_ctx_workspace_spills", "pds_ctx_workspace_bytes", "pds_ctx_set_timing", "pds_ctx_get_timing", "pds_ctx_get_timing_samples",
@@ -137,6 +138,16 @@ def load() -> C.CDLL:
         if hasattr(lib, "pds_ctx_workspace_spills"):  # (absent from older builds used in A/B runs)
             lib.pds_ctx_workspace_spills.argtypes = [C.c_void_p]
             lib.pds_ctx_workspace_spills.restype = C.c_longlong
+        for sfx, real in (("f64", C.c_double), ("f32", C.c_float)):  # (absent from older builds used in A/B runs)
+            if hasattr(lib, "pds_lr_multi_grouped_" + sfx):
+                # ctx, cols, n_targets, n_feat, n_rows, group_offsets, n_groups, space, add_bias, l2_reg, solver, singular_x_tol,
+                # coeffs, is_null, pred, resid, row_null
+                getattr(lib, "pds_lr_multi_grouped_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                                                      C.c_int64, C.c_int, C.c_int, real, C.c_int, real] + [C.c_void_p] * 5
+                # ctx, cols, keys, n_targets, n_feat, n_rows, space, add_bias, l2_reg, solver, singular_x_tol, max_groups, out_keys,
+                # coeffs, is_null, n_groups, pred, resid, row_null
+                getattr(lib, "pds_lr_multi_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                                                     C.c_int, real, C.c_int, real, C.c_int64] + [C.c_void_p] * 7
         if hasattr(lib, "pds_ctx_workspace_bytes"):
             lib.pds_ctx_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
             lib.pds_ctx_workspace_bytes.restype = C.c_longlong

@@ -32,6 +32,7 @@ namespace pds {
 #include "capi_glm_grouped.hpp"
 #include "capi_glm_report.hpp"
 #include "capi_rcond_grouped.hpp"
+#include "capi_multi_grouped.hpp"
 #include "capi_mixed.hpp"
 
 }  // namespace pds
@@ -136,7 +137,11 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     else if (n == "grouped_fused_late_permille") {
         if (value < 0 || value > 999) return fail(PDS_ERR_INVALID, "grouped_fused_late_permille: 0 (the default rule) or 1 .. 999");
         ctx->opt_fused_late_permille = (int64_t)value;
-    } else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
+    } else if (n == "grouped_multi_route") {
+        if (value < 0 || value > 2) return fail(PDS_ERR_INVALID, "grouped_multi_route: 0 (choose), 1 (one kernel) or 2 (per target)");
+        ctx->opt_multi_route = (int64_t)value;
+    } else if (n == "grouped_multi_waves") ctx->opt_multi_waves = value > 0 ? (int64_t)value : 0;
+    else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }
 
@@ -525,6 +530,31 @@ int pds_lr_rcond_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_
                             float* singular_values, uint8_t* is_null, int64_t* n_groups) {
     return pds::rcond_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, l2_reg, rcond, max_groups, out_keys, coeffs,
                                          singular_values, is_null, n_groups);
+}
+
+int pds_lr_multi_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_targets, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, double l2_reg, int solver, double singular_x_tol, double* coeffs,
+                             uint8_t* is_null, double* pred, double* resid, uint8_t* row_null) {
+    return pds::multi_grouped_impl<double>(ctx, cols, n_targets, n_feat, n_rows, group_offsets, n_groups, space, add_bias, l2_reg, solver,
+                                           singular_x_tol, coeffs, is_null, pred, resid, row_null);
+}
+int pds_lr_multi_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_targets, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                             int64_t n_groups, pds_space space, int add_bias, float l2_reg, int solver, float singular_x_tol, float* coeffs,
+                             uint8_t* is_null, float* pred, float* resid, uint8_t* row_null) {
+    return pds::multi_grouped_impl<float>(ctx, cols, n_targets, n_feat, n_rows, group_offsets, n_groups, space, add_bias, l2_reg, solver,
+                                          singular_x_tol, coeffs, is_null, pred, resid, row_null);
+}
+int pds_lr_multi_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_targets, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, double l2_reg, int solver, double singular_x_tol, int64_t max_groups, int64_t* out_keys, double* coeffs,
+                            uint8_t* is_null, int64_t* n_groups, double* pred, double* resid, uint8_t* row_null) {
+    return pds::multi_by_key_impl<double>(ctx, cols, keys, n_targets, n_feat, n_rows, space, add_bias, l2_reg, solver, singular_x_tol, max_groups,
+                                          out_keys, coeffs, is_null, n_groups, pred, resid, row_null);
+}
+int pds_lr_multi_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_targets, int n_feat, int64_t n_rows, pds_space space,
+                            int add_bias, float l2_reg, int solver, float singular_x_tol, int64_t max_groups, int64_t* out_keys, float* coeffs,
+                            uint8_t* is_null, int64_t* n_groups, float* pred, float* resid, uint8_t* row_null) {
+    return pds::multi_by_key_impl<float>(ctx, cols, keys, n_targets, n_feat, n_rows, space, add_bias, l2_reg, solver, singular_x_tol, max_groups,
+                                         out_keys, coeffs, is_null, n_groups, pred, resid, row_null);
 }
 
 int pds_lin_reg_report_f64(pds_ctx* ctx, const double* const* cols, const double* weights, int n_feat,

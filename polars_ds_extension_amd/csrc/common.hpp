@@ -136,6 +136,9 @@ struct pds_ctx {
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<float> kind_samples[8];  // the individual bracketed durations (ms), newest kept up to 4096 per class
+    // (behind everything else: the members above keep their places for the translation units that do not know these two)
+    int64_t opt_multi_route = 0;  // "grouped_multi_route": 0 choose, 1 the one-wave-per-group kernel, 2 one fused launch per target
+    int64_t opt_multi_waves = 0;  // "grouped_multi_waves": cap on the grid of the grouped multi-target kernel (0: every wave slot)
 };
 
 namespace pds {
@@ -390,6 +393,27 @@ int launch_grouped_glm_report_wo_pieces(pds_ctx* ctx, const T* const* d_cols, in
 template <typename T>
 int launch_grouped_rcond(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
                          int64_t n_groups, double l2_reg, double rcond, T* d_coeffs, T* d_svals, uint8_t* d_null);
+// ---- grouped_multi.hip: the multi-target fit per group (k targets, one design matrix), one wave per group; 1 .. 16 features, 1 .. 15
+// targets, the gated L D L' only (gate_tol > 0).  d_cols: x_0 .. x_{p-1}, t_0 .. t_{k-1}, padded to 32 valid entries.  d_coeffs
+// [n_groups][k][p'] (bias last), d_flags [n_groups]: 0 fitted, 1 null, 2 next to the gate (mark_suspects only): not answered, its
+// index appended to d_mark_list (any order, *d_mark_count of them; the caller zeroes the count) for the reference's factorisation.
+template <typename T>
+int launch_grouped_multi(pds_ctx* ctx, const T* const* d_cols, int n_feat, int n_targets, int bias, int64_t n_rows, const int64_t* d_off,
+                         int64_t n_groups, double l2_reg, double gate_tol, bool mark_suspects, T* d_coeffs, uint8_t* d_flags,
+                         int32_t* d_mark_list, unsigned* d_mark_count);
+// one target's block d_co [n][p'] / d_fl [n] -> target t of the groups d_list[i] (null: i) of d_coeffs [.][k][p']; the group's flag is
+// set (first) or added to
+template <typename T>
+int launch_multi_scatter(pds_ctx* ctx, const T* d_co, const uint8_t* d_fl, const int32_t* d_list, int64_t n, int t, int k, int pp, bool first,
+                         T* d_coeffs, uint8_t* d_flags);
+// NaN for all k p' coefficients of the flagged groups among d_list[i] (null: i), i < n; check_finite: a group with a coefficient that
+// is not finite is flagged first
+template <typename T>
+int launch_multi_null_fill(pds_ctx* ctx, uint8_t* d_flags, const int32_t* d_list, int64_t n, int kpp, bool check_finite, T* d_coeffs);
+template <typename T>
+int launch_multi_extract(pds_ctx* ctx, const T* d_coeffs, int64_t n_groups, int t, int k, int pp, T* d_out);  // target t -> [n_groups][p']
+// *d_bad = 1 when the offsets decrease or leave the frame (the caller zeroes it)
+int launch_multi_offsets_check(pds_ctx* ctx, const int64_t* d_off, int64_t n_groups, int64_t n_rows, unsigned* d_bad);
 // ---- mixed.hip: the random-intercept mixed model's passes (capi_mixed.hpp).  One record layout for the scatter partials and the
 // per-gamma sums (doubles): [0,256) the 16 x 16 feature block [i * 16 + j]; [256,272) the y column; [272,288) sum c m_f (profile
 // only); 288 the y diagonal; 289 sum c; 290 sum c m_y; 291 sum ln(1 + gamma n_g)

@@ -22,7 +22,7 @@ from . import _lib, config
 __all__ = [
     "Context", "default_context", "lin_reg", "lin_reg_report", "lin_reg_by", "lin_reg_report_by", "lin_reg_report_by_key", "rolling_lin_reg", "rolling_lin_reg_by", "rolling_lin_reg_by_key", "recursive_lin_reg_by",
     "recursive_lin_reg_by_key", "glm_by", "glm_by_key", "glm_report_by", "glm_report_by_key", "logistic_reg", "mixed_reml", "mixed_reml_profile",
-    "recursive_lin_reg", "lin_reg_w_rcond", "lin_reg_w_rcond_by", "lin_reg_w_rcond_by_key", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
+    "recursive_lin_reg", "lin_reg_w_rcond", "lin_reg_w_rcond_by", "lin_reg_w_rcond_by_key", "lin_reg_multi_by", "lin_reg_multi_by_key", "elastic_net_fit", "report_fit_from_moments", "report_partials", "report_finish", "gram_moments", "lin_reg_from_moments", "query_ar_coeffs",
 ]
 
 
@@ -110,7 +110,8 @@ class Context:
 
     def set_option(self, name: str, value) -> None:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
-        "glm_split_rows", "mixed_split_rows", "grouped_fused_waves", "grouped_fused_late_permille"; the
+        "glm_split_rows", "mixed_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
+        "grouped_multi_waves"; the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
 
@@ -479,6 +480,97 @@ def lin_reg_w_rcond_by_key(*x, target, key, add_bias: bool = False, rcond: float
 
     keys, (coeffs, sv, nulls), g = _by_key_retry(cols, max_groups, call)
     return keys, coeffs[:g], sv[:g], nulls[:g]
+
+
+MULTI_BY_LIMIT = "grouped multi-target lin_reg: up to 16 feature columns and 15 targets"
+
+
+def _multi_by_check(x, targets, what):
+    """Before a device is touched: the target list, the feature count, the limits of the grouped multi-target fit."""
+    if not isinstance(targets, (list, tuple)):
+        raise TypeError(f"{what}: `targets` is a list of target columns")
+    if len(targets) == 0:
+        raise ValueError("If `target` is a list, it cannot be empty.")
+    if len(x) < 1:
+        raise ValueError(f"{what}: need at least one feature column")
+    if len(x) > 16 or len(targets) > 15:
+        raise NotImplementedError(MULTI_BY_LIMIT)
+
+
+def _multi_by_args(add_bias, l2_reg, solver, singular_x_tol):
+    if singular_x_tol is None:  # dtype-aware default, expr_linear.py:184-186
+        singular_x_tol = 1e-12 if config.LIN_REG_EXPR_F64 else 1e-6
+    l2, tol = _real_args(l2_reg, singular_x_tol)
+    return int(bool(add_bias)), l2, _lib.SOLVERS.get(solver, 0), tol
+
+
+def _multi_pred_outs(cols, k, return_pred):
+    if not return_pred:
+        none = C.c_void_p(None)
+        return (None, None, None), (none, none, none)
+    pred, pr_p = _out_like(cols, (k, cols.n_rows))
+    resid, rs_p = _out_like(cols, (k, cols.n_rows))
+    rn, rn_p = _out_u8(cols, cols.n_rows)
+    return (pred, resid, rn), (pr_p, rs_p, rn_p)
+
+
+def lin_reg_multi_by(*x, targets, group_offsets, add_bias: bool = False, l2_reg: float = 0.0, solver: str = "qr",
+                     singular_x_tol: float | None = None, return_pred: bool = False, ctx: Context | None = None):
+    """
+    `lin_reg(*x, target=[t_0 .. t_{k-1}])` per group in one call (`pds_lr_multi_grouped_*`): group g = rows [group_offsets[g],
+    group_offsets[g+1]); the k targets share every group's design matrix, so the frame is staged once and a group's X'X is
+    factorised once for all k right-hand sides.  OLS / ridge, 1 .. 16 feature columns, 1 .. 15 targets (beyond:
+    NotImplementedError); torch CUDA tensors or NumPy arrays.
+    Returns (coeffs [G, k, p'] bias last, is_null [G]) in the memory space of the inputs; the gate and the null rule are
+    `lin_reg_by`'s, group for group, and a group is null for every target or for none (a NaN in one target nulls the group).
+    `return_pred=True` adds (pred [k, n], resid [k, n], row_null [n]) in the frame's row order; the rows of a null group are NaN and
+    flagged.  The context option "grouped_multi_route" picks the kernel (0 choose, 1 one kernel, 2 the fused kernel per target).
+    """
+    _multi_by_check(x, targets, "lin_reg_multi_by")
+    ctx = ctx or default_context()
+    k = len(targets)
+    cols = _Cols(targets[0], [*targets[1:], *x])  # C order: [t_0 .. t_{k-1}, x_1 .. x_p]
+    _follow(ctx, cols)
+    p = len(x)
+    bias, l2, sol, tol = _multi_by_args(add_bias, l2_reg, solver, singular_x_tol)
+    off, off_p = _offsets_arg(cols, group_offsets)
+    ng = int(off.shape[0]) - 1
+    coeffs, co_p = _out_like(cols, (ng, k, p + bias))
+    nulls, nu_p = _out_u8(cols, ng)
+    rows, rows_p = _multi_pred_outs(cols, k, return_pred)
+    _lib.check(ctx.fn("pds_lr_multi_grouped")(ctx._h, cols.cols, k, p, C.c_int64(cols.n_rows), off_p, C.c_int64(ng), cols.space, bias, l2, sol,
+                                              tol, co_p, nu_p, *rows_p))
+    return (coeffs, nulls, *rows) if return_pred else (coeffs, nulls)
+
+
+def lin_reg_multi_by_key(*x, targets, key, add_bias: bool = False, l2_reg: float = 0.0, solver: str = "qr",
+                         singular_x_tol: float | None = None, max_groups: int | None = None, return_pred: bool = False,
+                         ctx: Context | None = None):
+    """
+    `lin_reg_multi_by` for an integer key column in ANY row order (`pds_lr_multi_by_key_*`): the keys are ordered once for all k
+    targets (nothing moves when they are already non-decreasing) and every group is fitted.
+    Returns (keys [G] ascending, coeffs [G, k, p'], is_null [G]), with `return_pred=True` followed by (pred [k, n], resid [k, n],
+    row_null [n]) in the frame's own row order.
+    """
+    _multi_by_check(x, targets, "lin_reg_multi_by_key")
+    ctx = ctx or default_context()
+    k = len(targets)
+    cols = _Cols(targets[0], [*targets[1:], *x])
+    _follow(ctx, cols)
+    p = len(x)
+    bias, l2, sol, tol = _multi_by_args(add_bias, l2_reg, solver, singular_x_tol)
+    ky, k_p = _key_arg(cols, key)
+
+    def call(cap, ok_p, ng_p):
+        coeffs, co_p = _out_like(cols, (cap, k, p + bias))
+        nulls, nu_p = _out_u8(cols, cap)
+        rows, rows_p = _multi_pred_outs(cols, k, return_pred)
+        rc = ctx.fn("pds_lr_multi_by_key")(ctx._h, cols.cols, k_p, k, p, C.c_int64(cols.n_rows), cols.space, bias, l2, sol, tol, C.c_int64(cap),
+                                           ok_p, co_p, nu_p, ng_p, *rows_p)
+        return rc, (coeffs, nulls, rows)
+
+    keys, (coeffs, nulls, rows), g = _by_key_retry(cols, max_groups, call)
+    return (keys, coeffs[:g], nulls[:g], *rows) if return_pred else (keys, coeffs[:g], nulls[:g])
 
 
 def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = False, tol: float = 1e-5, max_iter: int = 2000,

@@ -50,9 +50,19 @@ def _dtype():
     return pl.Float64 if cfg.LIN_REG_EXPR_F64 else pl.Float32
 
 
+MULTI_BY_LIMIT = "grouped multi-target lin_reg: up to 16 feature columns and 15 targets"
+
+
 def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool = False, l1_reg: float = 0.0,
             l2_reg: float = 0.0, tol: float = 1e-5, solver: str = "qr", max_iter: int = 200, null_policy: str = "skip",
             positive: bool = False, singular_x_tol: float | None = None, by=None):
+    """
+    expr_linear.py:105-274.  `by` (an integer key column, any row order, nulls = one group): every group's fit from ONE plugin call.
+    With a list `target` of two or more, `by` gives the multi-target fit per group (`pl_lr_multi_by` / `pl_lr_multi_by_pred`: OLS /
+    ridge, 1 .. 16 features, up to 15 targets; `l1_reg`, `positive` and `weights` are not part of the multi-target call, as in the
+    reference): a Struct {<key>, target_0, target_1, ..} of coefficient lists per group, a group being null in every target field or in
+    none; or, with `return_pred`, {target_i_pred, target_i_resid, ..} per input row.
+    """
     if singular_x_tol is None:
         singular_x_tol = 1e-12 if cfg.LIN_REG_EXPR_F64 else 1e-6  # expr_linear.py:179-186
     if isinstance(target, list):  # expr_linear.py:188-233
@@ -61,12 +71,20 @@ def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool 
             raise ValueError("If `target` is a list, it cannot be empty.")
         if n_targets == 1:
             return lin_reg(*x, target=target[0], add_bias=add_bias, weights=weights, return_pred=return_pred, l1_reg=l1_reg,
-                           l2_reg=l2_reg, tol=tol, solver=solver, null_policy=null_policy, singular_x_tol=singular_x_tol)
+                           l2_reg=l2_reg, tol=tol, solver=solver, null_policy=null_policy, singular_x_tol=singular_x_tol, by=by)
         dt = _dtype()
         cols = [_formula(t).alias(f"target_{i}").cast(dt) for i, t in enumerate(target)]
         kwargs = {"bias": add_bias, "null_policy": null_policy, "solver": solver, "last_target_idx": n_targets, "l2_reg": l2_reg,
                   "singular_x_tol": singular_x_tol}
         cols.extend(_formula(z) for z in x)
+        if by is not None:  # one call fits every group and every target: the keys are ordered once, X'X is factorised once per group
+            if len(x) > 16 or n_targets > 15:
+                raise NotImplementedError(MULTI_BY_LIMIT)
+            if return_pred:
+                # Struct{target_i_pred, target_i_resid, ..}, one row per input row in the frame's own order
+                return _plugin("pl_lr_multi_by_pred", [_formula(by), *cols], kwargs).alias("lr_pred")
+            # Struct{key, target_0: List, target_1: List, ..}, one row per group, keys ascending
+            return _plugin("pl_lr_multi_by", [_formula(by), *cols], kwargs, changes_length=True).alias("coeffs_by")
         if return_pred:
             return _plugin("pl_lr_multi_pred", cols, kwargs).alias("lr_pred")
         return _plugin("pl_lr_multi", cols, kwargs, returns_scalar=True).alias("coeffs")
@@ -132,6 +150,9 @@ def lin_reg_by_group(df, by, *x, target, return_pred: bool = False, **kwargs):
     Returns a frame with one row per distinct key: columns *by and `coeffs` (a null list where the reference's per-group call
     returns a null list); integer keys come back ascending, other keys in order of first appearance.
     `return_pred=True` (tests/test_linear_exprs.py:435-474): the input frame with `pred` and `resid` columns, row for row.
+    A list `target` of two or more fits every target on every group in the same one call (`pl_lr_multi_by`): one list column per
+    target (`target_0`, `target_1`, ..) instead of `coeffs`, a null group null in all of them; with `return_pred` the columns
+    `target_i_pred` / `target_i_resid`.
     """
     if return_pred:
         if _is_integer_key(df, by):
