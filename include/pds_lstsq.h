@@ -61,7 +61,16 @@ typedef enum { PDS_NULL_RAISE = 0, PDS_NULL_SKIP = 1, PDS_NULL_FILL = 2, PDS_NUL
 typedef enum { PDS_SOLVER_QR = 0, PDS_SOLVER_SVD = 1, PDS_SOLVER_CHOLESKEY = 2 } pds_solver;
 
 /* StandardError::from(String): linear_regression.rs:113-132 */
-typedef enum { PDS_SE = 0, PDS_HC0 = 1, PDS_HC1 = 2, PDS_HC2 = 3, PDS_HC3 = 4 } pds_se_type;
+typedef enum {
+    PDS_SE = 0,
+    PDS_HC0 = 1,
+    PDS_HC1 = 2,
+    PDS_HC2 = 3,
+    PDS_HC3 = 4,
+    /* cluster-robust, pds_lin_reg_report_cluster_* only (every other entry point answers PDS_ERR_INVALID): */
+    PDS_CLUSTER = 5, /* CR1: G / (G - 1) * (n - 1) / (n - p') */
+    PDS_CLUSTER0 = 6 /* CR0: no small-sample factor */
+} pds_se_type;
 /* OR-ed into the se_type argument of pds_lin_reg_report_* (unweighted form): ignore `y_var` and take the target's sample
  * variance (ddof = 1) from the call's own pass over y (sums kept in f64 for both precisions).  Without the flag `y_var` is
  * used as given -- a NaN (what a null `target.var()` becomes, linear_regression.rs:836) propagates into r2 / adj_r2. */
@@ -89,6 +98,11 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             iteration, one by one (<= 0: the default, 16384; at least 64).
  *   "mixed_split_rows"                        pds_mixed_*: groups of more rows are cut into row chunks that are separate work items
  *                                             (<= 0: the default, 16384; at least 64).
+ *   "cluster_split_rows"                      pds_lin_reg_report_cluster_*: clusters of more rows are cut into row chunks that are separate
+ *                                             work items (<= 0: the default, 16384; at least 64).
+ *   "cluster_waves"                           the same entry points: cap on the number of waves a launch of the cluster pass starts
+ *                                             (<= 0: the default, 12 per compute unit).  Each wave adds up the clusters it walks, so
+ *                                             another cap gives other sums, to rounding; one setting repeats its bits.
  *   "grouped_fused_waves"                     pds_lr_grouped_* / pds_lr_by_key_* up to 16 features: cap on the number of waves the fused
  *                                             kernel starts (<= 0: the default, every wave slot of the device).
  *   "grouped_fused_late_permille"             the same kernel: share of the frame's rows, in 1/1000, dealt to the second half of its
@@ -96,7 +110,7 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
  *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
- * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
+ * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host restatement of how the fused grouped kernel deals groups to its waves (no device needed): wave w of `waves` fits the groups
  * [first_group[w], end_group[w]) -- those whose first row lies in the wave's share of the row range [group_offsets[0],
@@ -265,6 +279,29 @@ int pds_lin_reg_report_f64(pds_ctx* ctx, const double* const* cols, const double
 int pds_lin_reg_report_f32(pds_ctx* ctx, const float* const* cols, const float* weights,
                            int n_feat, int64_t n_rows, pds_space space, int add_bias, int se_type,
                            float y_var, pds_report_f32* out);
+
+/*
+ * pds_lin_reg_report_cluster_*: ONE model over the whole frame with cluster-robust standard errors (Stata's vce(cluster id),
+ * statsmodels' cov_type="cluster", R's vcovCL): V = c inv M inv, M = sum_g s_g s_g', s_g = X_g' e_g the score of cluster g.
+ * se_type: PDS_CLUSTER (CR1, c = G / (G - 1) * (n - 1) / (n - p')) or PDS_CLUSTER0 (CR0, c = 1), optionally | PDS_REPORT_DERIVE_YVAR;
+ * G counts the NON-EMPTY clusters.  t, p and the 95 % interval use the Student t with G - 1 degrees of freedom; beta, r2 and adj_r2
+ * are those of pds_lin_reg_report_*.  The report is two streams over the frame: the moment pass, and one pass that forms residuals,
+ * sum e^2 and the meat together.  f32 frames: moments and solve as in pds_lin_reg_report_f32, the cluster pass in f64 arithmetic.
+ *   grouped: cluster g = rows [cluster_offsets[g], cluster_offsets[g+1]); n_clusters + 1 int64 values, `space`-resident, starting at
+ *            0, ending at n_rows, non-decreasing (else PDS_ERR_INVALID).  Empty clusters contribute nothing and change no output bit.
+ *   by key:  keys = n_rows int64 values in any row order, `space`-resident; rows with equal keys form a cluster (ordered keys move
+ *            nothing; otherwise the stable sort + gather of the other by-key entry points).  *n_clusters receives G.
+ * Two calls give the same bits (no floating-point atomics).  Errors: 1 .. 16 feature columns (more: PDS_ERR_UNSUPPORTED); G < 2 is
+ * PDS_ERR_INVALID, n_rows <= p' PDS_ERR_TOO_FEW_ROWS -- refused, not approximated.  There is no weighted form.
+ */
+int pds_lin_reg_report_cluster_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* cluster_offsets,
+                                           int64_t n_clusters, pds_space space, int add_bias, int se_type, double y_var, pds_report_f64* out);
+int pds_lin_reg_report_cluster_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* cluster_offsets,
+                                           int64_t n_clusters, pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out);
+int pds_lin_reg_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                          pds_space space, int add_bias, int se_type, double y_var, pds_report_f64* out, int64_t* n_clusters);
+int pds_lin_reg_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                          pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out, int64_t* n_clusters);
 
 /*
  * Row-sharded `pl_lin_reg_report` / `pl_wls_report` (one process per GPU): the stages of

@@ -16,6 +16,7 @@ LIB_PATH = _HERE / "csrc" / "libpds_lstsq_hip.so"
 PDS_HOST, PDS_DEVICE = 0, 1
 SOLVERS = {"qr": 0, "svd": 1, "choleskey": 2}  # any other string -> qr (src/linear/lr/mod.rs:17-26)
 SE_TYPES = {"se": 0, "hc0": 1, "hc1": 2, "hc2": 3, "hc3": 4}
+CLUSTER_SE_TYPES = {"cluster": 5, "cluster0": 6}  # PDS_CLUSTER (CR1) / PDS_CLUSTER0 (CR0): pds_lin_reg_report_cluster_* only
 PDS_REPORT_DERIVE_YVAR = 0x100  # include/pds_lstsq.h
 
 EXPORTS = [
@@ -33,6 +34,8 @@ EXPORTS = [
     "pds_lr_f64", "pds_lr_f32", "pds_lr_pred_f64", "pds_lr_pred_f32", "pds_lr_rcond_f64", "pds_lr_rcond_f32", "pds_elastic_net_f64", "pds_elastic_net_f32", "pds_lr_nullable_f64", "pds_lr_nullable_f32", "pds_lr_multi_f64", "pds_lr_multi_f32",
     "pds_lin_reg_report_f64", "pds_lin_reg_report_f32",
     "pds_lin_reg_report_grouped_f64", "pds_lin_reg_report_grouped_f32", "pds_lin_reg_report_by_key_f64", "pds_lin_reg_report_by_key_f32",
+    "pds_lin_reg_report_cluster_grouped_f64", "pds_lin_reg_report_cluster_grouped_f32",
+    "pds_lin_reg_report_cluster_by_key_f64", "pds_lin_reg_report_cluster_by_key_f32",
     "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",

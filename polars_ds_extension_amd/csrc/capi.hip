@@ -34,6 +34,7 @@ namespace pds {
 #include "capi_rcond_grouped.hpp"
 #include "capi_multi_grouped.hpp"
 #include "capi_mixed.hpp"
+#include "capi_report_cluster.hpp"
 
 }  // namespace pds
 
@@ -132,6 +133,8 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     else if (n == "wide_f32_native") ctx->opt_wide_f32_native = value != 0;
     else if (n == "glm_split_rows") ctx->opt_glm_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "mixed_split_rows") ctx->opt_mixed_split_rows = value > 0 ? (int64_t)value : 0;
+    else if (n == "cluster_split_rows") ctx->opt_cluster_split_rows = value > 0 ? (int64_t)value : 0;
+    else if (n == "cluster_waves") ctx->opt_cluster_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_waves") ctx->opt_fused_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_late_permille") {
@@ -565,6 +568,23 @@ int pds_lin_reg_report_f64(pds_ctx* ctx, const double* const* cols, const double
 int pds_lin_reg_report_f32(pds_ctx* ctx, const float* const* cols, const float* weights, int n_feat, int64_t n_rows,
                            pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out) {
     return report_impl<float, pds_report_f32>(ctx, cols, weights, n_feat, n_rows, space, add_bias, se_type, y_var, out);
+}
+
+int pds_lin_reg_report_cluster_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* cluster_offsets,
+                                           int64_t n_clusters, pds_space space, int add_bias, int se_type, double y_var, pds_report_f64* out) {
+    return report_cluster_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, cluster_offsets, n_clusters, space, add_bias, se_type, y_var, out);
+}
+int pds_lin_reg_report_cluster_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* cluster_offsets,
+                                           int64_t n_clusters, pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out) {
+    return report_cluster_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, cluster_offsets, n_clusters, space, add_bias, se_type, y_var, out);
+}
+int pds_lin_reg_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                          pds_space space, int add_bias, int se_type, double y_var, pds_report_f64* out, int64_t* n_clusters) {
+    return report_cluster_by_key_impl<double, pds_report_f64>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, y_var, out, n_clusters);
+}
+int pds_lin_reg_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
+                                          pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out, int64_t* n_clusters) {
+    return report_cluster_by_key_impl<float, pds_report_f32>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, y_var, out, n_clusters);
 }
 
 int pds_report_fit_from_moments_f64(pds_ctx* ctx, const double* moments, int n_feat, int add_bias, double* beta, double* inv) {

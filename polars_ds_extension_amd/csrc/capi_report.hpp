@@ -63,7 +63,10 @@ static int report_second_pass(pds_ctx* ctx, const DeviceCols<T>& dc, int p, int6
 // ---- O(p'^2) host epilogue (linear_regression.rs:861-939): r2 / adj_r2, standard errors, t, p, confidence interval
 template <typename T, typename R>
 static void report_epilogue(int64_t n_rows, int p, int bias, int se_type, bool weighted, T y_var, const T* beta, const T* inv,
-                            const T* meat /*(p+2)^2 moment layout, HC only*/, const double* sums, R* out) {
+                            const T* meat /*(p+2)^2 moment layout, HC only*/, const double* sums, R* out,
+                            // PDS_CLUSTER / PDS_CLUSTER0 (capi_report_cluster.hpp): the cluster meat sum_g s_g s_g', p' x p' row-major, and
+                            // the number of non-empty clusters G
+                            const double* cluster_meat = nullptr, int64_t n_clusters = 0) {
     const int pp = p + bias, q = p + 2;
     const T dof = (T)n_rows - (T)pp;
     const T nf = (T)n_rows;
@@ -75,6 +78,19 @@ static void report_epilogue(int64_t n_rows, int p, int bias, int se_type, bool w
     if (se_type == PDS_SE) {
         const T mse = (weighted ? (T)sums[1] : ssr) / dof;
         for (int i = 0; i < pp; ++i) se[i] = (T)std::sqrt((double)(mse * inv[i + (size_t)i * pp]));
+    } else if (cluster_meat) {  // (only report_cluster_impl passes one; it has checked that se_type is one of the two cluster codes)
+        // V = c inv M inv; CR1: c = G / (G - 1) (n - 1) / (n - p'), CR0: c = 1
+        const double g = (double)n_clusters, nd = (double)n_rows;
+        const double factor = se_type == PDS_CLUSTER ? g / (g - 1.0) * ((nd - 1.0) / (nd - (double)pp)) : 1.0;
+        for (int i = 0; i < pp; ++i) {
+            double acc = 0.0;
+            for (int a = 0; a < pp; ++a) {
+                double t = 0.0;
+                for (int b = 0; b < pp; ++b) t += cluster_meat[(size_t)a * pp + b] * (double)inv[b + (size_t)i * pp];
+                acc += (double)inv[a + (size_t)i * pp] * t;
+            }
+            se[i] = (T)std::sqrt(acc * factor);
+        }
     } else {
         // var_hc_ii = inv_i . meat . inv_i ; meat is the (p+bias) leading block of the weighted moments
         const T factor = (se_type == PDS_HC1) ? nf / (T)(n_rows - pp) : (T)1;
@@ -88,14 +104,16 @@ static void report_epilogue(int64_t n_rows, int p, int bias, int se_type, bool w
             se[i] = (T)std::sqrt((double)((T)acc * factor));
         }
     }
-    const double t_alpha = student_t_ppf(0.975, (double)dof);
+    // t, p and the interval: Student t with n - p' degrees of freedom; clustered: G - 1 (Stata's vce(cluster), statsmodels' use_t)
+    const double t_dof = cluster_meat ? (double)(n_clusters - 1) : (double)dof;
+    const double t_alpha = student_t_ppf(0.975, t_dof);
     for (int i = 0; i < pp; ++i) {
         out->beta[i] = beta[i];
         out->std_err[i] = se[i];
         const T tv = beta[i] / se[i];
         out->t[i] = tv;
         bool err = false;
-        const double sf = student_t_sf(std::fabs((double)tv), (double)dof, &err);
+        const double sf = student_t_sf(std::fabs((double)tv), t_dof, &err);
         out->p[i] = err ? (T)NAN : (T)(2.0 * sf);
         out->ci_lower[i] = (T)((double)beta[i] - t_alpha * (double)se[i]);
         out->ci_upper[i] = (T)((double)beta[i] + t_alpha * (double)se[i]);

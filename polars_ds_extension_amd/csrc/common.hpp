@@ -131,6 +131,8 @@ struct pds_ctx {
     int64_t opt_glm_split_rows = 0;       // "glm_split_rows": groups above this many rows leave the grouped IRLS kernel (0: the default)
     int64_t opt_report_chunk_groups = 0;  // "report_chunk_groups": groups per pass of the grouped report (0: from its record budget)
     int64_t opt_mixed_split_rows = 0;     // "mixed_split_rows": groups above this many rows are cut into row chunks (0: the default)
+    int64_t opt_cluster_split_rows = 0;   // "cluster_split_rows": clusters above this many rows are cut into row chunks (0: the default)
+    int64_t opt_cluster_waves = 0;        // "cluster_waves": cap on the waves a launch of the cluster report's pass starts (0: the default)
     int64_t opt_fused_waves = 0;          // "grouped_fused_waves": cap on the grid of the fused grouped kernel (0: every wave slot)
     int64_t opt_fused_late_permille = 0;  // "grouped_fused_late_permille": rows, in 1/1000, of the grid's second half (0: grouped_split_dev.hpp)
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -440,6 +442,23 @@ int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const i
 // one gamma: sum_g c_g [m m' | m m_y | m], sum c, sum c m_y, sum c m_y^2, sum ln(1 + gamma n_g) -> one record at d_out
 int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const int64_t* d_off, int64_t n_groups, double gamma,
                          double* d_partials, double* d_stage, double* d_out);
+// ---- cluster_meat.hip: the cluster-robust report's pass (capi_report_cluster.hpp).  Records in the layout above: [0,256) the feature
+// block of the meat, [256,272) its bias column, 288 sum e^2 and 290 its compensation term (the sum is their sum), 289 the bias diagonal.
+constexpr int kClusterScoreStride = 18;  // doubles per chunk score: 16 features, the bias entry, one of padding
+// the row chunks of the clusters above the split threshold (device arrays the host filled); n_chunks = 0: none
+struct ClusterChunks {
+    int64_t n_chunks = 0, n_long = 0;
+    const int64_t *d_chunk_r0 = nullptr, *d_chunk_n = nullptr;  // per chunk
+    const int64_t *d_long_c0 = nullptr, *d_long_nc = nullptr;   // per long cluster: first chunk, chunks
+    double* d_scores = nullptr;                                  // n_chunks x kClusterScoreStride
+};
+int cluster_meat_blocks(const pds_ctx* ctx, int64_t n_work);  // partial records a launch over n_work work items writes
+// meat and sum e^2 of e = y - [x, 1] . beta (d_beta: features, then the bias when `bias`) -> one record at d_rec.  d_cols: x_0 ..
+// x_{p-1}, y.  d_partials: room for cluster_meat_blocks(n_clusters) + cluster_meat_blocks(n_chunks) + cluster_meat_blocks(n_long)
+// records, d_stage for a 64th of that (rounded up).
+template <typename T>
+int launch_cluster_meat(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_clusters, int64_t split_rows,
+                        const ClusterChunks& ch, const T* d_beta, int bias, double* d_partials, double* d_stage, double* d_rec);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream

@@ -593,7 +593,8 @@ def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = F
 
 
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", y_var: float | None = None,
-                   feature_names: Sequence[str] | None = None, null_policy: str = "raise", ctx: Context | None = None) -> dict:
+                   feature_names: Sequence[str] | None = None, null_policy: str = "raise", cluster=None, cluster_offsets=None,
+                   ctx: Context | None = None) -> dict:
     """
     pds.lin_reg_report (pl_lin_reg_report / pl_wls_report).  `y_var` is what Polars evaluates as
     `target.var()` (ddof=1) and hands to the plugin as input 0 (expr_linear.py:614-617); when omitted it
@@ -602,7 +603,18 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     pyarrow columns may carry nulls: `null_policy` then applies as in series_to_mat_for_lr (the reference's default for
     this expression is "raise", expr_linear.py:566); `y_var` must be given in that case (Polars computes it on the
     original target).
+
+    `std_err="cluster"` (CR1) / `"cluster0"` (CR0): cluster-robust standard errors of the ONE model over the whole frame (Stata's
+    vce(cluster id), statsmodels' cov_type="cluster").  The clusters are given either as `cluster`, an integer column in any row
+    order, or as `cluster_offsets` (cluster g = rows [cluster_offsets[g], cluster_offsets[g+1]), contiguous) -- exactly one of the
+    two, and neither with any other `std_err`.  The standard-error column is "cluster_se" / "cluster0_se", t / p / interval use
+    G - 1 degrees of freedom, and the result gains "n_clusters" (G, the non-empty clusters).  1 .. 16 features, no weights, NumPy
+    arrays or CUDA tensors (no pyarrow columns).
     """
+    if std_err in _lib.CLUSTER_SE_TYPES:
+        return _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, feature_names, cluster, cluster_offsets, ctx)
+    if cluster is not None or cluster_offsets is not None:
+        raise ValueError('`cluster` / `cluster_offsets` go with std_err="cluster" or "cluster0" only')
     ctx = ctx or default_context()
     arrow = weights is None and any(_is_arrow(c) for c in (target, *x))
     code, fill = parse_null_policy(null_policy)
@@ -655,6 +667,46 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
                                             cols.space, int(bool(add_bias)), se_code, yv,
                                             C.byref(rep)))
     return _report_dict(outs, rep, cols.n_feat, add_bias, std_err, weights is not None, feature_names, dt)
+
+
+def _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, feature_names, cluster, cluster_offsets, ctx):
+    """lin_reg_report(std_err="cluster" | "cluster0"): pds_lin_reg_report_cluster_by_key_* / _grouped_*."""
+    if (cluster is None) == (cluster_offsets is None):
+        raise ValueError(f'std_err="{std_err}": exactly one of `cluster` and `cluster_offsets` must be given')
+    if weights is not None:
+        raise _lib.PdsError(-5, "cluster-robust report: weights are not supported")  # PDS_ERR_UNSUPPORTED
+    if any(_is_arrow(c) for c in (target, *x)) or (cluster is not None and _is_arrow(cluster)):
+        raise NotImplementedError("cluster-robust report: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    se_code = _lib.CLUSTER_SE_TYPES[std_err]
+    if y_var is None:
+        y_var = 0.0
+        se_code |= _lib.PDS_REPORT_DERIVE_YVAR
+    dt = _dtype()
+    outs = {k: np.empty(pp, dtype=dt) for k in ("beta", "std_err", "t", "p", "ci_lower", "ci_upper")}
+    R = _lib.ReportF64 if config.LIN_REG_EXPR_F64 else _lib.ReportF32
+    rep = R(*[C.c_void_p(outs[k].ctypes.data) for k in ("beta", "std_err", "t", "p", "ci_lower", "ci_upper")], 0.0, 0.0)
+    yv = C.c_double(y_var) if config.LIN_REG_EXPR_F64 else C.c_float(y_var)
+    if cluster is not None:
+        k, k_p = _key_arg(cols, cluster)
+        ng = C.c_int64(0)
+        _lib.check(ctx.fn("pds_lin_reg_report_cluster_by_key")(ctx._h, cols.cols, k_p, cols.n_feat, C.c_int64(cols.n_rows), cols.space,
+                                                               int(bool(add_bias)), se_code, yv, C.byref(rep), C.byref(ng)))
+        n_clusters = int(ng.value)
+    else:
+        off, off_p = _offsets_arg(cols, cluster_offsets)
+        if off.ndim != 1 or int(off.shape[0]) < 2:
+            raise ValueError("`cluster_offsets` must be 1-D with at least two entries")
+        _lib.check(ctx.fn("pds_lin_reg_report_cluster_grouped")(ctx._h, cols.cols, cols.n_feat, C.c_int64(cols.n_rows), off_p,
+                                                                C.c_int64(int(off.shape[0]) - 1), cols.space, int(bool(add_bias)), se_code,
+                                                                yv, C.byref(rep)))
+        n_clusters = int((off[1:] > off[:-1]).sum())  # the non-empty ones
+    out = _report_dict(outs, rep, cols.n_feat, add_bias, std_err, False, feature_names, dt)
+    out["n_clusters"] = n_clusters
+    return out
 
 
 # ---- the stages of lin_reg_report as separate calls (row-sharded multi-GPU form: parallel.lin_reg_report_row_sharded)
@@ -716,7 +768,8 @@ def _report_dict(outs, rep, n_feat, add_bias, std_err, weighted, feature_names, 
     names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(n_feat)]
     if add_bias:
         names.append("__bias__")  # linear_regression.rs:843-845
-    se_name = {"se": "std_err", "hc0": "hc0_se", "hc1": "hc1_se", "hc2": "hc2_se", "hc3": "hc3_se"}.get(std_err, "std_err")
+    se_name = {"se": "std_err", "hc0": "hc0_se", "hc1": "hc1_se", "hc2": "hc2_se", "hc3": "hc3_se", "cluster": "cluster_se",
+               "cluster0": "cluster0_se"}.get(std_err, "std_err")
     if weighted:
         se_name = "std_err"
     return {
@@ -742,7 +795,8 @@ def _report_grouped_dict(outs, n_feat, add_bias, std_err, feature_names, g=None)
     names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(n_feat)]
     if add_bias:
         names.append("__bias__")  # linear_regression.rs:843-845
-    se_name = {"se": "std_err", "hc0": "hc0_se", "hc1": "hc1_se", "hc2": "hc2_se", "hc3": "hc3_se"}.get(std_err, "std_err")
+    se_name = {"se": "std_err", "hc0": "hc0_se", "hc1": "hc1_se", "hc2": "hc2_se", "hc3": "hc3_se", "cluster": "cluster_se",
+               "cluster0": "cluster0_se"}.get(std_err, "std_err")
     cut = (lambda a: a[:g]) if g is not None else (lambda a: a)
     return {
         "features": names, "beta": cut(outs["beta"][0]), se_name: cut(outs["std_err"][0]), "t": cut(outs["t"][0]),

@@ -211,18 +211,32 @@ def lin_reg_w_rcond_by_group(df, by, *x, target, **kwargs):
     return _join(keys, res, on=[_GID]).drop(_GID)
 
 
-def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None):
+def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None,
+                   cluster=None):
     """
     expr_linear.py:561-631.  `by` (an integer key column, any row order, nulls = one group): every group's report from ONE
     `pl_lin_reg_report_by` / `pl_wls_report_by` call, in long format -- a Struct {<key>, features, beta, <se>, t, p>|t|, 0.025, 0.975,
     r2, adj_r2} with p' rows per group, groups in ascending key order: after `unnest` what
     `group_by(by).agg(lin_reg_report(...)).explode(...)` gives.  var(y) is each group's own.  A group with fewer rows than
     coefficients keeps its rows with null numeric fields.  Keys of other dtypes or several key columns: `lin_reg_report_by_group`.
+    `std_err="cluster"` (CR1) / `"cluster0"` (CR0) with `cluster` (an integer key column, any row order, the null key its own
+    cluster): ONE model over the whole frame with cluster-robust standard errors from one `pl_lin_reg_report_cluster` call -- the
+    Struct of `pl_lin_reg_report` with the standard-error field named `cluster_se` / `cluster0_se`; t, p and the interval use G - 1
+    degrees of freedom.  `cluster` together with `by` or `weights` is not implemented.
     """
+    if std_err in ("cluster", "cluster0") or cluster is not None:
+        if std_err not in ("cluster", "cluster0"):
+            raise ValueError('`cluster` goes with std_err="cluster" or "cluster0" only')
+        if cluster is None:
+            raise ValueError(f'std_err="{std_err}" needs `cluster`, the key column of the clusters')
+        if by is not None or weights is not None:
+            raise NotImplementedError("lin_reg_report: `cluster` together with `by` or `weights` is not implemented")
     dt = _dtype()
     t = _formula(target).cast(dt)
     kwargs = {"bias": add_bias, "null_policy": null_policy, "std_err": std_err, "solver": "qr", "l1_reg": 0.0, "l2_reg": 0.0, "tol": 0.0}
     feats: List[Any] = [_formula(z) for z in x]
+    if cluster is not None:  # (no t.var() input: the library derives it from the target)
+        return _plugin("pl_lin_reg_report_cluster", [_formula(cluster), t, *feats], kwargs, changes_length=True).alias("lin_reg_report")
     if by is not None:  # (no t.var() input: in front of a keyed call it would be the frame's variance, not the group's)
         if weights is None:
             return _plugin("pl_lin_reg_report_by", [_formula(by), t, *feats], kwargs, changes_length=True).alias("lin_reg_report")
