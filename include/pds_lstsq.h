@@ -100,7 +100,10 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             (<= 0: the default, 16384; at least 64).
  *   "cluster_split_rows"                      pds_lin_reg_report_cluster_*: clusters of more rows are cut into row chunks that are separate
  *                                             work items (<= 0: the default, 16384; at least 64).
- *   "cluster_waves"                           the same entry points: cap on the number of waves a launch of the cluster pass starts
+ *   "within_split_rows"                       pds_lin_reg_within_*: absorbed groups of more rows are cut into row chunks that are separate
+ *                                             work items, in the statistics pass and in the per-row pass alike (<= 0: the default,
+ *                                             16384; at least 64).  Few, very long groups are the common fixed-effects shape.
+ *   "cluster_waves"                           pds_lin_reg_report_cluster_*: cap on the number of waves a launch of the cluster pass starts
  *                                             (<= 0: the default, 12 per compute unit).  Each wave adds up the clusters it walks, so
  *                                             another cap gives other sums, to rounding; one setting repeats its bits.
  *   "grouped_fused_waves"                     pds_lr_grouped_* / pds_lr_by_key_* up to 16 features: cap on the number of waves the fused
@@ -110,7 +113,7 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
  *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
- * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
+ * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, within_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* Host restatement of how the fused grouped kernel deals groups to its waves (no device needed): wave w of `waves` fits the groups
  * [first_group[w], end_group[w]) -- those whose first row lies in the wave's share of the row range [group_offsets[0],
@@ -302,6 +305,60 @@ int pds_lin_reg_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* col
                                           pds_space space, int add_bias, int se_type, double y_var, pds_report_f64* out, int64_t* n_clusters);
 int pds_lin_reg_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
                                           pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out, int64_t* n_clusters);
+
+/*
+ * pds_lin_reg_within_*: fixed-effects regression -- ONE model with an intercept per group, y_i = alpha_g(i) + x_i' beta + e_i, the
+ * within estimator; no dummy column is ever formed.  cols = [y, x1..xp], 1 .. 16 feature columns and NO intercept column (it is
+ * absorbed).  What follows is a DEFINITION of what the library computes; no equivalence with the small-sample conventions of any
+ * package is claimed.  n rows, G non-empty groups, p features, m_g the mean of [x, y] over group g,
+ * W = sum_g sum_{i in g} ([x_i, y_i] - m_g)([x_i, y_i] - m_g)':
+ *   beta solves W_xx beta = W_xy;  alpha_g = m_y,g - m_g' beta;  e_i = y_i - alpha_g - x_i' beta;  pred_i = y_i - e_i.
+ *   se_type PDS_SE:       V = s2 W_xx^-1, s2 = sum e^2 / (n - G - p); t, p and the 95 % interval use the Student t with n - G - p
+ *                         degrees of freedom.
+ *   se_type PDS_CLUSTER0: V = W_xx^-1 M W_xx^-1, M = sum_g s_g s_g', s_g = sum_{i in g} (x_i - m_g) e_i: the clusters are the absorbed
+ *                         groups.
+ *   se_type PDS_CLUSTER:  the same V times c = G / (G - 1) * (n - 1) / (n - p - 1): the absorbed effects, nested in the clusters, are
+ *                         not counted among the parameters, the one intercept is.  Both cluster forms use G - 1 degrees of freedom.
+ *   out->r2 = 1 - sum e^2 / W_yy (the within R^2), out->adj_r2 = 1 - (1 - r2)(n - G) / (n - G - p),
+ *   extra->r2_overall = 1 - sum e^2 / sum (y - ybar)^2.
+ * out->beta .. ci_upper: p host values each.  std_err .. ci_upper may ALL be NULL: the fit-only call (beta, r2, adj_r2; the pass
+ * then forms no scores).  extra (nullable): alpha / pred / resid are `space`-resident arrays of the frame's type, each nullable;
+ * pred and resid come back in the caller's row order.  A singleton group stays in (it counts in n and G and adds nothing to W or M;
+ * its alpha is y - x' beta).
+ *   grouped: group g = rows [group_offsets[g], group_offsets[g+1]); n_groups + 1 int64 values, `space`-resident, starting at 0,
+ *            ending at n_rows, non-decreasing (else PDS_ERR_INVALID).  alpha has n_groups entries.  An empty group counts nowhere and
+ *            changes no output bit; its alpha is NaN.
+ *   by key:  keys = n_rows int64 values in any row order, `space`-resident (ordered keys move nothing and give the bits of the
+ *            grouped form; otherwise the stable sort + gather of the other by-key entry points).  *n_groups receives G.  max_groups
+ *            and out_keys matter only when extra->alpha is given: alpha and out_keys (nullable) then have room for max_groups
+ *            entries, in ascending key order, and more distinct keys are PDS_ERR_INVALID with *n_groups set (nothing fitted).
+ * The call is two streams over the frame: the statistics pass of pds_mixed_* (group means, W, no cancellation) and one pass that forms
+ * alpha, residuals, sum e^2 and the scores together; the p x p solve runs on the host in f64.  f32 frames: f64 arithmetic throughout.
+ * Two calls give the same bits (no floating-point atomics).  Groups above the context option "within_split_rows" are cut into row
+ * chunks.  p-values come from pds_student_t_sf's algorithm with its ln-gamma prefactor evaluated free of cancellation (these entry
+ * points have no counterpart in the reference to stay bit-compatible with; at 1e4 .. 1e5 degrees of freedom the two differ by 1e-10).  Refused, never approximated: n - G - p <= 0 PDS_ERR_TOO_FEW_ROWS; a cluster form with G < 2 PDS_ERR_INVALID; a feature
+ * that is constant inside every group (collinear with the effects) PDS_ERR_NUMERIC, the message naming the column index; W_xx not
+ * positive definite otherwise PDS_ERR_NUMERIC; more than 16 features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.
+ * There is no weighted form.
+ */
+typedef struct {           /* every pointer nullable and `space`-resident */
+    void* alpha;           /* [n_groups] (by key: [max_groups], ascending key order) */
+    void* pred;            /* [n_rows], frame order */
+    void* resid;           /* [n_rows], frame order */
+    double r2_overall;
+    int64_t n_groups_used; /* G */
+    int64_t df_resid;      /* n - G - p ("se") or G - 1 (cluster forms) */
+} pds_within_out;
+int pds_lin_reg_within_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int se_type, pds_report_f64* out, pds_within_out* extra);
+int pds_lin_reg_within_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int se_type, pds_report_f32* out, pds_within_out* extra);
+int pds_lin_reg_within_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                  int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f64* out, pds_within_out* extra,
+                                  int64_t* n_groups);
+int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                  int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f32* out, pds_within_out* extra,
+                                  int64_t* n_groups);
 
 /*
  * Row-sharded `pl_lin_reg_report` / `pl_wls_report` (one process per GPU): the stages of

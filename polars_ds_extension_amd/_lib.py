@@ -16,6 +16,7 @@ LIB_PATH = _HERE / "csrc" / "libpds_lstsq_hip.so"
 PDS_HOST, PDS_DEVICE = 0, 1
 SOLVERS = {"qr": 0, "svd": 1, "choleskey": 2}  # any other string -> qr (src/linear/lr/mod.rs:17-26)
 SE_TYPES = {"se": 0, "hc0": 1, "hc1": 2, "hc2": 3, "hc3": 4}
+WITHIN_SE_TYPES = {"se": 0, "cluster": 5, "cluster0": 6}  # pds_lin_reg_within_*: the clusters are the absorbed groups
 CLUSTER_SE_TYPES = {"cluster": 5, "cluster0": 6}  # PDS_CLUSTER (CR1) / PDS_CLUSTER0 (CR0): pds_lin_reg_report_cluster_* only
 PDS_REPORT_DERIVE_YVAR = 0x100  # include/pds_lstsq.h
 
@@ -36,6 +37,7 @@ EXPORTS = [
     "pds_lin_reg_report_grouped_f64", "pds_lin_reg_report_grouped_f32", "pds_lin_reg_report_by_key_f64", "pds_lin_reg_report_by_key_f32",
     "pds_lin_reg_report_cluster_grouped_f64", "pds_lin_reg_report_cluster_grouped_f32",
     "pds_lin_reg_report_cluster_by_key_f64", "pds_lin_reg_report_cluster_by_key_f32",
+    "pds_lin_reg_within_grouped_f64", "pds_lin_reg_within_grouped_f32", "pds_lin_reg_within_by_key_f64", "pds_lin_reg_within_by_key_f32",
     "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
@@ -95,6 +97,12 @@ class GlmReportOut(C.Structure):
                                           "dispersion", "df_resid", "report_null")]
 
 
+class WithinOut(C.Structure):
+    """pds_within_out: nullable output pointers of the frame's type, one layout for both precisions."""
+    _fields_ = [("alpha", C.c_void_p), ("pred", C.c_void_p), ("resid", C.c_void_p), ("r2_overall", C.c_double),
+                ("n_groups_used", C.c_int64), ("df_resid", C.c_int64)]
+
+
 class PdsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[pds {code}] {msg}")
@@ -151,6 +159,13 @@ def load() -> C.CDLL:
                 # coeffs, is_null, n_groups, pred, resid, row_null
                 getattr(lib, "pds_lr_multi_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int,
                                                                      C.c_int, real, C.c_int, real, C.c_int64] + [C.c_void_p] * 7
+            if hasattr(lib, "pds_lin_reg_within_grouped_" + sfx):
+                # ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, se_type, out, extra
+                getattr(lib, "pds_lin_reg_within_grouped_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+                # ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups
+                getattr(lib, "pds_lin_reg_within_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "pds_ctx_workspace_bytes"):
             lib.pds_ctx_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
             lib.pds_ctx_workspace_bytes.restype = C.c_longlong

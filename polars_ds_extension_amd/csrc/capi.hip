@@ -35,6 +35,7 @@ namespace pds {
 #include "capi_multi_grouped.hpp"
 #include "capi_mixed.hpp"
 #include "capi_report_cluster.hpp"
+#include "capi_within.hpp"
 
 }  // namespace pds
 
@@ -135,6 +136,7 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     else if (n == "mixed_split_rows") ctx->opt_mixed_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "cluster_split_rows") ctx->opt_cluster_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "cluster_waves") ctx->opt_cluster_waves = value > 0 ? (int64_t)value : 0;
+    else if (n == "within_split_rows") ctx->opt_within_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_waves") ctx->opt_fused_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_late_permille") {
@@ -585,6 +587,24 @@ int pds_lin_reg_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* col
 int pds_lin_reg_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows,
                                           pds_space space, int add_bias, int se_type, float y_var, pds_report_f32* out, int64_t* n_clusters) {
     return report_cluster_by_key_impl<float, pds_report_f32>(ctx, cols, keys, n_feat, n_rows, space, add_bias, se_type, y_var, out, n_clusters);
+}
+int pds_lin_reg_within_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int se_type, pds_report_f64* out, pds_within_out* extra) {
+    return within_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, space, se_type, out, extra);
+}
+int pds_lin_reg_within_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                   int64_t n_groups, pds_space space, int se_type, pds_report_f32* out, pds_within_out* extra) {
+    return within_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, space, se_type, out, extra);
+}
+int pds_lin_reg_within_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                  int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f64* out, pds_within_out* extra,
+                                  int64_t* n_groups) {
+    return within_by_key_impl<double, pds_report_f64>(ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups);
+}
+int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                  int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f32* out, pds_within_out* extra,
+                                  int64_t* n_groups) {
+    return within_by_key_impl<float, pds_report_f32>(ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups);
 }
 
 int pds_report_fit_from_moments_f64(pds_ctx* ctx, const double* moments, int n_feat, int add_bias, double* beta, double* inv) {

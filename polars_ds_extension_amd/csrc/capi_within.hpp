@@ -1,0 +1,329 @@
+// capi_within.hpp -- fixed-effects (within) regression with one absorbed factor (pds_lin_reg_within_grouped_* / _by_key_*): ONE model
+// with an intercept per group, y_i = alpha_g(i) + x_i' beta + e_i, fitted without ever forming a dummy column.
+// Part of the one translation unit capi.hip (included there, inside namespace pds, in dependency order): the entry-point
+// pipelines are templates with internal linkage, split by concern, not by compilation unit.
+//
+// DEFINITIONS (what this file computes; no equivalence with any package's small-sample conventions is claimed).  n rows, G non-empty
+// groups, p features, no intercept column (it is absorbed); m_g the mean of [x, y] over group g and
+// W = sum_g sum_{i in g} ([x_i, y_i] - m_g)([x_i, y_i] - m_g)' the within scatter:
+//     beta solves W_xx beta = W_xy;   alpha_g = m_y,g - m_g' beta;   e_i = y_i - alpha_g - x_i' beta;   pred_i = y_i - e_i
+//     PDS_SE        V = s2 W_xx^-1, s2 = sum e^2 / (n - G - p); t, p and the 95 % interval: Student t, n - G - p degrees of freedom
+//     PDS_CLUSTER0  V = W_xx^-1 M W_xx^-1, M = sum_g s_g s_g', s_g = sum_{i in g} (x_i - m_g) e_i: the clusters ARE the absorbed groups
+//     PDS_CLUSTER   the same V times c = G / (G - 1) * (n - 1) / (n - p - 1): the absorbed effects, nested in the clusters, are not
+//                   counted among the parameters, the one intercept is -- a DEFINITION of this library.  Both cluster forms: G - 1
+//                   degrees of freedom
+//     r2 = 1 - sum e^2 / W_yy (the within R^2);   adj_r2 = 1 - (1 - r2)(n - G) / (n - G - p)
+//     r2_overall = 1 - sum e^2 / sum (y - ybar)^2,  sum (y - ybar)^2 = W_yy + sum_g n_g (m_y,g - ybar)^2
+// A singleton group stays in: it counts in n and G and adds nothing to W or M; its alpha is y - x' beta.  An empty group (offsets
+// form) counts nowhere and changes no output bit; its alpha is NaN.
+//
+// Stages: (1) launch_mixed_stats (mixed.hip, untouched, no beta0): W, the group means, the "varies inside some group" bits, in one
+// pass without cancellation, long groups cut into chunks; (2) the p x p Cholesky solve with the inverse on the host in f64 -- beta and
+// nothing else goes back to the device; (3) launch_within_pass (within_pass.hip): alpha, residuals, predictions, sum e^2 formed from
+// the residuals (W_yy - beta' W_xy cancels) and the meat of the centred scores, in ONE more pass over the frame over the same chunks.
+// r2_overall's between-group term is G values: the y means come back to the host beside the record.
+#pragma once
+
+// Absorbed groups above this many rows are cut into row chunks that are separate work items.  Context option "within_split_rows".
+constexpr int64_t kWithinSplitRowsDefault = 16384;
+
+// W_xx = L L' on the host (rec: the statistics record), beta from the two triangular solves, inv = W_xx^-1 (p x p row-major)
+static int within_solve(int p, const double* rec, unsigned vary, double* beta, double* inv) {
+    for (int j = 0; j < p; ++j)
+        if (!((vary >> j) & 1u))
+            return fail(PDS_ERR_NUMERIC, "fixed-effects regression: feature column " + std::to_string(j) +
+                                             " is constant inside every group (collinear with the absorbed effects)");
+    double l[kMaxFeatSmall * kMaxFeatSmall] = {0}, li[kMaxFeatSmall * kMaxFeatSmall] = {0};
+    for (int j = 0; j < p; ++j) {
+        const double ajj = rec[kMixedRecW + j * 16 + j];
+        double d = ajj;
+        for (int k = 0; k < j; ++k) d -= l[j * p + k] * l[j * p + k];
+        if (!(d > kMixedPivotTol * ajj)) return fail(PDS_ERR_NUMERIC, "fixed-effects regression: the within scatter of the features is not positive definite");
+        const double ljj = std::sqrt(d);
+        l[j * p + j] = ljj;
+        for (int i = j + 1; i < p; ++i) {
+            double v = rec[kMixedRecW + i * 16 + j];
+            for (int k = 0; k < j; ++k) v -= l[i * p + k] * l[j * p + k];
+            l[i * p + j] = v / ljj;
+        }
+    }
+    double z[kMaxFeatSmall];
+    for (int i = 0; i < p; ++i) {  // L z = W_xy
+        double v = rec[kMixedRecXY + i];
+        for (int k = 0; k < i; ++k) v -= l[i * p + k] * z[k];
+        z[i] = v / l[i * p + i];
+    }
+    for (int j = p - 1; j >= 0; --j) {  // L' beta = z
+        double v = z[j];
+        for (int k = j + 1; k < p; ++k) v -= l[k * p + j] * beta[k];
+        beta[j] = v / l[j * p + j];
+    }
+    for (int j = 0; j < p; ++j) {  // L^-1, then W_xx^-1 = L^-T L^-1
+        li[j * p + j] = 1.0 / l[j * p + j];
+        for (int i = j + 1; i < p; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= l[i * p + k] * li[k * p + j];
+            li[i * p + j] = v / l[i * p + i];
+        }
+    }
+    for (int i = 0; i < p; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double v = 0.0;
+            for (int k = i; k < p; ++k) v += li[k * p + i] * li[k * p + j];
+            inv[i * p + j] = inv[j * p + i] = v;
+        }
+    return PDS_OK;
+}
+
+static int within_check_se(int se_type) {
+    if (se_type >= PDS_HC0 && se_type <= PDS_HC3)
+        return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: HC0 - HC3 standard errors are not available with absorption");
+    if (se_type != PDS_SE && se_type != PDS_CLUSTER && se_type != PDS_CLUSTER0)
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: se_type is PDS_SE, PDS_CLUSTER or PDS_CLUSTER0");
+    return PDS_OK;
+}
+
+// cols / offsets live in `space`; the outputs of `extra` (and out_keys' caller) in `out_space`.  d_perm (nullable): row r of this
+// frame is row d_perm[r] of the caller's (the by-key form).
+template <typename T, typename R>
+static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
+                       pds_space out_space, int se_type, R* out, pds_within_out* extra, const uint32_t* d_perm = nullptr) {
+    if (!ctx || !cols || !offsets || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = within_check_se(se_type)) return rc;
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
+    if (n_rows <= 0 || n_groups <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    // the fit-only call: no standard errors asked for -> beta, r2, adj_r2 alone, and the pass without the meat
+    const bool want_se = out->std_err || out->t || out->p || out->ci_lower || out->ci_upper;
+    if (want_se && !(out->std_err && out->t && out->p && out->ci_lower && out->ci_upper))
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: std_err .. ci_upper are given together or not at all");
+    const bool meat = want_se && se_type != PDS_SE;
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int p = n_feat, nc = p + 1;
+    // ---- the offsets on the host: validation, the non-empty groups, the chunks of the long ones
+    std::vector<int64_t> off_copy;
+    const int64_t* h_off = nullptr;
+    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
+    const char* bad_off = "absorbed group offsets must be non-decreasing and cover the frame";
+    if (h_off[0] != 0 || h_off[n_groups] != n_rows) return fail(PDS_ERR_INVALID, bad_off);
+    int64_t n_nonempty = 0;
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const int64_t n = h_off[g + 1] - h_off[g];
+        if (n < 0 || h_off[g + 1] > n_rows) return fail(PDS_ERR_INVALID, bad_off);
+        n_nonempty += n > 0;
+    }
+    const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p;
+    if (extra) extra->n_groups_used = n_nonempty;
+    if (se_type != PDS_SE && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
+    if (df_se <= 0) return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #groups - #features <= 0. No conclusive result.");
+    // empty groups are dropped here (equal neighbours of the offsets), so that they cannot change which wave sums what; gmap is the
+    // place of a kept group among the caller's groups (alpha)
+    std::vector<int64_t> compact, gmap;
+    const bool empties = n_nonempty != n_groups;
+    const bool upload_off = space == PDS_HOST || empties;
+    if (empties) {
+        compact.reserve((size_t)n_nonempty + 1);
+        gmap.reserve((size_t)n_nonempty);
+        compact.push_back(h_off[0]);
+        for (int64_t g = 0; g < n_groups; ++g)
+            if (h_off[g + 1] != compact.back()) compact.push_back(h_off[g + 1]), gmap.push_back(g);
+        h_off = compact.data();
+        n_groups = n_nonempty;
+    }
+    const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
+    std::vector<int64_t> hc[4], hl[5];  // chunk: r0, n, group, first row of the group; long group: g, first chunk, chunks, first row, rows
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const int64_t r0 = h_off[g], n = h_off[g + 1] - r0;
+        if (n <= split) continue;
+        const int64_t k = (n + split - 1) / split;
+        hl[0].push_back(g);
+        hl[1].push_back((int64_t)hc[0].size());
+        hl[2].push_back(k);
+        hl[3].push_back(r0);
+        hl[4].push_back(n);
+        for (int64_t i = 0; i < k; ++i) {
+            hc[0].push_back(r0 + i * split);
+            hc[1].push_back(std::min<int64_t>(split, n - i * split));
+            hc[2].push_back(g);
+            hc[3].push_back(r0);
+        }
+    }
+    const int64_t n_chunks = (int64_t)hc[0].size(), n_long = (int64_t)hl[0].size();
+    // ---- workspace (its own block: the by-key form calls this with its ordered frame living in ctx->keyed)
+    const auto up = Bump::up;
+    const bool out_host = out_space == PDS_HOST;
+    T *d_alpha = nullptr, *d_pred = nullptr, *d_resid = nullptr;
+    StagedOuts g_outs(out_host, (size_t)n_all), row_outs(out_host, (size_t)n_rows);
+    if (extra) {
+        g_outs.add(&d_alpha, static_cast<T*>(extra->alpha), 1);
+        row_outs.add(&d_pred, static_cast<T*>(extra->pred), 1);
+        row_outs.add(&d_resid, static_cast<T*>(extra->resid), 1);
+    }
+    const size_t n_stat = (size_t)mixed_stats_blocks(ctx, n_groups) + (n_chunks > 0 ? (size_t)mixed_stats_blocks(ctx, n_chunks) : 0);
+    const size_t n_pass = (size_t)within_pass_blocks(ctx, n_groups) +
+                          (n_chunks > 0 ? (size_t)within_pass_blocks(ctx, n_chunks) + (size_t)within_pass_blocks(ctx, n_long) : 0);
+    const size_t n_rec = std::max(n_stat, n_pass), rec_bytes = (size_t)kMixedRecStride * sizeof(double);
+    size_t need = 8192 + up(sizeof(T*) * 18) + up((size_t)nc * n_groups * 8) + up(n_rec * rec_bytes) + up((n_rec / 64 + 1) * rec_bytes) +
+                  up(rec_bytes) + 512 + 9 * up((size_t)(n_chunks + n_long + 1) * 8) + up((size_t)(n_chunks + 1) * nc * 8) +
+                  up((size_t)(n_chunks + 1) * 4) + up((size_t)(n_chunks + 1) * kClusterScoreStride * 8) + up(kMaxFeatSmall * 8) +
+                  g_outs.bytes() + row_outs.bytes();
+    if (space == PDS_HOST) need += up((size_t)n_rows * sizeof(T)) * nc;
+    if (upload_off) need += up((size_t)(n_groups + 1) * 8);
+    if (empties) need += up((size_t)n_groups * 8);
+    if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
+    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
+    if (space == PDS_HOST)
+        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
+    std::vector<const T*> tbl;
+    const T** d_tbl = nullptr;
+    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+    const int64_t* d_off = offsets;
+    if (upload_off) {
+        int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
+        PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_off = t;
+    }
+    const int64_t* d_gmap = nullptr;
+    if (empties && extra && extra->alpha) {
+        int64_t* t = w.take<int64_t>((size_t)n_groups);
+        PDS_HIP_CHECK(hipMemcpyAsync(t, gmap.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_gmap = t;
+    }
+    double* d_means = w.take<double>((size_t)nc * n_groups);
+    double* d_partials = w.take<double>(n_rec * kMixedRecStride);
+    double* d_stage = w.take<double>((n_rec / 64 + 1) * kMixedRecStride);
+    double* d_rec = w.take<double>(kMixedRecStride);
+    unsigned* d_flags = w.take<unsigned>(64);
+    double* d_beta = w.take<double>(kMaxFeatSmall);
+    MixedChunks ch;
+    ch.n_chunks = n_chunks;
+    ch.n_long = n_long;
+    double* d_scores = nullptr;
+    if (n_chunks > 0) {
+        const int64_t* dcp[4];
+        const int64_t* dlp[5];
+        for (int i = 0; i < 4; ++i) {
+            int64_t* t = w.take<int64_t>((size_t)n_chunks);
+            PDS_HIP_CHECK(hipMemcpyAsync(t, hc[i].data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, ctx->stream));
+            dcp[i] = t;
+        }
+        for (int i = 0; i < 5; ++i) {
+            int64_t* t = w.take<int64_t>((size_t)n_long);
+            PDS_HIP_CHECK(hipMemcpyAsync(t, hl[i].data(), (size_t)n_long * 8, hipMemcpyHostToDevice, ctx->stream));
+            dlp[i] = t;
+        }
+        ch.d_chunk_r0 = dcp[0], ch.d_chunk_n = dcp[1], ch.d_chunk_g = dcp[2], ch.d_chunk_first = dcp[3];
+        ch.d_long_g = dlp[0], ch.d_long_c0 = dlp[1], ch.d_long_nc = dlp[2], ch.d_long_first = dlp[3], ch.d_long_n = dlp[4];
+        ch.d_sums = w.take<double>((size_t)n_chunks * nc);
+        ch.d_varies = w.take<unsigned>((size_t)n_chunks);
+        d_scores = w.take<double>((size_t)n_chunks * kClusterScoreStride);
+    }
+    g_outs.place(w);
+    row_outs.place(w);
+    // ---- stage 1: the statistics
+    if (int rc = launch_mixed_stats<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, nullptr, d_means, d_flags, d_partials, d_stage, d_rec)) return rc;
+    double stat[kMixedRecStride];
+    unsigned vary = 0;
+    const bool want_overall = extra != nullptr;
+    std::vector<double> my;
+    if (want_overall) {
+        my.resize((size_t)n_groups);
+        PDS_HIP_CHECK(hipMemcpyAsync(my.data(), d_means + (size_t)p * n_groups, (size_t)n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PDS_HIP_CHECK(hipMemcpyAsync(stat, d_rec, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, compact, gmap, hc, hl: sources of the copies)
+    // ---- stage 2: the solve
+    double beta[kMaxFeatSmall] = {0}, inv[kMaxFeatSmall * kMaxFeatSmall];
+    if (int rc = within_solve(p, stat, vary, beta, inv)) return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+    // ---- stage 3: the per-row pass
+    if (d_alpha && empties)  // (all bits set is a NaN in both formats: the alpha of an empty group)
+        PDS_HIP_CHECK(hipMemsetAsync(d_alpha, 0xFF, (size_t)n_all * sizeof(T), ctx->stream));
+    if (int rc = launch_within_pass<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, d_scores, d_beta, d_means, meat, d_gmap, d_perm, d_alpha, d_pred,
+                                       d_resid, d_partials, d_stage, d_rec))
+        return rc;
+    double rec[kMixedRecStride];
+    PDS_HIP_CHECK(hipMemcpyAsync(rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = staged_copy_back(ctx, g_outs, (size_t)n_all)) return rc;
+    if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (beta: source of the copy)
+    // ---- the O(p^2) epilogue
+    const double sse = rec[kMixedRecYY] + rec[kMixedRecCY], wyy = stat[kMixedRecYY];
+    const double nd = (double)n_rows, gd = (double)n_nonempty;
+    const double r2 = 1.0 - sse / wyy;
+    out->r2 = (T)r2;
+    out->adj_r2 = (T)(1.0 - (1.0 - r2) * ((nd - gd) / (double)df_se));
+    for (int i = 0; i < p; ++i) out->beta[i] = (T)beta[i];
+    const int64_t df = se_type == PDS_SE ? df_se : n_nonempty - 1;
+    if (extra) {
+        double ybar = 0.0, between = 0.0;
+        for (int64_t g = 0; g < n_groups; ++g) ybar += (double)(h_off[g + 1] - h_off[g]) * my[(size_t)g];
+        ybar /= nd;
+        for (int64_t g = 0; g < n_groups; ++g) {
+            const double d = my[(size_t)g] - ybar;
+            between += (double)(h_off[g + 1] - h_off[g]) * d * d;
+        }
+        extra->r2_overall = 1.0 - sse / (wyy + between);
+        extra->df_resid = df;
+    }
+    if (!want_se) return PDS_OK;
+    double se[kMaxFeatSmall];
+    if (se_type == PDS_SE) {
+        const double s2 = sse / (double)df_se;
+        for (int i = 0; i < p; ++i) se[i] = std::sqrt(s2 * inv[i * p + i]);
+    } else {
+        const double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0)) : 1.0;
+        for (int i = 0; i < p; ++i) {
+            double acc = 0.0;
+            for (int a = 0; a < p; ++a) {
+                double t = 0.0;
+                for (int b = 0; b < p; ++b) t += rec[kMixedRecW + a * 16 + b] * inv[b * p + i];
+                acc += inv[a * p + i] * t;
+            }
+            se[i] = std::sqrt(acc * factor);
+        }
+    }
+    const double t_alpha = student_t_ppf(0.975, (double)df);
+    for (int i = 0; i < p; ++i) {
+        out->std_err[i] = (T)se[i];
+        const double tv = beta[i] / se[i];
+        out->t[i] = (T)tv;
+        bool err = false;
+        const double sf = student_t_sf_wide(std::fabs(tv), (double)df, &err);
+        out->p[i] = err ? (T)NAN : (T)(2.0 * sf);
+        out->ci_lower[i] = (T)(beta[i] - t_alpha * se[i]);
+        out->ci_upper[i] = (T)(beta[i] + t_alpha * se[i]);
+    }
+    return PDS_OK;
+}
+
+// int64 keys in any row order: the shared key-ordering stage (ordered keys move nothing), then the contiguous form on the device frame.
+// max_groups / out_keys matter only when extra->alpha is asked for: alpha and out_keys then have room for max_groups entries.
+template <typename T, typename R>
+static int within_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int se_type,
+                              int64_t max_groups, int64_t* out_keys, R* out, pds_within_out* extra, int64_t* n_groups) {
+    if (!ctx || !cols || !keys || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = within_check_se(se_type)) return rc;
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
+    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    const bool want_alpha = extra && extra->alpha;
+    if (want_alpha && max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat);
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_alpha ? max_groups : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
+        return rc;
+    if (int rc = within_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, space, se_type, out, extra, kf.d_perm)) return rc;
+    if (want_alpha && out_keys) {
+        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                     ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return PDS_OK;
+}

@@ -141,6 +141,7 @@ struct pds_ctx {
     // (behind everything else: the members above keep their places for the translation units that do not know these two)
     int64_t opt_multi_route = 0;  // "grouped_multi_route": 0 choose, 1 the one-wave-per-group kernel, 2 one fused launch per target
     int64_t opt_multi_waves = 0;  // "grouped_multi_waves": cap on the grid of the grouped multi-target kernel (0: every wave slot)
+    int64_t opt_within_split_rows = 0;  // "within_split_rows": absorbed groups above this many rows are cut into row chunks (0: the default)
 };
 
 namespace pds {
@@ -459,6 +460,18 @@ int cluster_meat_blocks(const pds_ctx* ctx, int64_t n_work);  // partial records
 template <typename T>
 int launch_cluster_meat(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_clusters, int64_t split_rows,
                         const ClusterChunks& ch, const T* d_beta, int bias, double* d_partials, double* d_stage, double* d_rec);
+// ---- within_pass.hip: the fixed-effects regression's per-row pass (capi_within.hpp).  With beta (n_feat doubles) and the group means of
+// launch_mixed_stats (d_means, the same d_off / n_groups / split_rows / chunks): alpha_g = m_y - m . beta -> d_alpha[d_gmap ? d_gmap[g] : g],
+// e = (y - m_y) - (x - m) . beta -> d_resid, y - e -> d_pred (row r of the frame is row d_perm[r] of the outputs when d_perm is given),
+// sum e^2 (record slot 288 + its error term in 290) and, with `meat`, sum_g s_g s_g' of the centred scores (record slots [0,256)) ->
+// one record at d_rec.  d_alpha, d_pred, d_resid, d_gmap, d_perm: nullable.  d_scores: n_chunks x kClusterScoreStride doubles
+// (`meat` with chunks).  d_partials: room for within_pass_blocks(n_groups) + within_pass_blocks(n_chunks) + within_pass_blocks(n_long)
+// records, d_stage for a 64th of that (rounded up).
+int within_pass_blocks(const pds_ctx* ctx, int64_t n_work);
+template <typename T>
+int launch_within_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                       const MixedChunks& ch, double* d_scores, const double* d_beta, const double* d_means, bool meat, const int64_t* d_gmap,
+                       const uint32_t* d_perm, T* d_alpha, T* d_pred, T* d_resid, double* d_partials, double* d_stage, double* d_rec);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream
@@ -590,6 +603,7 @@ int launch_scale_sqrt_w(pds_ctx* ctx, const T* d_src /*nullable: ones*/, const T
 
 // ---- stats.cpp ----
 double student_t_sf(double x, double df, bool* err);
+double student_t_sf_wide(double x, double df, bool* err);  // the same tail with a cancellation-free prefactor (capi_within.hpp)
 double student_t_ppf(double q, double df);
 
 }  // namespace pds

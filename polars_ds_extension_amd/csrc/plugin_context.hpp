@@ -97,6 +97,8 @@ template <> struct Api<double> {
     static constexpr auto report_by_key = pds_lin_reg_report_by_key_f64;
     static constexpr auto report_cluster_grouped = pds_lin_reg_report_cluster_grouped_f64;
     static constexpr auto report_cluster_by_key = pds_lin_reg_report_cluster_by_key_f64;
+    static constexpr auto within_grouped = pds_lin_reg_within_grouped_f64;
+    static constexpr auto within_by_key = pds_lin_reg_within_by_key_f64;
     static constexpr auto wls_report_by_key = pds_wls_report_by_key_f64;
     static constexpr auto lr_nullable = pds_lr_nullable_f64;
     static constexpr auto lr = pds_lr_f64;
@@ -125,6 +127,8 @@ template <> struct Api<float> {
     static constexpr auto report_by_key = pds_lin_reg_report_by_key_f32;
     static constexpr auto report_cluster_grouped = pds_lin_reg_report_cluster_grouped_f32;
     static constexpr auto report_cluster_by_key = pds_lin_reg_report_cluster_by_key_f32;
+    static constexpr auto within_grouped = pds_lin_reg_within_grouped_f32;
+    static constexpr auto within_by_key = pds_lin_reg_within_by_key_f32;
     static constexpr auto wls_report_by_key = pds_wls_report_by_key_f32;
     static constexpr auto lr_nullable = pds_lr_nullable_f32;
     static constexpr auto lr = pds_lr_f32;

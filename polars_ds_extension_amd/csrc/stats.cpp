@@ -41,21 +41,30 @@ double ln_gamma(double x) {
     return std::log(s) + LN_2_SQRT_E_OVER_PI + (x - 0.5) * std::log((x - 0.5 + GAMMA_R) / E);
 }
 
-double beta_reg(double a, double b, double x, bool* err) {
+// what student_t_sf_wide knows more exactly than beta_reg can derive from the rounded x
+struct BetaRegExact {
+    double ln_bt;        // ln of the prefactor G(a + b) / (G(a) G(b)) x^a (1 - x)^b
+    double one_minus_x;  // 1 - x, not taken from the rounded x
+};
+
+// ex (nullable): student_t_sf_wide's prefactor and 1 - x; the continued fraction then also runs until it has converged (the
+// reference stops after 140 terms, which are too few from about 1e4 degrees of freedom on)
+double beta_reg(double a, double b, double x, bool* err, const BetaRegExact* ex = nullptr) {
     if (a <= 0.0 || b <= 0.0 || !(x >= 0.0 && x <= 1.0)) {
         if (err) *err = true;
         return NAN;
     }
-    const double bt = (x == 0.0 || x == 1.0)
-                          ? 0.0
-                          : std::exp(ln_gamma(a + b) - ln_gamma(a) - ln_gamma(b) + a * std::log(x) +
-                                     b * std::log(1.0 - x));
+    const double bt = ex ? std::exp(ex->ln_bt)  // (0 at x = 1 exactly; an x that only rounds to 1 keeps its tail)
+                         : (x == 0.0 || x == 1.0) ? 0.0
+                                                  : std::exp(ln_gamma(a + b) - ln_gamma(a) - ln_gamma(b) + a * std::log(x) +
+                                                             b * std::log(1.0 - x));
     const bool symm = x >= (a + 1.0) / (a + b + 2.0);
     const double eps = PREC_ACC;
     const double fpmin = DBL_MIN / eps;
+    const int terms = ex ? 1000001 : 141;
     if (symm) {
         std::swap(a, b);
-        x = 1.0 - x;
+        x = ex ? ex->one_minus_x : 1.0 - x;
     }
     const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
     double c = 1.0;
@@ -63,7 +72,7 @@ double beta_reg(double a, double b, double x, bool* err) {
     if (std::fabs(d) < fpmin) d = fpmin;
     d = 1.0 / d;
     double h = d;
-    for (int mi = 1; mi < 141; ++mi) {
+    for (int mi = 1; mi < terms; ++mi) {
         const double m = (double)mi;
         const double m2 = m * 2.0;
         double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
@@ -201,6 +210,29 @@ double student_t_sf(double x, double df, bool* err) {
     if (std::isinf(df)) return 0.5 * std::erfc(x / 1.41421356237309504880168872420969808);
     const double h = df / (df + x * x);
     const double ib = 0.5 * beta_reg(df / 2.0, 0.5, h, err);
+    return x <= 0.0 ? 1.0 - ib : ib;
+}
+
+// student_t_sf's algorithm with everything it loses at many degrees of freedom put right: the prefactor's lnG(a + 1/2) - lnG(a) -
+// lnG(1/2), a = df / 2, free of cancellation (for a >= 64 its asymptotic series 1/2 ln a - 1/(8a) + 1/(192a^3) - 1/(640a^5) +
+// 17/(14336a^7), whose next term is below 1e-19 there; below that lgamma, whose values are small), a ln x from log1p, 1 - x formed
+// directly, and the continued fraction run to convergence.  Measured against SciPy's t.sf over |t| <= 30 (relative; student_t_sf
+// beside it): 2e-12 (3e-10) at 2e4 degrees of freedom, 9e-12 (8e-10) at 1e5, 7e-11 (4e-9) at 1e6, 5e-10 (2e-7) at 1e7; below 500 both are
+// within 3e-12.  Entry points that have a counterpart in the reference keep student_t_sf; the fixed-effects report (capi_within.hpp)
+// has none.
+double student_t_sf_wide(double x, double df, bool* err) {
+    if (err) *err = false;
+    if (std::isinf(df)) return 0.5 * std::erfc(x / 1.41421356237309504880168872420969808);
+    const double a = df / 2.0;
+    const double ai = 1.0 / a, a2 = ai * ai;
+    const double d = a >= 64.0 ? 0.5 * std::log(a) + ai * (-1.0 / 8.0 + a2 * (1.0 / 192.0 + a2 * (-1.0 / 640.0 + a2 * (17.0 / 14336.0))))
+                               : std::lgamma(a + 0.5) - std::lgamma(a);
+    const double x2 = x * x;
+    const double h = df / (df + x2);
+    BetaRegExact ex;
+    ex.one_minus_x = x2 / (df + x2);
+    ex.ln_bt = d - 0.5 * LN_PI - a * std::log1p(x2 / df) + 0.5 * std::log(ex.one_minus_x);
+    const double ib = 0.5 * beta_reg(a, 0.5, h, err, &ex);
     return x <= 0.0 ? 1.0 - ib : ib;
 }
 

@@ -110,7 +110,7 @@ class Context:
 
     def set_option(self, name: str, value) -> None:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
-        "glm_split_rows", "mixed_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
+        "glm_split_rows", "mixed_split_rows", "cluster_split_rows", "cluster_waves", "within_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
         "grouped_multi_waves"; the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
@@ -296,14 +296,21 @@ def _lin_reg_arrow(x, target, add_bias, return_pred, null_policy, prm, ctx):
 
 def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool = False, l1_reg: float = 0.0,
             l2_reg: float = 0.0, tol: float = 1e-5, solver: str = "qr", max_iter: int = 200, positive: bool = False,
-            singular_x_tol: float | None = None, null_policy: str = "skip", ctx: Context | None = None):
+            singular_x_tol: float | None = None, null_policy: str = "skip", absorb=None, absorb_offsets=None,
+            ctx: Context | None = None):
     """
     pds.lin_reg on null-free column buffers (pl_lr / pl_lr_pred).
 
     Returns the coefficient vector (bias last) or None when the rank gate fires (the reference returns
     a null list).  With return_pred=True returns (pred, resid) -- or None when gated (the reference
     returns an all-null struct).
+
+    `absorb=key` / `absorb_offsets=off`: the fixed-effects fit with one intercept per group (see lin_reg_report); returns beta, or
+    (beta, pred, resid) with return_pred=True.  OLS only: the penalties, `solver` and `positive` do not apply.
     """
+    if absorb is not None or absorb_offsets is not None:
+        rep = _lin_reg_within(x, target, add_bias, weights, None, None, absorb, absorb_offsets, None, False, return_pred, None, ctx, fit_only=True)
+        return (rep["beta"], rep["pred"], rep["resid"]) if return_pred else rep["beta"]
     if isinstance(target, (list, tuple)):  # multi-target: expr_linear.py:188-228
         if len(target) == 0:
             raise ValueError("If `target` is a list, it cannot be empty.")
@@ -594,6 +601,7 @@ def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = F
 
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", y_var: float | None = None,
                    feature_names: Sequence[str] | None = None, null_policy: str = "raise", cluster=None, cluster_offsets=None,
+                   absorb=None, absorb_offsets=None, return_effects: bool = False, return_pred: bool = False,
                    ctx: Context | None = None) -> dict:
     """
     pds.lin_reg_report (pl_lin_reg_report / pl_wls_report).  `y_var` is what Polars evaluates as
@@ -610,7 +618,21 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     two, and neither with any other `std_err`.  The standard-error column is "cluster_se" / "cluster0_se", t / p / interval use
     G - 1 degrees of freedom, and the result gains "n_clusters" (G, the non-empty clusters).  1 .. 16 features, no weights, NumPy
     arrays or CUDA tensors (no pyarrow columns).
+
+    `absorb=key` (an integer column in any row order) or `absorb_offsets=off` (group g = rows [off[g], off[g+1]), contiguous) --
+    exactly one of the two: the fixed-effects regression y_i = alpha_g(i) + x_i' beta + e_i with one intercept per group, the within
+    estimator (pds_lin_reg_within_*; include/pds_lstsq.h states the definitions).  No intercept column: `add_bias=True` is refused.
+    `std_err` is "se" (n - G - p degrees of freedom), "cluster" or "cluster0" -- the clusters ARE the absorbed groups, so `cluster` /
+    `cluster_offsets` are refused.  r2 / adj_r2 are the within values; the dict gains "r2_overall", "n_groups" (G, the non-empty
+    groups) and "df_resid".  return_effects=True adds "effects" (alpha per group; NaN for an empty group of `absorb_offsets`) and
+    "effect_keys" (the distinct keys, ascending; group indices with `absorb_offsets`); return_pred=True adds "pred" and "resid" in the
+    frame's row order.  1 .. 16 features, no weights, NumPy arrays or CUDA tensors.
     """
+    if absorb is not None or absorb_offsets is not None:
+        return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, (cluster, cluster_offsets),
+                               return_effects, return_pred, None, ctx)
+    if return_effects or return_pred:
+        raise ValueError("`return_effects` / `return_pred` go with `absorb` or `absorb_offsets` only")
     if std_err in _lib.CLUSTER_SE_TYPES:
         return _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, feature_names, cluster, cluster_offsets, ctx)
     if cluster is not None or cluster_offsets is not None:
@@ -706,6 +728,78 @@ def _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, featur
         n_clusters = int((off[1:] > off[:-1]).sum())  # the non-empty ones
     out = _report_dict(outs, rep, cols.n_feat, add_bias, std_err, False, feature_names, dt)
     out["n_clusters"] = n_clusters
+    return out
+
+
+def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, clusters, return_effects, return_pred,
+                    max_groups, ctx, fit_only: bool = False):
+    """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*."""
+    if (absorb is None) == (absorb_offsets is None):
+        raise ValueError("exactly one of `absorb` and `absorb_offsets` must be given")
+    if add_bias:
+        raise ValueError("`add_bias=True` together with `absorb`: the intercept is absorbed by the group effects")
+    if clusters is not None and (clusters[0] is not None or clusters[1] is not None):
+        raise ValueError('`cluster` / `cluster_offsets` together with `absorb`: std_err="cluster" means the absorbed key')
+    if not fit_only and std_err not in _lib.WITHIN_SE_TYPES:
+        if std_err in _lib.SE_TYPES:
+            raise _lib.PdsError(-5, "fixed-effects regression: HC0 - HC3 standard errors are not available with absorption")  # PDS_ERR_UNSUPPORTED
+        raise ValueError('`absorb`: std_err is "se", "cluster" or "cluster0"')
+    if weights is not None:
+        raise NotImplementedError("fixed-effects regression: weights are not implemented")
+    if any(_is_arrow(c) for c in (target, *x)) or (absorb is not None and _is_arrow(absorb)):
+        raise NotImplementedError("fixed-effects regression: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
+    ctx = ctx or default_context()
+    cols = _Cols(target, x)
+    _follow(ctx, cols)
+    p, n, dt = cols.n_feat, cols.n_rows, _dtype()
+    keys = ("beta",) if fit_only else _REPORT_KEYS
+    outs = {k: np.empty(p, dtype=dt) for k in keys}
+    R = _lib.ReportF64 if config.LIN_REG_EXPR_F64 else _lib.ReportF32
+    rep = R(*[C.c_void_p(outs[k].ctypes.data) if k in outs else C.c_void_p(None) for k in _REPORT_KEYS], 0.0, 0.0)
+    se_code = _lib.WITHIN_SE_TYPES["se" if fit_only else std_err]
+    pred = resid = None
+    pred_p = resid_p = C.c_void_p(None)
+    if return_pred:
+        pred, pred_p = _out_like(cols, n)
+        resid, resid_p = _out_like(cols, n)
+    if absorb is not None:
+        k, k_p = _key_arg(cols, absorb)
+
+        def call(cap, keys_p, ng_p):
+            alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, C.c_void_p(None))
+            extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
+            rc = ctx.fn("pds_lin_reg_within_by_key")(ctx._h, cols.cols, k_p, p, C.c_int64(n), cols.space, se_code, C.c_int64(cap),
+                                                     keys_p if return_effects else C.c_void_p(None), C.byref(rep), C.byref(extra), ng_p)
+            return rc, (alpha, extra)
+
+        if return_effects:
+            effect_keys, (alpha, extra), g = _by_key_retry(cols, max_groups, call)
+            alpha = alpha[:g]
+        else:
+            ng = C.c_int64(0)
+            rc, (alpha, extra) = call(n, None, C.byref(ng))
+            _lib.check(rc)
+    else:
+        off, off_p = _offsets_arg(cols, absorb_offsets)
+        if off.ndim != 1 or int(off.shape[0]) < 2:
+            raise ValueError("`absorb_offsets` must be 1-D with at least two entries")
+        ng_all = int(off.shape[0]) - 1
+        alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, C.c_void_p(None))
+        extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
+        _lib.check(ctx.fn("pds_lin_reg_within_grouped")(ctx._h, cols.cols, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, se_code,
+                                                        C.byref(rep), C.byref(extra)))
+        effect_keys = np.arange(ng_all, dtype=np.int64)
+    if fit_only:
+        out = {"beta": outs["beta"]}
+    else:
+        out = _report_dict(outs, rep, p, False, std_err, False, feature_names, dt)
+        out["r2_overall"] = float(extra.r2_overall)
+        out["n_groups"] = int(extra.n_groups_used)
+        out["df_resid"] = int(extra.df_resid)
+    if return_effects:
+        out["effects"], out["effect_keys"] = alpha, effect_keys
+    if return_pred:
+        out["pred"], out["resid"] = pred, resid
     return out
 
 

@@ -212,7 +212,7 @@ def lin_reg_w_rcond_by_group(df, by, *x, target, **kwargs):
 
 
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None,
-                   cluster=None):
+                   cluster=None, absorb=None):
     """
     expr_linear.py:561-631.  `by` (an integer key column, any row order, nulls = one group): every group's report from ONE
     `pl_lin_reg_report_by` / `pl_wls_report_by` call, in long format -- a Struct {<key>, features, beta, <se>, t, p>|t|, 0.025, 0.975,
@@ -223,7 +223,24 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     cluster): ONE model over the whole frame with cluster-robust standard errors from one `pl_lin_reg_report_cluster` call -- the
     Struct of `pl_lin_reg_report` with the standard-error field named `cluster_se` / `cluster0_se`; t, p and the interval use G - 1
     degrees of freedom.  `cluster` together with `by` or `weights` is not implemented.
+    `absorb` (an integer key column, any row order, the null key its own group): the fixed-effects regression -- ONE model with an
+    intercept per group, the within estimator -- from one `pl_lin_reg_report_within` call.  The Struct of `pl_lin_reg_report` with p
+    rows (no `__bias__`: `add_bias=True` is refused); `std_err` is "se" (n - G - p degrees of freedom), "cluster" or "cluster0" --
+    the clusters are the absorbed groups, so `cluster` is refused; r2 / adj_r2 are the within values.  `absorb` together with `by`
+    or `weights` is not implemented; the effects and the per-row outputs are `lstsq.lin_reg_report(absorb=, ...)` only.
     """
+    if absorb is not None:
+        if add_bias:
+            raise ValueError("`add_bias=True` together with `absorb`: the intercept is absorbed by the group effects")
+        if cluster is not None:
+            raise ValueError('`cluster` together with `absorb`: std_err="cluster" means the absorbed key')
+        if std_err not in ("se", "cluster", "cluster0"):
+            raise ValueError('`absorb`: std_err is "se", "cluster" or "cluster0"')
+        if by is not None or weights is not None:
+            raise NotImplementedError("lin_reg_report: `absorb` together with `by` or `weights` is not implemented")
+        kwargs = {"bias": False, "null_policy": null_policy, "std_err": std_err, "solver": "qr", "l1_reg": 0.0, "l2_reg": 0.0, "tol": 0.0}
+        return _plugin("pl_lin_reg_report_within", [_formula(absorb), _formula(target).cast(_dtype()), *[_formula(z) for z in x]], kwargs,
+                       changes_length=True).alias("lin_reg_report")
     if std_err in ("cluster", "cluster0") or cluster is not None:
         if std_err not in ("cluster", "cluster0"):
             raise ValueError('`cluster` goes with std_err="cluster" or "cluster0" only')
