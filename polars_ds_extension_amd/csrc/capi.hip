@@ -24,6 +24,7 @@ namespace pds {
 #include "capi_report.hpp"
 #include "capi_staged_out.hpp"
 #include "capi_keyed_frame.hpp"
+#include "capi_group_chunks.hpp"
 #include "capi_grouped.hpp"
 #include "capi_report_grouped.hpp"
 #include "capi_multi.hpp"

@@ -138,45 +138,15 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     const int64_t* h_off = nullptr;
     if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_mixed_split_rows > 0 ? ctx->opt_mixed_split_rows : kMixedSplitRowsDefault, 64);
-    if (h_off[0] < 0 || h_off[n_groups] > n_rows) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
-    int64_t n_obs = 0, n_nonempty = 0;
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int64_t n = h_off[g + 1] - h_off[g];
-        if (n < 0) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
-        n_obs += n;
-        n_nonempty += n > 0;
-    }
-    // empty groups are dropped here (equal neighbours of the offsets), so that they cannot change which wave sums what: the device
-    // works on the non-empty groups alone and gives the bits it gives without them
-    std::vector<int64_t> compact;
-    const bool upload_off = space == PDS_HOST || n_nonempty != n_groups;
-    if (n_nonempty != n_groups) {
-        compact.reserve((size_t)n_nonempty + 1);
-        compact.push_back(h_off[0]);
-        for (int64_t g = 0; g < n_groups; ++g)
-            if (h_off[g + 1] != compact.back()) compact.push_back(h_off[g + 1]);
-        h_off = compact.data();
-        n_groups = n_nonempty;
-    }
+    GroupChunkPlan pl;  // (the device works on the non-empty groups alone)
+    if (int rc = plan_group_chunks(h_off, n_groups, n_rows, split, /*cover=*/false, space == PDS_HOST, /*want_gmap=*/false,
+                                   "group offsets must be non-decreasing and inside the frame", pl))
+        return rc;
+    const int64_t n_obs = pl.n_obs, n_nonempty = pl.n_nonempty, n_chunks = pl.n_chunks(), n_long = pl.n_long();
+    const bool upload_off = pl.upload_off;
+    h_off = pl.h_off;
+    n_groups = n_nonempty;
     if (n_obs <= p + 1) return fail(PDS_ERR_TOO_FEW_ROWS, "Not enough rows to fit a mixed model with this many fixed effects.");
-    std::vector<int64_t> hc[4], hl[5];  // chunk: r0, n, group, first row of the group; long group: g, first chunk, chunks, first row, rows
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int64_t r0 = h_off[g], n = h_off[g + 1] - r0;
-        if (n <= split) continue;
-        const int64_t k = (n + split - 1) / split;
-        hl[0].push_back(g);
-        hl[1].push_back((int64_t)hc[0].size());
-        hl[2].push_back(k);
-        hl[3].push_back(r0);
-        hl[4].push_back(n);
-        for (int64_t i = 0; i < k; ++i) {
-            hc[0].push_back(r0 + i * split);
-            hc[1].push_back(std::min<int64_t>(split, n - i * split));
-            hc[2].push_back(g);
-            hc[3].push_back(r0);
-        }
-    }
-    const int64_t n_chunks = (int64_t)hc[0].size(), n_long = (int64_t)hl[0].size();
     // ---- workspace
     const auto up = Bump::up;
     const int n_part = mixed_stats_blocks(ctx, n_groups) + (n_chunks > 0 ? mixed_stats_blocks(ctx, n_chunks) : 0);
@@ -208,26 +178,7 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     fr.d_rec = w.take<double>(kMixedRecStride);
     unsigned* d_flags = w.take<unsigned>(64);
     MixedChunks ch;
-    ch.n_chunks = n_chunks;
-    ch.n_long = n_long;
-    if (n_chunks > 0) {
-        const int64_t* dc[4];
-        const int64_t* dl[5];
-        for (int i = 0; i < 4; ++i) {
-            int64_t* t = w.take<int64_t>((size_t)n_chunks);
-            PDS_HIP_CHECK(hipMemcpyAsync(t, hc[i].data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, ctx->stream));
-            dc[i] = t;
-        }
-        for (int i = 0; i < 5; ++i) {
-            int64_t* t = w.take<int64_t>((size_t)n_long);
-            PDS_HIP_CHECK(hipMemcpyAsync(t, hl[i].data(), (size_t)n_long * 8, hipMemcpyHostToDevice, ctx->stream));
-            dl[i] = t;
-        }
-        ch.d_chunk_r0 = dc[0], ch.d_chunk_n = dc[1], ch.d_chunk_g = dc[2], ch.d_chunk_first = dc[3];
-        ch.d_long_g = dl[0], ch.d_long_c0 = dl[1], ch.d_long_nc = dl[2], ch.d_long_first = dl[3], ch.d_long_n = dl[4];
-        ch.d_sums = w.take<double>((size_t)n_chunks * nc);
-        ch.d_varies = w.take<unsigned>((size_t)n_chunks);
-    }
+    if (int rc = upload_mixed_chunks(ctx, w, pl, nc, ch)) return rc;
     double* d_beta0 = w.take<double>(kMixedQ);
     fr.p = p;
     fr.n_groups = n_groups;
@@ -243,7 +194,7 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
         unsigned vary = 0;
         PDS_HIP_CHECK(hipMemcpyAsync(rec, fr.d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
         PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, hc, hl, compact, beta0: sources of the copies)
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl, beta0: sources of the copies)
         fr.between = ~vary & ((1u << p) - 1u);
         std::memset(fr.w, 0, sizeof(fr.w));
         auto within = [&](int j) { return ((vary >> j) & 1u) != 0; };

@@ -31,44 +31,21 @@ static int report_cluster_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
     std::vector<int64_t> off_copy;
     const int64_t* h_off = nullptr;
     if (int rc = host_offsets(ctx, offsets, n_clusters, space, off_copy, h_off)) return rc;
-    const char* bad_off = "cluster offsets must be non-decreasing and cover the frame";
-    if (h_off[0] != 0 || h_off[n_clusters] != n_rows) return fail(PDS_ERR_INVALID, bad_off);
-    int64_t n_nonempty = 0;
-    for (int64_t g = 0; g < n_clusters; ++g) {
-        const int64_t n = h_off[g + 1] - h_off[g];
-        if (n < 0 || h_off[g + 1] > n_rows) return fail(PDS_ERR_INVALID, bad_off);
-        n_nonempty += n > 0;
-    }
+    const int64_t split = std::max<int64_t>(ctx->opt_cluster_split_rows > 0 ? ctx->opt_cluster_split_rows : kClusterSplitRowsDefault, 64);
+    GroupChunkPlan pl;
+    if (int rc = plan_group_chunks(h_off, n_clusters, n_rows, split, /*cover=*/true, space == PDS_HOST, /*want_gmap=*/false,
+                                   "cluster offsets must be non-decreasing and cover the frame", pl))
+        return rc;
+    const int64_t n_nonempty = pl.n_nonempty;
     if (n_clusters_used) *n_clusters_used = n_nonempty;
     if (n_nonempty < 2) return fail(PDS_ERR_INVALID, "cluster-robust standard errors need at least two non-empty clusters");
     if (n_rows <= pp) return fail(PDS_ERR_TOO_FEW_ROWS, "#Data <= #features. No conclusive result.");
-    // empty clusters are dropped here (equal neighbours of the offsets), so that they cannot change which wave sums what
-    std::vector<int64_t> compact;
-    const bool upload_off = space == PDS_HOST || n_nonempty != n_clusters;
-    if (n_nonempty != n_clusters) {
-        compact.reserve((size_t)n_nonempty + 1);
-        compact.push_back(h_off[0]);
-        for (int64_t g = 0; g < n_clusters; ++g)
-            if (h_off[g + 1] != compact.back()) compact.push_back(h_off[g + 1]);
-        h_off = compact.data();
-        n_clusters = n_nonempty;
-    }
-    const int64_t split = std::max<int64_t>(ctx->opt_cluster_split_rows > 0 ? ctx->opt_cluster_split_rows : kClusterSplitRowsDefault, 64);
-    std::vector<int64_t> hc[2], hl[2];  // chunk: r0, n; long cluster: first chunk, chunks
-    for (int64_t g = 0; g < n_clusters; ++g) {
-        const int64_t r0 = h_off[g], n = h_off[g + 1] - r0;
-        if (n <= split) continue;
-        const int64_t k = (n + split - 1) / split;
-        hl[0].push_back((int64_t)hc[0].size());
-        hl[1].push_back(k);
-        for (int64_t i = 0; i < k; ++i) {
-            hc[0].push_back(r0 + i * split);
-            hc[1].push_back(std::min<int64_t>(split, n - i * split));
-        }
-    }
+    const bool upload_off = pl.upload_off;  // (the device works on the non-empty clusters alone)
+    h_off = pl.h_off;
+    n_clusters = n_nonempty;
     ClusterChunks ch;
-    ch.n_chunks = (int64_t)hc[0].size();
-    ch.n_long = (int64_t)hl[0].size();
+    ch.n_chunks = pl.n_chunks();
+    ch.n_long = pl.n_long();
     // ---- workspace
     const auto up = Bump::up;
     const size_t n_rec = (size_t)cluster_meat_blocks(ctx, n_clusters) +
@@ -88,9 +65,10 @@ static int report_cluster_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
         d_off = t;
     }
     if (ch.n_chunks > 0) {
+        const std::vector<int64_t>* lists[4] = {&pl.hc[0], &pl.hc[1], &pl.hl[1], &pl.hl[2]};  // (what the cluster kernels read: no more is sent)
         const int64_t* d[4];
         for (int i = 0; i < 4; ++i) {
-            const std::vector<int64_t>& h = i < 2 ? hc[i] : hl[i - 2];
+            const std::vector<int64_t>& h = *lists[i];
             int64_t* t = reinterpret_cast<int64_t*>(ws_take(ctx, h.size() * 8));
             PDS_HIP_CHECK(hipMemcpyAsync(t, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
             d[i] = t;
@@ -119,7 +97,7 @@ static int report_cluster_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
     PDS_HIP_CHECK(hipMemcpyAsync(inv.data(), d_inv, sizeof(T) * pp * pp, hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
     if (derive_var) PDS_HIP_CHECK(hipMemcpyAsync(mom_y, d_ys, sizeof(mom_y), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (dc, compact, hc, hl: sources of the copies)
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (dc, pl: sources of the copies)
     if (derive_var) {
         const double nn = (double)n_rows, sy = mom_y[0], syy = mom_y[1];
         y_var = (T)((syy - sy * sy / nn) / (nn - 1.0));

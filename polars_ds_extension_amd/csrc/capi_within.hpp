@@ -17,7 +17,7 @@
 // A singleton group stays in: it counts in n and G and adds nothing to W or M; its alpha is y - x' beta.  An empty group (offsets
 // form) counts nowhere and changes no output bit; its alpha is NaN.
 //
-// Stages: (1) launch_mixed_stats (mixed.hip, untouched, no beta0): W, the group means, the "varies inside some group" bits, in one
+// Stages: (1) launch_mixed_stats (mixed.hip, no beta0): W, the group means, the "varies inside some group" bits, in one
 // pass without cancellation, long groups cut into chunks; (2) the p x p Cholesky solve with the inverse on the host in f64 -- beta and
 // nothing else goes back to the device; (3) launch_within_pass (within_pass.hip): alpha, residuals, predictions, sum e^2 formed from
 // the residuals (W_yy - beta' W_xy cancels) and the meat of the centred scores, in ONE more pass over the frame over the same chunks.
@@ -105,51 +105,20 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     std::vector<int64_t> off_copy;
     const int64_t* h_off = nullptr;
     if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
-    const char* bad_off = "absorbed group offsets must be non-decreasing and cover the frame";
-    if (h_off[0] != 0 || h_off[n_groups] != n_rows) return fail(PDS_ERR_INVALID, bad_off);
-    int64_t n_nonempty = 0;
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int64_t n = h_off[g + 1] - h_off[g];
-        if (n < 0 || h_off[g + 1] > n_rows) return fail(PDS_ERR_INVALID, bad_off);
-        n_nonempty += n > 0;
-    }
+    const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
+    // gmap is the place of a kept group among the caller's groups (alpha)
+    GroupChunkPlan pl;
+    if (int rc = plan_group_chunks(h_off, n_groups, n_rows, split, /*cover=*/true, space == PDS_HOST, /*want_gmap=*/true,
+                                   "absorbed group offsets must be non-decreasing and cover the frame", pl))
+        return rc;
+    const int64_t n_nonempty = pl.n_nonempty, n_chunks = pl.n_chunks(), n_long = pl.n_long();
     const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p;
     if (extra) extra->n_groups_used = n_nonempty;
     if (se_type != PDS_SE && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     if (df_se <= 0) return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #groups - #features <= 0. No conclusive result.");
-    // empty groups are dropped here (equal neighbours of the offsets), so that they cannot change which wave sums what; gmap is the
-    // place of a kept group among the caller's groups (alpha)
-    std::vector<int64_t> compact, gmap;
-    const bool empties = n_nonempty != n_groups;
-    const bool upload_off = space == PDS_HOST || empties;
-    if (empties) {
-        compact.reserve((size_t)n_nonempty + 1);
-        gmap.reserve((size_t)n_nonempty);
-        compact.push_back(h_off[0]);
-        for (int64_t g = 0; g < n_groups; ++g)
-            if (h_off[g + 1] != compact.back()) compact.push_back(h_off[g + 1]), gmap.push_back(g);
-        h_off = compact.data();
-        n_groups = n_nonempty;
-    }
-    const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
-    std::vector<int64_t> hc[4], hl[5];  // chunk: r0, n, group, first row of the group; long group: g, first chunk, chunks, first row, rows
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int64_t r0 = h_off[g], n = h_off[g + 1] - r0;
-        if (n <= split) continue;
-        const int64_t k = (n + split - 1) / split;
-        hl[0].push_back(g);
-        hl[1].push_back((int64_t)hc[0].size());
-        hl[2].push_back(k);
-        hl[3].push_back(r0);
-        hl[4].push_back(n);
-        for (int64_t i = 0; i < k; ++i) {
-            hc[0].push_back(r0 + i * split);
-            hc[1].push_back(std::min<int64_t>(split, n - i * split));
-            hc[2].push_back(g);
-            hc[3].push_back(r0);
-        }
-    }
-    const int64_t n_chunks = (int64_t)hc[0].size(), n_long = (int64_t)hl[0].size();
+    const bool empties = pl.dropped(), upload_off = pl.upload_off;  // (the device works on the non-empty groups alone)
+    h_off = pl.h_off;
+    n_groups = n_nonempty;
     // ---- workspace (its own block: the by-key form calls this with its ordered frame living in ctx->keyed)
     const auto up = Bump::up;
     const bool out_host = out_space == PDS_HOST;
@@ -188,7 +157,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     const int64_t* d_gmap = nullptr;
     if (empties && extra && extra->alpha) {
         int64_t* t = w.take<int64_t>((size_t)n_groups);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, gmap.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(t, pl.gmap.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
         d_gmap = t;
     }
     double* d_means = w.take<double>((size_t)nc * n_groups);
@@ -198,28 +167,8 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     unsigned* d_flags = w.take<unsigned>(64);
     double* d_beta = w.take<double>(kMaxFeatSmall);
     MixedChunks ch;
-    ch.n_chunks = n_chunks;
-    ch.n_long = n_long;
-    double* d_scores = nullptr;
-    if (n_chunks > 0) {
-        const int64_t* dcp[4];
-        const int64_t* dlp[5];
-        for (int i = 0; i < 4; ++i) {
-            int64_t* t = w.take<int64_t>((size_t)n_chunks);
-            PDS_HIP_CHECK(hipMemcpyAsync(t, hc[i].data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, ctx->stream));
-            dcp[i] = t;
-        }
-        for (int i = 0; i < 5; ++i) {
-            int64_t* t = w.take<int64_t>((size_t)n_long);
-            PDS_HIP_CHECK(hipMemcpyAsync(t, hl[i].data(), (size_t)n_long * 8, hipMemcpyHostToDevice, ctx->stream));
-            dlp[i] = t;
-        }
-        ch.d_chunk_r0 = dcp[0], ch.d_chunk_n = dcp[1], ch.d_chunk_g = dcp[2], ch.d_chunk_first = dcp[3];
-        ch.d_long_g = dlp[0], ch.d_long_c0 = dlp[1], ch.d_long_nc = dlp[2], ch.d_long_first = dlp[3], ch.d_long_n = dlp[4];
-        ch.d_sums = w.take<double>((size_t)n_chunks * nc);
-        ch.d_varies = w.take<unsigned>((size_t)n_chunks);
-        d_scores = w.take<double>((size_t)n_chunks * kClusterScoreStride);
-    }
+    if (int rc = upload_mixed_chunks(ctx, w, pl, nc, ch)) return rc;
+    double* d_scores = n_chunks > 0 ? w.take<double>((size_t)n_chunks * kClusterScoreStride) : nullptr;
     g_outs.place(w);
     row_outs.place(w);
     // ---- stage 1: the statistics
@@ -234,7 +183,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     }
     PDS_HIP_CHECK(hipMemcpyAsync(stat, d_rec, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, compact, gmap, hc, hl: sources of the copies)
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl: sources of the copies)
     // ---- stage 2: the solve
     double beta[kMaxFeatSmall] = {0}, inv[kMaxFeatSmall * kMaxFeatSmall];
     if (int rc = within_solve(p, stat, vary, beta, inv)) return rc;

@@ -2,8 +2,11 @@
 //     M = sum_g s_g s_g',   s_g = X_g' e_g   (p' values per cluster; with a bias its last entry is sum e),
 // and sum e^2, in ONE pass over the frame.
 //
+// The score / meat idiom itself (the compensated sum e^2, the score step, the park and its flush, the record, the long-cluster kernel)
+// is score_meat_dev.hpp's, shared with within_pass.hip; this file instantiates it with a bias entry (HAS_BIAS = true).
+//
 //   * cluster_meat_kernel: ONE wave walks clusters (grid stride) and takes the rows of a cluster 64 per step through a wave-private
-//     LDS tile (feature-major, row stride kCmStride: the wave-tile idiom of wave_tile_dev.hpp).  e_i = y_i - [x_i, 1] . beta is
+//     LDS tile (feature-major, row stride kScoreTileStride: the wave-tile idiom of wave_tile_dev.hpp).  e_i = y_i - [x_i, 1] . beta is
 //     formed per row in registers and written to the tile behind the features.  The score of the cluster comes from one
 //     v_mfma_f64_16x16x4 per four rows with operands (x, [e | 0 ..]) -- the side block of the Gram tile, as W_xy in mixed.hip --
 //     accumulated over the cluster's steps; the bias entry sum e is a per-lane register folded by wave_sum().  e^2 is summed per
@@ -16,52 +19,18 @@
 //     B = [s_bias | 0 ..] gives the bias column, and the bias diagonal is a wave-uniform register.  A short last batch is flushed
 //     with zero scores in the unused slots.  The wave keeps the meat across all the clusters it walks and writes ONE partial record.
 //   * clusters above `split_rows` are cut by the host into row chunks that are separate work items: cluster_chunk_scores_kernel
-//     (a wave per chunk: the chunk's score to memory, its e^2 into the wave's record) and cluster_long_meat_kernel (a cluster's
+//     (a wave per chunk: the chunk's score to memory, its e^2 into the wave's record) and score_long_meat_kernel<true> (a cluster's
 //     chunk scores added in chunk order, lane = entry, then the same parking and outer products).
-//   * records have the layout of mixed.hip's (common.hpp) and are added in index order in two stages by
-//     cluster_sum_records_kernel, the twin of mixed_sum_records_kernel with a compensated running sum per entry: no
-//     floating-point atomics anywhere, so two calls give the same bits.
+//   * records have the layout of mixed.hip's (common.hpp) and are added in index order in two stages by launch_sum_records
+//     (mixed.hip) with a compensated running sum per entry: no floating-point atomics anywhere, so two calls give the same bits.
 // Arithmetic is f64 for f64 and f32 frames alike (an f32 frame and its coefficients are converted on load).
-#include "wave_tile_dev.hpp"
+#include "score_meat_dev.hpp"
 
 #include <algorithm>
 
 namespace pds {
 
 namespace {
-
-constexpr int kCmStride = wave_tile_stride(64);  // doubles per feature row of the tile: 64 rows per step
-constexpr int kCmPark = kClusterScoreStride;     // doubles per parked score: 16 features, the bias entry, one of padding
-constexpr int kCmBatch = 4;                      // scores per outer-product instruction: its K dimension
-
-// the record slots of common.hpp's layout this pass fills: the 16 x 16 feature block, the bias column, sum e^2, the bias diagonal
-constexpr int kCmRecBias = kMixedRecXY, kCmRecEE = kMixedRecYY, kCmRecBB = kMixedRecC, kCmRecEC = kMixedRecCY;
-
-// s + v exactly: the rounded sum in s, its error added to c (Knuth's two-sum: no branch, any magnitudes)
-__device__ __forceinline__ void cm_two_sum(double& s, double& c, double v) {
-    const double t = s + v;
-    const double bb = t - s;
-    c += (s - (t - bb)) + (v - bb);
-    s = t;
-}
-
-// sum e^2 as value + error term
-struct CmSq {
-    double s = 0.0, c = 0.0;
-    __device__ __forceinline__ void add(double e) {
-        const double q = e * e;
-        c += fma(e, e, -q);  // (the product's own rounding error)
-        cm_two_sum(s, c, q);
-    }
-};
-
-// the meat a wave carries across its clusters, and the batch of parked scores in front of it
-struct CmMeat {
-    d4 m = {0.0, 0.0, 0.0, 0.0};   // the 16 x 16 feature block (D layout)
-    d4 mb = {0.0, 0.0, 0.0, 0.0};  // column 0: the bias column
-    double bb = 0.0;               // the bias diagonal (wave-uniform)
-    int parked = 0;                // scores in the park (wave-uniform)
-};
 
 // beta (features, then the bias or 0) as doubles
 template <typename T, int P>
@@ -71,40 +40,10 @@ __device__ __forceinline__ void cm_load_beta(const T* __restrict__ beta, int bia
     b[P] = bias ? (double)beta[P] : 0.0;
 }
 
-// the parked scores -> the meat; slots [parked, kCmBatch) are zeroed first
-__device__ __forceinline__ void cm_flush(double* park, int lane, int bias, CmMeat& mt) {
-    if (mt.parked == 0) return;
-    for (int k = mt.parked; k < kCmBatch; ++k)
-        if (lane < kCmPark) park[k * kCmPark + lane] = 0.0;
-    PDS_WAVE_LDS_SYNC();
-    const int f = lane & 15, kq = lane >> 4;
-    const double sv = park[kq * kCmPark + f];
-    mt.m = __builtin_amdgcn_mfma_f64_16x16x4f64(sv, sv, mt.m, 0, 0, 0);
-    if (bias) {
-        const double bv = f == 0 ? park[kq * kCmPark + 16] : 0.0;
-        mt.mb = __builtin_amdgcn_mfma_f64_16x16x4f64(sv, bv, mt.mb, 0, 0, 0);
-    }
-    PDS_WAVE_LDS_SYNC();  // (the operand reads are done before the next score is parked)
-    mt.parked = 0;
-}
-
-// a finished score in the D layout of the side block (column 0: entry (lane >> 4) + 4 reg in the lanes with lane & 15 == 0) and its
-// bias entry sb (wave-uniform) -> the park; a full park is flushed
-__device__ __forceinline__ void cm_park_d(double* park, int lane, int bias, const d4& sc, double sb, CmMeat& mt) {
-    double* slot = park + mt.parked * kCmPark;
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) slot[(lane >> 4) + 4 * reg] = sc[reg];
-    }
-    if (lane == 0) slot[16] = sb, slot[17] = 0.0;
-    mt.bb = fma(sb, sb, mt.bb);
-    if (++mt.parked == kCmBatch) cm_flush(park, lane, bias, mt);
-}
-
 // rows [r0, r0 + n) of the frame, 64 per step: their residuals' score into sc (side block, column 0), sum e into es, sum e^2 into ee
 template <typename T, int P>
 __device__ __forceinline__ void cm_stream_score(const gptr<T>* cx, gptr<T> cy, int64_t r0, int64_t n, const double* b, double* xt, int lane,
-                                                d4& sc, double& es, CmSq& ee) {
+                                                d4& sc, double& es, CompSq& ee) {
     const int f = lane & 15, kq = lane >> 4;
     for (int64_t base = 0; base < n; base += 64) {
         const int64_t r = base + lane;
@@ -119,44 +58,16 @@ __device__ __forceinline__ void cm_stream_score(const gptr<T>* cx, gptr<T> cy, i
 #pragma unroll
         for (int c = 0; c < P; ++c) {
             const double x = live ? (double)raw[c] : 0.0;
-            xt[c * kCmStride + lane] = x;
+            xt[c * kScoreTileStride + lane] = x;
             e = fma(-x, b[c], e);
         }
-        xt[P * kCmStride + lane] = e;
+        xt[P * kScoreTileStride + lane] = e;
         es += e;
         ee.add(e);
         PDS_WAVE_LDS_SYNC();
         const int rows = (int)std::min<int64_t>(64, n - base);
         const int steps = (rows + 3) >> 2;  // (the row slots past `rows` hold zeros)
-        for (int m = 0; m < steps; ++m) {
-            const int row = 4 * m + kq;
-            const double xv = f < P ? xt[f * kCmStride + row] : 0.0;
-            const double bv = f == 0 ? xt[P * kCmStride + row] : 0.0;
-            sc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, bv, sc, 0, 0, 0);
-        }
-    }
-}
-
-__device__ __forceinline__ void cm_write_record(double* rec, int lane, const CmMeat& mt, CmSq ee) {
-    wave_tile_for_d(
-        lane,
-        [&](int i, int c, double w, double side) {
-            rec[kMixedRecW + i * 16 + c] = w;
-            if (c == 0) rec[kCmRecBias + i] = side;
-        },
-        mt.m, mt.mb);
-    // the butterfly of wave_sum() on (value, error term) pairs; lane 0's order for the record
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double so = __shfl_xor(ee.s, o, 64), co = __shfl_xor(ee.c, o, 64);
-        ee.c += co;
-        cm_two_sum(ee.s, ee.c, so);
-    }
-    const double es = __shfl(ee.s, 0, 64), ec = __shfl(ee.c, 0, 64);
-    // the slots this pass does not use: the record sum reads all of them
-    if (lane < kMixedRecStride - kMixedRecCM) {
-        const int slot = kMixedRecCM + lane;
-        rec[slot] = slot == kCmRecEE ? es : (slot == kCmRecEC ? ec : (slot == kCmRecBB ? mt.bb : 0.0));
+        for (int m = 0; m < steps; ++m) score_rows4<P>(xt, 4 * m + kq, f, sc);
     }
 }
 
@@ -164,8 +75,8 @@ template <typename T, int P>
 __global__ __launch_bounds__(64) void cluster_meat_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ off, int64_t n_clusters,
                                                           int64_t split_rows, const T* __restrict__ beta, int bias,
                                                           double* __restrict__ partials) {
-    __shared__ double xt[(P + 1) * kCmStride + kCmBatch * kCmPark];  // features 0 .. P - 1, then e: [c * kCmStride + row]; the park
-    double* park = xt + (P + 1) * kCmStride;
+    __shared__ double xt[(P + 1) * kScoreTileStride + kScoreBatch * kScorePark];  // features 0 .. P - 1, then e: [c * kScoreTileStride + row]; the park
+    double* park = xt + (P + 1) * kScoreTileStride;
     const int lane = threadIdx.x;
     double b[P + 1];
     cm_load_beta<T, P>(beta, bias, b);
@@ -173,8 +84,9 @@ __global__ __launch_bounds__(64) void cluster_meat_kernel(const T* const* __rest
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    CmMeat mt;
-    CmSq ee;
+    ScoreMeat<true> mt;
+    mt.bias = bias;
+    CompSq ee;
     int64_t g = blockIdx.x;
     int64_t o0 = g < n_clusters ? off[g] : 0, o1 = g < n_clusters ? off[g + 1] : 0;  // (the host has validated the offsets)
     while (g < n_clusters) {
@@ -187,19 +99,19 @@ __global__ __launch_bounds__(64) void cluster_meat_kernel(const T* const* __rest
         double es = 0.0;
         cm_stream_score<T, P>(cx, cy, r0, n, b, xt, lane, sc, es, ee);
         const double sb = bias ? wave_sum(es) : 0.0;
-        cm_park_d(park, lane, bias, sc, sb, mt);
+        mt.park_d(park, lane, sc, sb);
     }
-    cm_flush(park, lane, bias, mt);
-    cm_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, mt, ee);
+    mt.flush(park, lane);
+    mt.write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, ee);
 }
 
-// a wave per chunk (grid stride): the chunk's score -> scores[k * kCmPark + entry]; the wave's record carries its sum e^2 alone
+// a wave per chunk (grid stride): the chunk's score -> scores[k * kScorePark + entry]; the wave's record carries its sum e^2 alone
 template <typename T, int P>
 __global__ __launch_bounds__(64) void cluster_chunk_scores_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ chunk_r0,
                                                                   const int64_t* __restrict__ chunk_n, int64_t n_chunks,
                                                                   const T* __restrict__ beta, int bias, double* __restrict__ scores,
                                                                   double* __restrict__ partials) {
-    __shared__ double xt[(P + 1) * kCmStride];
+    __shared__ double xt[(P + 1) * kScoreTileStride];
     const int lane = threadIdx.x;
     double b[P + 1];
     cm_load_beta<T, P>(beta, bias, b);
@@ -207,67 +119,15 @@ __global__ __launch_bounds__(64) void cluster_chunk_scores_kernel(const T* const
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    CmSq ee;
+    CompSq ee;
     for (int64_t k = blockIdx.x; k < n_chunks; k += gridDim.x) {
         d4 sc = {0.0, 0.0, 0.0, 0.0};
         double es = 0.0;
         cm_stream_score<T, P>(cx, cy, chunk_r0[k], chunk_n[k], b, xt, lane, sc, es, ee);
         const double sb = bias ? wave_sum(es) : 0.0;
-        double* out = scores + k * kCmPark;
-        if ((lane & 15) == 0) {
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) out[(lane >> 4) + 4 * reg] = sc[reg];
-        }
-        if (lane == 0) out[16] = sb, out[17] = 0.0;
+        score_store_d(scores + k * kScorePark, lane, sc, sb);
     }
-    CmMeat none;
-    cm_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, none, ee);
-}
-
-// one wave walks the long clusters (grid stride): chunk scores added in chunk order, lane = entry, then parked like any other score
-__global__ __launch_bounds__(64) void cluster_long_meat_kernel(const int64_t* __restrict__ long_c0, const int64_t* __restrict__ long_nc,
-                                                               int64_t n_long, const double* __restrict__ scores, int bias,
-                                                               double* __restrict__ partials) {
-    __shared__ double park[kCmBatch * kCmPark];
-    const int lane = threadIdx.x;
-    CmMeat mt;
-    for (int64_t j = blockIdx.x; j < n_long; j += gridDim.x) {
-        const int64_t c0 = long_c0[j], nc = long_nc[j];
-        double s = 0.0;
-        if (lane < kCmPark)
-            for (int64_t k = 0; k < nc; ++k) s += scores[(c0 + k) * kCmPark + lane];
-        const double sb = __shfl(s, 16, 64);
-        if (lane < kCmPark) park[mt.parked * kCmPark + lane] = s;
-        mt.bb = fma(sb, sb, mt.bb);
-        if (++mt.parked == kCmBatch) cm_flush(park, lane, bias, mt);
-    }
-    cm_flush(park, lane, bias, mt);
-    cm_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, mt, CmSq{});
-}
-
-// block b: out[b] = in[b per] + in[b per + 1] + ... in index order, entry by entry -- mixed_sum_records_kernel's twin with the
-// running sum's rounding errors collected beside it and added at the end
-__global__ __launch_bounds__(320) void cluster_sum_records_kernel(const double* __restrict__ in, int n_rec, int per, double* __restrict__ out) {
-    const int e = threadIdx.x;
-    if (e >= kMixedRecStride) return;
-    const int r0 = blockIdx.x * per, r1 = std::min(n_rec, r0 + per);
-    double s = 0.0, c = 0.0;
-    for (int r = r0; r < r1; ++r) cm_two_sum(s, c, in[(int64_t)r * kMixedRecStride + e]);
-    out[(int64_t)blockIdx.x * kMixedRecStride + e] = s + c;
-}
-
-// records [0, n_rec) of `d_rec` -> one record at d_out, in index order: blocks of 64 records, then the block sums
-int cluster_sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out) {
-    const int per = 64;
-    const int nb = (n_rec + per - 1) / per;
-    if (nb > 1) {
-        hipLaunchKernelGGL(cluster_sum_records_kernel, dim3(nb), dim3(320), 0, ctx->stream, d_rec, n_rec, per, d_stage);
-        hipLaunchKernelGGL(cluster_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, (const double*)d_stage, nb, nb, d_out);
-    } else {
-        hipLaunchKernelGGL(cluster_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, d_rec, n_rec, n_rec, d_out);
-    }
-    PDS_HIP_CHECK(hipGetLastError());
-    return PDS_OK;
+    ScoreMeat<true>{}.write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, ee);
 }
 
 }  // namespace
@@ -294,12 +154,12 @@ int launch_cluster_meat(pds_ctx* ctx, const T* const* d_cols, int n_feat, const 
         if (nbc > 0) {
             hipLaunchKernelGGL((cluster_chunk_scores_kernel<T, P>), dim3(nbc), dim3(64), 0, ctx->stream, d_cols, ch.d_chunk_r0, ch.d_chunk_n,
                                ch.n_chunks, d_beta, bias, ch.d_scores, d_partials + (int64_t)nb * kMixedRecStride);
-            hipLaunchKernelGGL(cluster_long_meat_kernel, dim3(nbl), dim3(64), 0, ctx->stream, ch.d_long_c0, ch.d_long_nc, ch.n_long,
+            hipLaunchKernelGGL((score_long_meat_kernel<true, int>), dim3(nbl), dim3(64), 0, ctx->stream, ch.d_long_c0, ch.d_long_nc, ch.n_long,
                                (const double*)ch.d_scores, bias, d_partials + (int64_t)(nb + nbc) * kMixedRecStride);
         }
     });
     PDS_HIP_CHECK(hipGetLastError());
-    return cluster_sum_records(ctx, d_partials, nb + nbc + nbl, d_stage, d_rec);
+    return launch_sum_records(ctx, d_partials, nb + nbc + nbl, d_stage, d_rec, /*compensated=*/true);
 }
 
 template int launch_cluster_meat<double>(pds_ctx*, const double* const*, int, const int64_t*, int64_t, int64_t, const ClusterChunks&, const double*,

@@ -422,6 +422,10 @@ int launch_multi_offsets_check(pds_ctx* ctx, const int64_t* d_off, int64_t n_gro
 // only); 288 the y diagonal; 289 sum c; 290 sum c m_y; 291 sum ln(1 + gamma n_g)
 constexpr int kMixedRecW = 0, kMixedRecXY = 256, kMixedRecCM = 272, kMixedRecYY = 288, kMixedRecC = 289, kMixedRecCY = 290, kMixedRecLD = 291;
 constexpr int kMixedRecStride = 296;
+// records [0, n_rec) of d_rec -> one record at d_out, added in index order entry by entry, in two stages (blocks of 64 records into
+// d_stage: room for a 64th of n_rec, rounded up; then the block sums).  compensated: every running sum carries its rounding errors
+// (two-sum) and adds them at the end -- other bits than the plain sum, so a pass keeps the one it was defined with.
+int launch_sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out, bool compensated);
 // the row chunks of the groups above the split threshold (device arrays the host filled); n_chunks = 0: none
 struct MixedChunks {
     int64_t n_chunks = 0, n_long = 0;

@@ -18,16 +18,17 @@
 //   * groups above `split_rows` are cut by the host into row chunks that are separate work items: mixed_chunk_sums_kernel (a wave
 //     per chunk), mixed_chunk_means_kernel (a group's chunk sums added in chunk order) and mixed_chunk_scatter_kernel (centred
 //     products of a chunk with its group's mean; again one partial record per wave).
-//   * mixed_sum_records_kernel adds partial records in index order (two stages); no floating-point atomics anywhere, so two calls
-//     give the same bits.
+//   * sum_records_kernel adds partial records in index order (two stages, launch_sum_records); no floating-point atomics anywhere, so
+//     two calls give the same bits.  It is the one record sum of the library: a plain running sum for this file's passes, a
+//     compensated one (its template flag) for the passes of cluster_meat.hip and within_pass.hip.
 //   * mixed_profile_kernel: for one gamma, 64 groups per step through the same LDS layout: sum_g c_g m m' (matrix instruction,
 //     operands (c m, m)), sum_g c_g m m_y and sum_g c_g m (second instruction), and sum c, sum c m_y, sum c m_y^2,
-//     sum ln(1 + gamma n_g) from per-lane registers; records summed by mixed_sum_records_kernel.  Empty groups contribute nothing.
+//     sum ln(1 + gamma n_g) from per-lane registers; records summed by sum_records_kernel.  Empty groups contribute nothing.
 //   * every frame kernel takes an optional coefficient vector beta0 (intercept first): the target column is then read as
 //     y - [1, x] . beta0, formed per row in registers.  The host runs the passes twice (capi_mixed.hpp): on y itself, then on the
 //     residual of a first GLS solution, so that r' H^-1 r comes out of sums of its own size instead of a difference of large ones.
 // Arithmetic is f64 for f64 and f32 frames alike (an f32 frame is converted on load).
-#include "wave_tile_dev.hpp"
+#include "score_meat_dev.hpp"  // (two_sum, for the compensated record sum; it includes wave_tile_dev.hpp)
 
 #include <algorithm>
 
@@ -274,14 +275,21 @@ __global__ __launch_bounds__(64) void mixed_chunk_scatter_kernel(const T* const*
     mx_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, acc, acc2, yy);
 }
 
-// block b: out[b] = in[b per] + in[b per + 1] + ... in index order, element by element
-__global__ __launch_bounds__(320) void mixed_sum_records_kernel(const double* __restrict__ in, int n_rec, int per, double* __restrict__ out) {
+// block b: out[b] = in[b per] + in[b per + 1] + ... in index order, entry by entry.  COMPENSATED: the running sum's rounding errors
+// are collected beside it (two_sum) and added at the end; without it a plain running sum.  The two give different bits: each caller
+// keeps the one its results were defined with.
+template <bool COMPENSATED>
+__global__ __launch_bounds__(320) void sum_records_kernel(const double* __restrict__ in, int n_rec, int per, double* __restrict__ out) {
     const int e = threadIdx.x;
     if (e >= kMixedRecStride) return;
     const int r0 = blockIdx.x * per, r1 = std::min(n_rec, r0 + per);
-    double s = 0.0;
-    for (int r = r0; r < r1; ++r) s += in[(int64_t)r * kMixedRecStride + e];
-    out[(int64_t)blockIdx.x * kMixedRecStride + e] = s;
+    double s = 0.0, c = 0.0;
+    for (int r = r0; r < r1; ++r) {
+        const double v = in[(int64_t)r * kMixedRecStride + e];
+        if constexpr (COMPENSATED) two_sum(s, c, v);
+        else s += v;
+    }
+    out[(int64_t)blockIdx.x * kMixedRecStride + e] = COMPENSATED ? s + c : s;
 }
 
 template <int P>
@@ -339,21 +347,22 @@ __global__ __launch_bounds__(64) void mixed_profile_kernel(const double* __restr
     if (lane > kMixedRecLD - kMixedRecYY && lane < kMixedRecStride - kMixedRecYY) rec[kMixedRecYY + lane] = 0.0;  // (padding)
 }
 
+}  // namespace
+
 // records [0, n_rec) of `d_rec` -> one record at d_out, in index order: blocks of `per` records, then the block sums
-int sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out) {
+int launch_sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out, bool compensated) {
     const int per = 64;
     const int nb = (n_rec + per - 1) / per;
+    const auto kernel = compensated ? sum_records_kernel<true> : sum_records_kernel<false>;
     if (nb > 1) {
-        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(nb), dim3(320), 0, ctx->stream, d_rec, n_rec, per, d_stage);
-        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, (const double*)d_stage, nb, nb, d_out);
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(320), 0, ctx->stream, d_rec, n_rec, per, d_stage);
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(320), 0, ctx->stream, (const double*)d_stage, nb, nb, d_out);
     } else {
-        hipLaunchKernelGGL(mixed_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, d_rec, n_rec, n_rec, d_out);
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(320), 0, ctx->stream, d_rec, n_rec, n_rec, d_out);
     }
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
-
-}  // namespace
 
 int mixed_stats_blocks(const pds_ctx* ctx, int64_t n_work) { return (int)std::max<int64_t>(1, std::min<int64_t>(n_work, (int64_t)ctx->num_cus * 8)); }
 int mixed_profile_blocks(const pds_ctx* ctx, int64_t n_groups) {
@@ -385,7 +394,7 @@ int launch_mixed_stats(pds_ctx* ctx, const T* const* d_cols, int n_feat, const i
         }
     });
     PDS_HIP_CHECK(hipGetLastError());
-    return sum_records(ctx, d_partials, nb + nbc, d_stage, d_w);
+    return launch_sum_records(ctx, d_partials, nb + nbc, d_stage, d_w, /*compensated=*/false);
 }
 
 int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const int64_t* d_off, int64_t n_groups, double gamma,
@@ -398,7 +407,7 @@ int launch_mixed_profile(pds_ctx* ctx, const double* d_means, int n_feat, const 
                            d_partials);
     });
     PDS_HIP_CHECK(hipGetLastError());
-    return sum_records(ctx, d_partials, nb, d_stage, d_out);
+    return launch_sum_records(ctx, d_partials, nb, d_stage, d_out, /*compensated=*/false);
 }
 
 template int launch_mixed_stats<double>(pds_ctx*, const double* const*, int, const int64_t*, int64_t, int64_t, const MixedChunks&, const double*,

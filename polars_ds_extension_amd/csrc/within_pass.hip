@@ -3,8 +3,9 @@
 // per-row quantity of y_i = alpha_g(i) + x_i' beta + e_i:
 //     alpha_g = m_y,g - m_g' beta,   e_i = (y_i - m_y,g) - (x_i - m_g)' beta  (= y_i - alpha_g - x_i' beta),   pred_i = y_i - e_i,
 //     sum e^2,   and, for errors clustered on the absorbed key, the meat M = sum_g s_g s_g',  s_g = sum_{i in g} (x_i - m_g) e_i.
-// It is cluster_meat.hip's pass with the rows centred on the way in; the helpers below that carry a cluster_meat.hip name in their
-// comment are that file's, restated here because they are private to its translation unit.
+// It is cluster_meat.hip's pass with the rows centred on the way in: the score / meat idiom (the compensated sum e^2, the score step,
+// the park and its flush, the record, the long-group kernel) is score_meat_dev.hpp's, instantiated here without a bias entry
+// (HAS_BIAS = false).
 //
 //   * within_pass_kernel<T, P, MEAT>: ONE wave walks groups (grid stride) and takes the rows of a group 64 per step.  The step's
 //     loads (P features, y, the row's place in the caller's frame when the frame was reordered) are issued back to back on a clamped
@@ -19,74 +20,19 @@
 //     accumulators and no park.
 //   * groups above `split_rows` are the chunks the statistics pass was given (MixedChunks): m_g and beta are known, so chunks are
 //     independent work items.  within_chunk_kernel (a wave per chunk: the rows' outputs, the chunk's sum e^2 into the wave's record,
-//     its score to memory; the group's first chunk writes alpha_g) and within_long_meat_kernel (a group's chunk scores added in chunk
-//     order, lane = entry, then parked and multiplied like any other score).
+//     its score to memory; the group's first chunk writes alpha_g) and score_long_meat_kernel<false> (a group's chunk scores added in
+//     chunk order, lane = entry, then parked and multiplied like any other score).
 //   * every wave writes ONE record in the layout of common.hpp (kMixedRecStride): [0,256) the meat, 288 sum e^2 and 290 its error
-//     term.  Records are added in index order with a compensated running sum per entry (within_sum_records_kernel): no
+//     term.  Records are added in index order with a compensated running sum per entry (launch_sum_records, mixed.hip): no
 //     floating-point atomics anywhere, so two calls give the same bits.
 // Arithmetic is f64 for f64 and f32 frames alike (an f32 frame is converted on load; beta and the means are f64).
-#include "wave_tile_dev.hpp"
+#include "score_meat_dev.hpp"
 
 #include <algorithm>
 
 namespace pds {
 
 namespace {
-
-constexpr int kWpStride = wave_tile_stride(64);  // doubles per feature row of the tile: 64 rows per step
-constexpr int kWpPark = kClusterScoreStride;     // doubles per parked score (cluster_meat.hip's chunk-score layout; entries 16, 17 are zero)
-constexpr int kWpBatch = 4;                      // scores per outer-product instruction: its K dimension
-
-constexpr int kWpRecEE = kMixedRecYY, kWpRecEC = kMixedRecCY;  // sum e^2 and its error term
-
-// s + v exactly: the rounded sum in s, its error added to c (cluster_meat.hip: cm_two_sum)
-__device__ __forceinline__ void wp_two_sum(double& s, double& c, double v) {
-    const double t = s + v;
-    const double bb = t - s;
-    c += (s - (t - bb)) + (v - bb);
-    s = t;
-}
-
-// sum e^2 as value + error term (cluster_meat.hip: CmSq)
-struct WpSq {
-    double s = 0.0, c = 0.0;
-    __device__ __forceinline__ void add(double e) {
-        const double q = e * e;
-        c += fma(e, e, -q);
-        wp_two_sum(s, c, q);
-    }
-};
-
-// the meat a wave carries across its groups, and the number of parked scores in front of it
-struct WpMeat {
-    d4 m = {0.0, 0.0, 0.0, 0.0};  // the 16 x 16 feature block (D layout)
-    int parked = 0;               // wave-uniform
-};
-
-// the parked scores -> the meat; slots [parked, kWpBatch) are zeroed first
-__device__ __forceinline__ void wp_flush(double* park, int lane, WpMeat& mt) {
-    if (mt.parked == 0) return;
-    for (int k = mt.parked; k < kWpBatch; ++k)
-        if (lane < kWpPark) park[k * kWpPark + lane] = 0.0;
-    PDS_WAVE_LDS_SYNC();
-    const int f = lane & 15, kq = lane >> 4;
-    const double sv = park[kq * kWpPark + f];
-    mt.m = __builtin_amdgcn_mfma_f64_16x16x4f64(sv, sv, mt.m, 0, 0, 0);
-    PDS_WAVE_LDS_SYNC();  // (the operand reads are done before the next score is parked)
-    mt.parked = 0;
-}
-
-// a finished score in the D layout of the side block (column 0: entry (lane >> 4) + 4 reg in the lanes with lane & 15 == 0) -> the
-// park; a full park is flushed
-__device__ __forceinline__ void wp_park_d(double* park, int lane, const d4& sc, WpMeat& mt) {
-    double* slot = park + mt.parked * kWpPark;
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) slot[(lane >> 4) + 4 * reg] = sc[reg];
-    }
-    if (lane == 0) slot[16] = 0.0, slot[17] = 0.0;
-    if (++mt.parked == kWpBatch) wp_flush(park, lane, mt);
-}
 
 // where the rows' outputs go: each nullable; perm (nullable): row r of the frame the kernels read is row perm[r] of the caller's
 template <typename T>
@@ -100,7 +46,7 @@ struct WpRowOut {
 // the score of these rows into sc (side block, column 0)
 template <typename T, int P, bool MEAT>
 __device__ __forceinline__ void wp_stream(const gptr<T>* cx, gptr<T> cy, int64_t r0, int64_t n, const double* m, const double* b,
-                                          const WpRowOut<T>& ro, double* xt, int lane, d4& sc, WpSq& ee) {
+                                          const WpRowOut<T>& ro, double* xt, int lane, d4& sc, CompSq& ee) {
     const int f = lane & 15, kq = lane >> 4;
     const bool rows_out = ro.pred || ro.resid;
     for (int64_t base = 0; base < n; base += 64) {
@@ -118,10 +64,10 @@ __device__ __forceinline__ void wp_stream(const gptr<T>* cx, gptr<T> cy, int64_t
 #pragma unroll
         for (int c = 0; c < P; ++c) {
             const double x = live ? (double)raw[c] - m[c] : 0.0;
-            if constexpr (MEAT) xt[c * kWpStride + lane] = x;
+            if constexpr (MEAT) xt[c * kScoreTileStride + lane] = x;
             e = fma(-x, b[c], e);
         }
-        if constexpr (MEAT) xt[P * kWpStride + lane] = e;
+        if constexpr (MEAT) xt[P * kScoreTileStride + lane] = e;
         ee.add(e);
         if (live) {
             if (ro.resid) ro.resid[ro_i] = (T)e;
@@ -131,12 +77,7 @@ __device__ __forceinline__ void wp_stream(const gptr<T>* cx, gptr<T> cy, int64_t
             PDS_WAVE_LDS_SYNC();
             const int rows = (int)std::min<int64_t>(64, n - base);
             const int steps = (rows + 3) >> 2;  // (the row slots past `rows` hold zeros)
-            for (int k = 0; k < steps; ++k) {
-                const int row = 4 * k + kq;
-                const double xv = f < P ? xt[f * kWpStride + row] : 0.0;
-                const double bv = f == 0 ? xt[P * kWpStride + row] : 0.0;
-                sc = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, bv, sc, 0, 0, 0);
-            }
+            for (int k = 0; k < steps; ++k) score_rows4<P>(xt, 4 * k + kq, f, sc);
         }
     }
 }
@@ -152,31 +93,14 @@ __device__ __forceinline__ double wp_group_means(const double* __restrict__ mean
     return a;
 }
 
-__device__ __forceinline__ void wp_write_record(double* rec, int lane, const WpMeat& mt, WpSq ee) {
-    wave_tile_for_d(lane, [&](int i, int c, double w) { rec[kMixedRecW + i * 16 + c] = w; }, mt.m);
-    // the butterfly of wave_sum() on (value, error term) pairs; lane 0's order for the record
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double so = __shfl_xor(ee.s, o, 64), co = __shfl_xor(ee.c, o, 64);
-        ee.c += co;
-        wp_two_sum(ee.s, ee.c, so);
-    }
-    const double es = __shfl(ee.s, 0, 64), ec = __shfl(ee.c, 0, 64);
-    // the slots behind the block: the record sum reads all of them
-    if (lane < kMixedRecStride - kMixedRecXY) {
-        const int slot = kMixedRecXY + lane;
-        rec[slot] = slot == kWpRecEE ? es : (slot == kWpRecEC ? ec : 0.0);
-    }
-}
-
 // alpha (nullable): one value per group, at gmap[g] (nullable: g) -- the group's index among the caller's groups, empty ones included
 template <typename T, int P, bool MEAT>
 __global__ __launch_bounds__(64) void within_pass_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ off, int64_t n_groups,
                                                          int64_t split_rows, const double* __restrict__ beta, const double* __restrict__ means,
                                                          const int64_t* __restrict__ gmap, T* __restrict__ alpha, WpRowOut<T> ro,
                                                          double* __restrict__ partials) {
-    __shared__ double xt[MEAT ? (P + 1) * kWpStride + kWpBatch * kWpPark : 1];  // features 0 .. P - 1, then e: [c * kWpStride + row]; the park
-    double* park = xt + (P + 1) * kWpStride;
+    __shared__ double xt[MEAT ? (P + 1) * kScoreTileStride + kScoreBatch * kScorePark : 1];  // features 0 .. P - 1, then e: [c * kScoreTileStride + row]; the park
+    double* park = xt + (P + 1) * kScoreTileStride;
     const int lane = threadIdx.x;
     double b[P];
 #pragma unroll
@@ -185,8 +109,8 @@ __global__ __launch_bounds__(64) void within_pass_kernel(const T* const* __restr
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    WpMeat mt;
-    WpSq ee;
+    ScoreMeat<false> mt;
+    CompSq ee;
     int64_t g = blockIdx.x;
     int64_t o0 = g < n_groups ? off[g] : 0, o1 = g < n_groups ? off[g + 1] : 0;  // (the host has validated the offsets)
     while (g < n_groups) {
@@ -200,13 +124,13 @@ __global__ __launch_bounds__(64) void within_pass_kernel(const T* const* __restr
         if (alpha && lane == 0) alpha[gmap ? gmap[gi] : gi] = (T)a;
         d4 sc = {0.0, 0.0, 0.0, 0.0};
         wp_stream<T, P, MEAT>(cx, cy, r0, n, m, b, ro, xt, lane, sc, ee);
-        if constexpr (MEAT) wp_park_d(park, lane, sc, mt);
+        if constexpr (MEAT) mt.park_d(park, lane, sc);
     }
-    if constexpr (MEAT) wp_flush(park, lane, mt);
-    wp_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, mt, ee);
+    if constexpr (MEAT) mt.flush(park, lane);
+    mt.write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, ee);
 }
 
-// a wave per chunk (grid stride): the rows' outputs, with MEAT the chunk's score -> scores[k * kWpPark + entry]; the wave's record
+// a wave per chunk (grid stride): the rows' outputs, with MEAT the chunk's score -> scores[k * kScorePark + entry]; the wave's record
 // carries its sum e^2 alone.  The first chunk of a group (chunk_r0 == chunk_first) writes the group's alpha.
 template <typename T, int P, bool MEAT>
 __global__ __launch_bounds__(64) void within_chunk_kernel(const T* const* __restrict__ cols, const int64_t* __restrict__ chunk_r0,
@@ -215,7 +139,7 @@ __global__ __launch_bounds__(64) void within_chunk_kernel(const T* const* __rest
                                                           const double* __restrict__ beta, const double* __restrict__ means,
                                                           const int64_t* __restrict__ gmap, T* __restrict__ alpha, WpRowOut<T> ro,
                                                           double* __restrict__ scores, double* __restrict__ partials) {
-    __shared__ double xt[MEAT ? (P + 1) * kWpStride : 1];
+    __shared__ double xt[MEAT ? (P + 1) * kScoreTileStride : 1];
     const int lane = threadIdx.x;
     double b[P];
 #pragma unroll
@@ -224,7 +148,7 @@ __global__ __launch_bounds__(64) void within_chunk_kernel(const T* const* __rest
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
-    WpSq ee;
+    CompSq ee;
     for (int64_t k = blockIdx.x; k < n_chunks; k += gridDim.x) {
         const int64_t gi = chunk_g[k], r0 = chunk_r0[k];
         double m[P + 1];
@@ -232,61 +156,9 @@ __global__ __launch_bounds__(64) void within_chunk_kernel(const T* const* __rest
         if (alpha && lane == 0 && r0 == chunk_first[k]) alpha[gmap ? gmap[gi] : gi] = (T)a;
         d4 sc = {0.0, 0.0, 0.0, 0.0};
         wp_stream<T, P, MEAT>(cx, cy, r0, chunk_n[k], m, b, ro, xt, lane, sc, ee);
-        if constexpr (MEAT) {
-            double* out = scores + k * kWpPark;
-            if ((lane & 15) == 0) {
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) out[(lane >> 4) + 4 * reg] = sc[reg];
-            }
-            if (lane == 0) out[16] = 0.0, out[17] = 0.0;
-        }
+        if constexpr (MEAT) score_store_d(scores + k * kScorePark, lane, sc, 0.0);
     }
-    WpMeat none;
-    wp_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, none, ee);
-}
-
-// one wave walks the long groups (grid stride): chunk scores added in chunk order, lane = entry, then parked like any other score
-// (cluster_long_meat_kernel's twin without the bias entry)
-__global__ __launch_bounds__(64) void within_long_meat_kernel(const int64_t* __restrict__ long_c0, const int64_t* __restrict__ long_nc,
-                                                              int64_t n_long, const double* __restrict__ scores, double* __restrict__ partials) {
-    __shared__ double park[kWpBatch * kWpPark];
-    const int lane = threadIdx.x;
-    WpMeat mt;
-    for (int64_t j = blockIdx.x; j < n_long; j += gridDim.x) {
-        const int64_t c0 = long_c0[j], nc = long_nc[j];
-        double s = 0.0;
-        if (lane < kWpPark)
-            for (int64_t k = 0; k < nc; ++k) s += scores[(c0 + k) * kWpPark + lane];
-        if (lane < kWpPark) park[mt.parked * kWpPark + lane] = s;
-        if (++mt.parked == kWpBatch) wp_flush(park, lane, mt);
-    }
-    wp_flush(park, lane, mt);
-    wp_write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, mt, WpSq{});
-}
-
-// block b: out[b] = in[b per] + in[b per + 1] + ... in index order, entry by entry, the running sum's rounding errors collected
-// beside it and added at the end (cluster_sum_records_kernel's twin)
-__global__ __launch_bounds__(320) void within_sum_records_kernel(const double* __restrict__ in, int n_rec, int per, double* __restrict__ out) {
-    const int e = threadIdx.x;
-    if (e >= kMixedRecStride) return;
-    const int r0 = blockIdx.x * per, r1 = std::min(n_rec, r0 + per);
-    double s = 0.0, c = 0.0;
-    for (int r = r0; r < r1; ++r) wp_two_sum(s, c, in[(int64_t)r * kMixedRecStride + e]);
-    out[(int64_t)blockIdx.x * kMixedRecStride + e] = s + c;
-}
-
-// records [0, n_rec) of `d_rec` -> one record at d_out, in index order: blocks of 64 records, then the block sums
-int within_sum_records(pds_ctx* ctx, const double* d_rec, int n_rec, double* d_stage, double* d_out) {
-    const int per = 64;
-    const int nb = (n_rec + per - 1) / per;
-    if (nb > 1) {
-        hipLaunchKernelGGL(within_sum_records_kernel, dim3(nb), dim3(320), 0, ctx->stream, d_rec, n_rec, per, d_stage);
-        hipLaunchKernelGGL(within_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, (const double*)d_stage, nb, nb, d_out);
-    } else {
-        hipLaunchKernelGGL(within_sum_records_kernel, dim3(1), dim3(320), 0, ctx->stream, d_rec, n_rec, n_rec, d_out);
-    }
-    PDS_HIP_CHECK(hipGetLastError());
-    return PDS_OK;
+    ScoreMeat<false>{}.write_record(partials + (int64_t)blockIdx.x * kMixedRecStride, lane, ee);
 }
 
 }  // namespace
@@ -322,10 +194,10 @@ int launch_within_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, const i
         else go(std::false_type{});
     });
     if (nbl > 0)
-        hipLaunchKernelGGL(within_long_meat_kernel, dim3(nbl), dim3(64), 0, ctx->stream, ch.d_long_c0, ch.d_long_nc, ch.n_long,
+        hipLaunchKernelGGL(score_long_meat_kernel<false>, dim3(nbl), dim3(64), 0, ctx->stream, ch.d_long_c0, ch.d_long_nc, ch.n_long,
                            (const double*)d_scores, d_partials + (int64_t)(nb + nbc) * kMixedRecStride);
     PDS_HIP_CHECK(hipGetLastError());
-    return within_sum_records(ctx, d_partials, nb + nbc + nbl, d_stage, d_rec);
+    return launch_sum_records(ctx, d_partials, nb + nbc + nbl, d_stage, d_rec, /*compensated=*/true);
 }
 
 template int launch_within_pass<double>(pds_ctx*, const double* const*, int, const int64_t*, int64_t, int64_t, const MixedChunks&, double*,

@@ -56,9 +56,20 @@ def test_source_lists_the_kernel():
     assert "cluster_meat.hip" in (csrc / "Makefile").read_text()
     assert '#include "capi_report_cluster.hpp"' in (csrc / "capi.hip").read_text()
     assert '#include "plugin_cluster.hpp"' in (csrc / "plugin.cpp").read_text()
-    text = (csrc / "cluster_meat.hip").read_text()
-    assert '#include "wave_tile_dev.hpp"' in text and "__builtin_amdgcn_mfma_f64_16x16x4f64" in text
-    assert not re.search(r"atomic(Add|Or|Max|Min|CAS|Exch)", text)  # no atomics in any sum
+    # the score / meat idiom is score_meat_dev.hpp's (shared with within_pass.hip), which builds on the wave tile
+    text, shared = (csrc / "cluster_meat.hip").read_text(), (csrc / "score_meat_dev.hpp").read_text()
+    assert '#include "score_meat_dev.hpp"' in text and '#include "wave_tile_dev.hpp"' in shared
+    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in shared
+    assert "score_rows4<P>" in text and "ScoreMeat<true>" in text and "score_long_meat_kernel<true, int>" in text  # (with a bias entry)
+    assert "launch_sum_records(" in text and "compensated=*/true" in text
+    # no atomics in any sum: the pass, the shared idiom, the record sum (mixed.hip, whose one integer atomicOr is the flag word's)
+    atomics = r"atomic(Add|Or|Max|Min|CAS|Exch)"
+    assert not re.search(atomics, text) and not re.search(atomics, shared)
+    mixed = (csrc / "mixed.hip").read_text()
+    sum_text = mixed[mixed.index("template <bool COMPENSATED>"):mixed.index("template <int P>\n__global__ __launch_bounds__(64) void mixed_profile_kernel")]
+    sum_text += mixed[mixed.index("int launch_sum_records("):mixed.index("int mixed_stats_blocks(")]
+    assert "sum_records_kernel(" in sum_text and "two_sum(s, c, v)" in sum_text and "hipLaunchKernelGGL" in sum_text
+    assert not re.search(atomics, sum_text)
 
 
 # ------------------------------------------------------------------------------------------------- the plugin layer on the mock device

@@ -109,9 +109,21 @@ def test_source_lists_the_kernel():
     csrc = ROOT / "polars_ds_extension_amd" / "csrc"
     assert "within_pass.hip" in (csrc / "Makefile").read_text()
     assert '#include "capi_within.hpp"' in (csrc / "capi.hip").read_text()
-    text = (csrc / "within_pass.hip").read_text()
-    assert '#include "wave_tile_dev.hpp"' in text and "__builtin_amdgcn_mfma_f64_16x16x4f64" in text
-    assert not re.search(r"atomic(Add|Or|Max|Min|CAS|Exch)", text)  # no atomics in any sum
+    # the score / meat idiom is score_meat_dev.hpp's (shared with cluster_meat.hip), which builds on the wave tile
+    text, shared = (csrc / "within_pass.hip").read_text(), (csrc / "score_meat_dev.hpp").read_text()
+    assert '#include "score_meat_dev.hpp"' in text and '#include "wave_tile_dev.hpp"' in shared
+    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in shared
+    assert "score_rows4<P>" in text and "ScoreMeat<false>" in text and "score_long_meat_kernel<false>" in text  # (no bias entry)
+    assert "launch_sum_records(" in text and "compensated=*/true" in text
+    # no atomics in any sum: the pass, the shared idiom, the record sum (mixed.hip, whose one integer atomicOr is the flag word's)
+    atomics = r"atomic(Add|Or|Max|Min|CAS|Exch)"
+    assert not re.search(atomics, text) and not re.search(atomics, shared)
+    mixed = (csrc / "mixed.hip").read_text()
+    sum_text = mixed[mixed.index("template <bool COMPENSATED>"):mixed.index("template <int P>\n__global__ __launch_bounds__(64) void mixed_profile_kernel")]
+    sum_text += mixed[mixed.index("int launch_sum_records("):mixed.index("int mixed_stats_blocks(")]
+    assert "sum_records_kernel(" in sum_text and "two_sum(s, c, v)" in sum_text and "hipLaunchKernelGGL" in sum_text
+    assert not re.search(atomics, sum_text)
+    assert not re.search(r"atomic(Add|Max|Min|CAS|Exch)", mixed)
 
 
 # ---- 3. argument errors, before any library call
