@@ -906,6 +906,60 @@ int pds_glm_report_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const f
                                  int64_t max_groups, int64_t* out_keys, float* coeffs, int32_t* n_iter, uint8_t* is_null, int64_t* n_groups,
                                  const pds_glm_report_out* out);
 /*
+ * pds_glm_report_robust_* / pds_glm_report_cluster_grouped_* / pds_glm_report_cluster_by_key_*: ONE model over the whole frame with
+ * robust (PDS_HC0 / PDS_HC1) or cluster-robust (PDS_CLUSTER / PDS_CLUSTER0) standard errors -- Stata's glm, vce(robust | cluster id),
+ * statsmodels' GLM.fit(cov_type="HC0" | "HC1" | "cluster"), R's sandwich::vcovHC / vcovCL on a glm.  cols = [y, x1..xp], 1 .. 16
+ * feature columns, the four families, `weights` / `offset` nullable with the meaning of pds_glm_irls_wo_*.  The fit is the existing
+ * one: coeffs, n_iter, deviance, null_deviance, pearson_chi2, dispersion and df_resid are bit for bit those of
+ * pds_glm_report_wo_grouped_* with group_offsets = [0, n_rows] on the same frame (the offsets and hc forms; the by-key form on the
+ * key-ordered frame).  What is new is the covariance.  At the coefficients AS STORED, x_i carrying the constant 1 last under a bias,
+ * everything in f64 for f64 and f32 frames alike:
+ *   eta_i = x_i . beta + o_i, mu_i = g^-1(eta_i); I = sum pw_i x_i x_i' / (g'(mu_i)^2 V(mu_i)), the information the plain report inverts
+ *   r_i = pw_i (y_i - mu_i) / (V(mu_i) g'(mu_i)): the score residual, general in (link, variance); a row with pw_i = 0 has r_i = 0
+ *   exactly (a select, so that whatever its mu is reaches no sum)
+ *   n = the rows of positive weight (all rows without weights), p' = coefficients
+ *   PDS_HC0:      M = sum_i r_i^2 x_i x_i', V = I^-1 M I^-1
+ *   PDS_HC1:      the same times n / (n - p')
+ *   PDS_CLUSTER0: s_g = sum_{i in g} r_i x_i, M = sum_g s_g s_g', V = I^-1 M I^-1
+ *   PDS_CLUSTER:  the same times G / (G - 1) * (n - 1) / (n - p'): statsmodels' default correction, the c of
+ *                 pds_lin_reg_report_cluster_*; G counts the clusters that hold at least one row of positive weight
+ *   The dispersion cancels in the sandwich and does not enter it (I^-1 = the plain report's cov / dispersion).
+ *   se_j = sqrt V_jj, z_j = beta_j / se_j, p_j = erfc(|z_j| / sqrt 2), lo / hi = beta_j -+ 1.959963984540054 se_j: the normal
+ *   distribution, as in every GLM report here; *n_clusters (a host int64, nullable) receives G for a caller who wants t(G - 1), 0 for
+ *   the hc kinds.  out->cov = V.  `out` has one group's room; its fields and coeffs / n_iter are `space`-resident.
+ *   report_null = 1 when the fit is null, I cannot be factorised or a diagonal entry of V is not a non-negative finite number: every
+ *   report field is then NaN except df_resid; the coefficients stay what the fit returned.
+ * cluster_offsets (grouped): n_offsets + 1 `space`-resident offsets, starting at 0, ending at n_rows, non-decreasing (else
+ * PDS_ERR_INVALID); empty clusters change no output bit.  keys (by key): n_rows int64 values in any row order (ordered keys move
+ * nothing; weights and offset travel with the frame).  Clusters above the context option "cluster_split_rows" are cut into row
+ * chunks; "cluster_waves" caps the waves of the pass.  No floating-point atomic: two calls give the same bits.
+ * Refused, never approximated: more than 16 features PDS_ERR_UNSUPPORTED; PDS_HC2 / PDS_HC3 (they need the leverages)
+ * PDS_ERR_UNSUPPORTED; any other se_type PDS_ERR_INVALID; a cluster form with G < 2 PDS_ERR_INVALID; PDS_HC1 / PDS_CLUSTER with
+ * n <= p' PDS_ERR_TOO_FEW_ROWS.  Penalties have no argument.
+ */
+int pds_glm_report_robust_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                              pds_space space, int add_bias, int link, int variance, double tol, int max_iter, int se_type, double* coeffs,
+                              int32_t* n_iter, const pds_glm_report_out* out, int64_t* n_clusters);
+int pds_glm_report_robust_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                              pds_space space, int add_bias, int link, int variance, float tol, int max_iter, int se_type, float* coeffs,
+                              int32_t* n_iter, const pds_glm_report_out* out, int64_t* n_clusters);
+int pds_glm_report_cluster_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat,
+                                       int64_t n_rows, const int64_t* cluster_offsets, int64_t n_offsets, pds_space space, int add_bias,
+                                       int link, int variance, double tol, int max_iter, int se_type, double* coeffs, int32_t* n_iter,
+                                       const pds_glm_report_out* out, int64_t* n_clusters);
+int pds_glm_report_cluster_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat,
+                                       int64_t n_rows, const int64_t* cluster_offsets, int64_t n_offsets, pds_space space, int add_bias,
+                                       int link, int variance, float tol, int max_iter, int se_type, float* coeffs, int32_t* n_iter,
+                                       const pds_glm_report_out* out, int64_t* n_clusters);
+int pds_glm_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                                      int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol,
+                                      int max_iter, int se_type, double* coeffs, int32_t* n_iter, const pds_glm_report_out* out,
+                                      int64_t* n_clusters);
+int pds_glm_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                                      int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol,
+                                      int max_iter, int se_type, float* coeffs, int32_t* n_iter, const pds_glm_report_out* out,
+                                      int64_t* n_clusters);
+/*
  * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
  * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on
  * chip by the one-sided Jacobi iteration of the single-system call, singular values below the cut are dropped, the coefficients are

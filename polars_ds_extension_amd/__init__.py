@@ -16,6 +16,7 @@ from .lstsq import (  # noqa: F401
     gather,
     glm_by,
     glm_by_key,
+    glm_report,
     glm_report_by,
     glm_report_by_key,
     gram_moments,

@@ -18,6 +18,7 @@ SOLVERS = {"qr": 0, "svd": 1, "choleskey": 2}  # any other string -> qr (src/lin
 SE_TYPES = {"se": 0, "hc0": 1, "hc1": 2, "hc2": 3, "hc3": 4}
 WITHIN_SE_TYPES = {"se": 0, "cluster": 5, "cluster0": 6}  # pds_lin_reg_within_*: the clusters are the absorbed groups
 CLUSTER_SE_TYPES = {"cluster": 5, "cluster0": 6}  # PDS_CLUSTER (CR1) / PDS_CLUSTER0 (CR0): pds_lin_reg_report_cluster_* only
+GLM_ROBUST_SE_TYPES = {"hc0": 1, "hc1": 2, "hc2": 3, "hc3": 4, "cluster": 5, "cluster0": 6}  # pds_glm_report_robust_* / _cluster_*
 PDS_REPORT_DERIVE_YVAR = 0x100  # include/pds_lstsq.h
 
 EXPORTS = [
@@ -27,6 +28,8 @@ EXPORTS = [
     "pds_glm_enet_f64", "pds_glm_enet_f32", "pds_glm_enet_grouped_f64", "pds_glm_enet_grouped_f32", "pds_glm_enet_by_key_f64", "pds_glm_enet_by_key_f32",
     "pds_glm_report_wo_grouped_f64", "pds_glm_report_wo_grouped_f32", "pds_glm_report_wo_by_key_f64", "pds_glm_report_wo_by_key_f32",
     "pds_glm_report_grouped_f64", "pds_glm_report_grouped_f32", "pds_glm_report_by_key_f64", "pds_glm_report_by_key_f32",
+    "pds_glm_report_robust_f64", "pds_glm_report_robust_f32", "pds_glm_report_cluster_grouped_f64", "pds_glm_report_cluster_grouped_f32",
+    "pds_glm_report_cluster_by_key_f64", "pds_glm_report_cluster_by_key_f32",
     "pds_lr_rcond_grouped_f64", "pds_lr_rcond_grouped_f32", "pds_lr_rcond_by_key_f64", "pds_lr_rcond_by_key_f32",
     "pds_lr_multi_grouped_f64", "pds_lr_multi_grouped_f32", "pds_lr_multi_by_key_f64", "pds_lr_multi_by_key_f32",
     "pds_mixed_reml_grouped_f64", "pds_mixed_reml_grouped_f32", "pds_mixed_reml_by_key_f64", "pds_mixed_reml_by_key_f32",

@@ -37,6 +37,7 @@ namespace pds {
 #include "capi_mixed.hpp"
 #include "capi_report_cluster.hpp"
 #include "capi_within.hpp"
+#include "capi_glm_sandwich.hpp"
 
 }  // namespace pds
 
@@ -295,6 +296,48 @@ int pds_glm_report_wo_by_key_f32(pds_ctx* ctx, const float* const* cols, const f
                                  const pds_glm_report_out* out) {
     return pds::glm_report_by_key_impl<float>(ctx, cols, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter, max_groups,
                                                out_keys, coeffs, n_iter, is_null, n_groups, out, weights, offset);
+}
+
+// the one-model report with robust / cluster-robust standard errors (capi_glm_sandwich.hpp)
+int pds_glm_report_robust_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                              pds_space space, int add_bias, int link, int variance, double tol, int max_iter, int se_type, double* coeffs,
+                              int32_t* n_iter, const pds_glm_report_out* out, int64_t* n_clusters) {
+    return pds::glm_sandwich_impl<double>(ctx, cols, weights, offset, n_feat, n_rows, nullptr, 0, space, add_bias, link, variance, tol, max_iter,
+                                       se_type, false, coeffs, n_iter, out, n_clusters);
+}
+int pds_glm_report_cluster_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat,
+                                       int64_t n_rows, const int64_t* cluster_offsets, int64_t n_offsets, pds_space space, int add_bias,
+                                       int link, int variance, double tol, int max_iter, int se_type, double* coeffs, int32_t* n_iter,
+                                       const pds_glm_report_out* out, int64_t* n_clusters) {
+    return pds::glm_sandwich_impl<double>(ctx, cols, weights, offset, n_feat, n_rows, cluster_offsets, n_offsets, space, add_bias, link, variance,
+                                       tol, max_iter, se_type, true, coeffs, n_iter, out, n_clusters);
+}
+int pds_glm_report_cluster_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                                      int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, double tol,
+                                      int max_iter, int se_type, double* coeffs, int32_t* n_iter, const pds_glm_report_out* out,
+                                      int64_t* n_clusters) {
+    return pds::glm_sandwich_by_key_impl<double>(ctx, cols, weights, offset, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter,
+                                              se_type, coeffs, n_iter, out, n_clusters);
+}
+int pds_glm_report_robust_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                              pds_space space, int add_bias, int link, int variance, float tol, int max_iter, int se_type, float* coeffs,
+                              int32_t* n_iter, const pds_glm_report_out* out, int64_t* n_clusters) {
+    return pds::glm_sandwich_impl<float>(ctx, cols, weights, offset, n_feat, n_rows, nullptr, 0, space, add_bias, link, variance, tol, max_iter,
+                                       se_type, false, coeffs, n_iter, out, n_clusters);
+}
+int pds_glm_report_cluster_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat,
+                                       int64_t n_rows, const int64_t* cluster_offsets, int64_t n_offsets, pds_space space, int add_bias,
+                                       int link, int variance, float tol, int max_iter, int se_type, float* coeffs, int32_t* n_iter,
+                                       const pds_glm_report_out* out, int64_t* n_clusters) {
+    return pds::glm_sandwich_impl<float>(ctx, cols, weights, offset, n_feat, n_rows, cluster_offsets, n_offsets, space, add_bias, link, variance,
+                                       tol, max_iter, se_type, true, coeffs, n_iter, out, n_clusters);
+}
+int pds_glm_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                                      int n_feat, int64_t n_rows, pds_space space, int add_bias, int link, int variance, float tol,
+                                      int max_iter, int se_type, float* coeffs, int32_t* n_iter, const pds_glm_report_out* out,
+                                      int64_t* n_clusters) {
+    return pds::glm_sandwich_by_key_impl<float>(ctx, cols, weights, offset, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter,
+                                              se_type, coeffs, n_iter, out, n_clusters);
 }
 
 // the elastic-net penalised fits: the argument lists of pds_glm_irls_* with l1_reg, l2_reg after `variance` (<= 0: no penalty)

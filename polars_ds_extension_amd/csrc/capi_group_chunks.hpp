@@ -66,6 +66,28 @@ static int plan_group_chunks(const int64_t* h_off, int64_t n_groups, int64_t n_r
     return PDS_OK;
 }
 
+// the plan's lists -> the device as the ClusterChunks the cluster kernels read (cluster_meat.hip, glm_meat.hip: per chunk r0 and n, per
+// long cluster its first chunk and its chunks: no more is sent) and room for the chunk scores; nothing is taken without chunks.
+// take(bytes) hands out device memory (ws_take of ctx->ws, or a Bump).  The copies are asynchronous: the plan outlives the caller's
+// next stream synchronisation.
+template <typename Take>
+static int upload_cluster_chunks(pds_ctx* ctx, Take&& take, const GroupChunkPlan& pl, ClusterChunks& ch) {
+    ch.n_chunks = pl.n_chunks();
+    ch.n_long = pl.n_long();
+    if (ch.n_chunks == 0) return PDS_OK;
+    const std::vector<int64_t>* lists[4] = {&pl.hc[0], &pl.hc[1], &pl.hl[1], &pl.hl[2]};
+    const int64_t* d[4];
+    for (int i = 0; i < 4; ++i) {
+        const std::vector<int64_t>& h = *lists[i];
+        int64_t* t = reinterpret_cast<int64_t*>(take(h.size() * 8));
+        PDS_HIP_CHECK(hipMemcpyAsync(t, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        d[i] = t;
+    }
+    ch.d_chunk_r0 = d[0], ch.d_chunk_n = d[1], ch.d_long_c0 = d[2], ch.d_long_nc = d[3];
+    ch.d_scores = reinterpret_cast<double*>(take((size_t)ch.n_chunks * kClusterScoreStride * 8));
+    return PDS_OK;
+}
+
 // the plan's lists -> the device, out of w, as the MixedChunks the kernels of mixed.hip and within_pass.hip read (nc = p + 1 columns:
 // d_sums); nothing is taken without chunks.  The copies are asynchronous: the plan outlives the caller's next stream synchronisation.
 static int upload_mixed_chunks(pds_ctx* ctx, Bump& w, const GroupChunkPlan& pl, int nc, MixedChunks& ch) {

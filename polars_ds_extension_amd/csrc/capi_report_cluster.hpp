@@ -64,18 +64,7 @@ static int report_cluster_impl(pds_ctx* ctx, const T* const* cols, int n_feat, i
         PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n_clusters + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         d_off = t;
     }
-    if (ch.n_chunks > 0) {
-        const std::vector<int64_t>* lists[4] = {&pl.hc[0], &pl.hc[1], &pl.hl[1], &pl.hl[2]};  // (what the cluster kernels read: no more is sent)
-        const int64_t* d[4];
-        for (int i = 0; i < 4; ++i) {
-            const std::vector<int64_t>& h = *lists[i];
-            int64_t* t = reinterpret_cast<int64_t*>(ws_take(ctx, h.size() * 8));
-            PDS_HIP_CHECK(hipMemcpyAsync(t, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            d[i] = t;
-        }
-        ch.d_chunk_r0 = d[0], ch.d_chunk_n = d[1], ch.d_long_c0 = d[2], ch.d_long_nc = d[3];
-        ch.d_scores = reinterpret_cast<double*>(ws_take(ctx, (size_t)ch.n_chunks * kClusterScoreStride * 8));
-    }
+    if (int rc = upload_cluster_chunks(ctx, [&](size_t bytes) { return ws_take(ctx, bytes); }, pl, ch)) return rc;
     T* d_mom = reinterpret_cast<T*>(ws_take(ctx, sizeof(T) * q * q));
     T* d_beta = reinterpret_cast<T*>(ws_take(ctx, sizeof(T) * (pp + 2)));
     T* d_inv = reinterpret_cast<T*>(ws_take(ctx, sizeof(T) * pp * pp));

@@ -464,6 +464,18 @@ int cluster_meat_blocks(const pds_ctx* ctx, int64_t n_work);  // partial records
 template <typename T>
 int launch_cluster_meat(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_clusters, int64_t split_rows,
                         const ClusterChunks& ch, const T* d_beta, int bias, double* d_partials, double* d_stage, double* d_rec);
+// ---- glm_meat.hip: the meat of the robust / cluster-robust one-model GLM report (capi_glm_sandwich.hpp) at the coefficients d_beta
+// (features, then the bias when `bias`) -> one record at d_rec.  d_cols: x_0 .. x_{p-1}, y, weights, offset (a table of n_feat + 3
+// device pointers; the last two nullable).  n_clusters > 0: the cluster forms (d_off, split_rows and ch as launch_cluster_meat; the
+// record's kMixedRecLD slot counts the clusters that hold a row of positive weight, its kMixedRecC slot is the bias diagonal);
+// in both forms the kMixedRecCM slot counts the rows of positive weight;
+// n_clusters = 0: the hc forms over row ranges (the bias diagonal is kMixedRecYY + kMixedRecCY).  d_partials: room for
+// glm_meat_records() records, d_stage for a 64th of that (rounded up).
+int glm_meat_records(const pds_ctx* ctx, int64_t n_rows, int64_t n_clusters, const ClusterChunks& ch);
+template <typename T>
+int launch_glm_meat(pds_ctx* ctx, const T* const* d_cols, int n_feat, int64_t n_rows, const int64_t* d_off, int64_t n_clusters,
+                    int64_t split_rows, const ClusterChunks& ch, const T* d_beta, int bias, int link, int variance, double* d_partials,
+                    double* d_stage, double* d_rec);
 // ---- within_pass.hip: the fixed-effects regression's per-row pass (capi_within.hpp).  With beta (n_feat doubles) and the group means of
 // launch_mixed_stats (d_means, the same d_off / n_groups / split_rows / chunks): alpha_g = m_y - m . beta -> d_alpha[d_gmap ? d_gmap[g] : g],
 // e = (y - m_y) - (x - m) . beta -> d_resid, y - e -> d_pred (row r of the frame is row d_perm[r] of the outputs when d_perm is given),

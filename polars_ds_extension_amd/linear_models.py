@@ -472,16 +472,29 @@ class GLM:
     def bias(self) -> float:
         return float(self._bias)
 
-    def fit(self, X, y, null_policy: str = "ignore", report: bool = False, sample_weight=None, offset=None):
+    def fit(self, X, y, null_policy: str = "ignore", report: bool = False, sample_weight=None, offset=None, std_err: str = "se",
+            cluster=None):
         """`sample_weight` / `offset` (one entry per row each): prior weights and an offset per row, R's `glm(weights=, offset=)`
         (`pds_glm_irls_wo_*`; `lstsq.glm_by` states the semantics).  A negative or non-finite weight, or fewer rows of positive weight
         than coefficients, raises.  Not together with a penalty; a null policy that drops rows drops them from the two columns too.
         `report=True`: the fit goes through the grouped entry point with ONE group covering the frame (`lstsq.glm_report_by`, up to
         16 features, no penalty) and fills `std_errors_`, `z_`, `p_values_`, `deviance_`, `null_deviance_`, `dispersion_`, `df_resid_`
         (the bias last; z and p from the normal distribution for every family); `report()` returns them.  The default path is the
-        one-model iteration, untouched."""
+        one-model iteration, untouched.
+        `std_err` ("se", "hc0", "hc1", "cluster", "cluster0"; with `report=True` only) and `cluster` (an integer column in any row
+        order, with the cluster kinds only): robust / cluster-robust standard errors (`lstsq.glm_report` states the definitions).  The
+        same attributes are then filled from the sandwich V, plus `cov_` (V), `n_clusters_` (0 for "hc0" / "hc1") and
+        `std_err_type_`; the default `std_err="se"` sets none of the three and is the call it was.  No penalty; the null policy must
+        not drop rows when `cluster` is given."""
+        if std_err != "se" or cluster is not None:
+            lstsq._glm_std_err_check("GLM.fit", std_err, cluster, None)
+            if not report:
+                raise ValueError("GLM.fit: `std_err` / `cluster` go with `report=True`")
+            if lstsq._pen_args(self.l1_reg, self.l2_reg):
+                raise NotImplementedError("GLM.fit: penalised fits have no report, robust or not")
         X = _as_matrix(X)
         y = _target(y, int(X.shape[0]))
+        n_given = int(X.shape[0])
         wo = sample_weight is not None or offset is not None
         if wo:  # the two columns ride through the null policy as two more feature columns: the rows it drops go from them too
             n_in, p_in = int(X.shape[0]), int(X.shape[1])
@@ -510,7 +523,9 @@ class GLM:
             raise ValueError("Not enough data.")  # LinearModel::fit, src/linear/lr/mod.rs:114-125
         self._report = None
         if report:
-            return self._fit_report(X, y, n, sample_weight, offset)
+            if cluster is not None and n != n_given:
+                raise ValueError("GLM.fit: `cluster` with a null policy that drops rows is not built")
+            return self._fit_report(X, y, n, sample_weight, offset, std_err, cluster)
         pen = lstsq._pen_args(self.l1_reg, self.l2_reg)
         cols, w_p, o_p = lstsq._glm_wo_cols("GLM.fit", _columns(X), y, sample_weight, offset, pen)
         ctx = lstsq.default_context()
@@ -529,9 +544,11 @@ class GLM:
         self.n_iter_ = int(n_iter.value)
         return self
 
-    def _fit_report(self, X, y, n: int, sample_weight=None, offset=None):
+    def _fit_report(self, X, y, n: int, sample_weight=None, offset=None, std_err: str = "se", cluster=None):
         if (sample_weight is not None or offset is not None) and lstsq._pen_args(self.l1_reg, self.l2_reg):
             raise NotImplementedError("GLM.fit: l1_reg / l2_reg together with sample_weight= / offset= is not built")
+        if std_err != "se":
+            return self._fit_report_robust(X, y, sample_weight, offset, std_err, cluster)
         rep = lstsq.glm_report_by(*_columns(X), target=y, group_offsets=[0, n], family=self.family, add_bias=self.add_bias, tol=self.tol,
                                   max_iter=self.max_iter, l1_reg=self.l1_reg, l2_reg=self.l2_reg, weights=sample_weight, offset=offset)
         host = {k: (v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)) for k, v in rep.items() if k != "features"}
@@ -544,6 +561,26 @@ class GLM:
         self.ci_lower_, self.ci_upper_ = host["0.025"][0].astype(np.float64), host["0.975"][0].astype(np.float64)
         self.deviance_, self.null_deviance_, self.dispersion_ = (float(host[k][0]) for k in ("deviance", "null_deviance", "dispersion"))
         self.df_resid_ = int(host["df_resid"][0])
+        self._report = True
+        return self
+
+    def _fit_report_robust(self, X, y, sample_weight, offset, std_err, cluster):
+        """report=True with std_err != "se": the one-model robust report (`lstsq.glm_report`), the same attributes from V"""
+        rep = lstsq.glm_report(*_columns(X), target=y, family=self.family, add_bias=self.add_bias, tol=self.tol, max_iter=self.max_iter,
+                               std_err=std_err, cluster=cluster, weights=sample_weight, offset=offset, return_cov=True)
+        host = {k: (v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)) for k, v in rep.items() if k not in ("features", "std_err_type")}
+        co = host["beta"].astype(np.float64)
+        if not np.isfinite(co).all():
+            raise ValueError("The fit did not end in finite coefficients.")
+        self._coeffs, self._bias = (co[:-1].copy(), float(co[-1])) if self.add_bias else (co.copy(), 0.0)
+        self.n_iter_ = int(host["n_iter"])
+        self.std_errors_, self.z_, self.p_values_ = (host[k].astype(np.float64) for k in ("std_err", "z", "p>|z|"))
+        self.ci_lower_, self.ci_upper_ = host["0.025"].astype(np.float64), host["0.975"].astype(np.float64)
+        self.deviance_, self.null_deviance_, self.dispersion_ = (float(host[k]) for k in ("deviance", "null_deviance", "dispersion"))
+        self.df_resid_ = int(host["df_resid"])
+        self.cov_ = host["cov"].astype(np.float64)
+        self.n_clusters_ = int(host["n_clusters"])
+        self.std_err_type_ = std_err
         self._report = True
         return self
 

@@ -1880,6 +1880,83 @@ def glm_report_by_key(*x, target, key, family: str = "gaussian", add_bias: bool 
     return d
 
 
+GLM_STD_ERR_TYPES = ("se", "hc0", "hc1", "cluster", "cluster0")
+
+
+def _glm_std_err_check(what, std_err, cluster, cluster_offsets):
+    """The argument rules of the robust GLM reports: which `std_err` exist, and that the clusters come with the cluster kinds alone."""
+    if std_err in ("hc2", "hc3"):
+        raise NotImplementedError(f'{what}: std_err="{std_err}" needs the leverages and is not built (one of {GLM_STD_ERR_TYPES})')
+    if std_err not in GLM_STD_ERR_TYPES:
+        raise ValueError(f"{what}: std_err={std_err!r} is not one of {GLM_STD_ERR_TYPES}")
+    if std_err in _lib.CLUSTER_SE_TYPES:
+        if (cluster is None) == (cluster_offsets is None):
+            raise ValueError(f'{what}: std_err="{std_err}" takes exactly one of `cluster` and `cluster_offsets`')
+    elif cluster is not None or cluster_offsets is not None:
+        raise ValueError(f'{what}: `cluster` / `cluster_offsets` go with std_err="cluster" or "cluster0" only')
+
+
+def glm_report(*x, target, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100, std_err: str = "se",
+               cluster=None, cluster_offsets=None, weights=None, offset=None, return_cov: bool = False,
+               feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+    """
+    ONE GLM over the whole frame and its report: the one-model twin of `glm_report_by`.  Returns the dict of `glm_report_by` un-batched
+    ("beta", "std_err", "z", "p>|z|", "0.025", "0.975" [p'] bias last; "deviance", "null_deviance", "pearson_chi2", "dispersion",
+    "df_resid", "n_iter", "report_null" scalars; "features"; "cov" [p', p'] with `return_cov`) plus "n_clusters" and
+    "std_err_type".  "is_null", the fit's own flag, comes with "se" only: the robust entry points return one flag, "report_null" (1
+    for a null fit, an I without an inverse or a V with a bad diagonal: the report fields are then NaN, "beta" is what the fit gave).  The normal distribution is used for every family; "n_clusters" is there for a caller who wants t(G - 1).
+    `std_err`:
+      "se"        model-based errors, cov = dispersion I^-1: `glm_report_by` with the one group [0, n).
+      "hc0"       robust: V = I^-1 M I^-1, M = sum_i r_i^2 x_i x_i', r_i = pw_i (y_i - mu_i) / (V(mu_i) g'(mu_i)) the score residual
+      "hc1"       the same times n / (n - p') (n: the rows of positive weight)
+      "cluster0"  cluster-robust: M = sum_g s_g s_g', s_g = sum_{i in g} r_i x_i
+      "cluster"   the same times G / (G - 1) * (n - 1) / (n - p'), statsmodels' default (G: the clusters with a row of positive weight)
+    (`pds_glm_report_robust_*` / `pds_glm_report_cluster_grouped_*` / `pds_glm_report_cluster_by_key_*`; include/pds_lstsq.h states
+    the definitions).  The dispersion cancels in the sandwich.  The clusters are `cluster`, an integer column in any row order, or
+    `cluster_offsets` (cluster g = rows [cluster_offsets[g], cluster_offsets[g+1]), contiguous, empty clusters allowed) -- exactly one
+    of the two with the cluster kinds, neither with any other (ValueError).  "hc2" / "hc3" raise NotImplementedError.  The fit, the
+    deviances, the dispersion and df_resid are bit for bit those of `glm_report_by(group_offsets=[0, n])` on the same frame.
+    1 .. 16 features, `weights` / `offset` as in `glm_by`, no penalties.
+    """
+    _glm_std_err_check("glm_report", std_err, cluster, cluster_offsets)
+    _glm_check(x, max_iter, "glm_report")
+    if std_err == "se":
+        n = int(target.shape[0]) if hasattr(target, "shape") else len(target)
+        d = glm_report_by(*x, target=target, group_offsets=np.array([0, n], dtype=np.int64), family=family, add_bias=add_bias, tol=tol,
+                          max_iter=max_iter, feature_names=feature_names, return_cov=return_cov, ctx=ctx, weights=weights, offset=offset)
+        d = {k: (v if k == "features" else v[0]) for k, v in d.items()}
+        d["n_clusters"] = 0
+        d["std_err_type"] = std_err
+        return d
+    link, var = _glm_family(family)
+    cols, w_p, o_p = _glm_wo_cols("glm_report", x, target, weights, offset, ())
+    ctx = ctx or default_context()
+    _follow(ctx, cols)
+    pp = cols.n_feat + int(bool(add_bias))
+    outs, rep = _glm_report_outs(cols, 1, pp, return_cov)
+    se_code = C.c_int(_lib.GLM_ROBUST_SE_TYPES[std_err])
+    ng = C.c_int64(0)
+    head = (ctx._h, cols.cols, w_p, o_p)
+    tail = (cols.space, int(bool(add_bias)), C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), se_code, outs["beta"][1],
+            outs["n_iter"][1], C.byref(rep), C.byref(ng))
+    if cluster is not None:
+        k, k_p = _key_arg(cols, cluster)
+        _lib.check(ctx.fn("pds_glm_report_cluster_by_key")(*head, k_p, cols.n_feat, C.c_int64(cols.n_rows), *tail))
+    elif cluster_offsets is not None:
+        off, off_p = _offsets_arg(cols, cluster_offsets)
+        if off.ndim != 1 or int(off.shape[0]) < 2:
+            raise ValueError("`cluster_offsets` must be 1-D with at least two entries")
+        _lib.check(ctx.fn("pds_glm_report_cluster_grouped")(*head, cols.n_feat, C.c_int64(cols.n_rows), off_p, C.c_int64(int(off.shape[0]) - 1),
+                                                            *tail))
+    else:
+        _lib.check(ctx.fn("pds_glm_report_robust")(*head, cols.n_feat, C.c_int64(cols.n_rows), *tail))
+    d = _glm_report_dict(outs, cols.n_feat, add_bias, feature_names, return_cov)
+    d = {k: (v if k == "features" else v[0]) for k, v in d.items() if k != "is_null"}  # (the entry points return one flag: report_null)
+    d["n_clusters"] = int(ng.value)
+    d["std_err_type"] = std_err
+    return d
+
+
 def logistic_reg(*x, target, add_bias: bool = True, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5, max_iter: int = 200,
                  return_pred: bool = False, ctx: Context | None = None):
     """

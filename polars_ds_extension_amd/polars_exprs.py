@@ -373,8 +373,8 @@ def glm_by_group(df, by, *x, target, family: str = "gaussian", return_pred: bool
     return _join(keys, res, on=[_GID]).drop(_GID)
 
 
-def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
-               null_policy: str = "raise", weights=None, offset=None):
+def glm_report(*x, target, by=None, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100,
+               null_policy: str = "raise", weights=None, offset=None, std_err: str = "se", cluster=None):
     """
     The report of one GLM per group from ONE `pl_glm_report_by` call (the GLM twin of `lin_reg_report(..., by=)`): `by` is an
     integer key column in any row order, nulls = one group.  Long format -- a Struct "glm_report" {<key>, features, beta, std_err, z,
@@ -384,14 +384,33 @@ def glm_report(*x, target, by, family: str = "gaussian", add_bias: bool = False,
     fields.  Penalised fits have no report.  Keys of other dtypes or several key columns: `glm_report_by_group`.
     `weights` / `offset` (column names or expressions): prior weights and an offset per row (`lstsq.glm_report_by` states the
     weighted definitions; `null_deviance` is null-valued NaN under an offset).  A null in either is an error whatever `null_policy`.
+    Without `by`: ONE model over the whole frame with robust standard errors from one `pl_glm_report_robust` call --
+    `std_err="hc0"` / `"hc1"`, or `"cluster"` / `"cluster0"` with `cluster` (an integer key column, any row order, the null key its own
+    cluster); `lstsq.glm_report` states the definitions.  A Struct "glm_report" of p' rows {features, beta, std_err, z, p>|z|, 0.025,
+    0.975, deviance, null_deviance, dispersion, n_iter, n_clusters}; z, p and the interval use the normal distribution, n_clusters
+    (0 for the hc kinds) is there for a caller who wants t(G - 1).  Model-based errors of one model (`by=None`, `std_err="se"`) are
+    `GLM.fit(report=True)` / `lstsq.glm_report`, not an expression (ValueError); robust errors of per-group reports (`by` with a
+    robust kind) are not built (NotImplementedError).
     """
     from .linear_models import GLM_FAMILIES
+    from .lstsq import _glm_std_err_check
 
+    _glm_std_err_check("glm_report", std_err, cluster, None)
+    if by is not None and std_err != "se":
+        raise NotImplementedError("glm_report: robust / clustered errors of per-group reports (`by` with std_err != \"se\") are not built")
+    if by is None and std_err == "se":
+        raise ValueError('glm_report: `by=None` with std_err="se" is no expression: use GLM.fit(report=True) or lstsq.glm_report')
     if family not in GLM_FAMILIES:
         raise NotImplementedError(f"GLM family {family!r}: one of {sorted(GLM_FAMILIES)}")
     if max_iter < 1:
         raise ValueError("`max_iter` must be > 1.")
     kwargs = {"bias": add_bias, "null_policy": null_policy, "family": family, "tol": abs(tol), "max_iter": max_iter}
+    if by is None:
+        # (every flag is sent: the symbol is new, there is no older kwargs dict to keep)
+        kwargs.update(std_err=std_err, has_cluster=cluster is not None, has_weights=weights is not None, has_offset=offset is not None)
+        lead = ([_formula(cluster)] if cluster is not None else []) + [_formula(c).cast(_dtype()) for c in (weights, offset) if c is not None]
+        cols = [*lead, _formula(target).cast(_dtype())] + [_formula(z) for z in x]
+        return _plugin("pl_glm_report_robust", cols, kwargs, changes_length=True).alias("glm_report")
     extra = []
     if weights is not None:
         kwargs["has_weights"] = True
