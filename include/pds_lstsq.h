@@ -361,6 +361,70 @@ int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const 
                                   int64_t* n_groups);
 
 /*
+ * pds_lin_reg_within2_*: fixed-effects regression with TWO absorbed factors -- ONE model with an intercept per level of each of two
+ * keys, y_i = alpha_g1(i) + gamma_g2(i) + x_i' beta + e_i (firm and year effects: two-way fixed effects); no dummy column is ever
+ * formed.  cols = [y, x1..xp], 1 .. 16 feature columns and NO intercept column.  What follows is a DEFINITION of what the library
+ * computes; no equivalence with the small-sample conventions of any package is claimed beyond this text.
+ *   n rows, p features.  Factor 1 has G1 occupied levels, factor 2 G2.  C is the number of connected components of the bipartite
+ *   graph whose edges are the occupied (level1, level2) cells; A = G1 + G2 - C is the rank of the absorbed dummies.  z~ is the column
+ *   z projected off both sets of dummies; X~, y~ the projected features and target.
+ *   beta solves X~'X~ beta = X~'y~;  e = y~ - X~ beta;  pred = y - e.
+ *   se_type PDS_SE:       V = s2 (X~'X~)^-1, s2 = sum e^2 / (n - p - A); t, p and the 95 % interval use the Student t with n - p - A
+ *                         degrees of freedom (the tail of pds_lin_reg_within_*).
+ *   se_type PDS_CLUSTER0: V = (X~'X~)^-1 M (X~'X~)^-1, M = sum_g s_g s_g', s_g = sum_{i in g} x~_i e_i: the clusters are the levels of
+ *                         the FIRST key.
+ *   se_type PDS_CLUSTER:  the same V times G1 / (G1 - 1) * (n - 1) / (n - K), K = p + 1 + (A - G1): the effects of the first factor,
+ *                         nested in the clusters, count as the one intercept; those of the second factor are counted.  With one
+ *                         factor this is the definition of pds_lin_reg_within_*.  Both cluster forms use G1 - 1 degrees of freedom.
+ *   out->r2 = 1 - sum e^2 / sum y~^2, out->adj_r2 = 1 - (1 - r2)(n - A) / (n - A - p), extra->r2_overall = 1 - sum e^2 / sum (y - ybar)^2.
+ * The projection is by alternating sweeps over all p + 1 columns in f64 (f32 frames too).  One sweep subtracts the factor-1 level
+ * means, then the factor-2 level means.  After each sweep delta = max_j max_level |factor-2 mean subtracted from column j in this
+ * sweep| / s_j, s_j the population standard deviation of the original column j (one moment pass; it is only a scale).  The sweeps stop
+ * when delta <= absorb_tol (> 0, else PDS_ERR_INVALID; 1e-8 is reghdfe's default).  absorb_max_iter (>= 1) sweeps without that:
+ * PDS_ERR_NUMERIC, the message says "did not converge" and gives the last delta; nothing is returned.  extra->n_iter is the number
+ * of sweeps used.  The device keeps the subtracted means as two tables and forms every working value from the row's original value:
+ * two reads of the frame per sweep, no write, and the rounding of one sweep is not carried into the next.
+ *   The first factor enters exactly as in pds_lin_reg_within_*: group_offsets (grouped), or int64 keys in any row order (by key: the
+ *   stable sort + gather of the other by-key entry points; *n_groups receives G1).  The second factor enters as dense int32 codes
+ *   per row in [0, n_levels2), `space`-resident, in the CALLER's row order (the by-key form gathers them through its row
+ *   permutation).  A code outside the range: PDS_ERR_INVALID.  Unused codes count nowhere.  Fewer than 2^31 rows per call.
+ * out: as pds_lin_reg_within_* (std_err .. ci_upper may ALL be NULL: the fit-only call).  extra (nullable): pred / resid are
+ * `space`-resident arrays of the frame's type, each nullable, in the caller's row order.
+ * Refused, never approximated: n - p - A <= 0 PDS_ERR_TOO_FEW_ROWS; a cluster form with G1 < 2 PDS_ERR_INVALID; a feature that is
+ * constant PDS_ERR_NUMERIC; a feature whose projected sum of squares sum x~^2 is not above min(1e-4, max(1e-12, (1e3 absorb_tol)^2)) -- 1e-10 at
+ * the default tolerance -- times its centred sum of squares sum (x - xbar)^2 (a function of the keys: collinear with the absorbed
+ * effects) PDS_ERR_NUMERIC, the message naming the column index; X~'X~ not positive definite otherwise PDS_ERR_NUMERIC; more than 16
+ * features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.  There is no weighted form, and the effects themselves are not
+ * returned (they need a normalisation).  A workspace the device cannot hold fails with the allocation's error.
+ * C is counted exactly by a union-find over the cells on the host, in one pass over the codes (a device frame's codes are fetched
+ * for it).  Two calls give the same bits (no floating-point atomics; every sum in a fixed order).  Levels of factor 1 above the
+ * context option "within_split_rows" are cut into row chunks; every level of factor 2 is cut into chunks of at most 1 024 gathered
+ * rows (of "within_split_rows" rows if that is smaller).
+ */
+typedef struct {            /* every pointer nullable and `space`-resident */
+    void* pred;             /* [n_rows], frame order */
+    void* resid;            /* [n_rows], frame order */
+    double r2_overall;
+    int64_t df_resid;       /* n - p - A ("se") or G1 - 1 (cluster forms) */
+    int64_t n_groups_used;  /* G1 */
+    int64_t n_groups2_used; /* G2 */
+    int64_t n_components;   /* C */
+    int64_t n_iter;         /* sweeps used */
+} pds_within2_out;
+int pds_lin_reg_within2_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                    int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                    double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra);
+int pds_lin_reg_within2_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                    int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                    double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra);
+int pds_lin_reg_within2_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                   int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                   pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups);
+int pds_lin_reg_within2_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                   int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                   pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups);
+
+/*
  * Row-sharded `pl_lin_reg_report` / `pl_wls_report` (one process per GPU): the stages of
  * pds_lin_reg_report_* as separate calls, the two exchange steps between them left to the caller.
  *   1. every rank: pds_moments_* on its rows                     -> all-reduce(SUM) of the (p+2)^2 block

@@ -41,6 +41,7 @@ EXPORTS = [
     "pds_lin_reg_report_cluster_grouped_f64", "pds_lin_reg_report_cluster_grouped_f32",
     "pds_lin_reg_report_cluster_by_key_f64", "pds_lin_reg_report_cluster_by_key_f32",
     "pds_lin_reg_within_grouped_f64", "pds_lin_reg_within_grouped_f32", "pds_lin_reg_within_by_key_f64", "pds_lin_reg_within_by_key_f32",
+    "pds_lin_reg_within2_grouped_f64", "pds_lin_reg_within2_grouped_f32", "pds_lin_reg_within2_by_key_f64", "pds_lin_reg_within2_by_key_f32",
     "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
@@ -106,6 +107,12 @@ class WithinOut(C.Structure):
                 ("n_groups_used", C.c_int64), ("df_resid", C.c_int64)]
 
 
+class Within2Out(C.Structure):
+    """pds_within2_out: the two-factor fixed-effects fit's nullable per-row outputs and its counts."""
+    _fields_ = [("pred", C.c_void_p), ("resid", C.c_void_p), ("r2_overall", C.c_double), ("df_resid", C.c_int64),
+                ("n_groups_used", C.c_int64), ("n_groups2_used", C.c_int64), ("n_components", C.c_int64), ("n_iter", C.c_int64)]
+
+
 class PdsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[pds {code}] {msg}")
@@ -169,6 +176,15 @@ def load() -> C.CDLL:
                 # ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups
                 getattr(lib, "pds_lin_reg_within_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pds_lin_reg_within2_grouped_" + sfx):
+                # ctx, cols, n_feat, n_rows, group_offsets, n_groups, codes2, n_levels2, space, se_type, absorb_tol, absorb_max_iter, out, extra
+                getattr(lib, "pds_lin_reg_within2_grouped_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                                                             C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                                             C.c_void_p, C.c_void_p]
+                # ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol, absorb_max_iter, out, extra, n_groups
+                getattr(lib, "pds_lin_reg_within2_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                                                            C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                                                            C.c_void_p, C.c_void_p]
         if hasattr(lib, "pds_ctx_workspace_bytes"):
             lib.pds_ctx_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
             lib.pds_ctx_workspace_bytes.restype = C.c_longlong

@@ -37,6 +37,7 @@ namespace pds {
 #include "capi_mixed.hpp"
 #include "capi_report_cluster.hpp"
 #include "capi_within.hpp"
+#include "capi_within2.hpp"
 #include "capi_glm_sandwich.hpp"
 
 }  // namespace pds
@@ -649,6 +650,30 @@ int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const 
                                   int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f32* out, pds_within_out* extra,
                                   int64_t* n_groups) {
     return within_by_key_impl<float, pds_report_f32>(ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups);
+}
+int pds_lin_reg_within2_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                    int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                    double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra) {
+    return within2_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type,
+                                                absorb_tol, absorb_max_iter, out, extra);
+}
+int pds_lin_reg_within2_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                    int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                    double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra) {
+    return within2_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type,
+                                               absorb_tol, absorb_max_iter, out, extra);
+}
+int pds_lin_reg_within2_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                   int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                   pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups) {
+    return within2_by_key_impl<double, pds_report_f64>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
+                                                       absorb_max_iter, out, extra, n_groups);
+}
+int pds_lin_reg_within2_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                   int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                   pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups) {
+    return within2_by_key_impl<float, pds_report_f32>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
+                                                      absorb_max_iter, out, extra, n_groups);
 }
 
 int pds_report_fit_from_moments_f64(pds_ctx* ctx, const double* moments, int n_feat, int add_bias, double* beta, double* inv) {

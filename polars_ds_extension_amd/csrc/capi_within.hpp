@@ -83,11 +83,21 @@ static int within_check_se(int se_type) {
     return PDS_OK;
 }
 
+// What the two-factor pipeline (capi_within2.hpp) tells the final stage when it hands it columns that are projected off a second
+// factor already.  Absent: the one-factor fit, whose bits do not depend on this struct.
+struct WithinMore {
+    int64_t extra_df = 0;         // absorbed degrees of freedom beyond one per group
+    double tss = 0.0;             // sum (y - ybar)^2 of the ORIGINAL target: r2_overall is formed from it
+    const double* css = nullptr;  // [p] sum (x - xbar)^2 of the original features: a feature has to keep ...
+    double min_share = 0.0;       // ... more than this share of it, or it is refused as collinear with the absorbed effects
+};
+
 // cols / offsets live in `space`; the outputs of `extra` (and out_keys' caller) in `out_space`.  d_perm (nullable): row r of this
-// frame is row d_perm[r] of the caller's (the by-key form).
+// frame is row d_perm[r] of the caller's (the by-key form).  R's value type may be narrower than T (f64 columns of an f32 report).
 template <typename T, typename R>
 static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
-                       pds_space out_space, int se_type, R* out, pds_within_out* extra, const uint32_t* d_perm = nullptr) {
+                       pds_space out_space, int se_type, R* out, pds_within_out* extra, const uint32_t* d_perm = nullptr,
+                       const WithinMore* more = nullptr) {
     if (!ctx || !cols || !offsets || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
     if (int rc = within_check_se(se_type)) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
@@ -112,7 +122,8 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
                                    "absorbed group offsets must be non-decreasing and cover the frame", pl))
         return rc;
     const int64_t n_nonempty = pl.n_nonempty, n_chunks = pl.n_chunks(), n_long = pl.n_long();
-    const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p;
+    const int64_t extra_df = more ? more->extra_df : 0;
+    const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p - extra_df;
     if (extra) extra->n_groups_used = n_nonempty;
     if (se_type != PDS_SE && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     if (df_se <= 0) return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #groups - #features <= 0. No conclusive result.");
@@ -175,7 +186,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     if (int rc = launch_mixed_stats<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, nullptr, d_means, d_flags, d_partials, d_stage, d_rec)) return rc;
     double stat[kMixedRecStride];
     unsigned vary = 0;
-    const bool want_overall = extra != nullptr;
+    const bool want_overall = extra != nullptr && !more;
     std::vector<double> my;
     if (want_overall) {
         my.resize((size_t)n_groups);
@@ -184,6 +195,11 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     PDS_HIP_CHECK(hipMemcpyAsync(stat, d_rec, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl: sources of the copies)
+    if (more && more->css)
+        for (int j = 0; j < p; ++j)
+            if (!(stat[kMixedRecW + j * 16 + j] > more->min_share * more->css[j]))
+                return fail(PDS_ERR_NUMERIC, "fixed-effects regression: feature column " + std::to_string(j) +
+                                                 " is a function of the absorbed keys (collinear with the absorbed effects)");
     // ---- stage 2: the solve
     double beta[kMaxFeatSmall] = {0}, inv[kMaxFeatSmall * kMaxFeatSmall];
     if (int rc = within_solve(p, stat, vary, beta, inv)) return rc;
@@ -201,13 +217,16 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (beta: source of the copy)
     // ---- the O(p^2) epilogue
     const double sse = rec[kMixedRecYY] + rec[kMixedRecCY], wyy = stat[kMixedRecYY];
-    const double nd = (double)n_rows, gd = (double)n_nonempty;
+    const double nd = (double)n_rows, gd = (double)n_nonempty, xd = (double)extra_df;  // (xd = 0: every term below keeps its bits)
     const double r2 = 1.0 - sse / wyy;
     out->r2 = (T)r2;
-    out->adj_r2 = (T)(1.0 - (1.0 - r2) * ((nd - gd) / (double)df_se));
+    out->adj_r2 = (T)(1.0 - (1.0 - r2) * ((nd - gd - xd) / (double)df_se));
     for (int i = 0; i < p; ++i) out->beta[i] = (T)beta[i];
     const int64_t df = se_type == PDS_SE ? df_se : n_nonempty - 1;
-    if (extra) {
+    if (extra && more) {
+        extra->r2_overall = 1.0 - sse / more->tss;
+        extra->df_resid = df;
+    } else if (extra) {
         double ybar = 0.0, between = 0.0;
         for (int64_t g = 0; g < n_groups; ++g) ybar += (double)(h_off[g + 1] - h_off[g]) * my[(size_t)g];
         ybar /= nd;
@@ -224,7 +243,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
         const double s2 = sse / (double)df_se;
         for (int i = 0; i < p; ++i) se[i] = std::sqrt(s2 * inv[i * p + i]);
     } else {
-        const double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0)) : 1.0;
+        const double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0 - xd)) : 1.0;
         for (int i = 0; i < p; ++i) {
             double acc = 0.0;
             for (int a = 0; a < p; ++a) {

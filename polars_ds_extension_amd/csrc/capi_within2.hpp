@@ -1,0 +1,319 @@
+// capi_within2.hpp -- fixed-effects regression with TWO absorbed factors (pds_lin_reg_within2_grouped_* / _by_key_*): ONE model with an
+// intercept per level of each of two keys, y_i = alpha_g1(i) + gamma_g2(i) + x_i' beta + e_i (firm and year effects: the two-way
+// fixed-effects model), fitted without ever forming a dummy column.
+// Part of the one translation unit capi.hip (included there, inside namespace pds, in dependency order): the entry-point
+// pipelines are templates with internal linkage, split by concern, not by compilation unit.
+//
+// DEFINITIONS (what this file computes; no equivalence with any package's small-sample conventions is claimed beyond this text).
+// n rows, p features (1 .. 16), no intercept column.  Factor 1 has G1 occupied levels, factor 2 G2.  C is the number of connected
+// components of the bipartite graph whose edges are the occupied (level1, level2) cells; A = G1 + G2 - C is the rank of the absorbed
+// dummies.  z~ is the column z projected off both sets of dummies; X~, y~ the projected features and target:
+//     beta solves X~'X~ beta = X~'y~;   e = y~ - X~ beta;   pred = y - e
+//     PDS_SE        V = s2 (X~'X~)^-1, s2 = sum e^2 / (n - p - A); t, p and the 95 % interval: Student t, n - p - A degrees of freedom
+//                   (student_t_sf_wide, as the one-factor fit)
+//     PDS_CLUSTER0  V = (X~'X~)^-1 M (X~'X~)^-1, M = sum_g s_g s_g', s_g = sum_{i in g} x~_i e_i: the clusters are the levels of the
+//                   FIRST key
+//     PDS_CLUSTER   the same V times G1 / (G1 - 1) * (n - 1) / (n - K), K = p + 1 + (A - G1): the effects of the first factor, nested in
+//                   the clusters, count as the one intercept, those of the second factor are counted.  With one factor (A = G1) this is
+//                   capi_within.hpp's definition.  Both cluster forms: G1 - 1 degrees of freedom
+//     r2 = 1 - sum e^2 / sum y~^2;   adj_r2 = 1 - (1 - r2)(n - A) / (n - A - p);   r2_overall = 1 - sum e^2 / sum (y - ybar)^2
+// PROJECTION by alternating sweeps over all p + 1 columns in f64 (f32 frames too).  One sweep subtracts the factor-1 level means, then
+// the factor-2 level means; delta = max_j max_level |factor-2 mean subtracted from column j in this sweep| / s_j, s_j the population
+// standard deviation of the original column j (from one moment pass: only a scale); the sweeps stop when delta <= absorb_tol
+// (> 0; 1e-8 is reghdfe's default).  absorb_max_iter sweeps without that: PDS_ERR_NUMERIC, "did not converge" with the last delta,
+// nothing returned.  The device keeps the subtracted means as two tables and forms a row's working value from its original value
+// (within2_sweep.hip): the same sweep, two reads of the frame and no write.
+// COLLINEARITY.  A feature that is a function of the keys is projected to (numerically) nothing: a feature whose projected sum of
+// squares is not above kWithin2ShareFloor = 1e-12, or (1e3 absorb_tol)^2 if that is larger (but at most 1e-4) -- 1e-10 at the default
+// tolerance --, times its centred sum of squares sum (x - xbar)^2 is refused by index with PDS_ERR_NUMERIC.  (What a sweep at tolerance delta leaves of
+// such a column is of the order delta s_j / (1 - rate) per row; 1e3 covers a convergence rate of 0.999.)
+// COMPONENTS.  C comes from a union-find over the cells on the host, in the same pass over the codes that validates them and counts
+// the levels of factor 2 (the codes of a device frame are fetched for it: 4 bytes per row).
+//
+// Stages: the factor-1 offsets and their chunks (plan_group_chunks); the codes of factor 2 in frame order on device and host; the host
+// pass (range, counts, components); launch_within2_init (f64 row-major copy, moments), the row -> level map, the code ordering
+// (launch_within2_order); the sweep loop ON THE HOST, one small blocking copy (the per-wave maxima of delta) per sweep; the projected
+// columns written column-major (launch_within2_final) and handed to the FINAL STAGE of the one-factor fit -- within_impl on them with
+// factor 1's offsets: its statistics pass, host solve, within pass, scores and meat -- told the extra absorbed degrees of freedom
+// G2 - C and the original target's sum of squares; pred / resid from the residuals and the ORIGINAL target (launch_within2_rows_out).
+#pragma once
+
+// every level of factor 2 is cut into chunks of at most this many gathered rows ("within_split_rows", if smaller, takes its place)
+constexpr int64_t kWithin2GatherChunkRows = 1024;
+constexpr double kWithin2ShareFloor = 1e-12, kWithin2ShareTolFactor = 1e3, kWithin2ShareCap = 1e-4;
+
+template <typename T, typename R>
+static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
+                        const int32_t* codes2, pds_space code_space, int64_t n_levels2, pds_space out_space, int se_type, double tol, int max_iter,
+                        R* out, pds_within2_out* extra, const uint32_t* d_perm = nullptr) {
+    if (!ctx || !cols || !offsets || !codes2 || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = within_check_se(se_type)) return rc;
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
+    if (n_rows <= 0 || n_groups <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression with two absorbed keys: fewer than 2^31 rows per call");
+    if (n_levels2 < 1 || n_levels2 >= (1ll << 31)) return fail(PDS_ERR_INVALID, "fixed-effects regression: n_levels2 is in [1, 2^31)");
+    if (!(tol > 0.0) || !std::isfinite(tol)) return fail(PDS_ERR_INVALID, "fixed-effects regression: absorb_tol must be > 0");
+    if (max_iter < 1) return fail(PDS_ERR_INVALID, "fixed-effects regression: absorb_max_iter must be >= 1");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    const bool want_se = out->std_err || out->t || out->p || out->ci_lower || out->ci_upper;
+    if (want_se && !(out->std_err && out->t && out->p && out->ci_lower && out->ci_upper))
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: std_err .. ci_upper are given together or not at all");
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int p = n_feat, nc = p + 1;
+    const int64_t n = n_rows;
+    // ---- factor 1: the offsets on the host, the non-empty levels, the chunks of the long ones
+    std::vector<int64_t> off_copy;
+    const int64_t* h_off = nullptr;
+    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
+    const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
+    GroupChunkPlan pl;
+    if (int rc = plan_group_chunks(h_off, n_groups, n, split, /*cover=*/true, /*offsets_on_host=*/true, /*want_gmap=*/false,
+                                   "absorbed group offsets must be non-decreasing and cover the frame", pl))
+        return rc;
+    h_off = pl.h_off;
+    const int64_t n1 = pl.n_nonempty, n_chunks1 = pl.n_chunks(), n_long1 = pl.n_long();
+    if (se_type != PDS_SE && n1 < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
+    // ---- workspace (ctx->ws: the by-key form's ordered frame lives in ctx->keyed, the final stage works in ctx->wkeyed)
+    const auto up = Bump::up;
+    const bool out_host = out_space == PDS_HOST, want_rows = extra && (extra->pred || extra->resid);
+    const int64_t chunk2 = std::max<int64_t>(64, std::min<int64_t>(split, kWithin2GatherChunkRows));
+    const int64_t lev_cap = std::min<int64_t>(n, n_levels2), c2_cap = n / chunk2 + lev_cap + 1;
+    const int n_init = within2_init_records(ctx, n);
+    const size_t sort_temp = within2_order_temp_bytes(n);
+    T *d_pred = nullptr, *d_resid = nullptr;
+    StagedOuts row_outs(out_host, (size_t)n);
+    if (extra) {
+        row_outs.add(&d_pred, static_cast<T*>(extra->pred), 1);
+        row_outs.add(&d_resid, static_cast<T*>(extra->resid), 1);
+    }
+    size_t need = 8192 + up(sizeof(T*) * 18) + up((size_t)(n1 + 1) * 8) + 9 * up((size_t)(n_chunks1 + n_long1 + 1) * 8) +
+                  up((size_t)(n_chunks1 + 1) * nc * 8) + up((size_t)(n_chunks1 + 1) * 4) + 6 * up((size_t)n * 4) + sort_temp +
+                  up((size_t)n * nc * 8) + up((size_t)n * 8) + up((size_t)n1 * nc * 8) + up((size_t)n_levels2 * nc * 8) + 2 * up((size_t)c2_cap * 8) +
+                  up((size_t)c2_cap * 4) + 3 * up((size_t)lev_cap * 8) + up((size_t)lev_cap * 4) + up((size_t)c2_cap * nc * 8) +
+                  up((size_t)n_init * 2 * nc * 8) + 3 * up(64 * 8) + up((size_t)within2_delta_blocks(ctx, lev_cap) * 8) + row_outs.bytes();
+    if (space == PDS_HOST) need += up((size_t)n * sizeof(T)) * nc;
+    if (int rc = ensure_ws(ctx, ctx->ws, need)) return rc;
+    Bump w{static_cast<char*>(ctx->ws.ptr)};
+    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
+    if (space == PDS_HOST)
+        if (int rc = cols_to_device<T>(ctx, w, src, n)) return rc;
+    std::vector<const T*> tbl;
+    const T** d_tbl = nullptr;
+    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
+    Within2Dev dev;
+    dev.n_rows = n;
+    dev.n1 = n1;
+    dev.split1 = split;
+    {
+        int64_t* t = w.take<int64_t>((size_t)n1 + 1);
+        PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n1 + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        dev.d_off1 = t;
+    }
+    if (int rc = upload_mixed_chunks(ctx, w, pl, nc, dev.ch1)) return rc;
+    // ---- the codes of factor 2 in frame order, on the device and on the host
+    const int32_t* d_in = codes2;
+    if (code_space == PDS_HOST) {
+        int32_t* t = w.take<int32_t>((size_t)n);
+        PDS_HIP_CHECK(hipMemcpyAsync(t, codes2, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_in = t;
+    }
+    dev.d_code2 = d_in;
+    if (d_perm) {
+        int32_t* t = w.take<int32_t>((size_t)n);
+        if (int rc = launch_within2_gather_codes(ctx, d_in, d_perm, n, t)) return rc;
+        dev.d_code2 = t;
+    }
+    std::vector<int32_t> code_copy;
+    const int32_t* h_code = codes2;
+    std::vector<int64_t> cnt2;
+    std::vector<uint32_t> parent;
+    try {
+        if (code_space != PDS_HOST || d_perm) {
+            code_copy.resize((size_t)n);
+            PDS_HIP_CHECK(hipMemcpyAsync(code_copy.data(), dev.d_code2, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            h_code = code_copy.data();
+        }
+        cnt2.assign((size_t)n_levels2, 0);
+        parent.resize((size_t)(n1 + n_levels2));
+    } catch (const std::bad_alloc&) {
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: no host memory for the codes of the second absorbed key");
+    }
+    // ---- the host pass: range, level counts, components (union-find over the cells; a merge adds one to the rank A)
+    for (size_t i = 0; i < parent.size(); ++i) parent[i] = (uint32_t)i;
+    auto find = [&](uint32_t a) {
+        while (parent[a] != a) {
+            parent[a] = parent[parent[a]];
+            a = parent[a];
+        }
+        return a;
+    };
+    int64_t rank_a = 0;
+    for (int64_t g = 0; g < n1; ++g) {
+        int64_t last = -1;
+        for (int64_t r = h_off[g]; r < h_off[g + 1]; ++r) {
+            const int64_t l = h_code[r];
+            if (l < 0 || l >= n_levels2) return fail(PDS_ERR_INVALID, "fixed-effects regression: a code of the second absorbed key is outside [0, n_levels2)");
+            ++cnt2[(size_t)l];
+            if (l == last) continue;
+            last = l;
+            const uint32_t a = find((uint32_t)g), b = find((uint32_t)(n1 + l));
+            if (a != b) {
+                parent[a] = b;
+                ++rank_a;
+            }
+        }
+    }
+    std::vector<int64_t> c_pos, c_n, l_c0, l_nc, l_n;
+    std::vector<int32_t> c_code, l_code;
+    {
+        int64_t pos = 0;
+        for (int64_t l = 0; l < n_levels2; ++l) {
+            const int64_t m = cnt2[(size_t)l];
+            if (m == 0) continue;
+            const int64_t k = (m + chunk2 - 1) / chunk2;
+            l_c0.push_back((int64_t)c_pos.size());
+            l_nc.push_back(k);
+            l_n.push_back(m);
+            l_code.push_back((int32_t)l);
+            for (int64_t i = 0; i < k; ++i) {
+                c_pos.push_back(pos + i * chunk2);
+                c_n.push_back(std::min<int64_t>(chunk2, m - i * chunk2));
+                c_code.push_back((int32_t)l);
+            }
+            pos += m;
+        }
+    }
+    const int64_t n2 = (int64_t)l_n.size(), n_comp = n1 + n2 - rank_a, extra_df = n2 - n_comp;
+    if (extra) {
+        extra->n_groups_used = n1;
+        extra->n_groups2_used = n2;
+        extra->n_components = n_comp;
+        extra->n_iter = 0;
+    }
+    if (n - p - rank_a <= 0)
+        return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #features - rank of the absorbed effects <= 0. No conclusive result.");
+    dev.n_chunks2 = (int64_t)c_pos.size();
+    dev.n_lev2 = n2;
+    auto put = [&](const auto& h, auto*& d) -> int {
+        using U = std::remove_const_t<std::remove_reference_t<decltype(h[0])>>;
+        U* t = w.take<U>(h.size());
+        PDS_HIP_CHECK(hipMemcpyAsync(t, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, ctx->stream));
+        d = t;
+        return PDS_OK;
+    };
+    if (int rc = put(c_pos, dev.d_c2_pos)) return rc;
+    if (int rc = put(c_n, dev.d_c2_n)) return rc;
+    if (int rc = put(c_code, dev.d_c2_code)) return rc;
+    if (int rc = put(l_c0, dev.d_l2_c0)) return rc;
+    if (int rc = put(l_nc, dev.d_l2_nc)) return rc;
+    if (int rc = put(l_n, dev.d_l2_n)) return rc;
+    if (int rc = put(l_code, dev.d_l2_code)) return rc;
+    dev.d_csum2 = w.take<double>((size_t)dev.n_chunks2 * nc);
+    // ---- the f64 copy and the moments; the row -> level map; the rows in code order
+    dev.d_w0 = w.take<double>((size_t)n * nc);
+    double* d_init = w.take<double>((size_t)n_init * 2 * nc);
+    double* d_mom = w.take<double>(64);
+    if (int rc = launch_within2_init<T>(ctx, d_tbl, p, n, dev.d_w0, d_init, d_mom)) return rc;
+    {
+        uint32_t* g1 = w.take<uint32_t>((size_t)n);
+        if (int rc = launch_within2_row_levels(ctx, dev.d_off1, n1, n, g1)) return rc;
+        dev.d_g1 = g1;
+        uint32_t *iota = w.take<uint32_t>((size_t)n), *sorted = w.take<uint32_t>((size_t)n), *idx2 = w.take<uint32_t>((size_t)n);
+        void* temp = w.take<char>(sort_temp);
+        if (int rc = launch_within2_order(ctx, dev.d_code2, n, n_levels2, iota, sorted, idx2, temp, sort_temp)) return rc;
+        dev.d_idx2 = idx2;
+    }
+    double mom[2 * (kMaxFeatSmall + 1)];
+    PDS_HIP_CHECK(hipMemcpyAsync(mom, d_mom, sizeof(double) * 2 * nc, hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, the chunk lists: sources of the copies)
+    double css[kMaxFeatSmall + 1], scale[64] = {0};
+    for (int c = 0; c < nc; ++c) {  // (kernel order: the features, then y)
+        css[c] = std::max(mom[nc + c] - mom[c] * mom[c] / (double)n, 0.0);
+        scale[c] = std::sqrt(css[c] / (double)n);
+        if (!(scale[c] > 0.0)) {
+            if (c < p) return fail(PDS_ERR_NUMERIC, "fixed-effects regression: feature column " + std::to_string(c) + " is constant or not finite");
+            scale[c] = 1.0;
+        }
+    }
+    dev.d_scale = w.take<double>(64);
+    PDS_HIP_CHECK(hipMemcpyAsync(dev.d_scale, scale, sizeof(scale), hipMemcpyHostToDevice, ctx->stream));
+    dev.d_a1 = w.take<double>((size_t)n1 * nc);
+    dev.d_a2 = w.take<double>((size_t)n_levels2 * nc);
+    PDS_HIP_CHECK(hipMemsetAsync(dev.d_a1, 0, (size_t)n1 * nc * 8, ctx->stream));
+    PDS_HIP_CHECK(hipMemsetAsync(dev.d_a2, 0, (size_t)n_levels2 * nc * 8, ctx->stream));
+    const int n_delta = within2_delta_blocks(ctx, n2);
+    dev.d_delta = w.take<double>((size_t)n_delta);
+    double* d_e = want_rows ? w.take<double>((size_t)n) : nullptr;
+    row_outs.place(w);
+    // ---- the sweeps: the loop lives here, bounded by absorb_max_iter
+    std::vector<double> h_delta((size_t)n_delta);
+    double delta = INFINITY;
+    int n_iter = 0;
+    bool converged = false;
+    while (n_iter < max_iter && !converged) {
+        if (int rc = launch_within2_sweep<T>(ctx, d_tbl, p, dev)) return rc;
+        ++n_iter;
+        PDS_HIP_CHECK(hipMemcpyAsync(h_delta.data(), dev.d_delta, (size_t)n_delta * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        delta = 0.0;
+        for (double v : h_delta) delta = (v > delta || v != v) ? v : delta;
+        if (delta != delta) return fail(PDS_ERR_NUMERIC, "fixed-effects regression: a level mean is not finite (NaN or infinite values in the frame)");
+        converged = delta <= tol;
+    }
+    if (extra) extra->n_iter = n_iter;
+    if (!converged) {
+        char msg[256];
+        std::snprintf(msg, sizeof(msg), "fixed-effects regression: the alternating sweeps did not converge in %d sweeps (last delta = %.3e, absorb_tol = %.3e)",
+                      n_iter, delta, tol);
+        return fail(PDS_ERR_NUMERIC, msg);
+    }
+    // ---- the final stage: the one-factor fit on the projected columns (they take the place of the f64 copy, which is done with)
+    double* d_z = dev.d_w0;
+    if (int rc = launch_within2_final<T>(ctx, d_tbl, p, dev, d_z)) return rc;
+    std::vector<const double*> zc((size_t)nc);
+    zc[0] = d_z + (size_t)p * n;
+    for (int j = 0; j < p; ++j) zc[(size_t)j + 1] = d_z + (size_t)j * n;
+    const double share = std::min(kWithin2ShareCap, std::max(kWithin2ShareFloor, (kWithin2ShareTolFactor * tol) * (kWithin2ShareTolFactor * tol)));
+    WithinMore more;
+    more.extra_df = extra_df;
+    more.tss = css[p];
+    more.css = css;
+    more.min_share = share;
+    pds_within_out wo{};
+    wo.resid = d_e;
+    if (int rc = within_impl<double, R>(ctx, zc.data(), p, n, dev.d_off1, n1, PDS_DEVICE, PDS_DEVICE, se_type, out, &wo, nullptr, &more)) return rc;
+    if (extra) {
+        extra->r2_overall = wo.r2_overall;
+        extra->df_resid = wo.df_resid;
+    }
+    if (want_rows) {
+        if (int rc = launch_within2_rows_out<T>(ctx, tbl[(size_t)p], d_e, d_perm, n, d_pred, d_resid)) return rc;
+        if (int rc = staged_copy_back(ctx, row_outs, (size_t)n)) return rc;
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return PDS_OK;
+}
+
+// int64 keys of factor 1 in any row order: the shared key-ordering stage, then the contiguous form on the ordered frame; the codes of
+// factor 2 stay in the caller's row order and are gathered through the row permutation.
+template <typename T, typename R>
+static int within2_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2, int n_feat,
+                               int64_t n_rows, pds_space space, int se_type, double tol, int max_iter, R* out, pds_within2_out* extra,
+                               int64_t* n_groups) {
+    if (!ctx || !cols || !keys || !codes2 || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = within_check_se(se_type)) return rc;
+    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
+    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression with two absorbed keys: fewer than 2^31 rows per call");
+    if (int rc = check_cols<T>(cols, n_feat)) return rc;
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    KeyedFrame<T> kf;
+    kf.src = frame_cols<T>(cols, n_feat);
+    Bump w{};
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w)) return rc;
+    return within2_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, codes2, space, n_levels2, space, se_type, tol,
+                              max_iter, out, extra, kf.d_perm);
+}

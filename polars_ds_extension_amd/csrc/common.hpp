@@ -155,7 +155,7 @@ inline const char* dev_env(const char*) { return nullptr; }
 #endif
 
 // kernel classes for the timing hooks
-enum { kKindMoments = 0, kKindGroupedMoments = 1, kKindSolve = 2, kKindPass2 = 3, kKindRolling = 4, kKindIter = 5 };
+enum { kKindMoments = 0, kKindGroupedMoments = 1, kKindSolve = 2, kKindPass2 = 3, kKindRolling = 4, kKindIter = 5, kKindSweep1 = 6, kKindSweep2 = 7 };
 // RAII: records a HIP event pair around the launches issued in its scope when ctx->timing is on
 struct KernelTimer {
     pds_ctx* ctx;
@@ -488,6 +488,42 @@ template <typename T>
 int launch_within_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
                        const MixedChunks& ch, double* d_scores, const double* d_beta, const double* d_means, bool meat, const int64_t* d_gmap,
                        const uint32_t* d_perm, T* d_alpha, T* d_pred, T* d_resid, double* d_partials, double* d_stage, double* d_rec);
+// ---- within2_sweep.hip: the alternating sweeps of the fixed-effects regression with two absorbed factors (capi_within2.hpp).  The device
+// arrays of one call (nc = p + 1): the state is a1 / a2, the accumulated level means; row r is worth (w_r - a1[g1(r)]) - a2[code2(r)].
+struct Within2Dev {
+    int64_t n_rows = 0, n1 = 0, split1 = 0;  // rows; occupied levels of factor 1; its levels above split1 rows are the chunks ch1
+    const int64_t* d_off1 = nullptr;         // n1 + 1 offsets
+    MixedChunks ch1;                         // (d_sums: the chunk sums)
+    const int32_t* d_code2 = nullptr;        // [n_rows] the code of factor 2 of every row, frame order, validated by the host
+    const uint32_t* d_idx2 = nullptr;        // [n_rows] the rows in ascending code order (launch_within2_order)
+    const uint32_t* d_g1 = nullptr;          // [n_rows] the level of factor 1 of every row (launch_within2_row_levels)
+    int64_t n_chunks2 = 0, n_lev2 = 0;       // chunks of idx2 (every level is cut from the start); occupied levels of factor 2
+    const int64_t *d_c2_pos = nullptr, *d_c2_n = nullptr;                       // per chunk: first place in idx2, rows
+    const int32_t* d_c2_code = nullptr;                                         // ... and the code
+    const int64_t *d_l2_c0 = nullptr, *d_l2_nc = nullptr, *d_l2_n = nullptr;    // per occupied level: first chunk, chunks, rows
+    const int32_t* d_l2_code = nullptr;                                         // ... and the code
+    double *d_csum2 = nullptr, *d_w0 = nullptr, *d_a1 = nullptr, *d_a2 = nullptr;  // n_chunks2 x nc; n_rows x nc; n1 x nc; codes x nc
+    double *d_scale = nullptr, *d_delta = nullptr;  // [nc] s_j; within2_delta_blocks(n_lev2) values per sweep, their maximum is delta
+};
+int within2_init_records(const pds_ctx* ctx, int64_t n_rows);    // records of 2 nc doubles launch_within2_init writes to d_partials
+int within2_delta_blocks(const pds_ctx* ctx, int64_t n_levels2);
+// the frame -> d_w0 (row-major f64) and d_moments[2 nc]: sum (x - x_0), sum (x - x_0)^2 per column, x_0 the first row's value
+template <typename T>
+int launch_within2_init(pds_ctx* ctx, const T* const* d_cols, int n_feat, int64_t n_rows, double* d_w0, double* d_partials, double* d_moments);
+int launch_within2_row_levels(pds_ctx* ctx, const int64_t* d_off, int64_t n_levels, int64_t n_rows, uint32_t* d_g1);
+int launch_within2_gather_codes(pds_ctx* ctx, const int32_t* d_in, const uint32_t* d_perm, int64_t n_rows, int32_t* d_out);
+size_t within2_order_temp_bytes(int64_t n_rows);
+int launch_within2_order(pds_ctx* ctx, const int32_t* d_code2, int64_t n_rows, int64_t n_codes, uint32_t* d_iota, uint32_t* d_sorted,
+                         uint32_t* d_idx2, void* d_temp, size_t temp_bytes);
+// one sweep: a1, a2 updated, d_delta written.  d_cols: x_0 .. x_{p-1}, y
+template <typename T>
+int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d);
+// the projected columns, f64, column-major in the kernels' order: d_z[c * n_rows + r]
+template <typename T>
+int launch_within2_final(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d, double* d_z);
+// resid[ro] = e[r], pred[ro] = y[r] - e[r], ro = d_perm ? d_perm[r] : r; d_pred / d_resid nullable
+template <typename T>
+int launch_within2_rows_out(pds_ctx* ctx, const T* d_y, const double* d_e, const uint32_t* d_perm, int64_t n_rows, T* d_pred, T* d_resid);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream

@@ -138,7 +138,7 @@ class Context:
         """Bytes held in one of the context's grow-only HBM workspaces (pds_ctx_workspace_bytes)."""
         return int(self._lib.pds_ctx_workspace_bytes(self._h, self.WORKSPACES.index(which)))
 
-    KINDS = ("moments", "grouped_moments", "solve", "pass2", "rolling", "iterative")
+    KINDS = ("moments", "grouped_moments", "solve", "pass2", "rolling", "iterative", "sweep_factor1", "sweep_factor2")
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.pds_ctx_set_timing(self._h, int(bool(enable))))
@@ -297,7 +297,7 @@ def _lin_reg_arrow(x, target, add_bias, return_pred, null_policy, prm, ctx):
 def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool = False, l1_reg: float = 0.0,
             l2_reg: float = 0.0, tol: float = 1e-5, solver: str = "qr", max_iter: int = 200, positive: bool = False,
             singular_x_tol: float | None = None, null_policy: str = "skip", absorb=None, absorb_offsets=None,
-            ctx: Context | None = None):
+            absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, ctx: Context | None = None):
     """
     pds.lin_reg on null-free column buffers (pl_lr / pl_lr_pred).
 
@@ -306,10 +306,12 @@ def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool 
     returns an all-null struct).
 
     `absorb=key` / `absorb_offsets=off`: the fixed-effects fit with one intercept per group (see lin_reg_report); returns beta, or
-    (beta, pred, resid) with return_pred=True.  OLS only: the penalties, `solver` and `positive` do not apply.
+    (beta, pred, resid) with return_pred=True.  OLS only: the penalties, `solver` and `positive` do not apply.  `absorb=[k1, k2]`: two
+    absorbed keys (`absorb_tol`, `absorb_max_iter`: see lin_reg_report).
     """
     if absorb is not None or absorb_offsets is not None:
-        rep = _lin_reg_within(x, target, add_bias, weights, None, None, absorb, absorb_offsets, None, False, return_pred, None, ctx, fit_only=True)
+        rep = _lin_reg_within(x, target, add_bias, weights, None, None, absorb, absorb_offsets, None, False, return_pred, None, ctx, fit_only=True,
+                              absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter)
         return (rep["beta"], rep["pred"], rep["resid"]) if return_pred else rep["beta"]
     if isinstance(target, (list, tuple)):  # multi-target: expr_linear.py:188-228
         if len(target) == 0:
@@ -602,7 +604,7 @@ def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = F
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", y_var: float | None = None,
                    feature_names: Sequence[str] | None = None, null_policy: str = "raise", cluster=None, cluster_offsets=None,
                    absorb=None, absorb_offsets=None, return_effects: bool = False, return_pred: bool = False,
-                   ctx: Context | None = None) -> dict:
+                   absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, ctx: Context | None = None) -> dict:
     """
     pds.lin_reg_report (pl_lin_reg_report / pl_wls_report).  `y_var` is what Polars evaluates as
     `target.var()` (ddof=1) and hands to the plugin as input 0 (expr_linear.py:614-617); when omitted it
@@ -627,10 +629,19 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     groups) and "df_resid".  return_effects=True adds "effects" (alpha per group; NaN for an empty group of `absorb_offsets`) and
     "effect_keys" (the distinct keys, ascending; group indices with `absorb_offsets`); return_pred=True adds "pred" and "resid" in the
     frame's row order.  1 .. 16 features, no weights, NumPy arrays or CUDA tensors.
+
+    `absorb=[k1, k2]` (a list or tuple of exactly two integer columns): TWO absorbed factors, y_i = alpha_k1(i) + gamma_k2(i) +
+    x_i' beta + e_i -- firm and year effects, the two-way fixed-effects model (pds_lin_reg_within2_*; include/pds_lstsq.h states the
+    definitions).  The columns are projected off both sets of dummies by alternating sweeps until the largest level mean subtracted
+    in a sweep is `absorb_tol` (> 0; 1e-8) standard deviations of its column; `absorb_max_iter` sweeps without that raise PdsError
+    (PDS_ERR_NUMERIC, "did not converge").  With A = G1 + G2 - (connected components of the cells), "se" has n - p - A degrees of
+    freedom; "cluster" / "cluster0" cluster on the FIRST key.  The dict is the one-key dict plus "n_groups2" (G2), "n_components"
+    and "n_iter" (sweeps used).  return_pred=True works as above; return_effects=True is not implemented with two keys (the effects
+    need a normalisation), nor are three or more keys; `absorb_offsets` cannot be combined with a second key.
     """
     if absorb is not None or absorb_offsets is not None:
         return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, (cluster, cluster_offsets),
-                               return_effects, return_pred, None, ctx)
+                               return_effects, return_pred, None, ctx, absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter)
     if return_effects or return_pred:
         raise ValueError("`return_effects` / `return_pred` go with `absorb` or `absorb_offsets` only")
     if std_err in _lib.CLUSTER_SE_TYPES:
@@ -732,8 +743,24 @@ def _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, featur
 
 
 def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, clusters, return_effects, return_pred,
-                    max_groups, ctx, fit_only: bool = False):
-    """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*."""
+                    max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000):
+    """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*; absorb=[k1, k2]: _within2_*."""
+    key2 = None
+    if isinstance(absorb, (list, tuple)):
+        if len(absorb) > 2:
+            raise NotImplementedError("fixed-effects regression: three or more absorbed keys are not implemented")
+        if len(absorb) != 2:
+            raise ValueError("`absorb` is one integer column or a list of exactly two")
+        if absorb_offsets is not None:
+            raise ValueError("`absorb_offsets` together with a second absorbed key: give both keys as `absorb=[k1, k2]`")
+        if return_effects:
+            raise NotImplementedError("fixed-effects regression: `return_effects` with two absorbed keys is not implemented "
+                                      "(the effects need a normalisation)")
+        if not float(absorb_tol) > 0.0:
+            raise ValueError("`absorb_tol` must be > 0")
+        if int(absorb_max_iter) < 1:
+            raise ValueError("`absorb_max_iter` must be >= 1")
+        absorb, key2 = absorb
     if (absorb is None) == (absorb_offsets is None):
         raise ValueError("exactly one of `absorb` and `absorb_offsets` must be given")
     if add_bias:
@@ -746,7 +773,7 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         raise ValueError('`absorb`: std_err is "se", "cluster" or "cluster0"')
     if weights is not None:
         raise NotImplementedError("fixed-effects regression: weights are not implemented")
-    if any(_is_arrow(c) for c in (target, *x)) or (absorb is not None and _is_arrow(absorb)):
+    if any(_is_arrow(c) for c in (target, *x)) or (absorb is not None and _is_arrow(absorb)) or (key2 is not None and _is_arrow(key2)):
         raise NotImplementedError("fixed-effects regression: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
     ctx = ctx or default_context()
     cols = _Cols(target, x)
@@ -762,7 +789,15 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
     if return_pred:
         pred, pred_p = _out_like(cols, n)
         resid, resid_p = _out_like(cols, n)
-    if absorb is not None:
+    if key2 is not None:
+        k, k_p = _key_arg(cols, absorb)
+        codes2, codes2_p, n_levels2 = _dense_codes(cols, key2)
+        extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
+        ng = C.c_int64(0)
+        _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
+                                                        C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep), C.byref(extra),
+                                                        C.byref(ng)))
+    elif absorb is not None:
         k, k_p = _key_arg(cols, absorb)
 
         def call(cap, keys_p, ng_p):
@@ -796,11 +831,37 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         out["r2_overall"] = float(extra.r2_overall)
         out["n_groups"] = int(extra.n_groups_used)
         out["df_resid"] = int(extra.df_resid)
+        if key2 is not None:
+            out["n_groups2"], out["n_components"], out["n_iter"] = int(extra.n_groups2_used), int(extra.n_components), int(extra.n_iter)
     if return_effects:
         out["effects"], out["effect_keys"] = alpha, effect_keys
     if return_pred:
         out["pred"], out["resid"] = pred, resid
     return out
+
+
+def _dense_codes(cols: "_Cols", key):
+    """The second absorbed key as dense int32 codes per row in the inputs' space (plumbing, not the hot path): (codes, address, levels)."""
+    if cols.space == _lib.PDS_DEVICE:
+        import torch
+
+        t = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError("an absorbed key must be an integer column")
+        t = t.to(device=cols.keep[0].device)
+        if t.ndim != 1 or int(t.shape[0]) != cols.n_rows:
+            raise ValueError("`key` must have one entry per row")
+        uniq, inv = torch.unique(t, return_inverse=True)
+        codes = inv.to(torch.int32).contiguous()
+        return codes, C.c_void_p(int(codes.data_ptr())), int(uniq.shape[0])
+    a = key.detach().cpu().numpy() if _is_torch(key) else np.asarray(key)
+    if a.dtype.kind not in "iu":
+        raise ValueError("an absorbed key must be an integer column")
+    if a.ndim != 1 or int(a.shape[0]) != cols.n_rows:
+        raise ValueError("`key` must have one entry per row")
+    uniq, inv = np.unique(a, return_inverse=True)
+    codes = np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
+    return codes, C.c_void_p(codes.ctypes.data), int(uniq.shape[0])
 
 
 # ---- the stages of lin_reg_report as separate calls (row-sharded multi-GPU form: parallel.lin_reg_report_row_sharded)

@@ -227,9 +227,13 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     intercept per group, the within estimator -- from one `pl_lin_reg_report_within` call.  The Struct of `pl_lin_reg_report` with p
     rows (no `__bias__`: `add_bias=True` is refused); `std_err` is "se" (n - G - p degrees of freedom), "cluster" or "cluster0" --
     the clusters are the absorbed groups, so `cluster` is refused; r2 / adj_r2 are the within values.  `absorb` together with `by`
-    or `weights` is not implemented; the effects and the per-row outputs are `lstsq.lin_reg_report(absorb=, ...)` only.
+    or `weights` is not implemented; the effects and the per-row outputs are `lstsq.lin_reg_report(absorb=, ...)` only, and so are
+    two absorbed keys (`absorb=[k1, k2]`).
     """
     if absorb is not None:
+        if isinstance(absorb, (list, tuple)):
+            raise NotImplementedError("lin_reg_report: a list of absorbed keys is not available as an expression; two absorbed keys are "
+                                      "`lstsq.lin_reg_report(..., absorb=[k1, k2])` on column buffers")
         if add_bias:
             raise ValueError("`add_bias=True` together with `absorb`: the intercept is absorbed by the group effects")
         if cluster is not None:
