@@ -140,7 +140,8 @@ long long pds_ctx_workspace_bytes(const pds_ctx* ctx, int which);
  * Measurement hooks (bench.py): with timing enabled every kernel class is bracketed by a HIP event
  * pair recorded on the context's stream.  pds_ctx_get_timing synchronises and returns, per class,
  * the summed duration in ms and the number of bracketed launches.  Classes: 0 Gram/moments (single
- * system, incl. its finalize), 1 grouped Gram, 2 batched solve, 3 residual pass, 4 rolling, 5 CD/NNLS.
+ * system, incl. its finalize), 1 grouped Gram, 2 batched solve, 3 residual pass, 4 rolling, 5 CD/NNLS,
+ * 6 / 7 the factor-1 / factor-2 kernels of a sweep of pds_lin_reg_within2_*, 8 its graph pass (level counts, components, effects).
  */
 int pds_ctx_set_timing(pds_ctx* ctx, int enable);
 int pds_ctx_get_timing(pds_ctx* ctx, double* ms_sum, long long* counts, int n_kinds, int reset);
@@ -394,10 +395,15 @@ int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const 
  * constant PDS_ERR_NUMERIC; a feature whose projected sum of squares sum x~^2 is not above min(1e-4, max(1e-12, (1e3 absorb_tol)^2)) -- 1e-10 at
  * the default tolerance -- times its centred sum of squares sum (x - xbar)^2 (a function of the keys: collinear with the absorbed
  * effects) PDS_ERR_NUMERIC, the message naming the column index; X~'X~ not positive definite otherwise PDS_ERR_NUMERIC; more than 16
- * features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.  There is no weighted form, and the effects themselves are not
- * returned (they need a normalisation).  A workspace the device cannot hold fails with the allocation's error.
- * C is counted exactly by a union-find over the cells on the host, in one pass over the codes (a device frame's codes are fetched
- * for it).  Two calls give the same bits (no floating-point atomics; every sum in a fixed order).  Levels of factor 1 above the
+ * features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.  There is no weighted form; the effects themselves come from
+ * pds_lin_reg_within2_fx_* below.  A workspace the device cannot hold fails with the allocation's error.
+ * C is counted exactly on the device: every row is an edge between its level of factor 1 and its code of factor 2, and rounds of
+ * hooking (32-bit integer atomicMin of the smaller root into the larger) and pointer jumping label every level with the smallest
+ * level index of its component, in at most 2 ceil(log2(G1 + n_levels2)) + 1 rounds (a root that neither hooks nor is hooked into
+ * in one round hooks in the next, so the trees of a component at least halve in two rounds; more: PDS_ERR_NUMERIC,
+ * "component labelling did not finish", never a wrong count).  The range of the codes is checked by a kernel that reads nothing else, before anything is indexed
+ * by a code; the level counts of factor 2 are exact integers from the ordered codes.  The host reads O(n_levels2 + G1) integers and
+ * no row.  Two calls give the same bits (no floating-point atomics; every sum in a fixed order).  Levels of factor 1 above the
  * context option "within_split_rows" are cut into row chunks; every level of factor 2 is cut into chunks of at most 1 024 gathered
  * rows (of "within_split_rows" rows if that is smaller).
  */
@@ -423,6 +429,62 @@ int pds_lin_reg_within2_by_key_f64(pds_ctx* ctx, const double* const* cols, cons
 int pds_lin_reg_within2_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
                                    int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
                                    pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups);
+
+/*
+ * pds_lin_reg_within2_fx_*: pds_lin_reg_within2_* with the ESTIMATED EFFECTS alpha (per level of factor 1) and gamma (per code of
+ * factor 2) of y_i = alpha_g1(i) + gamma_g2(i) + x_i' beta + e_i.  The argument lists are those of pds_lin_reg_within2_* plus a
+ * trailing pds_within2_effects* fx (nullable: the call is then pds_lin_reg_within2_* itself); out and extra receive the same bits.
+ * The effects are identified only up to one constant per connected component of the cells, so what follows is a DEFINITION of what
+ * the library returns; no equivalence with a package's convention is claimed beyond this text.
+ *   a1 [level of factor 1][column], a2 [code of factor 2][column]: the level means the sweeps have subtracted in all, columns
+ *   x_1 .. x_p, y.  alpha' [level of factor 1]: the one-factor effects pds_lin_reg_within_* defines, of the projected columns (of the
+ *   order of absorb_tol; with them y_i - alpha - gamma - x_i' beta - resid_i is zero to rounding).
+ *     alpha_raw[g] = a1[g][y] - sum_j beta_j a1[g][j] + alpha'[g];    gamma_raw[l] = a2[l][y] - sum_j beta_j a2[l][j]
+ *   NORMALISATION: in every component the reference level is the LOWEST occupied code of factor 2 in it; with c = gamma_raw at that
+ *   code, alpha_g = alpha_raw[g] + c and gamma_l = gamma_raw[l] - c.  gamma at every reference level is exactly 0.0: these are the
+ *   coefficients of the regression on the features, one dummy per level of factor 1 and one per level of factor 2 less the first
+ *   level of factor 2 in every component.  f64 arithmetic, terms in ascending column order; the outputs have the frame's type.
+ *   component1 / component2: the component of every level as the index, in effects1, of the smallest level of factor 1 in it.
+ *   A code of factor 2 that no row uses: gamma NaN, component -1.
+ *   grouped: effects1 / component1 have n_groups entries, indexed by the caller's groups; an empty group: NaN / -1.  cap1 and keys1
+ *            are not read.
+ *   by key:  effects1 / component1 / keys1 (the distinct keys, ascending) have room for cap1 entries when any of them is given, and
+ *            more distinct keys are PDS_ERR_INVALID with *n_groups set (nothing fitted), as pds_lin_reg_within_by_key_*.
+ * n_graph_rounds receives the rounds the component labelling took.
+ */
+typedef struct {              /* every pointer nullable and `space`-resident */
+    void* effects1;           /* [n_groups] (by key: [cap1], ascending key order), the frame's type */
+    void* effects2;           /* [n_levels2], the frame's type */
+    int32_t* component1;      /* as effects1 */
+    int32_t* component2;      /* [n_levels2] */
+    int64_t* keys1;           /* by key: [cap1] */
+    int64_t cap1;             /* by key: room in effects1 / component1 / keys1 */
+    int64_t n_graph_rounds;   /* out */
+} pds_within2_effects;
+int pds_lin_reg_within2_fx_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx);
+int pds_lin_reg_within2_fx_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx);
+int pds_lin_reg_within2_fx_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx);
+int pds_lin_reg_within2_fx_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx);
+/*
+ * pds_absorb_components_i32: the graph pass of pds_lin_reg_within2_* alone.  codes1 / codes2: n_rows dense int32 codes each, in
+ * [0, n_levels1) / [0, n_levels2), `space`-resident, rows in any order (a code outside its range: PDS_ERR_INVALID, found before
+ * anything is indexed by a code).  component1 [n_levels1] / component2 [n_levels2] (nullable, `space`-resident): the component of every
+ * level as the smallest code of key 1 in it, -1 for a code no row uses.  *n1 / *n2: the codes in use, *n_components: the connected
+ * components of the graph of the occupied cells, *n_rounds: the rounds taken (each nullable).  Fewer than 2^31 rows per call.
+ */
+int pds_absorb_components_i32(pds_ctx* ctx, const int32_t* codes1, int64_t n_levels1, const int32_t* codes2, int64_t n_levels2, int64_t n_rows,
+                              pds_space space, int32_t* component1, int32_t* component2, int64_t* n1, int64_t* n2, int64_t* n_components,
+                              int* n_rounds);
 
 /*
  * Row-sharded `pl_lin_reg_report` / `pl_wls_report` (one process per GPU): the stages of

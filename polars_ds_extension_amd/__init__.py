@@ -11,8 +11,10 @@ from .lstsq import (  # noqa: F401
     Context,
     DeviceBlock,
     GroupedFit,
+    absorb_components,
     allreduce_sum,
     default_context,
+    fixed_effects,
     gather,
     glm_by,
     glm_by_key,

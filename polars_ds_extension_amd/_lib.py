@@ -42,6 +42,8 @@ EXPORTS = [
     "pds_lin_reg_report_cluster_by_key_f64", "pds_lin_reg_report_cluster_by_key_f32",
     "pds_lin_reg_within_grouped_f64", "pds_lin_reg_within_grouped_f32", "pds_lin_reg_within_by_key_f64", "pds_lin_reg_within_by_key_f32",
     "pds_lin_reg_within2_grouped_f64", "pds_lin_reg_within2_grouped_f32", "pds_lin_reg_within2_by_key_f64", "pds_lin_reg_within2_by_key_f32",
+    "pds_lin_reg_within2_fx_grouped_f64", "pds_lin_reg_within2_fx_grouped_f32", "pds_lin_reg_within2_fx_by_key_f64", "pds_lin_reg_within2_fx_by_key_f32",
+    "pds_absorb_components_i32",
     "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
@@ -111,6 +113,12 @@ class Within2Out(C.Structure):
     """pds_within2_out: the two-factor fixed-effects fit's nullable per-row outputs and its counts."""
     _fields_ = [("pred", C.c_void_p), ("resid", C.c_void_p), ("r2_overall", C.c_double), ("df_resid", C.c_int64),
                 ("n_groups_used", C.c_int64), ("n_groups2_used", C.c_int64), ("n_components", C.c_int64), ("n_iter", C.c_int64)]
+
+
+class Within2Effects(C.Structure):
+    """pds_within2_effects: the estimated effects and components of the two-factor fit, nullable outputs in the frame's space."""
+    _fields_ = [("effects1", C.c_void_p), ("effects2", C.c_void_p), ("component1", C.c_void_p), ("component2", C.c_void_p),
+                ("keys1", C.c_void_p), ("cap1", C.c_int64), ("n_graph_rounds", C.c_int64)]
 
 
 class PdsError(RuntimeError):
@@ -185,6 +193,12 @@ def load() -> C.CDLL:
                 getattr(lib, "pds_lin_reg_within2_by_key_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                                                             C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                                             C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pds_lin_reg_within2_fx_grouped_" + sfx):  # the within2 lists plus a trailing pds_within2_effects*
+                getattr(lib, "pds_lin_reg_within2_fx_grouped_" + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_grouped_" + sfx).argtypes + [C.c_void_p]
+                getattr(lib, "pds_lin_reg_within2_fx_by_key_" + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_by_key_" + sfx).argtypes + [C.c_void_p]
+        if hasattr(lib, "pds_absorb_components_i32"):
+            # ctx, codes1, n_levels1, codes2, n_levels2, n_rows, space, component1, component2, n1, n2, n_components, n_rounds
+            lib.pds_absorb_components_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 6
         if hasattr(lib, "pds_ctx_workspace_bytes"):
             lib.pds_ctx_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
             lib.pds_ctx_workspace_bytes.restype = C.c_longlong

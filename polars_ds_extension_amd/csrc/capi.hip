@@ -457,7 +457,7 @@ int pds_ctx_get_timing(pds_ctx* ctx, double* ms_sum, long long* counts, int n_ki
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (auto& e : ctx->ev_pending) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess && e.kind >= 0 && e.kind < 8) {
+        if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess && e.kind >= 0 && e.kind < pds::kNumKinds) {
             ctx->kind_ms[e.kind] += ms;
             ctx->kind_count[e.kind] += 1;
             auto& sm = ctx->kind_samples[e.kind];
@@ -468,12 +468,12 @@ int pds_ctx_get_timing(pds_ctx* ctx, double* ms_sum, long long* counts, int n_ki
         ctx->ev_pool.push_back(e.b);
     }
     ctx->ev_pending.clear();
-    for (int k = 0; k < n_kinds && k < 8; ++k) {
+    for (int k = 0; k < n_kinds && k < pds::kNumKinds; ++k) {
         if (ms_sum) ms_sum[k] = ctx->kind_ms[k];
         if (counts) counts[k] = ctx->kind_count[k];
     }
     if (reset)
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < pds::kNumKinds; ++k) {
             ctx->kind_ms[k] = 0;
             ctx->kind_count[k] = 0;
         }
@@ -481,7 +481,7 @@ int pds_ctx_get_timing(pds_ctx* ctx, double* ms_sum, long long* counts, int n_ki
 }
 
 int pds_ctx_get_timing_samples(pds_ctx* ctx, int kind, double* ms_out, int cap, int reset) {
-    if (!ctx || kind < 0 || kind >= 8) return -1;
+    if (!ctx || kind < 0 || kind >= pds::kNumKinds) return -1;
     if (pds_ctx_get_timing(ctx, nullptr, nullptr, 0, 0) != PDS_OK) return -1;  // drains the pending event pairs
     auto& sm = ctx->kind_samples[kind];
     const int n = (int)std::min<size_t>(sm.size(), (size_t)std::max(cap, 0));
@@ -674,6 +674,37 @@ int pds_lin_reg_within2_by_key_f32(pds_ctx* ctx, const float* const* cols, const
                                    pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups) {
     return within2_by_key_impl<float, pds_report_f32>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
                                                       absorb_max_iter, out, extra, n_groups);
+}
+int pds_lin_reg_within2_fx_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx) {
+    return within2_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type,
+                                                absorb_tol, absorb_max_iter, out, extra, nullptr, fx);
+}
+int pds_lin_reg_within2_fx_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx) {
+    return within2_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type,
+                                               absorb_tol, absorb_max_iter, out, extra, nullptr, fx);
+}
+int pds_lin_reg_within2_fx_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx) {
+    return within2_by_key_impl<double, pds_report_f64>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
+                                                       absorb_max_iter, out, extra, n_groups, fx);
+}
+int pds_lin_reg_within2_fx_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx) {
+    return within2_by_key_impl<float, pds_report_f32>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
+                                                      absorb_max_iter, out, extra, n_groups, fx);
+}
+int pds_absorb_components_i32(pds_ctx* ctx, const int32_t* codes1, int64_t n_levels1, const int32_t* codes2, int64_t n_levels2, int64_t n_rows,
+                              pds_space space, int32_t* component1, int32_t* component2, int64_t* n1, int64_t* n2, int64_t* n_components,
+                              int* n_rounds) {
+    return absorb_components_impl(ctx, codes1, n_levels1, codes2, n_levels2, n_rows, space, component1, component2, n1, n2, n_components, n_rounds);
 }
 
 int pds_report_fit_from_moments_f64(pds_ctx* ctx, const double* moments, int n_feat, int add_bias, double* beta, double* inv) {

@@ -90,6 +90,7 @@ struct WithinMore {
     double tss = 0.0;             // sum (y - ybar)^2 of the ORIGINAL target: r2_overall is formed from it
     const double* css = nullptr;  // [p] sum (x - xbar)^2 of the original features: a feature has to keep ...
     double min_share = 0.0;       // ... more than this share of it, or it is refused as collinear with the absorbed effects
+    double* beta_f64 = nullptr;   // [p] out (nullable): beta as solved, before it is rounded to the report's type
 };
 
 // cols / offsets live in `space`; the outputs of `extra` (and out_keys' caller) in `out_space`.  d_perm (nullable): row r of this
@@ -222,6 +223,8 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     out->r2 = (T)r2;
     out->adj_r2 = (T)(1.0 - (1.0 - r2) * ((nd - gd - xd) / (double)df_se));
     for (int i = 0; i < p; ++i) out->beta[i] = (T)beta[i];
+    if (more && more->beta_f64)
+        for (int i = 0; i < p; ++i) more->beta_f64[i] = beta[i];
     const int64_t df = se_type == PDS_SE ? df_se : n_nonempty - 1;
     if (extra && more) {
         extra->r2_overall = 1.0 - sse / more->tss;

@@ -27,12 +27,19 @@
 // squares is not above kWithin2ShareFloor = 1e-12, or (1e3 absorb_tol)^2 if that is larger (but at most 1e-4) -- 1e-10 at the default
 // tolerance --, times its centred sum of squares sum (x - xbar)^2 is refused by index with PDS_ERR_NUMERIC.  (What a sweep at tolerance delta leaves of
 // such a column is of the order delta s_j / (1 - rate) per row; 1e3 covers a convergence rate of 0.999.)
-// COMPONENTS.  C comes from a union-find over the cells on the host, in the same pass over the codes that validates them and counts
-// the levels of factor 2 (the codes of a device frame are fetched for it: 4 bytes per row).
+// COMPONENTS.  C comes from the device (within2_graph.hip): every row is an edge between its level of factor 1 and its code of factor
+// 2, and hook-and-compress rounds of integer atomicMin label every node with the smallest node index of its component, in at most
+// 2 ceil(log2(G1 + n_levels2)) + 1 rounds (the trees of a component halve in two rounds: within2_graph.hip has the argument; more: PDS_ERR_NUMERIC, "component labelling did not finish").  The range of the codes is
+// checked by a kernel that reads nothing else, before anything is indexed by a code; the level counts of factor 2 are the run
+// boundaries of the ordered codes.  The host reads O(n_levels2 + G1) integers, never O(rows).
+// EFFECTS (pds_lin_reg_within2_fx_*; a DEFINITION, stated in include/pds_lstsq.h).  With the tables a1 / a2 the sweeps ended with, beta
+// and alpha', the one-factor effects of the projected columns (the final stage's alpha: of the order of absorb_tol):
+//     alpha_raw[g] = a1[g][y] - sum_j beta_j a1[g][j] + alpha'[g];   gamma_raw[l] = a2[l][y] - sum_j beta_j a2[l][j]
+// and, in every component, c = gamma_raw at the LOWEST occupied code of factor 2 in it:  alpha_g = alpha_raw + c, gamma_l = gamma_raw - c.
 //
-// Stages: the factor-1 offsets and their chunks (plan_group_chunks); the codes of factor 2 in frame order on device and host; the host
-// pass (range, counts, components); launch_within2_init (f64 row-major copy, moments), the row -> level map, the code ordering
-// (launch_within2_order); the sweep loop ON THE HOST, one small blocking copy (the per-wave maxima of delta) per sweep; the projected
+// Stages: the factor-1 offsets and their chunks (plan_group_chunks); the codes of factor 2 in frame order on the device and their range
+// check; the row -> level map, the code ordering (launch_within2_order), the level starts and the graph pass (within2_components);
+// launch_within2_init (f64 row-major copy, moments); the sweep loop ON THE HOST, one small blocking copy (the per-wave maxima of delta) per sweep; the projected
 // columns written column-major (launch_within2_final) and handed to the FINAL STAGE of the one-factor fit -- within_impl on them with
 // factor 1's offsets: its statistics pass, host solve, within pass, scores and meat -- told the extra absorbed degrees of freedom
 // G2 - C and the original target's sum of squares; pred / resid from the residuals and the ORIGINAL target (launch_within2_rows_out).
@@ -45,8 +52,9 @@ constexpr double kWithin2ShareFloor = 1e-12, kWithin2ShareTolFactor = 1e3, kWith
 template <typename T, typename R>
 static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
                         const int32_t* codes2, pds_space code_space, int64_t n_levels2, pds_space out_space, int se_type, double tol, int max_iter,
-                        R* out, pds_within2_out* extra, const uint32_t* d_perm = nullptr) {
+                        R* out, pds_within2_out* extra, const uint32_t* d_perm = nullptr, pds_within2_effects* fx = nullptr) {
     if (!ctx || !cols || !offsets || !codes2 || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
+    if (fx && n_groups >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: the effects of fewer than 2^31 groups per call");
     if (int rc = within_check_se(se_type)) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
@@ -67,8 +75,10 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     const int64_t* h_off = nullptr;
     if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
+    // the effects of factor 1 go out at the caller's group indices: gmap is the place of a kept group among them
+    const bool want_fx1 = fx && (fx->effects1 || fx->component1), want_fx = fx && (want_fx1 || fx->effects2 || fx->component2);
     GroupChunkPlan pl;
-    if (int rc = plan_group_chunks(h_off, n_groups, n, split, /*cover=*/true, /*offsets_on_host=*/true, /*want_gmap=*/false,
+    if (int rc = plan_group_chunks(h_off, n_groups, n, split, /*cover=*/true, /*offsets_on_host=*/true, /*want_gmap=*/want_fx,
                                    "absorbed group offsets must be non-decreasing and cover the frame", pl))
         return rc;
     h_off = pl.h_off;
@@ -87,7 +97,23 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         row_outs.add(&d_pred, static_cast<T*>(extra->pred), 1);
         row_outs.add(&d_resid, static_cast<T*>(extra->resid), 1);
     }
-    size_t need = 8192 + up(sizeof(T*) * 18) + up((size_t)(n1 + 1) * 8) + 9 * up((size_t)(n_chunks1 + n_long1 + 1) * 8) +
+    const int64_t n_all = n_groups, n_nodes = n1 + n_levels2;
+    T *d_eff1 = nullptr, *d_eff2 = nullptr;
+    int32_t *d_comp1 = nullptr, *d_comp2 = nullptr;
+    StagedOuts g_outs(out_host, (size_t)n_all), l_outs(out_host, (size_t)n_levels2);
+    if (fx) {
+        g_outs.add(&d_eff1, static_cast<T*>(fx->effects1), 1);
+        g_outs.add(&d_comp1, fx->component1, 1);
+        l_outs.add(&d_eff2, static_cast<T*>(fx->effects2), 1);
+        l_outs.add(&d_comp2, fx->component2, 1);
+        fx->n_graph_rounds = 0;
+    }
+    const size_t graph_bytes = up((size_t)(n_levels2 + 1) * 4) + 2 * up((size_t)n_nodes * 4) + up(within2_graph_flag_bytes()) +
+                               up(within2_graph_count_bytes());
+    const size_t fx_bytes = want_fx ? 2 * up((size_t)n1 * 8) + up((size_t)n_levels2 * 8) + up((size_t)n1 * 4) + up(kMaxFeatSmall * 8) +
+                                          g_outs.bytes() + l_outs.bytes()
+                                    : 0;
+    size_t need = graph_bytes + fx_bytes + 8192 + up(sizeof(T*) * 18) + up((size_t)(n1 + 1) * 8) + 9 * up((size_t)(n_chunks1 + n_long1 + 1) * 8) +
                   up((size_t)(n_chunks1 + 1) * nc * 8) + up((size_t)(n_chunks1 + 1) * 4) + 6 * up((size_t)n * 4) + sort_temp +
                   up((size_t)n * nc * 8) + up((size_t)n * 8) + up((size_t)n1 * nc * 8) + up((size_t)n_levels2 * nc * 8) + 2 * up((size_t)c2_cap * 8) +
                   up((size_t)c2_cap * 4) + 3 * up((size_t)lev_cap * 8) + up((size_t)lev_cap * 4) + up((size_t)c2_cap * nc * 8) +
@@ -111,12 +137,21 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         dev.d_off1 = t;
     }
     if (int rc = upload_mixed_chunks(ctx, w, pl, nc, dev.ch1)) return rc;
-    // ---- the codes of factor 2 in frame order, on the device and on the host
+    // ---- the codes of factor 2 in frame order on the device, and their range BEFORE any kernel indexes anything by a code
     const int32_t* d_in = codes2;
     if (code_space == PDS_HOST) {
         int32_t* t = w.take<int32_t>((size_t)n);
         PDS_HIP_CHECK(hipMemcpyAsync(t, codes2, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
         d_in = t;
+    }
+    int* d_flags = w.take<int>(within2_graph_flag_bytes() / sizeof(int));
+    {
+        int bad = 0;
+        PDS_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(int), ctx->stream));
+        if (int rc = launch_within2_range_check(ctx, d_in, n, n_levels2, d_flags)) return rc;
+        PDS_HIP_CHECK(hipMemcpyAsync(&bad, d_flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (bad) return fail(PDS_ERR_INVALID, "fixed-effects regression: a code of the second absorbed key is outside [0, n_levels2)");
     }
     dev.d_code2 = d_in;
     if (d_perm) {
@@ -124,53 +159,41 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         if (int rc = launch_within2_gather_codes(ctx, d_in, d_perm, n, t)) return rc;
         dev.d_code2 = t;
     }
-    std::vector<int32_t> code_copy;
-    const int32_t* h_code = codes2;
-    std::vector<int64_t> cnt2;
-    std::vector<uint32_t> parent;
+    // ---- the row -> level map; the rows in code order; the level counts of factor 2 from the ordered codes (run boundaries)
+    uint32_t* d_start = w.take<uint32_t>((size_t)n_levels2 + 1);
+    {
+        uint32_t* g1 = w.take<uint32_t>((size_t)n);
+        if (int rc = launch_within2_row_levels(ctx, dev.d_off1, n1, n, g1)) return rc;
+        dev.d_g1 = g1;
+        uint32_t *iota = w.take<uint32_t>((size_t)n), *sorted = w.take<uint32_t>((size_t)n), *idx2 = w.take<uint32_t>((size_t)n);
+        void* temp = w.take<char>(sort_temp);
+        if (int rc = launch_within2_order(ctx, dev.d_code2, n, n_levels2, iota, sorted, idx2, temp, sort_temp)) return rc;
+        dev.d_idx2 = idx2;
+        if (int rc = launch_within2_level_starts(ctx, sorted, n, n_levels2, d_start)) return rc;
+    }
+    // ---- the components of the graph of the cells, on the device (within2_graph.hip): the host reads O(n_levels2 + G1) integers from here on
+    uint32_t *d_label = w.take<uint32_t>((size_t)n_nodes), *d_root = w.take<uint32_t>((size_t)n_nodes);
+    int64_t* d_counts = w.take<int64_t>(within2_graph_count_bytes() / sizeof(int64_t));
+    int64_t n_comp = 0;
+    int n_rounds = 0;
+    if (int rc = within2_components(ctx, dev.d_g1, reinterpret_cast<const uint32_t*>(dev.d_code2), n, n1, n_levels2, nullptr, d_label, d_root, d_flags,
+                                    d_counts, nullptr, nullptr, &n_comp, &n_rounds))
+        return rc;
+    if (fx) fx->n_graph_rounds = n_rounds;
+    std::vector<uint32_t> start2;
     try {
-        if (code_space != PDS_HOST || d_perm) {
-            code_copy.resize((size_t)n);
-            PDS_HIP_CHECK(hipMemcpyAsync(code_copy.data(), dev.d_code2, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            h_code = code_copy.data();
-        }
-        cnt2.assign((size_t)n_levels2, 0);
-        parent.resize((size_t)(n1 + n_levels2));
+        start2.resize((size_t)n_levels2 + 1);
     } catch (const std::bad_alloc&) {
-        return fail(PDS_ERR_INVALID, "fixed-effects regression: no host memory for the codes of the second absorbed key");
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: no host memory for the level counts of the second absorbed key");
     }
-    // ---- the host pass: range, level counts, components (union-find over the cells; a merge adds one to the rank A)
-    for (size_t i = 0; i < parent.size(); ++i) parent[i] = (uint32_t)i;
-    auto find = [&](uint32_t a) {
-        while (parent[a] != a) {
-            parent[a] = parent[parent[a]];
-            a = parent[a];
-        }
-        return a;
-    };
-    int64_t rank_a = 0;
-    for (int64_t g = 0; g < n1; ++g) {
-        int64_t last = -1;
-        for (int64_t r = h_off[g]; r < h_off[g + 1]; ++r) {
-            const int64_t l = h_code[r];
-            if (l < 0 || l >= n_levels2) return fail(PDS_ERR_INVALID, "fixed-effects regression: a code of the second absorbed key is outside [0, n_levels2)");
-            ++cnt2[(size_t)l];
-            if (l == last) continue;
-            last = l;
-            const uint32_t a = find((uint32_t)g), b = find((uint32_t)(n1 + l));
-            if (a != b) {
-                parent[a] = b;
-                ++rank_a;
-            }
-        }
-    }
+    PDS_HIP_CHECK(hipMemcpyAsync(start2.data(), d_start, start2.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> c_pos, c_n, l_c0, l_nc, l_n;
     std::vector<int32_t> c_code, l_code;
     {
         int64_t pos = 0;
         for (int64_t l = 0; l < n_levels2; ++l) {
-            const int64_t m = cnt2[(size_t)l];
+            const int64_t m = (int64_t)start2[(size_t)l + 1] - (int64_t)start2[(size_t)l];
             if (m == 0) continue;
             const int64_t k = (m + chunk2 - 1) / chunk2;
             l_c0.push_back((int64_t)c_pos.size());
@@ -185,7 +208,7 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
             pos += m;
         }
     }
-    const int64_t n2 = (int64_t)l_n.size(), n_comp = n1 + n2 - rank_a, extra_df = n2 - n_comp;
+    const int64_t n2 = (int64_t)l_n.size(), rank_a = n1 + n2 - n_comp, extra_df = n2 - n_comp;
     if (extra) {
         extra->n_groups_used = n1;
         extra->n_groups2_used = n2;
@@ -211,20 +234,11 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     if (int rc = put(l_n, dev.d_l2_n)) return rc;
     if (int rc = put(l_code, dev.d_l2_code)) return rc;
     dev.d_csum2 = w.take<double>((size_t)dev.n_chunks2 * nc);
-    // ---- the f64 copy and the moments; the row -> level map; the rows in code order
+    // ---- the f64 copy and the moments
     dev.d_w0 = w.take<double>((size_t)n * nc);
     double* d_init = w.take<double>((size_t)n_init * 2 * nc);
     double* d_mom = w.take<double>(64);
     if (int rc = launch_within2_init<T>(ctx, d_tbl, p, n, dev.d_w0, d_init, d_mom)) return rc;
-    {
-        uint32_t* g1 = w.take<uint32_t>((size_t)n);
-        if (int rc = launch_within2_row_levels(ctx, dev.d_off1, n1, n, g1)) return rc;
-        dev.d_g1 = g1;
-        uint32_t *iota = w.take<uint32_t>((size_t)n), *sorted = w.take<uint32_t>((size_t)n), *idx2 = w.take<uint32_t>((size_t)n);
-        void* temp = w.take<char>(sort_temp);
-        if (int rc = launch_within2_order(ctx, dev.d_code2, n, n_levels2, iota, sorted, idx2, temp, sort_temp)) return rc;
-        dev.d_idx2 = idx2;
-    }
     double mom[2 * (kMaxFeatSmall + 1)];
     PDS_HIP_CHECK(hipMemcpyAsync(mom, d_mom, sizeof(double) * 2 * nc, hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, the chunk lists: sources of the copies)
@@ -247,6 +261,18 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     dev.d_delta = w.take<double>((size_t)n_delta);
     double* d_e = want_rows ? w.take<double>((size_t)n) : nullptr;
     row_outs.place(w);
+    double *d_alpha1 = nullptr, *d_graw = nullptr, *d_beta = nullptr;
+    int64_t* d_gmap = nullptr;
+    uint32_t* d_ref = nullptr;
+    if (want_fx) {
+        d_alpha1 = w.take<double>((size_t)n1);
+        d_gmap = w.take<int64_t>((size_t)n1);
+        d_graw = w.take<double>((size_t)n_levels2);
+        d_ref = w.take<uint32_t>((size_t)n1);
+        d_beta = w.take<double>(kMaxFeatSmall);
+        g_outs.place(w);
+        l_outs.place(w);
+    }
     // ---- the sweeps: the loop lives here, bounded by absorb_max_iter
     std::vector<double> h_delta((size_t)n_delta);
     double delta = INFINITY;
@@ -281,8 +307,11 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     more.tss = css[p];
     more.css = css;
     more.min_share = share;
+    double beta_h[kMaxFeatSmall] = {0};
+    more.beta_f64 = want_fx ? beta_h : nullptr;
     pds_within_out wo{};
     wo.resid = d_e;
+    wo.alpha = d_alpha1;  // (the one-factor effects of the projected columns: of the order of absorb_tol, they close the identity)
     if (int rc = within_impl<double, R>(ctx, zc.data(), p, n, dev.d_off1, n1, PDS_DEVICE, PDS_DEVICE, se_type, out, &wo, nullptr, &more)) return rc;
     if (extra) {
         extra->r2_overall = wo.r2_overall;
@@ -291,8 +320,25 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     if (want_rows) {
         if (int rc = launch_within2_rows_out<T>(ctx, tbl[(size_t)p], d_e, d_perm, n, d_pred, d_resid)) return rc;
         if (int rc = staged_copy_back(ctx, row_outs, (size_t)n)) return rc;
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
+    // ---- the effects: from the tables the sweeps ended with, beta as solved and the labels of the graph pass
+    if (want_fx) {
+        // beta_h and the plan's map are sources of asynchronous copies: the stream is synchronised at once, so that no error path
+        // below can leave this frame while a copy still reads it
+        PDS_HIP_CHECK(hipMemcpyAsync(d_beta, beta_h, sizeof(beta_h), hipMemcpyHostToDevice, ctx->stream));
+        if (pl.dropped()) PDS_HIP_CHECK(hipMemcpyAsync(d_gmap, pl.gmap.data(), (size_t)n1 * 8, hipMemcpyHostToDevice, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (pl.dropped()) {  // (all bits set: NaN in both formats and -1, what an empty group of the caller's gets)
+            if (d_eff1) PDS_HIP_CHECK(hipMemsetAsync(d_eff1, 0xFF, (size_t)n_all * sizeof(T), ctx->stream));
+            if (d_comp1) PDS_HIP_CHECK(hipMemsetAsync(d_comp1, 0xFF, (size_t)n_all * 4, ctx->stream));
+        }
+        if (int rc = launch_within2_effects<T>(ctx, dev.d_a1, dev.d_a2, d_beta, d_alpha1, d_label, pl.dropped() ? d_gmap : nullptr, p, n1, n_levels2, d_graw,
+                                               d_ref, d_eff1, d_eff2, d_comp1, d_comp2))
+            return rc;
+        if (int rc = staged_copy_back(ctx, g_outs, (size_t)n_all)) return rc;
+        if (int rc = staged_copy_back(ctx, l_outs, (size_t)n_levels2)) return rc;
+    }
+    if (want_rows || want_fx) PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (the staged outputs are with the caller)
     return PDS_OK;
 }
 
@@ -301,8 +347,11 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
 template <typename T, typename R>
 static int within2_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2, int n_feat,
                                int64_t n_rows, pds_space space, int se_type, double tol, int max_iter, R* out, pds_within2_out* extra,
-                               int64_t* n_groups) {
+                               int64_t* n_groups, pds_within2_effects* fx = nullptr) {
     if (!ctx || !cols || !keys || !codes2 || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
+    // fx->cap1 matters only when an output per level of key 1 is asked for: each then has room for cap1 entries
+    const bool want_keys = fx && (fx->effects1 || fx->component1 || fx->keys1);
+    if (want_keys && fx->cap1 < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (int rc = within_check_se(se_type)) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
@@ -313,7 +362,71 @@ static int within2_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
     Bump w{};
-    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w)) return rc;
-    return within2_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, codes2, space, n_levels2, space, se_type, tol,
-                              max_iter, out, extra, kf.d_perm);
+    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_keys ? fx->cap1 : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
+        return rc;
+    if (int rc = within2_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, codes2, space, n_levels2, space, se_type, tol,
+                                    max_iter, out, extra, kf.d_perm, fx))
+        return rc;
+    if (fx && fx->keys1) {
+        PDS_HIP_CHECK(hipMemcpyAsync(fx->keys1, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                     ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return PDS_OK;
+}
+
+// The graph pass alone: two dense code columns in any row order -> the component of every level ("mobility groups").
+static int absorb_components_impl(pds_ctx* ctx, const int32_t* codes1, int64_t n_levels1, const int32_t* codes2, int64_t n_levels2, int64_t n_rows,
+                                  pds_space space, int32_t* component1, int32_t* component2, int64_t* n1, int64_t* n2, int64_t* n_components,
+                                  int* n_rounds) {
+    if (!ctx || !codes1 || !codes2) return fail(PDS_ERR_INVALID, "null argument");
+    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
+    if (n_rows >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "components of two absorbed keys: fewer than 2^31 rows per call");
+    if (n_levels1 < 1 || n_levels1 >= (1ll << 31)) return fail(PDS_ERR_INVALID, "components of two absorbed keys: n_levels1 is in [1, 2^31)");
+    if (n_levels2 < 1 || n_levels2 >= (1ll << 31)) return fail(PDS_ERR_INVALID, "components of two absorbed keys: n_levels2 is in [1, 2^31)");
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    const auto up = Bump::up;
+    const bool host = space == PDS_HOST;
+    const int64_t n = n_rows, n_nodes = n_levels1 + n_levels2;
+    int32_t *d_comp1 = nullptr, *d_comp2 = nullptr;
+    StagedOuts outs1(host, (size_t)n_levels1), outs2(host, (size_t)n_levels2);
+    outs1.add(&d_comp1, component1, 1);
+    outs2.add(&d_comp2, component2, 1);
+    const size_t need = 8192 + (host ? 2 * up((size_t)n * 4) : 0) + up(within2_graph_flag_bytes()) + up(within2_graph_count_bytes()) +
+                        2 * up((size_t)n_nodes * 4) + up((size_t)n_levels1 * 4) + outs1.bytes() + outs2.bytes();
+    if (int rc = ensure_ws(ctx, ctx->ws, need)) return rc;
+    Bump w{static_cast<char*>(ctx->ws.ptr)};
+    const int32_t* d_c[2] = {codes1, codes2};
+    if (host)
+        for (const int32_t*& c : d_c) {
+            int32_t* t = w.take<int32_t>((size_t)n);
+            PDS_HIP_CHECK(hipMemcpyAsync(t, c, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+            c = t;
+        }
+    // the range of both columns before anything is indexed by a code
+    int* d_flags = w.take<int>(within2_graph_flag_bytes() / sizeof(int));
+    int bad[2] = {0, 0};
+    PDS_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(bad), ctx->stream));
+    if (int rc = launch_within2_range_check(ctx, d_c[0], n, n_levels1, d_flags)) return rc;
+    if (int rc = launch_within2_range_check(ctx, d_c[1], n, n_levels2, d_flags + 1)) return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(bad, d_flags, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (bad[0]) return fail(PDS_ERR_INVALID, "components of two absorbed keys: a code of the first key is outside [0, n_levels1)");
+    if (bad[1]) return fail(PDS_ERR_INVALID, "components of two absorbed keys: a code of the second key is outside [0, n_levels2)");
+    int64_t* d_counts = w.take<int64_t>(within2_graph_count_bytes() / sizeof(int64_t));
+    uint32_t *d_label = w.take<uint32_t>((size_t)n_nodes), *d_root = w.take<uint32_t>((size_t)n_nodes), *d_occ = w.take<uint32_t>((size_t)n_levels1);
+    outs1.place(w);
+    outs2.place(w);
+    const uint32_t *d_u = reinterpret_cast<const uint32_t*>(d_c[0]), *d_v = reinterpret_cast<const uint32_t*>(d_c[1]);
+    PDS_HIP_CHECK(hipMemsetAsync(d_occ, 0, (size_t)n_levels1 * 4, ctx->stream));
+    if (int rc = launch_within2_mark(ctx, d_u, n, d_occ)) return rc;
+    if (int rc = within2_components(ctx, d_u, d_v, n, n_levels1, n_levels2, d_occ, d_label, d_root, d_flags, d_counts, n1, n2, n_components, n_rounds))
+        return rc;
+    if (d_comp1 || d_comp2) {
+        if (int rc = launch_within2_components_out(ctx, d_label, d_occ, n_levels1, n_levels2, d_comp1, d_comp2)) return rc;
+        if (int rc = staged_copy_back(ctx, outs1, (size_t)n_levels1)) return rc;
+        if (int rc = staged_copy_back(ctx, outs2, (size_t)n_levels2)) return rc;
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return PDS_OK;
 }

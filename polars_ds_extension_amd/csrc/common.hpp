@@ -135,9 +135,9 @@ struct pds_ctx {
     int64_t opt_cluster_waves = 0;        // "cluster_waves": cap on the waves a launch of the cluster report's pass starts (0: the default)
     int64_t opt_fused_waves = 0;          // "grouped_fused_waves": cap on the grid of the fused grouped kernel (0: every wave slot)
     int64_t opt_fused_late_permille = 0;  // "grouped_fused_late_permille": rows, in 1/1000, of the grid's second half (0: grouped_split_dev.hpp)
-    double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long kind_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<float> kind_samples[8];  // the individual bracketed durations (ms), newest kept up to 4096 per class
+    double kind_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long long kind_count[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<float> kind_samples[9];  // the individual bracketed durations (ms), newest kept up to 4096 per class
     // (behind everything else: the members above keep their places for the translation units that do not know these two)
     int64_t opt_multi_route = 0;  // "grouped_multi_route": 0 choose, 1 the one-wave-per-group kernel, 2 one fused launch per target
     int64_t opt_multi_waves = 0;  // "grouped_multi_waves": cap on the grid of the grouped multi-target kernel (0: every wave slot)
@@ -155,7 +155,8 @@ inline const char* dev_env(const char*) { return nullptr; }
 #endif
 
 // kernel classes for the timing hooks
-enum { kKindMoments = 0, kKindGroupedMoments = 1, kKindSolve = 2, kKindPass2 = 3, kKindRolling = 4, kKindIter = 5, kKindSweep1 = 6, kKindSweep2 = 7 };
+enum { kKindMoments = 0, kKindGroupedMoments = 1, kKindSolve = 2, kKindPass2 = 3, kKindRolling = 4, kKindIter = 5, kKindSweep1 = 6, kKindSweep2 = 7, kKindGraph = 8,
+       kNumKinds = 9 };
 // RAII: records a HIP event pair around the launches issued in its scope when ctx->timing is on
 struct KernelTimer {
     pds_ctx* ctx;
@@ -494,7 +495,7 @@ struct Within2Dev {
     int64_t n_rows = 0, n1 = 0, split1 = 0;  // rows; occupied levels of factor 1; its levels above split1 rows are the chunks ch1
     const int64_t* d_off1 = nullptr;         // n1 + 1 offsets
     MixedChunks ch1;                         // (d_sums: the chunk sums)
-    const int32_t* d_code2 = nullptr;        // [n_rows] the code of factor 2 of every row, frame order, validated by the host
+    const int32_t* d_code2 = nullptr;        // [n_rows] the code of factor 2 of every row, frame order, its range checked on the device
     const uint32_t* d_idx2 = nullptr;        // [n_rows] the rows in ascending code order (launch_within2_order)
     const uint32_t* d_g1 = nullptr;          // [n_rows] the level of factor 1 of every row (launch_within2_row_levels)
     int64_t n_chunks2 = 0, n_lev2 = 0;       // chunks of idx2 (every level is cut from the start); occupied levels of factor 2
@@ -524,6 +525,33 @@ int launch_within2_final(pds_ctx* ctx, const T* const* d_cols, int n_feat, const
 // resid[ro] = e[r], pred[ro] = y[r] - e[r], ro = d_perm ? d_perm[r] : r; d_pred / d_resid nullable
 template <typename T>
 int launch_within2_rows_out(pds_ctx* ctx, const T* d_y, const double* d_e, const uint32_t* d_perm, int64_t n_rows, T* d_pred, T* d_resid);
+// ---- within2_graph.hip: the graph of the occupied cells (capi_within2.hpp).  Nodes: n_a levels of factor 1, then n_b codes of factor 2;
+// row r is the edge (d_u[r], n_a + d_v[r]).
+// *d_flag |= 1 if a code is outside [0, n_levels): reads the codes alone.  The caller zeroes the flag and reads it back
+int launch_within2_range_check(pds_ctx* ctx, const int32_t* d_codes, int64_t n_rows, int64_t n_levels, int* d_flag);
+// d_start[l], l = 0 .. n_levels: the rows whose code is below l, from the ascending codes of launch_within2_order (d_sorted)
+int launch_within2_level_starts(pds_ctx* ctx, const uint32_t* d_sorted, int64_t n_rows, int64_t n_levels, uint32_t* d_start);
+int launch_within2_mark(pds_ctx* ctx, const uint32_t* d_u, int64_t n_rows, uint32_t* d_occ);  // d_occ[d_u[r]] = 1
+size_t within2_graph_count_bytes();  // d_counts of within2_components
+size_t within2_graph_flag_bytes();   // d_flags
+// Hook and compress, the rounds driven from here (blocking: a few bytes come back per round).  d_label [n_a + n_b] ends as the smallest
+// node index of every node's component; d_root: as much scratch.  d_occ (nullable: every level of factor 1 holds a row): the levels
+// of factor 1 that hold one.  *n1 / *n2: occupied levels, *n_components: components that hold a row, *n_rounds: rounds taken, at most
+// 2 ceil(log2(n_a + n_b)) + 1 -- more is PDS_ERR_NUMERIC, "component labelling did not finish".
+int within2_components(pds_ctx* ctx, const uint32_t* d_u, const uint32_t* d_v, int64_t n_rows, int64_t n_a, int64_t n_b, const uint32_t* d_occ,
+                       uint32_t* d_label, uint32_t* d_root, int* d_flags, int64_t* d_counts, int64_t* n1, int64_t* n2, int64_t* n_components,
+                       int* n_rounds);
+// d_comp1 [n_a] / d_comp2 [n_b] (nullable): the label of every level, -1 for one no row uses
+int launch_within2_components_out(pds_ctx* ctx, const uint32_t* d_label, const uint32_t* d_occ, int64_t n_a, int64_t n_b, int32_t* d_comp1,
+                                  int32_t* d_comp2);
+// The estimated effects from the converged tables d_a1 [n_a x (p + 1)] / d_a2 [n_levels2 x (p + 1)], beta (p doubles) and the
+// one-factor effects of the projected columns d_alpha1 [n_a] (include/pds_lstsq.h states the normalisation).  d_gmap (nullable): level g
+// of factor 1 is entry d_gmap[g] of d_eff1 / d_comp1 and is named so in the components.  d_graw [n_levels2], d_ref [n_a]: scratch.
+// Outputs nullable.
+template <typename T>
+int launch_within2_effects(pds_ctx* ctx, const double* d_a1, const double* d_a2, const double* d_beta, const double* d_alpha1, const uint32_t* d_label,
+                           const int64_t* d_gmap, int n_feat, int64_t n_a, int64_t n_levels2, double* d_graw, uint32_t* d_ref, T* d_eff1, T* d_eff2,
+                           int32_t* d_comp1, int32_t* d_comp2);
 // ---- leverage_mid.hip: HC2 / HC3 leverages of 17 .. 64 f64 features on the matrix cores (PDS_ERR_UNSUPPORTED: not applicable, nothing done)
 int launch_grouped_moments_stream(pds_ctx* ctx, const DeviceCols<double>& dc, int n_feat, int64_t n_frame, const int64_t* d_off, int64_t n_groups,
                                   double* d_records);  // grouped_mid.hip: grouped Gram records, 17 .. 64 f64 features, one stream

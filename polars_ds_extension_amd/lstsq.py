@@ -138,16 +138,17 @@ class Context:
         """Bytes held in one of the context's grow-only HBM workspaces (pds_ctx_workspace_bytes)."""
         return int(self._lib.pds_ctx_workspace_bytes(self._h, self.WORKSPACES.index(which)))
 
-    KINDS = ("moments", "grouped_moments", "solve", "pass2", "rolling", "iterative", "sweep_factor1", "sweep_factor2")
+    KINDS = ("moments", "grouped_moments", "solve", "pass2", "rolling", "iterative", "sweep_factor1", "sweep_factor2", "graph")
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.pds_ctx_set_timing(self._h, int(bool(enable))))
 
     def get_timing(self, reset: bool = True) -> dict:
         """Per kernel class: (summed ms, launches) measured with HIP events on the context's stream."""
-        ms = (C.c_double * 8)()
-        cnt = (C.c_longlong * 8)()
-        _lib.check(self._lib.pds_ctx_get_timing(self._h, ms, cnt, 8, int(bool(reset))))
+        nk = len(self.KINDS)
+        ms = (C.c_double * nk)()
+        cnt = (C.c_longlong * nk)()
+        _lib.check(self._lib.pds_ctx_get_timing(self._h, ms, cnt, nk, int(bool(reset))))
         return {k: (ms[i], int(cnt[i])) for i, k in enumerate(self.KINDS)}
 
     def get_timing_samples(self, kind: str, reset: bool = True) -> list:
@@ -636,8 +637,8 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     in a sweep is `absorb_tol` (> 0; 1e-8) standard deviations of its column; `absorb_max_iter` sweeps without that raise PdsError
     (PDS_ERR_NUMERIC, "did not converge").  With A = G1 + G2 - (connected components of the cells), "se" has n - p - A degrees of
     freedom; "cluster" / "cluster0" cluster on the FIRST key.  The dict is the one-key dict plus "n_groups2" (G2), "n_components"
-    and "n_iter" (sweeps used).  return_pred=True works as above; return_effects=True is not implemented with two keys (the effects
-    need a normalisation), nor are three or more keys; `absorb_offsets` cannot be combined with a second key.
+    and "n_iter" (sweeps used).  return_pred=True works as above; return_effects=True is refused with two keys (the effects
+    need a normalisation: `fixed_effects` returns them under its own), and so are three or more keys; `absorb_offsets` cannot be combined with a second key.
     """
     if absorb is not None or absorb_offsets is not None:
         return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, (cluster, cluster_offsets),
@@ -743,8 +744,9 @@ def _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, featur
 
 
 def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, clusters, return_effects, return_pred,
-                    max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000):
-    """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*; absorb=[k1, k2]: _within2_*."""
+                    max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, effects2: bool = False):
+    """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*; absorb=[k1, k2]: _within2_*;
+    effects2 (fixed_effects): pds_lin_reg_within2_fx_by_key_*."""
     key2 = None
     if isinstance(absorb, (list, tuple)):
         if len(absorb) > 2:
@@ -755,7 +757,7 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
             raise ValueError("`absorb_offsets` together with a second absorbed key: give both keys as `absorb=[k1, k2]`")
         if return_effects:
             raise NotImplementedError("fixed-effects regression: `return_effects` with two absorbed keys is not implemented "
-                                      "(the effects need a normalisation)")
+                                      "(the effects need a normalisation): lstsq.fixed_effects returns them under its own")
         if not float(absorb_tol) > 0.0:
             raise ValueError("`absorb_tol` must be > 0")
         if int(absorb_max_iter) < 1:
@@ -789,9 +791,27 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
     if return_pred:
         pred, pred_p = _out_like(cols, n)
         resid, resid_p = _out_like(cols, n)
-    if key2 is not None:
+    if key2 is not None and effects2:
         k, k_p = _key_arg(cols, absorb)
-        codes2, codes2_p, n_levels2 = _dense_codes(cols, key2)
+        codes2, codes2_p, n_levels2, effect_keys2 = _dense_codes(cols, key2)
+        alpha2, alpha2_p = _out_like(cols, n_levels2)
+        comp2, comp2_p = _out_int(cols, n_levels2, "int32")
+
+        def call(cap, keys_p, ng_p):
+            alpha, alpha_p = _out_like(cols, cap)
+            comp1, comp1_p = _out_int(cols, cap, "int32")
+            extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
+            fx = _lib.Within2Effects(alpha_p, alpha2_p, comp1_p, comp2_p, keys_p, cap, 0)
+            rc = ctx.fn("pds_lin_reg_within2_fx_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
+                                                         C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep), C.byref(extra), ng_p,
+                                                         C.byref(fx))
+            return rc, (alpha, comp1, extra, fx)
+
+        effect_keys, (alpha, comp1, extra, fx), g = _by_key_retry(cols, max_groups, call)
+        alpha, comp1 = alpha[:g], comp1[:g]
+    elif key2 is not None:
+        k, k_p = _key_arg(cols, absorb)
+        codes2, codes2_p, n_levels2, _ = _dense_codes(cols, key2)
         extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
         ng = C.c_int64(0)
         _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
@@ -833,35 +853,103 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         out["df_resid"] = int(extra.df_resid)
         if key2 is not None:
             out["n_groups2"], out["n_components"], out["n_iter"] = int(extra.n_groups2_used), int(extra.n_components), int(extra.n_iter)
-    if return_effects:
+    if return_effects or effects2:
         out["effects"], out["effect_keys"] = alpha, effect_keys
+    if effects2:
+        out["effects2"], out["effect_keys2"], out["component"], out["component2"] = alpha2, effect_keys2, comp1, comp2
+        out["n_graph_rounds"] = int(fx.n_graph_rounds)
     if return_pred:
         out["pred"], out["resid"] = pred, resid
     return out
 
 
-def _dense_codes(cols: "_Cols", key):
-    """The second absorbed key as dense int32 codes per row in the inputs' space (plumbing, not the hot path): (codes, address, levels)."""
-    if cols.space == _lib.PDS_DEVICE:
+def _codes_of(key, device, n_rows=None):
+    """An integer key column as dense int32 codes per row (plumbing, not the hot path): (codes, address, the distinct keys ascending).
+    `device`: the torch device the codes are wanted on, None for host memory."""
+    if device is not None:
         import torch
 
         t = key if _is_torch(key) else torch.as_tensor(np.asarray(key))
         if t.dtype.is_floating_point or t.dtype == torch.bool:
             raise ValueError("an absorbed key must be an integer column")
-        t = t.to(device=cols.keep[0].device)
-        if t.ndim != 1 or int(t.shape[0]) != cols.n_rows:
+        t = t.to(device=device)
+        if t.ndim != 1 or (n_rows is not None and int(t.shape[0]) != n_rows):
             raise ValueError("`key` must have one entry per row")
         uniq, inv = torch.unique(t, return_inverse=True)
         codes = inv.to(torch.int32).contiguous()
-        return codes, C.c_void_p(int(codes.data_ptr())), int(uniq.shape[0])
+        return codes, C.c_void_p(int(codes.data_ptr())), uniq
     a = key.detach().cpu().numpy() if _is_torch(key) else np.asarray(key)
     if a.dtype.kind not in "iu":
         raise ValueError("an absorbed key must be an integer column")
-    if a.ndim != 1 or int(a.shape[0]) != cols.n_rows:
+    if a.ndim != 1 or (n_rows is not None and int(a.shape[0]) != n_rows):
         raise ValueError("`key` must have one entry per row")
     uniq, inv = np.unique(a, return_inverse=True)
     codes = np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
-    return codes, C.c_void_p(codes.ctypes.data), int(uniq.shape[0])
+    return codes, C.c_void_p(codes.ctypes.data), uniq
+
+
+def _dense_codes(cols: "_Cols", key):
+    """The second absorbed key as dense int32 codes per row in the inputs' space: (codes, address, levels, the distinct keys ascending)."""
+    codes, codes_p, uniq = _codes_of(key, cols.keep[0].device if cols.space == _lib.PDS_DEVICE else None, cols.n_rows)
+    return codes, codes_p, int(uniq.shape[0]), uniq
+
+
+def fixed_effects(*x, target, absorb, std_err: str = "se", absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, return_pred: bool = False,
+                  feature_names: Sequence[str] | None = None, add_bias: bool = False, weights=None, max_groups: int | None = None,
+                  ctx: Context | None = None) -> dict:
+    """
+    The two-way fixed-effects regression y_i = alpha_k1(i) + gamma_k2(i) + x_i' beta + e_i WITH its estimated effects
+    (pds_lin_reg_within2_fx_by_key_*; include/pds_lstsq.h states the definitions).  `absorb=[k1, k2]`: exactly two integer columns.
+    Every entry of lin_reg_report(absorb=[k1, k2]) with the same arguments, bit for bit, plus
+        "effects" / "effect_keys"     alpha per distinct key of k1, ascending
+        "effects2" / "effect_keys2"   gamma per distinct key of k2, ascending
+        "component" / "component2"    the connected component of every level, as the index in "effect_keys" of its smallest level of k1
+        "n_graph_rounds"              the rounds the component labelling took
+    The effects are identified up to one constant per component.  The normalisation is a DEFINITION: in every component gamma is
+    exactly 0.0 at the smallest key of k2 that occurs in it -- the coefficients of the regression on the features, a dummy per level
+    of k1 and a dummy per level of k2 less that one per component.  NumPy arrays or CUDA tensors; a device frame gets device outputs.
+    `max_groups`: a bound on the distinct keys of k1 (the outputs are sized for it), as in the other by-key calls.
+    """
+    if not isinstance(absorb, (list, tuple)) or len(absorb) < 2:
+        raise ValueError("fixed_effects: `absorb` is a list of exactly two integer columns; the effects of ONE absorbed key come from "
+                         "lin_reg_report(absorb=k, return_effects=True)")
+    return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, None, None, False, return_pred, max_groups, ctx,
+                           absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, effects2=True)
+
+
+def absorb_components(k1, k2, ctx: Context | None = None) -> dict:
+    """
+    The connected components of the bipartite graph whose edges are the (k1, k2) pairs that occur -- the "mobility groups" inside which
+    the effects of a two-way fixed-effects model can be compared (pds_absorb_components_i32).  k1, k2: integer columns of equal length,
+    NumPy arrays or CUDA tensors, rows in any order.  Returns "n_groups" / "n_groups2" (distinct keys), "n_components", "keys1" /
+    "keys2" (the distinct keys, ascending), "component1" / "component2" (per distinct key, the index in "keys1" of the smallest key
+    of k1 in its component) and "n_rounds" (rounds of the labelling).  Device columns get device outputs.
+    """
+    for k in (k1, k2):
+        if _is_arrow(k):
+            raise NotImplementedError("absorb_components: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
+    device = next((k.device for k in (k1, k2) if _is_torch(k) and k.is_cuda), None)
+    codes1, codes1_p, keys1 = _codes_of(k1, device)
+    codes2, codes2_p, keys2 = _codes_of(k2, device, int(codes1.shape[0]))
+    n = int(codes1.shape[0])
+    if n == 0:
+        raise ValueError("absorb_components: the key columns are empty")
+    ctx = ctx or default_context()
+    if device is not None:
+        import torch
+
+        ctx.follow_torch_stream(device)
+        comp = [torch.empty(int(u.shape[0]), dtype=torch.int32, device=device) for u in (keys1, keys2)]
+        comp_p = [C.c_void_p(int(c.data_ptr())) for c in comp]
+    else:
+        comp = [np.empty(int(u.shape[0]), dtype=np.int32) for u in (keys1, keys2)]
+        comp_p = [C.c_void_p(c.ctypes.data) for c in comp]
+    n1, n2, nc, rounds = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+    _lib.check(ctx._lib.pds_absorb_components_i32(ctx._h, codes1_p, C.c_int64(int(keys1.shape[0])), codes2_p, C.c_int64(int(keys2.shape[0])),
+                                                  C.c_int64(n), _lib.PDS_DEVICE if device is not None else _lib.PDS_HOST, comp_p[0], comp_p[1],
+                                                  C.byref(n1), C.byref(n2), C.byref(nc), C.byref(rounds)))
+    return {"n_groups": int(n1.value), "n_groups2": int(n2.value), "n_components": int(nc.value), "keys1": keys1, "component1": comp[0],
+            "keys2": keys2, "component2": comp[1], "n_rounds": int(rounds.value)}
 
 
 # ---- the stages of lin_reg_report as separate calls (row-sharded multi-GPU form: parallel.lin_reg_report_row_sharded)

@@ -10,7 +10,11 @@ kernels ("sweep_factor1": contiguous levels, reads the frame) and of the factor-
 sums and delta), frame bytes / sweep time against the 8 TB/s HBM peak and against the model of 2 reads of the frame per sweep, the
 f64 copy + moments ("moments"), the code ordering with the final stage's statistics pass ("grouped_moments"), the projected columns
 with the final stage's row pass ("pass2"), and what is left of the call: the host's pass over the codes (range, counts, components)
-with the copies and the per-sweep synchronisations.  One more call with absorb_max_iter=1 (it fails after one sweep) is timed by the
+with the copies and the per-sweep synchronisations -- since the graph pass runs on the device (csrc/within2_graph.hip, class "graph":
+level counts, hook-and-compress rounds, and the effects kernels of fixed_effects) that is the range check's and the rounds' small copies.
+`fixed_effects` (the report plus the estimated effects) is timed beside the report, with the rounds the labelling took.  `--lib PATH`
+loads another build of the library (an earlier commit's, for an A/B in a series of processes that alternate the two builds; symbols it
+lacks are left out of the record).  One more call with absorb_max_iter=1 (it fails after one sweep) is timed by the
 wall clock: everything in front of the sweeps -- the host pass among it -- and one sweep.  Lines are appended to profiles/within2_report_bench.txt
 (`--out`).  No time here is a pass condition.
 """
@@ -70,8 +74,13 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "within2_report_bench.txt"))
+    ap.add_argument("--lib", default=None, help="another build of libpds_lstsq_hip.so to measure")
+    ap.add_argument("--label", default="this")
     a = ap.parse_args()
     OUT = a.out or None
+    if a.lib:
+        pds._lib.LIB_PATH = Path(a.lib).resolve()
+    has_fx = hasattr(pds._lib.load(), "pds_lin_reg_within2_fx_by_key_f64")
     dev = torch.device("cuda", 0)
     ctx = pds.Context(0)
     ctx.set_stream(torch.cuda.current_stream(dev))
@@ -86,6 +95,8 @@ def main():
         "one_key_se": lambda: pds.lin_reg_report(*X, target=y, std_err="se", absorb=firm, ctx=ctx),
         "one_key_cluster": lambda: pds.lin_reg_report(*X, target=y, std_err="cluster", absorb=firm, ctx=ctx),
     }
+    if has_fx:
+        fns["fixed_effects_se"] = lambda: pds.fixed_effects(*X, target=y, std_err="se", absorb=[firm, period], absorb_tol=a.tol, ctx=ctx)
     t = timed_alternating(fns, a.reps)
     kern = {}
     for k in ("two_keys_se", "one_key_se"):
@@ -115,7 +126,7 @@ def main():
     sweeps = rep["n_iter"]
     frame_bytes = n * (p + 1) * 8
     s1, s2 = tm["sweep_factor1"][0] / sweeps, tm["sweep_factor2"][0] / sweeps
-    rec = {"bench": "within2_report", "rows": n, "firms": rep["n_groups"], "periods": rep["n_groups2"], "components": rep["n_components"], "p": p,
+    rec = {"bench": "within2_report", "build": a.label, "rows": n, "firms": rep["n_groups"], "periods": rep["n_groups2"], "components": rep["n_components"], "p": p,
            "absorb_tol": a.tol, "frame_GB": round(frame_bytes / 1e9, 3), "sweeps": sweeps}
     for k in fns:
         rec[k + "_ms"], rec[k + "_ms_best"], rec[k + "_ms_worst"] = (round(v, 3) for v in t[k])
@@ -127,9 +138,19 @@ def main():
     rec["copy_and_moments_kernels_ms"] = round(tm["moments"][0], 3)
     rec["code_ordering_and_final_statistics_kernels_ms"] = round(tm["grouped_moments"][0], 3)
     rec["projected_columns_and_final_row_pass_kernels_ms"] = round(tm["pass2"][0], 3)
-    all_kernels = sum(tm[k][0] for k in ("moments", "grouped_moments", "pass2", "sweep_factor1", "sweep_factor2"))
+    rec["graph_pass_kernels_ms"], rec["graph_pass_launches"] = round(tm["graph"][0], 3), tm["graph"][1]
+    all_kernels = sum(tm[k][0] for k in ("moments", "grouped_moments", "pass2", "sweep_factor1", "sweep_factor2", "graph"))
     rec["all_kernels_ms"] = round(all_kernels, 3)
     rec["call_less_kernels_ms"] = round(t["two_keys_se"][0] - all_kernels, 3)
+    if has_fx:
+        ctx.set_timing(True)
+        ctx.get_timing()
+        fe = fns["fixed_effects_se"]()
+        ctx.synchronize()
+        rec["fixed_effects_graph_rounds"] = fe["n_graph_rounds"]
+        rec["fixed_effects_graph_and_effects_kernels_ms"] = round(ctx.get_timing()["graph"][0], 3)
+        ctx.set_timing(False)
+        rec["fixed_effects_over_report_se"] = round(t["fixed_effects_se"][0] / t["two_keys_se"][0], 3)
     rec["torch_unique_of_key2_ms"] = round(unique_ms, 3)
     rec["call_stopped_after_one_sweep_wall_ms"] = round(one_sweep_wall_ms, 3)
     one = kern["one_key_se"][0]
