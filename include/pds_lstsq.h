@@ -103,6 +103,9 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *   "within_split_rows"                       pds_lin_reg_within_*: absorbed groups of more rows are cut into row chunks that are separate
  *                                             work items, in the statistics pass and in the per-row pass alike (<= 0: the default,
  *                                             16384; at least 64).  Few, very long groups are the common fixed-effects shape.
+ *   "within2_accel"                           pds_lin_reg_within2_* (the _fx_ forms included): 0 plain alternating sweeps, the default;
+ *                                             1 Irons-Tuck cycles of two sweeps and one extrapolation (see there).  Any other value is
+ *                                             PDS_ERR_INVALID.  A call reads the option once, when it starts.
  *   "cluster_waves"                           pds_lin_reg_report_cluster_*: cap on the number of waves a launch of the cluster pass starts
  *                                             (<= 0: the default, 12 per compute unit).  Each wave adds up the clusters it walks, so
  *                                             another cap gives other sums, to rounding; one setting repeats its bits.
@@ -113,8 +116,11 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
  *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
- * value: 0 / 1 (report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, within_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
+ * value: 0 / 1 (within2_accel: nothing else; report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, within_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
+/* The value an option has now, as pds_ctx_set_option stored it (a count given as <= 0 reads back as 0, "the default").  Unknown names
+ * are PDS_ERR_INVALID.  A caller that sets an option for one call reads it first and puts that value back. */
+int pds_ctx_get_option(const pds_ctx* ctx, const char* name, long long* value);
 /* Host restatement of how the fused grouped kernel deals groups to its waves (no device needed): wave w of `waves` fits the groups
  * [first_group[w], end_group[w]) -- those whose first row lies in the wave's share of the row range [group_offsets[0],
  * group_offsets[n_groups]).  late_permille = 0: equal shares of the rows; 1 .. 999: that share of the rows goes to the second half of
@@ -406,6 +412,23 @@ int pds_lin_reg_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const 
  * no row.  Two calls give the same bits (no floating-point atomics; every sum in a fixed order).  Levels of factor 1 above the
  * context option "within_split_rows" are cut into row chunks; every level of factor 2 is cut into chunks of at most 1 024 gathered
  * rows (of "within_split_rows" rows if that is smaller).
+ * ACCELERATION (context option "within2_accel" = 1; 0, the default, is the plain iteration above, bit for bit; a DEFINITION).  A sweep
+ * is exactly the sweep above.  m2(k) is the table of factor-2 level means sweep k subtracts; its scaled maximum is that sweep's delta.
+ * The factor-1 step of a sweep does not depend on the factor-1 means subtracted so far, so the state of the iteration is the table a2
+ * of factor-2 means subtracted in all.  The accelerated iteration (Irons-Tuck) runs cycles of two sweeps:
+ *     1. sweep; Delta1 = its m2.  delta <= absorb_tol: stop.
+ *     2. sweep; Delta2 = its m2.  delta <= absorb_tol: stop.
+ *     3. per column j, over the occupied codes of factor 2:  d = Delta2 - Delta1,  c_j = sum Delta2 d / sum d^2,
+ *        a2[.][j] <- a2[.][j] - c_j Delta2[.][j].  c_j is 0 -- the column is left alone -- when the denominator is 0 or when a sum or
+ *        the quotient is not finite.  The sums are unweighted (not weighted by level counts).
+ * Only a2 is extrapolated; the next sweep's factor-1 step rebuilds the factor-1 means from it.  Convergence is judged by a sweep's
+ * delta and by nothing else, so the call always ends on a sweep and everything after the sweeps -- the final stage, pred / resid, the
+ * effects and their normalisation -- is formed as without acceleration.  absorb_max_iter and extra->n_iter count SWEEPS only; the
+ * "did not converge" error is the same (an extrapolation after the last sweep allowed is not made).  The two sums of a column are
+ * taken in a fixed order that depends on the number of occupied codes of factor 2 and the device alone -- not on scheduling, on
+ * "within_split_rows" or on the row order: two calls give the same bits, and the by-key form on shuffled rows the bits of the
+ * grouped form.  An extrapolation reads and writes tables of n_levels2 x (p + 1) doubles; the frame is read twice per sweep as before.
+ * All eight pds_lin_reg_within2_* entry points honour the option; none has another argument for it.
  */
 typedef struct {            /* every pointer nullable and `space`-resident */
     void* pred;             /* [n_rows], frame order */

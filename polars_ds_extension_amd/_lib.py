@@ -23,7 +23,7 @@ PDS_REPORT_DERIVE_YVAR = 0x100  # include/pds_lstsq.h
 
 EXPORTS = [
     "pds_last_error", "pds_version", "pds_ctx_create", "pds_ctx_destroy", "pds_ctx_set_stream",
-    "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_grouped_fused_split", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_glm_irls_grouped_f64", "pds_glm_irls_grouped_f32", "pds_glm_irls_by_key_f64", "pds_glm_irls_by_key_f32",
+    "pds_ctx_synchronize", "pds_ctx_num_cus", "pds_ctx_set_option", "pds_ctx_get_option", "pds_grouped_fused_split", "pds_set_host_staging", "pds_rows_to_cols_f64", "pds_rows_to_cols_f32", "pds_glm_irls_f64", "pds_glm_irls_f32", "pds_glm_irls_grouped_f64", "pds_glm_irls_grouped_f32", "pds_glm_irls_by_key_f64", "pds_glm_irls_by_key_f32",
     "pds_glm_irls_wo_f64", "pds_glm_irls_wo_f32", "pds_glm_irls_wo_grouped_f64", "pds_glm_irls_wo_grouped_f32", "pds_glm_irls_wo_by_key_f64", "pds_glm_irls_wo_by_key_f32",
     "pds_glm_enet_f64", "pds_glm_enet_f32", "pds_glm_enet_grouped_f64", "pds_glm_enet_grouped_f32", "pds_glm_enet_by_key_f64", "pds_glm_enet_by_key_f32",
     "pds_glm_report_wo_grouped_f64", "pds_glm_report_wo_grouped_f32", "pds_glm_report_wo_by_key_f64", "pds_glm_report_wo_by_key_f32",
@@ -162,6 +162,8 @@ def load() -> C.CDLL:
         lib.pds_ctx_synchronize.argtypes = [C.c_void_p]
         lib.pds_ctx_num_cus.argtypes = [C.c_void_p]
         lib.pds_ctx_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
+        if hasattr(lib, "pds_ctx_get_option"):  # (absent from older builds used in A/B runs)
+            lib.pds_ctx_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong)]
         if hasattr(lib, "pds_set_host_staging"):
             lib.pds_set_host_staging.argtypes = [C.c_double, C.c_double]
         if hasattr(lib, "pds_ctx_workspace_spills"):  # (absent from older builds used in A/B runs)

@@ -140,7 +140,10 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
     else if (n == "cluster_split_rows") ctx->opt_cluster_split_rows = value > 0 ? (int64_t)value : 0;
     else if (n == "cluster_waves") ctx->opt_cluster_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "within_split_rows") ctx->opt_within_split_rows = value > 0 ? (int64_t)value : 0;
-    else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
+    else if (n == "within2_accel") {
+        if (value != 0 && value != 1) return fail(PDS_ERR_INVALID, "within2_accel: 0 (plain sweeps) or 1 (Irons-Tuck)");
+        ctx->opt_within2_accel = (int64_t)value;
+    } else if (n == "report_chunk_groups") ctx->opt_report_chunk_groups = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_waves") ctx->opt_fused_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "grouped_fused_late_permille") {
         if (value < 0 || value > 999) return fail(PDS_ERR_INVALID, "grouped_fused_late_permille: 0 (the default rule) or 1 .. 999");
@@ -149,6 +152,26 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
         if (value < 0 || value > 2) return fail(PDS_ERR_INVALID, "grouped_multi_route: 0 (choose), 1 (one kernel) or 2 (per target)");
         ctx->opt_multi_route = (int64_t)value;
     } else if (n == "grouped_multi_waves") ctx->opt_multi_waves = value > 0 ? (int64_t)value : 0;
+    else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
+    return PDS_OK;
+}
+
+int pds_ctx_get_option(const pds_ctx* ctx, const char* name, long long* value) {
+    if (!ctx || !name || !value) return fail(PDS_ERR_INVALID, "null argument");
+    const std::string n(name);
+    if (n == "keyed_sort") *value = ctx->opt_keyed_sort ? 1 : 0;
+    else if (n == "wide_f32_native") *value = ctx->opt_wide_f32_native ? 1 : 0;
+    else if (n == "glm_split_rows") *value = ctx->opt_glm_split_rows;
+    else if (n == "mixed_split_rows") *value = ctx->opt_mixed_split_rows;
+    else if (n == "cluster_split_rows") *value = ctx->opt_cluster_split_rows;
+    else if (n == "cluster_waves") *value = ctx->opt_cluster_waves;
+    else if (n == "within_split_rows") *value = ctx->opt_within_split_rows;
+    else if (n == "within2_accel") *value = ctx->opt_within2_accel;
+    else if (n == "report_chunk_groups") *value = ctx->opt_report_chunk_groups;
+    else if (n == "grouped_fused_waves") *value = ctx->opt_fused_waves;
+    else if (n == "grouped_fused_late_permille") *value = ctx->opt_fused_late_permille;
+    else if (n == "grouped_multi_route") *value = ctx->opt_multi_route;
+    else if (n == "grouped_multi_waves") *value = ctx->opt_multi_waves;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }

@@ -23,6 +23,18 @@
 // (> 0; 1e-8 is reghdfe's default).  absorb_max_iter sweeps without that: PDS_ERR_NUMERIC, "did not converge" with the last delta,
 // nothing returned.  The device keeps the subtracted means as two tables and forms a row's working value from its original value
 // (within2_sweep.hip): the same sweep, two reads of the frame and no write.
+// ACCELERATION (context option "within2_accel" = 1, Irons-Tuck; 0, the default: plain sweeps; a DEFINITION, stated in
+// include/pds_lstsq.h).  The factor-1 step rebuilds a1 from a2 (a1 += mean1(w - a1 - a2) does not depend on the old a1), so the state of
+// the iteration is a2 alone, an affine fixed-point map.  A sweep is exactly the plain sweep; m2(k) is the table of factor-2 level means
+// sweep k subtracts (what is added to a2; its scaled maximum is delta).  Cycles of two sweeps:
+//     1. sweep, Delta1 = its m2; delta <= tol: stop.     2. sweep, Delta2 = its m2; delta <= tol: stop.
+//     3. per column j over the occupied codes of factor 2: d = Delta2 - Delta1, c_j = sum Delta2 d / sum d^2,
+//        a2[.][j] -= c_j Delta2[.][j];  c_j = 0 (the column is left alone) when the denominator is 0 or a sum or the quotient is not finite.
+// Only a2 is extrapolated (a1 is stale for one factor-1 step); convergence is judged by a sweep's delta alone, the call ends on a sweep,
+// absorb_max_iter and n_iter count sweeps and nothing else (an extrapolation after the last sweep allowed is not made).  The two sums of
+// a column: per wave of the level kernel over the levels it walks, ascending (the grid depends on the number of occupied codes alone),
+// the waves' records added in index order by one wave on the device -- no floating-point atomics, nothing read by the host, no extra
+// read of the frame.  The unweighted dot products are the choice: weighting by level counts took 2.5 x the sweeps on the few-movers frame.
 // COLLINEARITY.  A feature that is a function of the keys is projected to (numerically) nothing: a feature whose projected sum of
 // squares is not above kWithin2ShareFloor = 1e-12, or (1e3 absorb_tol)^2 if that is larger (but at most 1e-4) -- 1e-10 at the default
 // tolerance --, times its centred sum of squares sum (x - xbar)^2 is refused by index with PDS_ERR_NUMERIC.  (What a sweep at tolerance delta leaves of
@@ -119,6 +131,8 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
                   up((size_t)c2_cap * 4) + 3 * up((size_t)lev_cap * 8) + up((size_t)lev_cap * 4) + up((size_t)c2_cap * nc * 8) +
                   up((size_t)n_init * 2 * nc * 8) + 3 * up(64 * 8) + up((size_t)within2_delta_blocks(ctx, lev_cap) * 8) + row_outs.bytes();
     if (space == PDS_HOST) need += up((size_t)n * sizeof(T)) * nc;
+    const bool accel = ctx->opt_within2_accel == 1;  // (the option as it stands when the call starts)
+    if (accel) need += 2 * up((size_t)n_levels2 * nc * 8) + up((size_t)within2_delta_blocks(ctx, lev_cap) * 2 * nc * 8) + up(64 * 8);
     if (int rc = ensure_ws(ctx, ctx->ws, need)) return rc;
     Bump w{static_cast<char*>(ctx->ws.ptr)};
     std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
@@ -259,6 +273,12 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     PDS_HIP_CHECK(hipMemsetAsync(dev.d_a2, 0, (size_t)n_levels2 * nc * 8, ctx->stream));
     const int n_delta = within2_delta_blocks(ctx, n2);
     dev.d_delta = w.take<double>((size_t)n_delta);
+    if (accel) {  // Delta1 / Delta2 (written and read at occupied codes only: no memset), a record per wave of the level kernel, c_j
+        dev.d_dm1 = w.take<double>((size_t)n_levels2 * nc);
+        dev.d_dm2 = w.take<double>((size_t)n_levels2 * nc);
+        dev.d_arec = w.take<double>((size_t)n_delta * 2 * nc);
+        dev.d_coef = w.take<double>(64);
+    }
     double* d_e = want_rows ? w.take<double>((size_t)n) : nullptr;
     row_outs.place(w);
     double *d_alpha1 = nullptr, *d_graw = nullptr, *d_beta = nullptr;
@@ -273,13 +293,15 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         g_outs.place(w);
         l_outs.place(w);
     }
-    // ---- the sweeps: the loop lives here, bounded by absorb_max_iter
+    // ---- the sweeps: the loop lives here, bounded by absorb_max_iter.  Accelerated: cycles of two sweeps, the second followed by the
+    // extrapolation of a2 unless it converged or was the last sweep allowed; only a sweep's delta is ever looked at
     std::vector<double> h_delta((size_t)n_delta);
     double delta = INFINITY;
     int n_iter = 0;
     bool converged = false;
     while (n_iter < max_iter && !converged) {
-        if (int rc = launch_within2_sweep<T>(ctx, d_tbl, p, dev)) return rc;
+        const int phase = accel ? 1 + (n_iter & 1) : 0;
+        if (int rc = launch_within2_sweep<T>(ctx, d_tbl, p, dev, phase)) return rc;
         ++n_iter;
         PDS_HIP_CHECK(hipMemcpyAsync(h_delta.data(), dev.d_delta, (size_t)n_delta * 8, hipMemcpyDeviceToHost, ctx->stream));
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -287,6 +309,8 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         for (double v : h_delta) delta = (v > delta || v != v) ? v : delta;
         if (delta != delta) return fail(PDS_ERR_NUMERIC, "fixed-effects regression: a level mean is not finite (NaN or infinite values in the frame)");
         converged = delta <= tol;
+        if (phase == 2 && !converged && n_iter < max_iter)
+            if (int rc = launch_within2_extrapolate(ctx, p, dev)) return rc;
     }
     if (extra) extra->n_iter = n_iter;
     if (!converged) {

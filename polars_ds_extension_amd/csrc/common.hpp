@@ -142,6 +142,7 @@ struct pds_ctx {
     int64_t opt_multi_route = 0;  // "grouped_multi_route": 0 choose, 1 the one-wave-per-group kernel, 2 one fused launch per target
     int64_t opt_multi_waves = 0;  // "grouped_multi_waves": cap on the grid of the grouped multi-target kernel (0: every wave slot)
     int64_t opt_within_split_rows = 0;  // "within_split_rows": absorbed groups above this many rows are cut into row chunks (0: the default)
+    int64_t opt_within2_accel = 0;      // "within2_accel": 0 plain alternating sweeps, 1 Irons-Tuck cycles (capi_within2.hpp)
 };
 
 namespace pds {
@@ -505,6 +506,9 @@ struct Within2Dev {
     const int32_t* d_l2_code = nullptr;                                         // ... and the code
     double *d_csum2 = nullptr, *d_w0 = nullptr, *d_a1 = nullptr, *d_a2 = nullptr;  // n_chunks2 x nc; n_rows x nc; n1 x nc; codes x nc
     double *d_scale = nullptr, *d_delta = nullptr;  // [nc] s_j; within2_delta_blocks(n_lev2) values per sweep, their maximum is delta
+    // the accelerated iteration only ("within2_accel" = 1; null otherwise): the means of the two sweeps of a cycle, codes x nc each; one
+    // record [sum Delta2 d (nc) | sum d d (nc)] per wave of the level kernel, within2_delta_blocks(n_lev2) of them; c_j [64]
+    double *d_dm1 = nullptr, *d_dm2 = nullptr, *d_arec = nullptr, *d_coef = nullptr;
 };
 int within2_init_records(const pds_ctx* ctx, int64_t n_rows);    // records of 2 nc doubles launch_within2_init writes to d_partials
 int within2_delta_blocks(const pds_ctx* ctx, int64_t n_levels2);
@@ -516,9 +520,12 @@ int launch_within2_gather_codes(pds_ctx* ctx, const int32_t* d_in, const uint32_
 size_t within2_order_temp_bytes(int64_t n_rows);
 int launch_within2_order(pds_ctx* ctx, const int32_t* d_code2, int64_t n_rows, int64_t n_codes, uint32_t* d_iota, uint32_t* d_sorted,
                          uint32_t* d_idx2, void* d_temp, size_t temp_bytes);
-// one sweep: a1, a2 updated, d_delta written.  d_cols: x_0 .. x_{p-1}, y
+// one sweep: a1, a2 updated, d_delta written.  d_cols: x_0 .. x_{p-1}, y.  accel_phase 0: the plain sweep; 1 / 2: the first / second
+// sweep of an accelerated cycle -- the same sweep, which also writes d_dm1 / d_dm2 and (2) the records d_arec
 template <typename T>
-int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d);
+int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d, int accel_phase = 0);
+// the extrapolation that ends a cycle: c_j from d_arec into d_coef, a2 -= c_j d_dm2 over the occupied codes.  Tables only
+int launch_within2_extrapolate(pds_ctx* ctx, int n_feat, const Within2Dev& d);
 // the projected columns, f64, column-major in the kernels' order: d_z[c * n_rows + r]
 template <typename T>
 int launch_within2_final(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d, double* d_z);

@@ -22,6 +22,9 @@
 //     w0 and the row of a1 (its level of factor 1 from the row map g1).  w2_level2_kernel: a wave per level, lane = column, the
 //     chunk sums in chunk order, a2 += mean, and the level's |mean| / s_j into the wave's running maximum; one value per wave goes to
 //     d_delta, the host takes the maximum of those.
+//   * the accelerated iteration ("within2_accel" = 1; capi_within2.hpp has the scheme): w2_level2_accel_kernel<SECOND> is w2_level2_kernel
+//     that also keeps the sweep's means (Delta1 / Delta2) and, on the second sweep of a cycle, one record of sum Delta2 d and sum d d per
+//     wave; w2_accel_coef_kernel (one wave) adds the records in index order into c_j; w2_accel_apply_kernel: a2 -= c_j Delta2.
 //   * w2_final_kernel<T, P>: z, column-major f64, for the final stage (the statistics pass and the within pass of the one-factor fit).
 //   * w2_rows_out_kernel<T>: resid = e and pred = y - e, y the ORIGINAL target, in the caller's row order and type.
 // No floating-point atomics, every sum in a fixed order: two calls give the same bits.  Every loop is bounded by a count known at
@@ -275,6 +278,82 @@ __global__ __launch_bounds__(64) void w2_level2_kernel(const double* __restrict_
     if (lane == 0) delta[blockIdx.x] = dmax;
 }
 
+// w2_level2_kernel for the accelerated iteration (Irons-Tuck, "within2_accel" = 1: capi_within2.hpp has the scheme): the same walk, the
+// same sums and the same update of a2; besides, the level's mean m goes to dm_out[code] (Delta1 on the first sweep of a cycle, Delta2
+// on the second), and on the SECOND sweep the lane adds m d and d d, d = m - dm_prev[code], over the levels the wave walks, in ascending
+// level order: one record [num (nc) | den (nc)] per wave.  The grid is within2_delta_blocks(n_levels): rec has that many records.
+template <bool SECOND>
+__global__ __launch_bounds__(64) void w2_level2_accel_kernel(const double* __restrict__ sums, const int64_t* __restrict__ lev_c0,
+                                                             const int64_t* __restrict__ lev_nc, const int64_t* __restrict__ lev_n,
+                                                             const int32_t* __restrict__ lev_code, int64_t n_levels, int nc, double* __restrict__ a2,
+                                                             const double* __restrict__ scale, double* __restrict__ delta,
+                                                             const double* __restrict__ dm_prev, double* __restrict__ dm_out, double* __restrict__ rec) {
+    const int lane = threadIdx.x;
+    double dmax = 0.0, num = 0.0, den = 0.0;
+    if (lane < nc) {
+        const double s_j = scale[lane];
+        for (int64_t v = blockIdx.x; v < n_levels; v += gridDim.x) {
+            const int64_t c0 = lev_c0[v], k = lev_nc[v];
+            double s = 0.0;
+            for (int64_t i = 0; i < k; ++i) s += sums[(c0 + i) * nc + lane];
+            const double m = s / (double)lev_n[v];
+            const int64_t at = (int64_t)lev_code[v] * nc + lane;
+            a2[at] += m;
+            dm_out[at] = m;
+            if (SECOND) {
+                const double d = m - dm_prev[at];
+                num = fma(m, d, num);
+                den = fma(d, d, den);
+            }
+            dmax = w2_max_nan(dmax, fabs(m) / s_j);
+        }
+        if (SECOND) {
+            rec[(int64_t)blockIdx.x * (2 * nc) + lane] = num;
+            rec[(int64_t)blockIdx.x * (2 * nc) + nc + lane] = den;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) dmax = w2_max_nan(dmax, __shfl_xor(dmax, m, 64));
+    if (lane == 0) delta[blockIdx.x] = dmax;
+}
+
+// one wave, lane = column: the records of a cycle added in index order, eight loads in flight; c_j = sum m d / sum d d, and 0 (the
+// column is left alone) when the denominator is 0 or a sum, or the quotient, is not finite
+__global__ __launch_bounds__(64) void w2_accel_coef_kernel(const double* __restrict__ rec, int n_rec, int nc, double* __restrict__ coef) {
+    const int lane = threadIdx.x;
+    if (lane >= nc) return;
+    double num = 0.0, den = 0.0;
+    for (int i0 = 0; i0 < n_rec; i0 += 8) {
+        double a[8], b[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u < n_rec ? i0 + u : n_rec - 1;
+            a[u] = rec[(int64_t)i * (2 * nc) + lane];
+            b[u] = rec[(int64_t)i * (2 * nc) + nc + lane];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const bool live = i0 + u < n_rec;
+            num += live ? a[u] : 0.0;
+            den += live ? b[u] : 0.0;
+        }
+    }
+    const double c = num / den;
+    coef[lane] = (den != 0.0 && isfinite(num) && isfinite(den) && isfinite(c)) ? c : 0.0;
+}
+
+// a2[code][j] -= c_j Delta2[code][j] over the occupied codes: tables only
+__global__ __launch_bounds__(256) void w2_accel_apply_kernel(const int32_t* __restrict__ lev_code, int64_t n_levels, int nc,
+                                                             const double* __restrict__ coef, const double* __restrict__ dm2, double* __restrict__ a2) {
+    const int64_t total = n_levels * nc;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t v = i / nc;
+        const int j = (int)(i - v * nc);
+        const int64_t at = (int64_t)lev_code[v] * nc + j;
+        a2[at] = fma(-coef[j], dm2[at], a2[at]);
+    }
+}
+
 template <typename T, int P>
 __global__ __launch_bounds__(256) void w2_final_kernel(const T* const* __restrict__ cols, const int32_t* __restrict__ code2,
                                                        const uint32_t* __restrict__ g1, const double* __restrict__ a1, const double* __restrict__ a2,
@@ -360,7 +439,9 @@ int launch_within2_order(pds_ctx* ctx, const int32_t* d_code2, int64_t n_rows, i
 }
 
 template <typename T>
-int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d) {
+int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const Within2Dev& d, int accel_phase) {
+    if (accel_phase < 0 || accel_phase > 2 || (accel_phase && !(d.d_dm1 && d.d_dm2 && d.d_arec)))
+        return fail(PDS_ERR_INVALID, "fixed-effects regression: the accelerated sweep needs its tables");
     if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
     const int nc = n_feat + 1;
     const int nb1 = w2_waves(ctx, d.n1), nbc = d.ch1.n_chunks > 0 ? w2_waves(ctx, d.ch1.n_chunks) : 0;
@@ -381,9 +462,30 @@ int launch_within2_sweep(pds_ctx* ctx, const T* const* d_cols, int n_feat, const
         KernelTimer timer(ctx, kKindSweep2);
         hipLaunchKernelGGL((w2_chunk2_kernel<P>), dim3(nb2), dim3(64), 0, ctx->stream, (const double*)d.d_w0, d.d_idx2, d.d_g1, (const double*)d.d_a1,
                            (const double*)d.d_a2, d.d_c2_pos, d.d_c2_n, d.d_c2_code, d.n_chunks2, d.d_csum2);
-        hipLaunchKernelGGL(w2_level2_kernel, dim3(nbl), dim3(64), 0, ctx->stream, (const double*)d.d_csum2, d.d_l2_c0, d.d_l2_nc, d.d_l2_n,
-                           d.d_l2_code, d.n_lev2, nc, d.d_a2, (const double*)d.d_scale, d.d_delta);
+        if (accel_phase == 0)
+            hipLaunchKernelGGL(w2_level2_kernel, dim3(nbl), dim3(64), 0, ctx->stream, (const double*)d.d_csum2, d.d_l2_c0, d.d_l2_nc, d.d_l2_n,
+                               d.d_l2_code, d.n_lev2, nc, d.d_a2, (const double*)d.d_scale, d.d_delta);
+        else if (accel_phase == 1)
+            hipLaunchKernelGGL(w2_level2_accel_kernel<false>, dim3(nbl), dim3(64), 0, ctx->stream, (const double*)d.d_csum2, d.d_l2_c0, d.d_l2_nc,
+                               d.d_l2_n, d.d_l2_code, d.n_lev2, nc, d.d_a2, (const double*)d.d_scale, d.d_delta, (const double*)nullptr, d.d_dm1,
+                               (double*)nullptr);
+        else
+            hipLaunchKernelGGL(w2_level2_accel_kernel<true>, dim3(nbl), dim3(64), 0, ctx->stream, (const double*)d.d_csum2, d.d_l2_c0, d.d_l2_nc,
+                               d.d_l2_n, d.d_l2_code, d.n_lev2, nc, d.d_a2, (const double*)d.d_scale, d.d_delta, (const double*)d.d_dm1, d.d_dm2,
+                               d.d_arec);
     });
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
+// after the second sweep of a cycle: c_j from the cycle's records (on the device: the host does not read them), then a2 -= c_j Delta2
+int launch_within2_extrapolate(pds_ctx* ctx, int n_feat, const Within2Dev& d) {
+    if (n_feat < 1 || n_feat > kMaxFeatSmall || !(d.d_dm2 && d.d_arec && d.d_coef)) return fail(PDS_ERR_INVALID, "fixed-effects regression: the accelerated sweep needs its tables");
+    const int nc = n_feat + 1;
+    KernelTimer timer(ctx, kKindSweep2);
+    hipLaunchKernelGGL(w2_accel_coef_kernel, dim3(1), dim3(64), 0, ctx->stream, (const double*)d.d_arec, within2_delta_blocks(ctx, d.n_lev2), nc, d.d_coef);
+    hipLaunchKernelGGL(w2_accel_apply_kernel, dim3(w2_row_blocks(ctx, d.n_lev2 * nc)), dim3(256), 0, ctx->stream, d.d_l2_code, d.n_lev2, nc,
+                       (const double*)d.d_coef, (const double*)d.d_dm2, d.d_a2);
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
@@ -410,8 +512,8 @@ int launch_within2_rows_out(pds_ctx* ctx, const T* d_y, const double* d_e, const
 
 template int launch_within2_init<double>(pds_ctx*, const double* const*, int, int64_t, double*, double*, double*);
 template int launch_within2_init<float>(pds_ctx*, const float* const*, int, int64_t, double*, double*, double*);
-template int launch_within2_sweep<double>(pds_ctx*, const double* const*, int, const Within2Dev&);
-template int launch_within2_sweep<float>(pds_ctx*, const float* const*, int, const Within2Dev&);
+template int launch_within2_sweep<double>(pds_ctx*, const double* const*, int, const Within2Dev&, int);
+template int launch_within2_sweep<float>(pds_ctx*, const float* const*, int, const Within2Dev&, int);
 template int launch_within2_final<double>(pds_ctx*, const double* const*, int, const Within2Dev&, double*);
 template int launch_within2_final<float>(pds_ctx*, const float* const*, int, const Within2Dev&, double*);
 template int launch_within2_rows_out<double>(pds_ctx*, const double*, const double*, const uint32_t*, int64_t, double*, double*);

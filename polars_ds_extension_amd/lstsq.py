@@ -11,6 +11,7 @@ All arithmetic happens in libpds_lstsq_hip.so; nothing here computes a regressio
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 from typing import Sequence
@@ -111,9 +112,15 @@ class Context:
     def set_option(self, name: str, value) -> None:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
         "glm_split_rows", "mixed_split_rows", "cluster_split_rows", "cluster_waves", "within_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
-        "grouped_multi_waves"; the
+        "grouped_multi_waves", "within2_accel" (0: plain sweeps of the two-key fixed-effects calls, the default; 1: Irons-Tuck cycles); the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
+
+    def get_option(self, name: str) -> int:
+        """The value the option has now (pds_ctx_get_option), whoever set it."""
+        v = C.c_longlong(0)
+        _lib.check(self._lib.pds_ctx_get_option(self._h, str(name).encode(), C.byref(v)))
+        return int(v.value)
 
     @property
     def num_cus(self) -> int:
@@ -298,7 +305,7 @@ def _lin_reg_arrow(x, target, add_bias, return_pred, null_policy, prm, ctx):
 def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool = False, l1_reg: float = 0.0,
             l2_reg: float = 0.0, tol: float = 1e-5, solver: str = "qr", max_iter: int = 200, positive: bool = False,
             singular_x_tol: float | None = None, null_policy: str = "skip", absorb=None, absorb_offsets=None,
-            absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, ctx: Context | None = None):
+            absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, absorb_accel: str | None = None, ctx: Context | None = None):
     """
     pds.lin_reg on null-free column buffers (pl_lr / pl_lr_pred).
 
@@ -308,11 +315,12 @@ def lin_reg(*x, target, add_bias: bool = False, weights=None, return_pred: bool 
 
     `absorb=key` / `absorb_offsets=off`: the fixed-effects fit with one intercept per group (see lin_reg_report); returns beta, or
     (beta, pred, resid) with return_pred=True.  OLS only: the penalties, `solver` and `positive` do not apply.  `absorb=[k1, k2]`: two
-    absorbed keys (`absorb_tol`, `absorb_max_iter`: see lin_reg_report).
+    absorbed keys (`absorb_tol`, `absorb_max_iter`, `absorb_accel`: see lin_reg_report; "irons_tuck" runs cycles of two sweeps and an
+    extrapolation, and `absorb_max_iter` counts sweeps).
     """
-    if absorb is not None or absorb_offsets is not None:
+    if absorb is not None or absorb_offsets is not None or absorb_accel is not None:
         rep = _lin_reg_within(x, target, add_bias, weights, None, None, absorb, absorb_offsets, None, False, return_pred, None, ctx, fit_only=True,
-                              absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter)
+                              absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, absorb_accel=absorb_accel)
         return (rep["beta"], rep["pred"], rep["resid"]) if return_pred else rep["beta"]
     if isinstance(target, (list, tuple)):  # multi-target: expr_linear.py:188-228
         if len(target) == 0:
@@ -605,7 +613,8 @@ def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = F
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", y_var: float | None = None,
                    feature_names: Sequence[str] | None = None, null_policy: str = "raise", cluster=None, cluster_offsets=None,
                    absorb=None, absorb_offsets=None, return_effects: bool = False, return_pred: bool = False,
-                   absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, ctx: Context | None = None) -> dict:
+                   absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, absorb_accel: str | None = None,
+                   ctx: Context | None = None) -> dict:
     """
     pds.lin_reg_report (pl_lin_reg_report / pl_wls_report).  `y_var` is what Polars evaluates as
     `target.var()` (ddof=1) and hands to the plugin as input 0 (expr_linear.py:614-617); when omitted it
@@ -639,10 +648,18 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     freedom; "cluster" / "cluster0" cluster on the FIRST key.  The dict is the one-key dict plus "n_groups2" (G2), "n_components"
     and "n_iter" (sweeps used).  return_pred=True works as above; return_effects=True is refused with two keys (the effects
     need a normalisation: `fixed_effects` returns them under its own), and so are three or more keys; `absorb_offsets` cannot be combined with a second key.
+    `absorb_accel` (two keys only, else ValueError): None -- what the context's option "within2_accel" says (plain sweeps unless it was
+    set); "none" -- plain sweeps; "irons_tuck" -- the accelerated iteration.  A CYCLE is two sweeps, each exactly the plain sweep and
+    each judged by its own delta, followed by one extrapolation of the table of factor-2 means along the last sweep's step (per
+    column, c = <step2, step2 - step1> / |step2 - step1|^2; tables only, no read of the frame).  The call always ends on a sweep;
+    "n_iter" and `absorb_max_iter` count SWEEPS, never extrapolations.  On frames whose plain sweeps converge slowly (few movers
+    between the levels) the sweep count falls several times; it is never meant to rise.  A string sets the option for this call and
+    puts the previous value back afterwards, also when the call raises.
     """
-    if absorb is not None or absorb_offsets is not None:
+    if absorb is not None or absorb_offsets is not None or absorb_accel is not None:
         return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, (cluster, cluster_offsets),
-                               return_effects, return_pred, None, ctx, absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter)
+                               return_effects, return_pred, None, ctx, absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter,
+                               absorb_accel=absorb_accel)
     if return_effects or return_pred:
         raise ValueError("`return_effects` / `return_pred` go with `absorb` or `absorb_offsets` only")
     if std_err in _lib.CLUSTER_SE_TYPES:
@@ -743,10 +760,35 @@ def _lin_reg_report_cluster(x, target, add_bias, weights, std_err, y_var, featur
     return out
 
 
+# `absorb_accel` -> the context option "within2_accel"
+ABSORB_ACCEL = {"none": 0, "irons_tuck": 1}
+
+
+@contextlib.contextmanager
+def _accel_option(ctx, absorb_accel):
+    """`absorb_accel` for the library calls inside: the option is read from the context (pds_ctx_get_option), set, and the value read
+    goes back whatever the calls do.  None leaves the context alone."""
+    if absorb_accel is None:
+        yield
+        return
+    before = ctx.get_option("within2_accel")
+    ctx.set_option("within2_accel", ABSORB_ACCEL[absorb_accel])
+    try:
+        yield
+    finally:
+        ctx.set_option("within2_accel", before)
+
+
 def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, clusters, return_effects, return_pred,
-                    max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, effects2: bool = False):
+                    max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, effects2: bool = False,
+                    absorb_accel: str | None = None):
     """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*; absorb=[k1, k2]: _within2_*;
     effects2 (fixed_effects): pds_lin_reg_within2_fx_by_key_*."""
+    if absorb_accel is not None:
+        if absorb_accel not in ABSORB_ACCEL:
+            raise ValueError('`absorb_accel` is None, "none" or "irons_tuck"')
+        if not isinstance(absorb, (list, tuple)) or len(absorb) != 2 or absorb_offsets is not None:
+            raise ValueError("`absorb_accel` goes with two absorbed keys, `absorb=[k1, k2]`, only")
     key2 = None
     if isinstance(absorb, (list, tuple)):
         if len(absorb) > 2:
@@ -807,16 +849,18 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
                                                          C.byref(fx))
             return rc, (alpha, comp1, extra, fx)
 
-        effect_keys, (alpha, comp1, extra, fx), g = _by_key_retry(cols, max_groups, call)
+        with _accel_option(ctx, absorb_accel):
+            effect_keys, (alpha, comp1, extra, fx), g = _by_key_retry(cols, max_groups, call)
         alpha, comp1 = alpha[:g], comp1[:g]
     elif key2 is not None:
         k, k_p = _key_arg(cols, absorb)
         codes2, codes2_p, n_levels2, _ = _dense_codes(cols, key2)
         extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
         ng = C.c_int64(0)
-        _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
-                                                        C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep), C.byref(extra),
-                                                        C.byref(ng)))
+        with _accel_option(ctx, absorb_accel):
+            _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space,
+                                                            se_code, C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep),
+                                                            C.byref(extra), C.byref(ng)))
     elif absorb is not None:
         k, k_p = _key_arg(cols, absorb)
 
@@ -896,7 +940,7 @@ def _dense_codes(cols: "_Cols", key):
 
 def fixed_effects(*x, target, absorb, std_err: str = "se", absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, return_pred: bool = False,
                   feature_names: Sequence[str] | None = None, add_bias: bool = False, weights=None, max_groups: int | None = None,
-                  ctx: Context | None = None) -> dict:
+                  absorb_accel: str | None = None, ctx: Context | None = None) -> dict:
     """
     The two-way fixed-effects regression y_i = alpha_k1(i) + gamma_k2(i) + x_i' beta + e_i WITH its estimated effects
     (pds_lin_reg_within2_fx_by_key_*; include/pds_lstsq.h states the definitions).  `absorb=[k1, k2]`: exactly two integer columns.
@@ -909,12 +953,15 @@ def fixed_effects(*x, target, absorb, std_err: str = "se", absorb_tol: float = 1
     exactly 0.0 at the smallest key of k2 that occurs in it -- the coefficients of the regression on the features, a dummy per level
     of k1 and a dummy per level of k2 less that one per component.  NumPy arrays or CUDA tensors; a device frame gets device outputs.
     `max_groups`: a bound on the distinct keys of k1 (the outputs are sized for it), as in the other by-key calls.
+    `absorb_accel`: None (the context's option "within2_accel"), "none" or "irons_tuck" -- cycles of two plain sweeps and one
+    extrapolation of the factor-2 table, see lin_reg_report; "n_iter" counts sweeps.  The call ends on a sweep, so the effects and
+    their normalisation are formed from the tables exactly as without acceleration.
     """
     if not isinstance(absorb, (list, tuple)) or len(absorb) < 2:
         raise ValueError("fixed_effects: `absorb` is a list of exactly two integer columns; the effects of ONE absorbed key come from "
                          "lin_reg_report(absorb=k, return_effects=True)")
     return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, None, None, False, return_pred, max_groups, ctx,
-                           absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, effects2=True)
+                           absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, effects2=True, absorb_accel=absorb_accel)
 
 
 def absorb_components(k1, k2, ctx: Context | None = None) -> dict:

@@ -17,6 +17,13 @@ loads another build of the library (an earlier commit's, for an A/B in a series 
 lacks are left out of the record).  One more call with absorb_max_iter=1 (it fails after one sweep) is timed by the
 wall clock: everything in front of the sweeps -- the host pass among it -- and one sweep.  Lines are appended to profiles/within2_report_bench.txt
 (`--out`).  No time here is a pass condition.
+
+`--accel` measures the accelerated iteration (absorb_accel="irons_tuck": cycles of two sweeps and an extrapolation of the factor-2
+table) instead, into profiles/within2_accel_bench.txt: on the panel above (at `--tol` and at 1e-13), and on a FEW-MOVERS frame at scale built with
+tests/within2_cases.py::movers_frame's rule at p = 4 (`--movers WORKERS,FIRMS,MOVERS`, 6 rows per worker), the plain and the
+accelerated call alternate in this one process, `--reps` warmed calls each by device events; per frame one record with both calls'
+times and sweep counts, the time per sweep of each (call time / sweeps, and the sweep kernels' time / sweeps from the timing
+classes; the extrapolation's two kernels are in "sweep_factor2"), and the ratios plain / accelerated of the times and of the sweeps.
 """
 import argparse
 import json
@@ -64,6 +71,49 @@ def make_panel(gen, dev, firms, periods, drop, p):
     return X, y, firm, period
 
 
+def make_movers(dev, workers, firms, movers, p=4):
+    """tests/within2_cases.py::movers_frame (seed 0, 6 rows per worker) on the device: (X, y, worker, firm)"""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import numpy as np
+    import within2_cases as c2
+
+    F, y, off, k1, k2 = c2.movers_frame(p, 0, workers, firms, 6, movers)
+    X = [torch.from_numpy(np.ascontiguousarray(F[:, j])).to(dev) for j in range(p)]
+    return X, torch.from_numpy(np.array(y)).to(dev), torch.from_numpy(np.array(k1)).to(dev), torch.from_numpy(np.array(k2)).to(dev)
+
+
+def accel_record(ctx, name, X, y, k1, k2, tol, reps, label):
+    """the plain and the accelerated report on one frame, alternating in this process"""
+    fns = {m: (lambda m=m: pds.lin_reg_report(*X, target=y, std_err="se", absorb=[k1, k2], absorb_tol=tol, absorb_max_iter=100_000,
+                                              absorb_accel=m, ctx=ctx)) for m in ("none", "irons_tuck")}
+    t = timed_alternating(fns, reps)
+    n, p = int(y.numel()), len(X)
+    rec = {"bench": "within2_accel", "build": label, "frame": name, "rows": n, "p": p, "absorb_tol": tol}
+    per = {}
+    for m, fn in fns.items():
+        ctx.set_timing(True)
+        ctx.get_timing()
+        r = fn()
+        ctx.synchronize()
+        tm = ctx.get_timing()
+        ctx.set_timing(False)
+        key = "plain" if m == "none" else "accel"
+        sweeps = r["n_iter"]
+        rec.update({"levels1": r["n_groups"], "levels2": r["n_groups2"], "components": r["n_components"]})
+        rec[key + "_sweeps"] = sweeps
+        rec[key + "_ms"], rec[key + "_ms_best"], rec[key + "_ms_worst"] = (round(v, 3) for v in t[m])
+        rec[key + "_call_ms_per_sweep"] = round(t[m][0] / sweeps, 5)
+        rec[key + "_sweep_kernels_ms_per_sweep"] = round((tm["sweep_factor1"][0] + tm["sweep_factor2"][0]) / sweeps, 5)
+        rec[key + "_sweep_kernel_launches"] = tm["sweep_factor1"][1] + tm["sweep_factor2"][1]
+        rec[key + "_call_less_sweep_kernels_ms"] = round(t[m][0] - (tm["sweep_factor1"][0] + tm["sweep_factor2"][0]), 3)
+        per[key] = rec[key + "_sweep_kernels_ms_per_sweep"]
+    rec["sweeps_plain_over_accel"] = round(rec["plain_sweeps"] / rec["accel_sweeps"], 3)
+    rec["time_plain_over_accel"] = round(rec["plain_ms"] / rec["accel_ms"], 3)
+    rec["call_ms_per_sweep_accel_over_plain"] = round(rec["accel_call_ms_per_sweep"] / rec["plain_call_ms_per_sweep"], 4)
+    rec["sweep_kernels_ms_per_sweep_accel_over_plain"] = round(per["accel"] / per["plain"], 4)
+    emit(rec)
+
+
 def main():
     global OUT
     ap = argparse.ArgumentParser()
@@ -76,7 +126,11 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "within2_report_bench.txt"))
     ap.add_argument("--lib", default=None, help="another build of libpds_lstsq_hip.so to measure")
     ap.add_argument("--label", default="this")
+    ap.add_argument("--accel", action="store_true", help="the accelerated iteration against the plain one (profiles/within2_accel_bench.txt)")
+    ap.add_argument("--movers", default="300000,200,15000", help="--accel: workers,firms,movers of the few-movers frame (6 rows per worker)")
     a = ap.parse_args()
+    if a.accel and a.out == ap.get_default("out"):
+        a.out = str(ROOT / "profiles" / "within2_accel_bench.txt")
     OUT = a.out or None
     if a.lib:
         pds._lib.LIB_PATH = Path(a.lib).resolve()
@@ -89,6 +143,14 @@ def main():
     p = a.features
     X, y, firm, period = make_panel(gen, dev, int(a.firms), a.periods, a.drop, p)
     n = int(y.numel())
+    if a.accel:
+        for tol in sorted({a.tol, 1e-13}, reverse=True):
+            accel_record(ctx, f"panel {int(a.firms)} x {a.periods} less {a.drop:.0%}", X, y, firm, period, tol, a.reps, a.label)
+        del X, y, firm, period
+        workers, firms, movers = (int(v) for v in a.movers.split(","))
+        accel_record(ctx, f"few movers {workers} workers x 6 rows in {firms} firms, {movers} movers", *make_movers(dev, workers, firms, movers),
+                     a.tol, a.reps, a.label)
+        return
     fns = {
         "two_keys_se": lambda: pds.lin_reg_report(*X, target=y, std_err="se", absorb=[firm, period], absorb_tol=a.tol, ctx=ctx),
         "two_keys_cluster": lambda: pds.lin_reg_report(*X, target=y, std_err="cluster", absorb=[firm, period], absorb_tol=a.tol, ctx=ctx),
