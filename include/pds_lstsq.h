@@ -346,7 +346,7 @@ int pds_lin_reg_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols
  * points have no counterpart in the reference to stay bit-compatible with; at 1e4 .. 1e5 degrees of freedom the two differ by 1e-10).  Refused, never approximated: n - G - p <= 0 PDS_ERR_TOO_FEW_ROWS; a cluster form with G < 2 PDS_ERR_INVALID; a feature
  * that is constant inside every group (collinear with the effects) PDS_ERR_NUMERIC, the message naming the column index; W_xx not
  * positive definite otherwise PDS_ERR_NUMERIC; more than 16 features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.
- * There is no weighted form.
+ * There is no weighted form.  Clusters on a key other than the absorbed one: pds_lin_reg_within_cl_* below.
  */
 typedef struct {           /* every pointer nullable and `space`-resident */
     void* alpha;           /* [n_groups] (by key: [max_groups], ascending key order) */
@@ -508,6 +508,72 @@ int pds_lin_reg_within2_fx_by_key_f32(pds_ctx* ctx, const float* const* cols, co
 int pds_absorb_components_i32(pds_ctx* ctx, const int32_t* codes1, int64_t n_levels1, const int32_t* codes2, int64_t n_levels2, int64_t n_rows,
                               pds_space space, int32_t* component1, int32_t* component2, int64_t* n1, int64_t* n2, int64_t* n_components,
                               int* n_rounds);
+
+/*
+ * pds_lin_reg_within_cl_* / pds_lin_reg_within2_cl_*: the fixed-effects regressions above with standard errors clustered on ANY key --
+ * a key that is not an absorbed key (absorb firm and year, cluster on state), or the second absorbed key.  The argument lists are
+ * those of pds_lin_reg_within_* and of pds_lin_reg_within2_fx_* (fx still nullable) plus a trailing pds_cluster_key* cl.  cl == NULL:
+ * the call IS the one without the suffix, bit for bit.  What follows is a DEFINITION of what the library computes; no equivalence with
+ * the small-sample conventions of any package is claimed.
+ *   x~, y~ are the columns projected off the absorbed dummies, B = (X~'X~)^-1, e = y~ - X~ beta: all formed by the fit exactly as
+ *   without a cluster key (beta, r2, adj_r2, r2_overall, pred, resid, n_iter and the effects are the same bits).
+ *   cl->codes: n_rows dense int32 codes in [0, cl->n_levels), in the CALLER's row order, `space`-resident (the by-key forms gather them
+ *   through their row permutation).  A code that no row uses counts nowhere.  A code outside the range: PDS_ERR_INVALID; the range is
+ *   checked by a kernel that reads nothing else, before anything is indexed by a code.  Gc is the number of occupied codes.
+ *   s_c = sum_{i in c} x~_i e_i,  M = sum_c s_c s_c'.
+ *   se_type PDS_CLUSTER0: V = B M B.
+ *   se_type PDS_CLUSTER:  the same V times Gc / (Gc - 1) * (n - 1) / (n - K),
+ *                         K = p + sum_f (nested_f ? 0 : A_f) + (some factor nested ? 1 : 0),  A_1 = G1,  A_2 = G2 - C (= A - G1).
+ *                         Factor f is NESTED when every occupied level of it has all its rows in one cluster: its effects are then
+ *                         not counted among the parameters, and the one intercept is counted in their place.  This K reproduces both
+ *                         definitions above: one key clustered on itself gives K = p + 1, two keys clustered on the first give
+ *                         K = p + 1 + (A - G1).  With no factor nested K = p + A.
+ *   t, p and the 95 % interval use the Student t with Gc - 1 degrees of freedom; extra->df_resid = Gc - 1.
+ * Refused: Gc < 2 PDS_ERR_INVALID; se_type PDS_SE together with a cluster key PDS_ERR_INVALID (and std_err .. ci_upper must be given);
+ * 2^31 rows or more PDS_ERR_UNSUPPORTED; everything the calls without the suffix refuse.  cl->n_clusters receives Gc, cl->nested1 /
+ * cl->nested2 whether factor 1 / factor 2 is nested in the clusters (nested2 = 0 with one factor).
+ * The meat is a gather: the rows are ordered by a stable radix sort of (code, row), the cluster sizes are exact integers from the run
+ * boundaries, every occupied cluster is cut into chunks of at most 1 024 rows of that order ("within_split_rows" rows if that is
+ * smaller).  One more contiguous pass over the frame stages every row's score x~_i e_i row-major (p doubles per row, padded to an even
+ * count: n x p x 8 bytes of workspace, which fails with the allocation's error if the device cannot hold it); a wave per chunk gathers
+ * the staged rows and sums them by a fixed-order butterfly; a cluster's chunk scores are added in chunk order.  Nestedness is decided
+ * from integers alone (the minimum and maximum cluster code over every level's rows).  No floating-point atomics: two calls give the
+ * same bits, and the by-key form on shuffled rows gives the bits of the grouped form.
+ */
+typedef struct {
+    const int32_t* codes;     /* [n_rows], `space`-resident, the caller's row order */
+    int64_t n_levels;
+    int64_t n_clusters;       /* out: Gc */
+    int32_t nested1, nested2; /* out; nested2 = 0 with one factor */
+} pds_cluster_key;
+int pds_lin_reg_within_cl_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                      int64_t n_groups, pds_space space, int se_type, pds_report_f64* out, pds_within_out* extra,
+                                      pds_cluster_key* cl);
+int pds_lin_reg_within_cl_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                      int64_t n_groups, pds_space space, int se_type, pds_report_f32* out, pds_within_out* extra,
+                                      pds_cluster_key* cl);
+int pds_lin_reg_within_cl_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                     int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f64* out, pds_within_out* extra,
+                                     int64_t* n_groups, pds_cluster_key* cl);
+int pds_lin_reg_within_cl_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                     int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f32* out, pds_within_out* extra,
+                                     int64_t* n_groups, pds_cluster_key* cl);
+int pds_lin_reg_within2_cl_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx, pds_cluster_key* cl);
+int pds_lin_reg_within2_cl_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra,
+                                       pds_within2_effects* fx, pds_cluster_key* cl);
+int pds_lin_reg_within2_cl_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx,
+                                      pds_cluster_key* cl);
+int pds_lin_reg_within2_cl_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx,
+                                      pds_cluster_key* cl);
 
 /*
  * Row-sharded `pl_lin_reg_report` / `pl_wls_report` (one process per GPU): the stages of

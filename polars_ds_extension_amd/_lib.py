@@ -44,6 +44,8 @@ EXPORTS = [
     "pds_lin_reg_within2_grouped_f64", "pds_lin_reg_within2_grouped_f32", "pds_lin_reg_within2_by_key_f64", "pds_lin_reg_within2_by_key_f32",
     "pds_lin_reg_within2_fx_grouped_f64", "pds_lin_reg_within2_fx_grouped_f32", "pds_lin_reg_within2_fx_by_key_f64", "pds_lin_reg_within2_fx_by_key_f32",
     "pds_absorb_components_i32",
+    "pds_lin_reg_within_cl_grouped_f64", "pds_lin_reg_within_cl_grouped_f32", "pds_lin_reg_within_cl_by_key_f64", "pds_lin_reg_within_cl_by_key_f32",
+    "pds_lin_reg_within2_cl_grouped_f64", "pds_lin_reg_within2_cl_grouped_f32", "pds_lin_reg_within2_cl_by_key_f64", "pds_lin_reg_within2_cl_by_key_f32",
     "pds_wls_report_grouped_f64", "pds_wls_report_grouped_f32", "pds_wls_report_by_key_f64", "pds_wls_report_by_key_f32",
     "pds_student_t_sf_device",
     "pds_report_fit_from_moments_f64", "pds_report_fit_from_moments_f32", "pds_report_partials_f64", "pds_report_partials_f32",
@@ -119,6 +121,11 @@ class Within2Effects(C.Structure):
     """pds_within2_effects: the estimated effects and components of the two-factor fit, nullable outputs in the frame's space."""
     _fields_ = [("effects1", C.c_void_p), ("effects2", C.c_void_p), ("component1", C.c_void_p), ("component2", C.c_void_p),
                 ("keys1", C.c_void_p), ("cap1", C.c_int64), ("n_graph_rounds", C.c_int64)]
+
+
+class ClusterKey(C.Structure):
+    """pds_cluster_key: the cluster codes of pds_lin_reg_within_cl_* / pds_lin_reg_within2_cl_* and what the call reports about them."""
+    _fields_ = [("codes", C.c_void_p), ("n_levels", C.c_int64), ("n_clusters", C.c_int64), ("nested1", C.c_int32), ("nested2", C.c_int32)]
 
 
 class PdsError(RuntimeError):
@@ -198,6 +205,10 @@ def load() -> C.CDLL:
             if hasattr(lib, "pds_lin_reg_within2_fx_grouped_" + sfx):  # the within2 lists plus a trailing pds_within2_effects*
                 getattr(lib, "pds_lin_reg_within2_fx_grouped_" + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_grouped_" + sfx).argtypes + [C.c_void_p]
                 getattr(lib, "pds_lin_reg_within2_fx_by_key_" + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_by_key_" + sfx).argtypes + [C.c_void_p]
+            if hasattr(lib, "pds_lin_reg_within_cl_grouped_" + sfx):  # the within / within2_fx lists plus a trailing pds_cluster_key*
+                for form in ("grouped_", "by_key_"):
+                    getattr(lib, "pds_lin_reg_within_cl_" + form + sfx).argtypes = getattr(lib, "pds_lin_reg_within_" + form + sfx).argtypes + [C.c_void_p]
+                    getattr(lib, "pds_lin_reg_within2_cl_" + form + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_fx_" + form + sfx).argtypes + [C.c_void_p]
         if hasattr(lib, "pds_absorb_components_i32"):
             # ctx, codes1, n_levels1, codes2, n_levels2, n_rows, space, component1, component2, n1, n2, n_components, n_rounds
             lib.pds_absorb_components_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 6

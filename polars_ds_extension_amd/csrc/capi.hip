@@ -36,6 +36,7 @@ namespace pds {
 #include "capi_multi_grouped.hpp"
 #include "capi_mixed.hpp"
 #include "capi_report_cluster.hpp"
+#include "capi_within_cluster.hpp"
 #include "capi_within.hpp"
 #include "capi_within2.hpp"
 #include "capi_glm_sandwich.hpp"
@@ -46,6 +47,21 @@ namespace pds {
 // extern "C"
 // =============================================================================================
 using namespace pds;
+
+// pds_cluster_key -> the WithinCluster the pipelines take (null: the call without a cluster key); its outputs back to the caller
+template <typename F>
+static int with_cluster_key(pds_cluster_key* cl, pds_space space, F&& call) {
+    if (!cl) return call(nullptr);
+    pds::WithinCluster wc;
+    wc.codes = cl->codes;
+    wc.code_space = space;
+    wc.n_levels = cl->n_levels;
+    const int rc = call(&wc);
+    cl->n_clusters = wc.n_clusters;
+    cl->nested1 = wc.nested1;
+    cl->nested2 = wc.nested2;
+    return rc;
+}
 
 extern "C" {
 
@@ -723,6 +739,66 @@ int pds_lin_reg_within2_fx_by_key_f32(pds_ctx* ctx, const float* const* cols, co
                                       pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx) {
     return within2_by_key_impl<float, pds_report_f32>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol,
                                                       absorb_max_iter, out, extra, n_groups, fx);
+}
+int pds_lin_reg_within_cl_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                      int64_t n_groups, pds_space space, int se_type, pds_report_f64* out, pds_within_out* extra, pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, space, se_type, out, extra, nullptr, nullptr, wc);
+    });
+}
+int pds_lin_reg_within_cl_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                     int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f64* out, pds_within_out* extra, int64_t* n_groups,
+                                     pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within_by_key_impl<double, pds_report_f64>(ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups, wc);
+    });
+}
+int pds_lin_reg_within2_cl_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f64* out, pds_within2_out* extra, pds_within2_effects* fx,
+                                       pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within2_impl<double, pds_report_f64>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type, absorb_tol,
+                                        absorb_max_iter, out, extra, nullptr, fx, wc);
+    });
+}
+int pds_lin_reg_within2_cl_by_key_f64(pds_ctx* ctx, const double* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f64* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx, pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within2_by_key_impl<double, pds_report_f64>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol, absorb_max_iter, out,
+                                               extra, n_groups, fx, wc);
+    });
+}
+int pds_lin_reg_within_cl_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                      int64_t n_groups, pds_space space, int se_type, pds_report_f32* out, pds_within_out* extra, pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, space, se_type, out, extra, nullptr, nullptr, wc);
+    });
+}
+int pds_lin_reg_within_cl_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                                     int se_type, int64_t max_groups, int64_t* out_keys, pds_report_f32* out, pds_within_out* extra, int64_t* n_groups,
+                                     pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within_by_key_impl<float, pds_report_f32>(ctx, cols, keys, n_feat, n_rows, space, se_type, max_groups, out_keys, out, extra, n_groups, wc);
+    });
+}
+int pds_lin_reg_within2_cl_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows, const int64_t* group_offsets,
+                                       int64_t n_groups, const int32_t* codes2, int64_t n_levels2, pds_space space, int se_type,
+                                       double absorb_tol, int absorb_max_iter, pds_report_f32* out, pds_within2_out* extra, pds_within2_effects* fx,
+                                       pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within2_impl<float, pds_report_f32>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, codes2, space, n_levels2, space, se_type, absorb_tol,
+                                        absorb_max_iter, out, extra, nullptr, fx, wc);
+    });
+}
+int pds_lin_reg_within2_cl_by_key_f32(pds_ctx* ctx, const float* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2,
+                                      int n_feat, int64_t n_rows, pds_space space, int se_type, double absorb_tol, int absorb_max_iter,
+                                      pds_report_f32* out, pds_within2_out* extra, int64_t* n_groups, pds_within2_effects* fx, pds_cluster_key* cl) {
+    return with_cluster_key(cl, space, [&](WithinCluster* wc) {
+        return within2_by_key_impl<float, pds_report_f32>(ctx, cols, keys, codes2, n_levels2, n_feat, n_rows, space, se_type, absorb_tol, absorb_max_iter, out,
+                                               extra, n_groups, fx, wc);
+    });
 }
 int pds_absorb_components_i32(pds_ctx* ctx, const int32_t* codes1, int64_t n_levels1, const int32_t* codes2, int64_t n_levels2, int64_t n_rows,
                               pds_space space, int32_t* component1, int32_t* component2, int64_t* n1, int64_t* n2, int64_t* n_components,

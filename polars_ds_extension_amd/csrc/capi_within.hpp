@@ -12,6 +12,7 @@
 //     PDS_CLUSTER   the same V times c = G / (G - 1) * (n - 1) / (n - p - 1): the absorbed effects, nested in the clusters, are not
 //                   counted among the parameters, the one intercept is -- a DEFINITION of this library.  Both cluster forms: G - 1
 //                   degrees of freedom
+//     (clusters on ANY other key, through the struct WithinCluster: capi_within_cluster.hpp has the definitions and the stages)
 //     r2 = 1 - sum e^2 / W_yy (the within R^2);   adj_r2 = 1 - (1 - r2)(n - G) / (n - G - p)
 //     r2_overall = 1 - sum e^2 / sum (y - ybar)^2,  sum (y - ybar)^2 = W_yy + sum_g n_g (m_y,g - ybar)^2
 // A singleton group stays in: it counts in n and G and adds nothing to W or M; its alpha is y - x' beta.  An empty group (offsets
@@ -98,7 +99,7 @@ struct WithinMore {
 template <typename T, typename R>
 static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
                        pds_space out_space, int se_type, R* out, pds_within_out* extra, const uint32_t* d_perm = nullptr,
-                       const WithinMore* more = nullptr) {
+                       const WithinMore* more = nullptr, WithinCluster* cl = nullptr) {
     if (!ctx || !cols || !offsets || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
     if (int rc = within_check_se(se_type)) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
@@ -109,7 +110,9 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     const bool want_se = out->std_err || out->t || out->p || out->ci_lower || out->ci_upper;
     if (want_se && !(out->std_err && out->t && out->p && out->ci_lower && out->ci_upper))
         return fail(PDS_ERR_INVALID, "fixed-effects regression: std_err .. ci_upper are given together or not at all");
-    const bool meat = want_se && se_type != PDS_SE;
+    if (int rc = within_cluster_check(cl, se_type, n_rows, want_se)) return rc;
+    // a cluster key (capi_within_cluster.hpp): the within pass forms no scores, the meat comes from the gathered row scores
+    const bool meat = want_se && se_type != PDS_SE && !cl;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int p = n_feat, nc = p + 1;
     // ---- the offsets on the host: validation, the non-empty groups, the chunks of the long ones
@@ -126,7 +129,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     const int64_t extra_df = more ? more->extra_df : 0;
     const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p - extra_df;
     if (extra) extra->n_groups_used = n_nonempty;
-    if (se_type != PDS_SE && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
+    if (se_type != PDS_SE && !cl && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     if (df_se <= 0) return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #groups - #features <= 0. No conclusive result.");
     const bool empties = pl.dropped(), upload_off = pl.upload_off;  // (the device works on the non-empty groups alone)
     h_off = pl.h_off;
@@ -144,7 +147,8 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     const size_t n_stat = (size_t)mixed_stats_blocks(ctx, n_groups) + (n_chunks > 0 ? (size_t)mixed_stats_blocks(ctx, n_chunks) : 0);
     const size_t n_pass = (size_t)within_pass_blocks(ctx, n_groups) +
                           (n_chunks > 0 ? (size_t)within_pass_blocks(ctx, n_chunks) + (size_t)within_pass_blocks(ctx, n_long) : 0);
-    const size_t n_rec = std::max(n_stat, n_pass), rec_bytes = (size_t)kMixedRecStride * sizeof(double);
+    const size_t n_meat = cl ? (size_t)cluster_meat_records(ctx, std::min<int64_t>(n_rows, cl->n_levels)) : 0;
+    const size_t n_rec = std::max(std::max(n_stat, n_pass), n_meat), rec_bytes = (size_t)kMixedRecStride * sizeof(double);
     size_t need = 8192 + up(sizeof(T*) * 18) + up((size_t)nc * n_groups * 8) + up(n_rec * rec_bytes) + up((n_rec / 64 + 1) * rec_bytes) +
                   up(rec_bytes) + 512 + 9 * up((size_t)(n_chunks + n_long + 1) * 8) + up((size_t)(n_chunks + 1) * nc * 8) +
                   up((size_t)(n_chunks + 1) * 4) + up((size_t)(n_chunks + 1) * kClusterScoreStride * 8) + up(kMaxFeatSmall * 8) +
@@ -152,6 +156,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     if (space == PDS_HOST) need += up((size_t)n_rows * sizeof(T)) * nc;
     if (upload_off) need += up((size_t)(n_groups + 1) * 8);
     if (empties) need += up((size_t)n_groups * 8);
+    if (cl) need += within_cluster_bytes(*cl, n_rows, p, split);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
     Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
     std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
@@ -183,6 +188,9 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     double* d_scores = n_chunks > 0 ? w.take<double>((size_t)n_chunks * kClusterScoreStride) : nullptr;
     g_outs.place(w);
     row_outs.place(w);
+    WithinClusterDev cd;
+    if (cl)
+        if (int rc = within_cluster_open(ctx, w, *cl, n_rows, p, split, cd)) return rc;
     // ---- stage 1: the statistics
     if (int rc = launch_mixed_stats<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, nullptr, d_means, d_flags, d_partials, d_stage, d_rec)) return rc;
     double stat[kMixedRecStride];
@@ -211,8 +219,12 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     if (int rc = launch_within_pass<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, d_scores, d_beta, d_means, meat, d_gmap, d_perm, d_alpha, d_pred,
                                        d_resid, d_partials, d_stage, d_rec))
         return rc;
-    double rec[kMixedRecStride];
+    double rec[kMixedRecStride], crec[kMixedRecStride];
     PDS_HIP_CHECK(hipMemcpyAsync(rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cl) {  // (the records and d_rec are free again: the stream has the copy of `rec` in front of these kernels)
+        if (int rc = within_cluster_meat<T>(ctx, *cl, cd, d_tbl, p, d_off, n_groups, split, ch, d_beta, d_means, d_partials, d_stage, d_rec)) return rc;
+        PDS_HIP_CHECK(hipMemcpyAsync(crec, d_rec, sizeof(crec), hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (int rc = staged_copy_back(ctx, g_outs, (size_t)n_all)) return rc;
     if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (beta: source of the copy)
@@ -225,7 +237,7 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     for (int i = 0; i < p; ++i) out->beta[i] = (T)beta[i];
     if (more && more->beta_f64)
         for (int i = 0; i < p; ++i) more->beta_f64[i] = beta[i];
-    const int64_t df = se_type == PDS_SE ? df_se : n_nonempty - 1;
+    const int64_t df = se_type == PDS_SE ? df_se : (cl ? cl->n_clusters : n_nonempty) - 1;
     if (extra && more) {
         extra->r2_overall = 1.0 - sse / more->tss;
         extra->df_resid = df;
@@ -246,12 +258,19 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
         const double s2 = sse / (double)df_se;
         for (int i = 0; i < p; ++i) se[i] = std::sqrt(s2 * inv[i * p + i]);
     } else {
-        const double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0 - xd)) : 1.0;
+        double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0 - xd)) : 1.0;
+        const double* meat_rec = rec;
+        if (cl) {  // K counts the effects of a factor that is not nested in the clusters, and one intercept if some factor is
+            const int64_t k_par = p + (cl->nested1 ? 0 : n_nonempty) + (cl->nested2 ? 0 : extra_df) + (cl->nested1 || cl->nested2 ? 1 : 0);
+            const double gc = (double)cl->n_clusters;
+            factor = se_type == PDS_CLUSTER ? gc / (gc - 1.0) * ((nd - 1.0) / (nd - (double)k_par)) : 1.0;
+            meat_rec = crec;
+        }
         for (int i = 0; i < p; ++i) {
             double acc = 0.0;
             for (int a = 0; a < p; ++a) {
                 double t = 0.0;
-                for (int b = 0; b < p; ++b) t += rec[kMixedRecW + a * 16 + b] * inv[b * p + i];
+                for (int b = 0; b < p; ++b) t += meat_rec[kMixedRecW + a * 16 + b] * inv[b * p + i];
                 acc += inv[a * p + i] * t;
             }
             se[i] = std::sqrt(acc * factor);
@@ -275,7 +294,8 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
 // max_groups / out_keys matter only when extra->alpha is asked for: alpha and out_keys then have room for max_groups entries.
 template <typename T, typename R>
 static int within_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int se_type,
-                              int64_t max_groups, int64_t* out_keys, R* out, pds_within_out* extra, int64_t* n_groups) {
+                              int64_t max_groups, int64_t* out_keys, R* out, pds_within_out* extra, int64_t* n_groups,
+                              WithinCluster* cl = nullptr) {
     if (!ctx || !cols || !keys || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (int rc = within_check_se(se_type)) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
@@ -290,7 +310,9 @@ static int within_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t*
     Bump w{};
     if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_alpha ? max_groups : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
         return rc;
-    if (int rc = within_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, space, se_type, out, extra, kf.d_perm)) return rc;
+    if (cl) cl->d_code_perm = kf.d_perm;  // (the cluster codes stay in the caller's row order and are gathered through the permutation)
+    if (int rc = within_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, space, se_type, out, extra, kf.d_perm, nullptr, cl))
+        return rc;
     if (want_alpha && out_keys) {
         PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                      ctx->stream));

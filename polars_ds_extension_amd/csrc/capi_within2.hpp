@@ -57,14 +57,15 @@
 // G2 - C and the original target's sum of squares; pred / resid from the residuals and the ORIGINAL target (launch_within2_rows_out).
 #pragma once
 
-// every level of factor 2 is cut into chunks of at most this many gathered rows ("within_split_rows", if smaller, takes its place)
-constexpr int64_t kWithin2GatherChunkRows = 1024;
+// every level of factor 2 is cut into chunks of at most kWithin2GatherChunkRows gathered rows ("within_split_rows", if smaller, takes
+// its place): the constant lives in capi_within_cluster.hpp, whose cluster chunks follow the same rule
 constexpr double kWithin2ShareFloor = 1e-12, kWithin2ShareTolFactor = 1e3, kWithin2ShareCap = 1e-4;
 
 template <typename T, typename R>
 static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n_rows, const int64_t* offsets, int64_t n_groups, pds_space space,
                         const int32_t* codes2, pds_space code_space, int64_t n_levels2, pds_space out_space, int se_type, double tol, int max_iter,
-                        R* out, pds_within2_out* extra, const uint32_t* d_perm = nullptr, pds_within2_effects* fx = nullptr) {
+                        R* out, pds_within2_out* extra, const uint32_t* d_perm = nullptr, pds_within2_effects* fx = nullptr,
+                        WithinCluster* cl = nullptr) {
     if (!ctx || !cols || !offsets || !codes2 || !out || !out->beta) return fail(PDS_ERR_INVALID, "null argument");
     if (fx && n_groups >= (1ll << 31)) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: the effects of fewer than 2^31 groups per call");
     if (int rc = within_check_se(se_type)) return rc;
@@ -79,6 +80,7 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     const bool want_se = out->std_err || out->t || out->p || out->ci_lower || out->ci_upper;
     if (want_se && !(out->std_err && out->t && out->p && out->ci_lower && out->ci_upper))
         return fail(PDS_ERR_INVALID, "fixed-effects regression: std_err .. ci_upper are given together or not at all");
+    if (int rc = within_cluster_check(cl, se_type, n_rows, want_se)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int p = n_feat, nc = p + 1;
     const int64_t n = n_rows;
@@ -95,7 +97,7 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         return rc;
     h_off = pl.h_off;
     const int64_t n1 = pl.n_nonempty, n_chunks1 = pl.n_chunks(), n_long1 = pl.n_long();
-    if (se_type != PDS_SE && n1 < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
+    if (se_type != PDS_SE && !cl && n1 < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     // ---- workspace (ctx->ws: the by-key form's ordered frame lives in ctx->keyed, the final stage works in ctx->wkeyed)
     const auto up = Bump::up;
     const bool out_host = out_space == PDS_HOST, want_rows = extra && (extra->pred || extra->resid);
@@ -336,7 +338,13 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     pds_within_out wo{};
     wo.resid = d_e;
     wo.alpha = d_alpha1;  // (the one-factor effects of the projected columns: of the order of absorb_tol, they close the identity)
-    if (int rc = within_impl<double, R>(ctx, zc.data(), p, n, dev.d_off1, n1, PDS_DEVICE, PDS_DEVICE, se_type, out, &wo, nullptr, &more)) return rc;
+    if (cl) {  // the cluster codes are gathered through the row permutation; factor 2's nestedness walks its ordered row index
+        cl->d_code_perm = d_perm;
+        cl->d_idx2 = dev.d_idx2;
+        cl->d_start2 = d_start;
+        cl->n_levels2 = n_levels2;
+    }
+    if (int rc = within_impl<double, R>(ctx, zc.data(), p, n, dev.d_off1, n1, PDS_DEVICE, PDS_DEVICE, se_type, out, &wo, nullptr, &more, cl)) return rc;
     if (extra) {
         extra->r2_overall = wo.r2_overall;
         extra->df_resid = wo.df_resid;
@@ -371,7 +379,7 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
 template <typename T, typename R>
 static int within2_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, const int32_t* codes2, int64_t n_levels2, int n_feat,
                                int64_t n_rows, pds_space space, int se_type, double tol, int max_iter, R* out, pds_within2_out* extra,
-                               int64_t* n_groups, pds_within2_effects* fx = nullptr) {
+                               int64_t* n_groups, pds_within2_effects* fx = nullptr, WithinCluster* cl = nullptr) {
     if (!ctx || !cols || !keys || !codes2 || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     // fx->cap1 matters only when an output per level of key 1 is asked for: each then has room for cap1 entries
     const bool want_keys = fx && (fx->effects1 || fx->component1 || fx->keys1);
@@ -389,7 +397,7 @@ static int within2_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t
     if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_keys ? fx->cap1 : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
         return rc;
     if (int rc = within2_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, codes2, space, n_levels2, space, se_type, tol,
-                                    max_iter, out, extra, kf.d_perm, fx))
+                                    max_iter, out, extra, kf.d_perm, fx, cl))
         return rc;
     if (fx && fx->keys1) {
         PDS_HIP_CHECK(hipMemcpyAsync(fx->keys1, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,

@@ -490,6 +490,25 @@ template <typename T>
 int launch_within_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
                        const MixedChunks& ch, double* d_scores, const double* d_beta, const double* d_means, bool meat, const int64_t* d_gmap,
                        const uint32_t* d_perm, T* d_alpha, T* d_pred, T* d_resid, double* d_partials, double* d_stage, double* d_rec);
+// ---- within_cluster.hip: the fixed-effects regression's errors clustered on any key (capi_within_cluster.hpp).  Row r's score
+// x~_r e_r is staged row-major at d_rows[r * cluster_row_stride(p)]: p doubles, padded to an even count.
+constexpr int cluster_row_stride(int p) { return (p + 1) & ~1; }
+// d_flags[0] |= 1 when a level of factor 1 (rows [d_off1[l], d_off1[l + 1]), n1 levels) holds two cluster codes; d_flags[1] the same
+// for factor 2 (d_start2 nullable: one factor; level l is the places [d_start2[l], d_start2[l + 1]) of d_idx2).  d_codes: the
+// cluster code of every row, frame order.  Both flags are zeroed here; the caller reads them back.
+int launch_cluster_nested(pds_ctx* ctx, const int64_t* d_off1, int64_t n1, const uint32_t* d_start2, int64_t n_levels2, const uint32_t* d_idx2,
+                          const int32_t* d_codes, int* d_flags);
+// launch_within_pass's arguments (the same d_off / n_groups / split_rows / chunks, beta, the group means): the row scores -> d_rows
+template <typename T>
+int launch_within_row_scores(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                             const MixedChunks& ch, const double* d_beta, const double* d_means, double* d_rows);
+int cluster_meat_records(const pds_ctx* ctx, int64_t n_clusters);  // partial records launch_cluster_gather_meat writes
+// d_idx: the rows in cluster order; chunk k is its places [d_chunk_pos[k], + d_chunk_n[k]), all of one cluster; cluster j is the chunks
+// [d_cl_c0[j], + d_cl_nc[j]).  d_scores: n_chunks x kClusterScoreStride doubles.  The meat sum_c s_c s_c' -> slots [0,256) of one
+// record at d_rec.  d_partials: room for cluster_meat_records(n_clusters) records, d_stage for a 64th of that (rounded up).
+int launch_cluster_gather_meat(pds_ctx* ctx, int n_feat, const double* d_rows, const uint32_t* d_idx, const int64_t* d_chunk_pos,
+                               const int64_t* d_chunk_n, int64_t n_chunks, const int64_t* d_cl_c0, const int64_t* d_cl_nc, int64_t n_clusters,
+                               double* d_scores, double* d_partials, double* d_stage, double* d_rec);
 // ---- within2_sweep.hip: the alternating sweeps of the fixed-effects regression with two absorbed factors (capi_within2.hpp).  The device
 // arrays of one call (nc = p + 1): the state is a1 / a2, the accumulated level means; row r is worth (w_r - a1[g1(r)]) - a2[code2(r)].
 struct Within2Dev {

@@ -613,7 +613,7 @@ def elastic_net_fit(*x, target, l1_reg: float, l2_reg: float, add_bias: bool = F
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", y_var: float | None = None,
                    feature_names: Sequence[str] | None = None, null_policy: str = "raise", cluster=None, cluster_offsets=None,
                    absorb=None, absorb_offsets=None, return_effects: bool = False, return_pred: bool = False,
-                   absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, absorb_accel: str | None = None,
+                   absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, absorb_accel: str | None = None, cluster_key=None,
                    ctx: Context | None = None) -> dict:
     """
     pds.lin_reg_report (pl_lin_reg_report / pl_wls_report).  `y_var` is what Polars evaluates as
@@ -655,11 +655,23 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     "n_iter" and `absorb_max_iter` count SWEEPS, never extrapolations.  On frames whose plain sweeps converge slowly (few movers
     between the levels) the sweep count falls several times; it is never meant to rise.  A string sets the option for this call and
     puts the previous value back afterwards, also when the call raises.
+
+    `cluster_key` (with `absorb=k`, `absorb_offsets=` or `absorb=[k1, k2]`, and std_err "cluster" or "cluster0" only): the standard
+    errors are clustered on THIS key instead of the (first) absorbed one -- absorb firm and year and cluster on state, or cluster on
+    the second absorbed key (pds_lin_reg_within_cl_* / pds_lin_reg_within2_cl_*; include/pds_lstsq.h states the definitions).  An
+    integer column, NumPy array or CUDA tensor, in any row order; it is coded densely like the second absorbed key.  The fit itself
+    is untouched: beta, r2, "n_iter", pred and resid are the bits of the call without `cluster_key`.  The dict gains "n_clusters" (Gc,
+    the distinct keys) and "absorb_nested" (one bool per absorbed key: every level of it lies inside one cluster); "df_resid" is
+    Gc - 1.  "cluster" scales by Gc / (Gc - 1) * (n - 1) / (n - K), where K counts p, the absorbed effects of every key that is NOT
+    nested, and one intercept if some key is nested.  ValueError: without absorption, together with `cluster` / `cluster_offsets`,
+    with std_err="se", or when the column is not an integer column.
     """
+    if cluster_key is not None and absorb is None and absorb_offsets is None:
+        raise ValueError("`cluster_key` goes with `absorb` or `absorb_offsets` only; without absorption the clusters are `cluster=`")
     if absorb is not None or absorb_offsets is not None or absorb_accel is not None:
         return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, (cluster, cluster_offsets),
                                return_effects, return_pred, None, ctx, absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter,
-                               absorb_accel=absorb_accel)
+                               absorb_accel=absorb_accel, cluster_key=cluster_key)
     if return_effects or return_pred:
         raise ValueError("`return_effects` / `return_pred` go with `absorb` or `absorb_offsets` only")
     if std_err in _lib.CLUSTER_SE_TYPES:
@@ -781,9 +793,9 @@ def _accel_option(ctx, absorb_accel):
 
 def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, absorb_offsets, clusters, return_effects, return_pred,
                     max_groups, ctx, fit_only: bool = False, absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, effects2: bool = False,
-                    absorb_accel: str | None = None):
+                    absorb_accel: str | None = None, cluster_key=None):
     """lin_reg / lin_reg_report(absorb= | absorb_offsets=): pds_lin_reg_within_by_key_* / _grouped_*; absorb=[k1, k2]: _within2_*;
-    effects2 (fixed_effects): pds_lin_reg_within2_fx_by_key_*."""
+    effects2 (fixed_effects): pds_lin_reg_within2_fx_by_key_*; cluster_key: the _cl_ forms of all of these."""
     if absorb_accel is not None:
         if absorb_accel not in ABSORB_ACCEL:
             raise ValueError('`absorb_accel` is None, "none" or "irons_tuck"')
@@ -810,7 +822,16 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
     if add_bias:
         raise ValueError("`add_bias=True` together with `absorb`: the intercept is absorbed by the group effects")
     if clusters is not None and (clusters[0] is not None or clusters[1] is not None):
+        if cluster_key is not None:
+            raise ValueError("`cluster_key` together with `cluster` / `cluster_offsets`: with absorption the clusters are `cluster_key` alone")
         raise ValueError('`cluster` / `cluster_offsets` together with `absorb`: std_err="cluster" means the absorbed key')
+    if cluster_key is not None:
+        if fit_only or std_err not in _lib.CLUSTER_SE_TYPES:
+            raise ValueError('`cluster_key` goes with std_err="cluster" or "cluster0" only')
+        if _is_arrow(cluster_key):
+            raise NotImplementedError("fixed-effects regression: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
+        if not _is_int_column(cluster_key):
+            raise ValueError("`cluster_key` must be an integer column")
     if not fit_only and std_err not in _lib.WITHIN_SE_TYPES:
         if std_err in _lib.SE_TYPES:
             raise _lib.PdsError(-5, "fixed-effects regression: HC0 - HC3 standard errors are not available with absorption")  # PDS_ERR_UNSUPPORTED
@@ -833,6 +854,11 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
     if return_pred:
         pred, pred_p = _out_like(cols, n)
         resid, resid_p = _out_like(cols, n)
+    ck = None
+    if cluster_key is not None:  # dense codes in the inputs' space, like the second absorbed key
+        codes_c, codes_c_p, n_levels_c, _ = _dense_codes(cols, cluster_key)
+        ck = _lib.ClusterKey(codes_c_p, n_levels_c, 0, 0, 0)
+    cl_args = () if ck is None else (C.byref(ck),)
     if key2 is not None and effects2:
         k, k_p = _key_arg(cols, absorb)
         codes2, codes2_p, n_levels2, effect_keys2 = _dense_codes(cols, key2)
@@ -844,9 +870,9 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
             comp1, comp1_p = _out_int(cols, cap, "int32")
             extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
             fx = _lib.Within2Effects(alpha_p, alpha2_p, comp1_p, comp2_p, keys_p, cap, 0)
-            rc = ctx.fn("pds_lin_reg_within2_fx_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
-                                                         C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep), C.byref(extra), ng_p,
-                                                         C.byref(fx))
+            name = "pds_lin_reg_within2_fx_by_key" if ck is None else "pds_lin_reg_within2_cl_by_key"
+            rc = ctx.fn(name)(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space, se_code,
+                              C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep), C.byref(extra), ng_p, C.byref(fx), *cl_args)
             return rc, (alpha, comp1, extra, fx)
 
         with _accel_option(ctx, absorb_accel):
@@ -858,17 +884,23 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         extra = _lib.Within2Out(pred_p, resid_p, 0.0, 0, 0, 0, 0, 0)
         ng = C.c_int64(0)
         with _accel_option(ctx, absorb_accel):
-            _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space,
-                                                            se_code, C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep),
-                                                            C.byref(extra), C.byref(ng)))
+            if ck is None:
+                _lib.check(ctx.fn("pds_lin_reg_within2_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space,
+                                                                se_code, C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep),
+                                                                C.byref(extra), C.byref(ng)))
+            else:  # (no effects asked for: fx is NULL)
+                _lib.check(ctx.fn("pds_lin_reg_within2_cl_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space,
+                                                                   se_code, C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep),
+                                                                   C.byref(extra), C.byref(ng), None, C.byref(ck)))
     elif absorb is not None:
         k, k_p = _key_arg(cols, absorb)
 
         def call(cap, keys_p, ng_p):
             alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, C.c_void_p(None))
             extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
-            rc = ctx.fn("pds_lin_reg_within_by_key")(ctx._h, cols.cols, k_p, p, C.c_int64(n), cols.space, se_code, C.c_int64(cap),
-                                                     keys_p if return_effects else C.c_void_p(None), C.byref(rep), C.byref(extra), ng_p)
+            name = "pds_lin_reg_within_by_key" if ck is None else "pds_lin_reg_within_cl_by_key"
+            rc = ctx.fn(name)(ctx._h, cols.cols, k_p, p, C.c_int64(n), cols.space, se_code, C.c_int64(cap),
+                              keys_p if return_effects else C.c_void_p(None), C.byref(rep), C.byref(extra), ng_p, *cl_args)
             return rc, (alpha, extra)
 
         if return_effects:
@@ -885,8 +917,9 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         ng_all = int(off.shape[0]) - 1
         alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, C.c_void_p(None))
         extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
-        _lib.check(ctx.fn("pds_lin_reg_within_grouped")(ctx._h, cols.cols, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, se_code,
-                                                        C.byref(rep), C.byref(extra)))
+        name = "pds_lin_reg_within_grouped" if ck is None else "pds_lin_reg_within_cl_grouped"
+        _lib.check(ctx.fn(name)(ctx._h, cols.cols, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, se_code, C.byref(rep), C.byref(extra),
+                                *cl_args))
         effect_keys = np.arange(ng_all, dtype=np.int64)
     if fit_only:
         out = {"beta": outs["beta"]}
@@ -897,6 +930,9 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
         out["df_resid"] = int(extra.df_resid)
         if key2 is not None:
             out["n_groups2"], out["n_components"], out["n_iter"] = int(extra.n_groups2_used), int(extra.n_components), int(extra.n_iter)
+        if ck is not None:
+            out["n_clusters"] = int(ck.n_clusters)
+            out["absorb_nested"] = (bool(ck.nested1), bool(ck.nested2)) if key2 is not None else (bool(ck.nested1),)
     if return_effects or effects2:
         out["effects"], out["effect_keys"] = alpha, effect_keys
     if effects2:
@@ -905,6 +941,15 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
     if return_pred:
         out["pred"], out["resid"] = pred, resid
     return out
+
+
+def _is_int_column(key) -> bool:
+    """Whether a key column holds integers (asked before anything is copied or coded)."""
+    if _is_torch(key):
+        import torch
+
+        return not (key.dtype.is_floating_point or key.dtype.is_complex or key.dtype == torch.bool)
+    return np.asarray(key).dtype.kind in "iu"
 
 
 def _codes_of(key, device, n_rows=None):
@@ -940,7 +985,7 @@ def _dense_codes(cols: "_Cols", key):
 
 def fixed_effects(*x, target, absorb, std_err: str = "se", absorb_tol: float = 1e-8, absorb_max_iter: int = 10_000, return_pred: bool = False,
                   feature_names: Sequence[str] | None = None, add_bias: bool = False, weights=None, max_groups: int | None = None,
-                  absorb_accel: str | None = None, ctx: Context | None = None) -> dict:
+                  absorb_accel: str | None = None, cluster_key=None, ctx: Context | None = None) -> dict:
     """
     The two-way fixed-effects regression y_i = alpha_k1(i) + gamma_k2(i) + x_i' beta + e_i WITH its estimated effects
     (pds_lin_reg_within2_fx_by_key_*; include/pds_lstsq.h states the definitions).  `absorb=[k1, k2]`: exactly two integer columns.
@@ -956,12 +1001,15 @@ def fixed_effects(*x, target, absorb, std_err: str = "se", absorb_tol: float = 1
     `absorb_accel`: None (the context's option "within2_accel"), "none" or "irons_tuck" -- cycles of two plain sweeps and one
     extrapolation of the factor-2 table, see lin_reg_report; "n_iter" counts sweeps.  The call ends on a sweep, so the effects and
     their normalisation are formed from the tables exactly as without acceleration.
+    `cluster_key`: as in lin_reg_report -- the errors clustered on this key (std_err "cluster" / "cluster0"), "n_clusters" and
+    "absorb_nested" added, "df_resid" = Gc - 1; every other entry, the effects included, as without it.
     """
     if not isinstance(absorb, (list, tuple)) or len(absorb) < 2:
         raise ValueError("fixed_effects: `absorb` is a list of exactly two integer columns; the effects of ONE absorbed key come from "
                          "lin_reg_report(absorb=k, return_effects=True)")
     return _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb, None, None, False, return_pred, max_groups, ctx,
-                           absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, effects2=True, absorb_accel=absorb_accel)
+                           absorb_tol=absorb_tol, absorb_max_iter=absorb_max_iter, effects2=True, absorb_accel=absorb_accel,
+                           cluster_key=cluster_key)
 
 
 def absorb_components(k1, k2, ctx: Context | None = None) -> dict:

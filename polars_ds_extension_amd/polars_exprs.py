@@ -212,7 +212,7 @@ def lin_reg_w_rcond_by_group(df, by, *x, target, **kwargs):
 
 
 def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: str = "se", null_policy: str = "raise", by=None,
-                   cluster=None, absorb=None):
+                   cluster=None, absorb=None, cluster_key=None):
     """
     expr_linear.py:561-631.  `by` (an integer key column, any row order, nulls = one group): every group's report from ONE
     `pl_lin_reg_report_by` / `pl_wls_report_by` call, in long format -- a Struct {<key>, features, beta, <se>, t, p>|t|, 0.025, 0.975,
@@ -228,8 +228,12 @@ def lin_reg_report(*x, target, add_bias: bool = False, weights=None, std_err: st
     rows (no `__bias__`: `add_bias=True` is refused); `std_err` is "se" (n - G - p degrees of freedom), "cluster" or "cluster0" --
     the clusters are the absorbed groups, so `cluster` is refused; r2 / adj_r2 are the within values.  `absorb` together with `by`
     or `weights` is not implemented; the effects and the per-row outputs are `lstsq.lin_reg_report(absorb=, ...)` only, and so are
-    two absorbed keys (`absorb=[k1, k2]`).
+    two absorbed keys (`absorb=[k1, k2]`).  `cluster_key` (errors clustered on a key other than the absorbed one) has no plugin symbol:
+    NotImplementedError, `lstsq.lin_reg_report(absorb=, cluster_key=)` on column buffers has it.
     """
+    if cluster_key is not None:
+        raise NotImplementedError("lin_reg_report: `cluster_key` is not available as an expression; standard errors clustered on any key "
+                                  "are `lstsq.lin_reg_report(..., absorb=, cluster_key=)` on column buffers")
     if absorb is not None:
         if isinstance(absorb, (list, tuple)):
             raise NotImplementedError("lin_reg_report: a list of absorbed keys is not available as an expression; two absorbed keys are "
