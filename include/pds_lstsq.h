@@ -116,7 +116,13 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
  *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
- * value: 0 / 1 (within2_accel: nothing else; report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, within_split_rows, cluster_waves, grouped_fused_waves: a count).  Unknown names are PDS_ERR_INVALID. */
+ *   "rolling_waves"                           pds_rolling_lr_* / pds_recursive_lr_* and their grouped forms, up to 12 coefficients (up to 8
+ *                                             when grouped): cap on the number of waves any launch of the tiled kernels starts (<= 0: the
+ *                                             default grid; two-wave blocks round down to whole blocks, at least one).  A wave then walks
+ *                                             several tiles of a small frame.  The option changes no result bit: a tile's anchor and
+ *                                             arithmetic do not depend on which wave walks it.  The per-segment kernels of wider fits
+ *                                             have no tile loop and do not take it.
+ * value: 0 / 1 (within2_accel: nothing else; report_chunk_groups, glm_split_rows, mixed_split_rows, cluster_split_rows, within_split_rows, cluster_waves, grouped_fused_waves, rolling_waves: a count).  Unknown names are PDS_ERR_INVALID. */
 int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value);
 /* The value an option has now, as pds_ctx_set_option stored it (a count given as <= 0 reads back as 0, "the default").  Unknown names
  * are PDS_ERR_INVALID.  A caller that sets an option for one call reads it first and puts that value back. */

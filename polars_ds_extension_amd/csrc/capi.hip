@@ -168,6 +168,7 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
         if (value < 0 || value > 2) return fail(PDS_ERR_INVALID, "grouped_multi_route: 0 (choose), 1 (one kernel) or 2 (per target)");
         ctx->opt_multi_route = (int64_t)value;
     } else if (n == "grouped_multi_waves") ctx->opt_multi_waves = value > 0 ? (int64_t)value : 0;
+    else if (n == "rolling_waves") ctx->opt_rolling_waves = value > 0 ? (int64_t)value : 0;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }
@@ -188,6 +189,7 @@ int pds_ctx_get_option(const pds_ctx* ctx, const char* name, long long* value) {
     else if (n == "grouped_fused_late_permille") *value = ctx->opt_fused_late_permille;
     else if (n == "grouped_multi_route") *value = ctx->opt_multi_route;
     else if (n == "grouped_multi_waves") *value = ctx->opt_multi_waves;
+    else if (n == "rolling_waves") *value = ctx->opt_rolling_waves;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }

@@ -138,11 +138,12 @@ struct pds_ctx {
     double kind_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long kind_count[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<float> kind_samples[9];  // the individual bracketed durations (ms), newest kept up to 4096 per class
-    // (behind everything else: the members above keep their places for the translation units that do not know these two)
+    // (behind everything else: the members above keep their places for the translation units that do not know these)
     int64_t opt_multi_route = 0;  // "grouped_multi_route": 0 choose, 1 the one-wave-per-group kernel, 2 one fused launch per target
     int64_t opt_multi_waves = 0;  // "grouped_multi_waves": cap on the grid of the grouped multi-target kernel (0: every wave slot)
     int64_t opt_within_split_rows = 0;  // "within_split_rows": absorbed groups above this many rows are cut into row chunks (0: the default)
     int64_t opt_within2_accel = 0;      // "within2_accel": 0 plain alternating sweeps, 1 Irons-Tuck cycles (capi_within2.hpp)
+    int64_t opt_rolling_waves = 0;      // "rolling_waves": cap on the waves a launch of the tiled rolling / expanding kernels starts (0: the default grid)
 };
 
 namespace pds {

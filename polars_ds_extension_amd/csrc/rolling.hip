@@ -484,6 +484,14 @@ static int launch_tile_prefix_seg(pds_ctx* ctx, double* tot, const uint8_t* tfla
     return PDS_OK;
 }
 
+// "rolling_waves" (tests): cap on the waves one launch of the tiled kernels starts; blocks of several waves round down to whole
+// blocks, at least one.  Every kernel here walks `for (t = first; t < ntiles; t += stride)` and a tile's anchor and arithmetic
+// do not depend on the wave that walks it, so the cap changes no result bit -- it makes waves walk several tiles of a small frame.
+static int64_t cap_roll_blocks(const pds_ctx* ctx, int64_t blocks, int waves_per_block) {
+    if (ctx->opt_rolling_waves <= 0) return blocks;
+    return std::min<int64_t>(blocks, std::max<int64_t>(ctx->opt_rolling_waves / waves_per_block, 1));
+}
+
 template <typename T, int PP, int FULLP>
 static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool expanding, const double* seed_moments,
                        T* d_coeffs, T* d_pred, uint8_t* d_valid) {
@@ -494,7 +502,7 @@ static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool 
     int64_t nb = (ntiles + kRollWaves - 1) / kRollWaves;
     int per_cu = 2 * PDS_ROLL_WPE;  // blocks of kRollWaves waves: PDS_ROLL_WPE waves per SIMD
     if (const char* e = dev_env("PDS_ROLL_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e));
-    nb = std::min<int64_t>(std::max<int64_t>(nb, 1), (int64_t)ctx->num_cus * per_cu);
+    nb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(nb, 1), (int64_t)ctx->num_cus * per_cu), kRollWaves);
     auto kern0 = roll_kernel_ptr<T, PP, 0, FULLP>();
     auto kern1 = roll_kernel_ptr<T, PP, 1, FULLP>();
     auto kern2 = roll_kernel_ptr<T, PP, 2, FULLP>();
@@ -511,7 +519,7 @@ static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool 
             constexpr int M = decltype(mode_c)::value;
             constexpr int64_t tile = M == 0 ? kSegTileRoll : kSegTile;
             const int64_t seg_tiles = (ra.n + tile - 1) / tile;
-            const int64_t sb = std::min<int64_t>(std::max<int64_t>(seg_tiles, 1), (int64_t)ctx->num_cus * 4);
+            const int64_t sb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(seg_tiles, 1), (int64_t)ctx->num_cus * 4), 1);
             // window == one stage: the rows leaving the window are the previous stage's rows, kept in registers (no second read
             // stream); PDS_ROLL_OLD_STREAM=1 keeps the two-stream form for that window too (A/B)
             static const bool old_stream = [] { const char* e = dev_env("PDS_ROLL_OLD_STREAM"); return e && e[0] == '1'; }();
@@ -558,7 +566,7 @@ static int launch_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs ra, bool 
         if constexpr (PP <= 8) {
             if (seg) {  // streaming totals (rolling_seg_dev.hpp): HBM bound instead of a full pass of the rolling kernel
                 using SD = SegDims<T, PP>;
-                const int64_t tb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12);
+                const int64_t tb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12), 1);
                 hipLaunchKernelGGL((rolling_totals_kernel<T, PP, FULLP>), dim3((unsigned)tb), dim3(64),
                                    (size_t)SD::NV * kSegStride * sizeof(double), ctx->stream, dc.d_ptrs, ra, tot, RollGroups{});
                 totals_done = true;
@@ -624,7 +632,7 @@ static int launch_grouped_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs r
     if (!expanding) {
         ra.mode = 0;
         const int64_t seg_tiles = (ra.n + kSegTileRoll - 1) / kSegTileRoll;
-        const int64_t sb = std::min<int64_t>(std::max<int64_t>(seg_tiles, 1), (int64_t)ctx->num_cus * 4);
+        const int64_t sb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(seg_tiles, 1), (int64_t)ctx->num_cus * 4), 1);
         hipLaunchKernelGGL((rolling_seg_kernel<T, PP, 0, FULLP, 0, 1>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES, ctx->stream,
                            dc.d_ptrs, ra, (const double*)nullptr, d_coeffs, d_pred, d_valid, grp);
     } else {
@@ -634,12 +642,12 @@ static int launch_grouped_pp_f(pds_ctx* ctx, const DeviceCols<T>& dc, RollArgs r
         grp.tile_flag = reinterpret_cast<uint8_t*>(ws_take(ctx, (size_t)ntiles));
         if (!tot || !grp.tile_flag) return fail(PDS_ERR_HIP, "workspace allocation failed");
         ra.mode = 1;
-        const int64_t tb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12);
+        const int64_t tb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 12), 1);
         hipLaunchKernelGGL((rolling_totals_kernel<T, PP, FULLP, 1>), dim3((unsigned)tb), dim3(64), (size_t)NV * kSegStride * sizeof(double),
                            ctx->stream, dc.d_ptrs, ra, tot, grp);
         if (int rc = launch_tile_prefix_seg(ctx, tot, grp.tile_flag, ntiles, NV)) return rc;
         ra.mode = 2;
-        const int64_t sb = std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 4);
+        const int64_t sb = cap_roll_blocks(ctx, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->num_cus * 4), 1);
         hipLaunchKernelGGL((rolling_seg_kernel<T, PP, 2, FULLP, 0, 1>), dim3((unsigned)sb), dim3(64), (size_t)SD::LDS_BYTES, ctx->stream,
                            dc.d_ptrs, ra, (const double*)tot, d_coeffs, d_pred, d_valid, grp);
     }

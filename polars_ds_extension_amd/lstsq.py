@@ -112,7 +112,8 @@ class Context:
     def set_option(self, name: str, value) -> None:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
         "glm_split_rows", "mixed_split_rows", "cluster_split_rows", "cluster_waves", "within_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
-        "grouped_multi_waves", "within2_accel" (0: plain sweeps of the two-key fixed-effects calls, the default; 1: Irons-Tuck cycles); the
+        "grouped_multi_waves", "within2_accel" (0: plain sweeps of the two-key fixed-effects calls, the default; 1: Irons-Tuck cycles),
+        "rolling_waves" (cap on the waves a launch of the tiled rolling / expanding kernels starts; it changes no result bit); the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
 
