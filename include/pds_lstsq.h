@@ -1181,6 +1181,73 @@ int pds_glm_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, co
                                       int max_iter, int se_type, float* coeffs, int32_t* n_iter, const pds_glm_report_out* out,
                                       int64_t* n_clusters);
 /*
+ * pds_glm_within_grouped_* / pds_glm_within_by_key_*: the fixed-effects GLM -- ONE generalised linear model with an intercept per
+ * group, g(E y_i) = alpha_g(i) + x_i' beta + o_i, fitted by IRLS with the group effects absorbed (Stata's ppmlhdfe y x, absorb(firm),
+ * fixest::fepois(y ~ x | firm) / feglm): no dummy column is ever formed.  cols = [y, x1..xp], 1 .. 16 feature columns and NO intercept
+ * column (it is absorbed); `weights` / `offset` nullable, link / variance as in pds_glm_irls_wo_*.  What follows is a DEFINITION of what
+ * the library computes; no equivalence with the small-sample conventions of any package is claimed.
+ *   Rows and groups that count.  A weight that is negative or not finite, anywhere: PDS_ERR_INVALID.  A row counts if pw_i > 0.  A
+ *     group is DROPPED if it has no counting row, if (variance poisson) every counting row has y == 0, or if (variance binomial) every
+ *     counting row has y == 0 or every one has y == 1: its effect would be -inf or +inf (fepois and ppmlhdfe drop such groups too).  The
+ *     comparisons are exact and are made once, before the first iteration.  Rows of dropped groups count nowhere.  Gaussian and gamma
+ *     drop only groups without a counting row.  Singletons that are not dropped stay in.  n_rows_used and n_groups_used are the counting
+ *     rows of the kept groups and the kept groups; n_groups_dropped counts the non-empty groups that were dropped.
+ *   Start.  binomial: mu = (y + 0.5) / 2; otherwise mu = (y + ybar) / 2 with ybar = sum pw y / sum pw over the used rows; eta = g(mu).
+ *   Iteration.  w_i = pw_i / (g'(mu_i)^2 V(mu_i));  z_i = (eta_i - o_i) + g'(mu_i)(y_i - mu_i);  m_g the w-weighted mean of [x, z] over
+ *     group g;  W = sum_g sum_{i in g} w_i ([x_i, z_i] - m_g)([x_i, z_i] - m_g)';  beta solves W_xx beta = W_xz;
+ *     alpha_g = m_z,g - m_x,g . beta;  eta_i = alpha_g + x_i . beta + o_i;  mu = g^-1(eta).  By Frisch-Waugh this is exactly the IRLS
+ *     step of the design with one dummy column per kept group.
+ *   Stopping.  beta starts at 0; the iteration stops when max_j |beta_new,j - beta_j| < tol or after max_iter iterations.  n_iter
+ *     counts iterations, converged says which of the two ended it.  A beta or W that is not finite: PDS_ERR_NUMERIC.  There is no step
+ *     halving.
+ *   Report, at the returned beta, alpha and the last W_xx: deviance and pearson_chi2 as in pds_glm_report_wo_*, summed over the used
+ *     rows; df_resid = n_rows_used - n_groups_used - p; dispersion phi = 1 (poisson, binomial), pearson_chi2 / df_resid (gaussian, gamma).
+ *     PDS_SE        V = phi W_xx^-1
+ *     PDS_CLUSTER0  V = W_xx^-1 M W_xx^-1, M = sum_g s_g s_g', s_g = sum_{i in g} r_i (x_i - m_x,g),
+ *                   r_i = pw_i (y_i - mu_i) / (V(mu_i) g'(mu_i)): the clusters ARE the absorbed groups
+ *     PDS_CLUSTER   the same V times G / (G - 1) * (n - 1) / (n - p - 1), G = n_groups_used, n = n_rows_used (the definition of
+ *                   pds_lin_reg_within_*)
+ *     z_j = beta_j / se_j, p_j = erfc(|z_j| / sqrt 2), lo / hi = beta_j -+ 1.959963984540054 se_j: the normal distribution, as in every
+ *     GLM report here.  out->cov = V, p x p row-major.
+ * The report fields are host doubles for both precisions (an f32 frame is fitted in f64 arithmetic).  alpha / pred: nullable,
+ * `space`-resident arrays of the frame's type.  alpha: one value per group, NaN for a dropped or empty group; pred = mu_i per row in the
+ * caller's row order, NaN on the rows of dropped groups, a value on the zero-weight rows of kept groups.
+ *   grouped: group g = rows [group_offsets[g], group_offsets[g+1]); n_groups + 1 int64 values, `space`-resident, starting at 0, ending
+ *            at n_rows, non-decreasing (else PDS_ERR_INVALID).  alpha has n_groups entries.  An empty group changes no output bit.
+ *   by key:  keys = n_rows int64 values in any row order (ordered keys move nothing and give the bits of the grouped form; weights and
+ *            offset travel with the frame).  *n_groups receives the distinct keys.  max_groups and out_keys matter only when out->alpha
+ *            is given: alpha and out_keys (nullable) then have room for max_groups entries, in ascending key order, and more distinct
+ *            keys are PDS_ERR_INVALID with *n_groups set (nothing fitted).
+ * The call is one pre-pass, one stream over the frame per iteration (the state between iterations is beta and the group means; one
+ * blocking copy of a record and a p x p host solve per iteration) and one final pass.  No floating-point atomic: two calls give the same
+ * bits.  Groups above the context option "within_split_rows" are cut into row chunks.  Refused, never approximated: a feature that does
+ * not vary inside any kept group (exact comparison with the group's first counting row) PDS_ERR_NUMERIC, the message naming the column
+ * index; a pivot of W_xx below 1e-13 of its diagonal PDS_ERR_NUMERIC; df_resid <= 0 PDS_ERR_TOO_FEW_ROWS; a cluster kind with fewer than
+ * two kept groups PDS_ERR_INVALID; more than 16 features PDS_ERR_UNSUPPORTED; PDS_HC0 .. PDS_HC3 PDS_ERR_UNSUPPORTED.  Two absorbed
+ * keys, clusters on another key and penalties have no argument.
+ */
+typedef struct {
+    double beta[16], std_err[16], z[16], p[16], ci_lower[16], ci_upper[16]; /* the first p entries */
+    double cov[256];                                                         /* p x p, row-major */
+    double deviance, pearson_chi2, dispersion;
+    int64_t n_groups_used, n_groups_dropped, n_rows_used, df_resid;
+    int32_t n_iter, converged;
+    void* alpha; /* in, nullable: [n_groups] (by key: [max_groups], ascending key order) */
+    void* pred;  /* in, nullable: [n_rows], frame order */
+} pds_glm_within_out;
+int pds_glm_within_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int link, int variance, double tol,
+                               int max_iter, int se_type, pds_glm_within_out* out);
+int pds_glm_within_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int link, int variance, float tol,
+                               int max_iter, int se_type, pds_glm_within_out* out);
+int pds_glm_within_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                              int n_feat, int64_t n_rows, pds_space space, int link, int variance, double tol, int max_iter, int se_type,
+                              int64_t max_groups, int64_t* out_keys, pds_glm_within_out* out, int64_t* n_groups);
+int pds_glm_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                              int n_feat, int64_t n_rows, pds_space space, int link, int variance, float tol, int max_iter, int se_type,
+                              int64_t max_groups, int64_t* out_keys, pds_glm_within_out* out, int64_t* n_groups);
+/*
  * pds_lr_rcond_grouped_* / pds_lr_rcond_by_key_*: `lin_reg_w_rcond` per group in one call -- for every group g what pds_lr_rcond_*
  * computes on g's rows alone (faer_solve_lr_rcond, lr_solvers.rs:225-254): X'X (+ l2_reg on the feature diagonals) is decomposed on
  * chip by the one-sided Jacobi iteration of the single-system call, singular values below the cut are dropped, the coefficients are

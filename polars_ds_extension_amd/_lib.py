@@ -30,6 +30,7 @@ EXPORTS = [
     "pds_glm_report_grouped_f64", "pds_glm_report_grouped_f32", "pds_glm_report_by_key_f64", "pds_glm_report_by_key_f32",
     "pds_glm_report_robust_f64", "pds_glm_report_robust_f32", "pds_glm_report_cluster_grouped_f64", "pds_glm_report_cluster_grouped_f32",
     "pds_glm_report_cluster_by_key_f64", "pds_glm_report_cluster_by_key_f32",
+    "pds_glm_within_grouped_f64", "pds_glm_within_grouped_f32", "pds_glm_within_by_key_f64", "pds_glm_within_by_key_f32",
     "pds_lr_rcond_grouped_f64", "pds_lr_rcond_grouped_f32", "pds_lr_rcond_by_key_f64", "pds_lr_rcond_by_key_f32",
     "pds_lr_multi_grouped_f64", "pds_lr_multi_grouped_f32", "pds_lr_multi_by_key_f64", "pds_lr_multi_by_key_f32",
     "pds_mixed_reml_grouped_f64", "pds_mixed_reml_grouped_f32", "pds_mixed_reml_by_key_f64", "pds_mixed_reml_by_key_f32",
@@ -109,6 +110,15 @@ class WithinOut(C.Structure):
     """pds_within_out: nullable output pointers of the frame's type, one layout for both precisions."""
     _fields_ = [("alpha", C.c_void_p), ("pred", C.c_void_p), ("resid", C.c_void_p), ("r2_overall", C.c_double),
                 ("n_groups_used", C.c_int64), ("df_resid", C.c_int64)]
+
+
+class GlmWithinOut(C.Structure):
+    """pds_glm_within_out: the fixed-effects GLM's report (host doubles for both precisions), its counts and the nullable alpha / pred
+    outputs of the frame's type."""
+    _fields_ = [(k, C.c_double * 16) for k in ("beta", "std_err", "z", "p", "ci_lower", "ci_upper")] + [
+        ("cov", C.c_double * 256), ("deviance", C.c_double), ("pearson_chi2", C.c_double), ("dispersion", C.c_double),
+        ("n_groups_used", C.c_int64), ("n_groups_dropped", C.c_int64), ("n_rows_used", C.c_int64), ("df_resid", C.c_int64),
+        ("n_iter", C.c_int32), ("converged", C.c_int32), ("alpha", C.c_void_p), ("pred", C.c_void_p)]
 
 
 class Within2Out(C.Structure):
@@ -209,6 +219,13 @@ def load() -> C.CDLL:
                 for form in ("grouped_", "by_key_"):
                     getattr(lib, "pds_lin_reg_within_cl_" + form + sfx).argtypes = getattr(lib, "pds_lin_reg_within_" + form + sfx).argtypes + [C.c_void_p]
                     getattr(lib, "pds_lin_reg_within2_cl_" + form + sfx).argtypes = getattr(lib, "pds_lin_reg_within2_fx_" + form + sfx).argtypes + [C.c_void_p]
+            if hasattr(lib, "pds_glm_within_grouped_" + sfx):
+                # ctx, cols, weights, offset, n_feat, n_rows, group_offsets, n_groups, space, link, variance, tol, max_iter, se_type, out
+                getattr(lib, "pds_glm_within_grouped_" + sfx).argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                                                                             C.c_int, C.c_int, real, C.c_int, C.c_int, C.c_void_p]
+                # ctx, cols, weights, offset, keys, n_feat, n_rows, space, link, variance, tol, max_iter, se_type, max_groups, out_keys, out, n_groups
+                getattr(lib, "pds_glm_within_by_key_" + sfx).argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, real,
+                                                                                            C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 3
         if hasattr(lib, "pds_absorb_components_i32"):
             # ctx, codes1, n_levels1, codes2, n_levels2, n_rows, space, component1, component2, n1, n2, n_components, n_rounds
             lib.pds_absorb_components_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 6

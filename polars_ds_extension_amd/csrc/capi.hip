@@ -40,6 +40,7 @@ namespace pds {
 #include "capi_within.hpp"
 #include "capi_within2.hpp"
 #include "capi_glm_sandwich.hpp"
+#include "capi_glm_within.hpp"
 
 }  // namespace pds
 
@@ -380,6 +381,32 @@ int pds_glm_report_cluster_by_key_f32(pds_ctx* ctx, const float* const* cols, co
                                       int64_t* n_clusters) {
     return pds::glm_sandwich_by_key_impl<float>(ctx, cols, weights, offset, keys, n_feat, n_rows, space, add_bias, link, variance, tol, max_iter,
                                               se_type, coeffs, n_iter, out, n_clusters);
+}
+
+// the fixed-effects GLM: IRLS with one absorbed factor (capi_glm_within.hpp)
+int pds_glm_within_grouped_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int link, int variance, double tol,
+                               int max_iter, int se_type, pds_glm_within_out* out) {
+    return pds::glm_within_impl<double>(ctx, cols, weights, offset, n_feat, n_rows, group_offsets, n_groups, space, space, link, variance, tol,
+                                        max_iter, se_type, out);
+}
+int pds_glm_within_grouped_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, int n_feat, int64_t n_rows,
+                               const int64_t* group_offsets, int64_t n_groups, pds_space space, int link, int variance, float tol,
+                               int max_iter, int se_type, pds_glm_within_out* out) {
+    return pds::glm_within_impl<float>(ctx, cols, weights, offset, n_feat, n_rows, group_offsets, n_groups, space, space, link, variance, tol,
+                                       max_iter, se_type, out);
+}
+int pds_glm_within_by_key_f64(pds_ctx* ctx, const double* const* cols, const double* weights, const double* offset, const int64_t* keys,
+                              int n_feat, int64_t n_rows, pds_space space, int link, int variance, double tol, int max_iter, int se_type,
+                              int64_t max_groups, int64_t* out_keys, pds_glm_within_out* out, int64_t* n_groups) {
+    return pds::glm_within_by_key_impl<double>(ctx, cols, weights, offset, keys, n_feat, n_rows, space, link, variance, tol, max_iter, se_type,
+                                               max_groups, out_keys, out, n_groups);
+}
+int pds_glm_within_by_key_f32(pds_ctx* ctx, const float* const* cols, const float* weights, const float* offset, const int64_t* keys,
+                              int n_feat, int64_t n_rows, pds_space space, int link, int variance, float tol, int max_iter, int se_type,
+                              int64_t max_groups, int64_t* out_keys, pds_glm_within_out* out, int64_t* n_groups) {
+    return pds::glm_within_by_key_impl<float>(ctx, cols, weights, offset, keys, n_feat, n_rows, space, link, variance, tol, max_iter, se_type,
+                                              max_groups, out_keys, out, n_groups);
 }
 
 // the elastic-net penalised fits: the argument lists of pds_glm_irls_* with l1_reg, l2_reg after `variance` (<= 0: no penalty)

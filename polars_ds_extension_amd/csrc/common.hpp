@@ -491,6 +491,34 @@ template <typename T>
 int launch_within_pass(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
                        const MixedChunks& ch, double* d_scores, const double* d_beta, const double* d_means, bool meat, const int64_t* d_gmap,
                        const uint32_t* d_perm, T* d_alpha, T* d_pred, T* d_resid, double* d_partials, double* d_stage, double* d_rec);
+// ---- glm_within.hip: the fixed-effects GLM's passes (capi_glm_within.hpp).  d_cols: x_0 .. x_{p-1}, y, weights, offset (a table of
+// n_feat + 3 device pointers; the last two nullable); d_off / n_groups: the non-empty groups; ch: the chunks of the groups above
+// split_rows (upload_mixed_chunks with nc = p + 2: d_sums holds the chunk sums of an iteration, d_varies the chunks' pre-pass words).
+int glm_within_iter_blocks(const pds_ctx* ctx, int64_t n_work);   // partial records a launch of the iteration writes per work list
+int glm_within_final_blocks(const pds_ctx* ctx, int64_t n_work);  // ... and of the final pass
+// the pre-pass: d_gstat [3 x n_groups] the counting rows (pw > 0), sum pw, sum pw y of every group; d_drop [n_groups] 1 for a group
+// that is dropped (no counting row; variance 1: every counting y is 0; variance 2: every one is 0 or every one is 1); d_flags[0]: the
+// features that vary inside some kept group, d_flags[1]: a weight is negative or not finite.  d_cpre: n_chunks x (3 + p) doubles.
+template <typename T>
+int launch_glm_within_pre(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                          const MixedChunks& ch, int variance, double* d_cpre, double* d_gstat, int32_t* d_drop, unsigned* d_flags);
+// one iteration: with eta = alpha_g + x . beta + o from (d_beta, d_means_in) -- or the start rule from ybar when `first` -- the weighted
+// group means -> d_means_out [(p + 1) x n_groups] (features, then z) and the centred weighted scatter -> one record at d_rec (W_xx in
+// [0,256), W_xz in [256,272)).  d_partials: room for glm_within_iter_blocks(n_groups) + glm_within_iter_blocks(n_chunks) records,
+// d_stage for a 64th of that (rounded up).
+template <typename T>
+int launch_glm_within_iter(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                           const MixedChunks& ch, const int32_t* d_drop, int link, int variance, bool first, double ybar, const double* d_beta,
+                           const double* d_means_in, double* d_means_out, double* d_partials, double* d_stage, double* d_rec);
+// the final pass at (d_beta, d_means): alpha_g -> d_alpha[d_gmap ? d_gmap[g] : g] (kept groups only), mu_i -> d_pred (through d_perm;
+// NaN on the rows of dropped groups), the deviance (record slots 288 + 290), Pearson's chi2 (289 + 291) and, with `meat`, sum_g s_g s_g'
+// of the centred scores ([0,256)) -> one record at d_rec.  d_scores: n_chunks x kClusterScoreStride doubles (`meat` with chunks).
+// d_partials: room for glm_within_final_blocks of n_groups, n_chunks and n_long records, d_stage for a 64th of that (rounded up).
+template <typename T>
+int launch_glm_within_final(pds_ctx* ctx, const T* const* d_cols, int n_feat, const int64_t* d_off, int64_t n_groups, int64_t split_rows,
+                            const MixedChunks& ch, double* d_scores, const int32_t* d_drop, int link, int variance, const double* d_beta,
+                            const double* d_means, bool meat, const int64_t* d_gmap, const uint32_t* d_perm, T* d_alpha, T* d_pred,
+                            double* d_partials, double* d_stage, double* d_rec);
 // ---- within_cluster.hip: the fixed-effects regression's errors clustered on any key (capi_within_cluster.hpp).  Row r's score
 // x~_r e_r is staged row-major at d_rows[r * cluster_row_stride(p)]: p doubles, padded to an even count.
 constexpr int cluster_row_stride(int p) { return (p + 1) & ~1; }

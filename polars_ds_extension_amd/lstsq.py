@@ -2143,7 +2143,8 @@ def _glm_std_err_check(what, std_err, cluster, cluster_offsets):
 
 def glm_report(*x, target, family: str = "gaussian", add_bias: bool = False, tol: float = 1e-8, max_iter: int = 100, std_err: str = "se",
                cluster=None, cluster_offsets=None, weights=None, offset=None, return_cov: bool = False,
-               feature_names: Sequence[str] | None = None, ctx: Context | None = None) -> dict:
+               feature_names: Sequence[str] | None = None, ctx: Context | None = None, absorb=None, absorb_offsets=None,
+               return_effects: bool = False, return_pred: bool = False, max_groups: int | None = None) -> dict:
     """
     ONE GLM over the whole frame and its report: the one-model twin of `glm_report_by`.  Returns the dict of `glm_report_by` un-batched
     ("beta", "std_err", "z", "p>|z|", "0.025", "0.975" [p'] bias last; "deviance", "null_deviance", "pearson_chi2", "dispersion",
@@ -2162,7 +2163,26 @@ def glm_report(*x, target, family: str = "gaussian", add_bias: bool = False, tol
     of the two with the cluster kinds, neither with any other (ValueError).  "hc2" / "hc3" raise NotImplementedError.  The fit, the
     deviances, the dispersion and df_resid are bit for bit those of `glm_report_by(group_offsets=[0, n])` on the same frame.
     1 .. 16 features, `weights` / `offset` as in `glm_by`, no penalties.
+
+    `absorb=key` (an integer column in any row order, NumPy or CUDA) or `absorb_offsets=off` (group g = rows [off[g], off[g+1]),
+    contiguous): the FIXED-EFFECTS GLM, g(E y) = alpha_group + x . beta + o with one intercept per group absorbed -- a PPML gravity
+    model with pair effects, a logit over a firm panel -- fitted by IRLS in which every step is a weighted within regression
+    (`pds_glm_within_by_key_*` / `_grouped_*`; include/pds_lstsq.h states the definitions: what is dropped, the start, the stopping
+    rule, the report).  `add_bias=True` is a ValueError (the intercept is absorbed).  `std_err` is "se" (cov = dispersion W_xx^-1),
+    "cluster" or "cluster0" -- the clusters ARE the absorbed groups, so `cluster` / `cluster_offsets` are a ValueError; "hc0" .. "hc3"
+    raise NotImplementedError.  A group without a row of positive weight, a poisson group whose counting y are all 0 and a binomial
+    group whose counting y are all 0 or all 1 are dropped with their rows.  The dict holds the report fields above ("null_deviance" is
+    NaN, "report_null" 0, "n_clusters" the kept groups with the cluster kinds) plus "n_groups" (kept), "n_groups_dropped",
+    "n_rows_used", "df_resid" = n_rows_used - n_groups - p, "n_iter", "converged"; return_effects=True adds "effects" (alpha per group,
+    NaN for a dropped or empty group) and "effect_keys" (the distinct keys ascending; group indices with `absorb_offsets`),
+    return_pred=True adds "pred" (mu per row in frame order, NaN on the rows of dropped groups).  Refused: two absorbed keys, a
+    cluster key other than the absorbed one, penalties, more than 16 features.  Without `absorb` / `absorb_offsets` nothing changes.
     """
+    if absorb is not None or absorb_offsets is not None:
+        return _glm_within(x, target, family, add_bias, tol, max_iter, std_err, cluster, cluster_offsets, weights, offset, return_cov,
+                           feature_names, ctx, absorb, absorb_offsets, return_effects, return_pred, max_groups)
+    if return_effects or return_pred:
+        raise ValueError("`return_effects` / `return_pred` go with `absorb` or `absorb_offsets` only")
     _glm_std_err_check("glm_report", std_err, cluster, cluster_offsets)
     _glm_check(x, max_iter, "glm_report")
     if std_err == "se":
@@ -2199,6 +2219,83 @@ def glm_report(*x, target, family: str = "gaussian", add_bias: bool = False, tol
     d = {k: (v if k == "features" else v[0]) for k, v in d.items() if k != "is_null"}  # (the entry points return one flag: report_null)
     d["n_clusters"] = int(ng.value)
     d["std_err_type"] = std_err
+    return d
+
+
+def _glm_within(x, target, family, add_bias, tol, max_iter, std_err, cluster, cluster_offsets, weights, offset, return_cov, feature_names,
+                ctx, absorb, absorb_offsets, return_effects, return_pred, max_groups):
+    """glm_report(absorb= | absorb_offsets=): pds_glm_within_by_key_* / _grouped_*.  The report fields are host arrays of the
+    frame's type; "effects" and "pred" live where the inputs live."""
+    if isinstance(absorb, (list, tuple)):
+        raise NotImplementedError("fixed-effects GLM: two or more absorbed keys are not implemented (`absorb` is one integer column)")
+    if (absorb is None) == (absorb_offsets is None):
+        raise ValueError("exactly one of `absorb` and `absorb_offsets` must be given")
+    if add_bias:
+        raise ValueError("`add_bias=True` together with `absorb`: the intercept is absorbed by the group effects")
+    if cluster is not None or cluster_offsets is not None:
+        raise ValueError('`cluster` / `cluster_offsets` together with `absorb`: std_err="cluster" means the absorbed key')
+    if std_err in _lib.SE_TYPES and std_err != "se":
+        raise NotImplementedError(f'fixed-effects GLM: std_err="{std_err}" is not available with absorption ("se", "cluster", "cluster0")')
+    if std_err not in _lib.WITHIN_SE_TYPES:
+        raise ValueError('`absorb`: std_err is "se", "cluster" or "cluster0"')
+    if len(x) < 1:
+        raise ValueError("glm_report: need at least one feature column")
+    if max_iter < 1:
+        raise ValueError("`max_iter` must be > 1.")
+    link, var = _glm_family(family)
+    if any(_is_arrow(c) for c in (target, *x)) or (absorb is not None and _is_arrow(absorb)):
+        raise NotImplementedError("fixed-effects GLM: pyarrow columns are not supported (NumPy arrays or CUDA tensors)")
+    if absorb is not None and not _is_int_column(absorb):
+        raise ValueError("an absorbed key must be an integer column")
+    cols, w_p, o_p = _glm_wo_cols("glm_report", x, target, weights, offset, ())
+    ctx = ctx or default_context()
+    _follow(ctx, cols)
+    p, n, dt = cols.n_feat, cols.n_rows, _dtype()
+    se_code = C.c_int(_lib.WITHIN_SE_TYPES[std_err])
+    pred, pred_p = _out_like(cols, n) if return_pred else (None, C.c_void_p(None))
+    tail = (C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), se_code)
+    if absorb is not None:
+        k, k_p = _key_arg(cols, absorb)
+
+        def call(cap, keys_p, ng_p):
+            alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, C.c_void_p(None))
+            rep = _lib.GlmWithinOut()
+            rep.alpha, rep.pred = alpha_p, pred_p
+            rc = ctx.fn("pds_glm_within_by_key")(ctx._h, cols.cols, w_p, o_p, k_p, p, C.c_int64(n), cols.space, *tail, C.c_int64(cap),
+                                                 keys_p if return_effects else C.c_void_p(None), C.byref(rep), ng_p)
+            return rc, (alpha, rep)
+
+        if return_effects:
+            effect_keys, (alpha, rep), g = _by_key_retry(cols, max_groups, call)
+            alpha = alpha[:g]
+        else:
+            ng = C.c_int64(0)
+            rc, (alpha, rep) = call(n, None, C.byref(ng))
+            _lib.check(rc)
+    else:
+        off, off_p = _offsets_arg(cols, absorb_offsets)
+        if off.ndim != 1 or int(off.shape[0]) < 2:
+            raise ValueError("`absorb_offsets` must be 1-D with at least two entries")
+        ng_all = int(off.shape[0]) - 1
+        alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, C.c_void_p(None))
+        rep = _lib.GlmWithinOut()
+        rep.alpha, rep.pred = alpha_p, pred_p
+        _lib.check(ctx.fn("pds_glm_within_grouped")(ctx._h, cols.cols, w_p, o_p, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, *tail,
+                                                    C.byref(rep)))
+        effect_keys = np.arange(ng_all, dtype=np.int64)
+    names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(p)]
+    vec = lambda field: np.array(field[:p], dtype=np.float64).astype(dt)  # noqa: E731
+    d = {"features": names, "beta": vec(rep.beta), "std_err": vec(rep.std_err), "z": vec(rep.z), "p>|z|": vec(rep.p), "0.025": vec(rep.ci_lower),
+         "0.975": vec(rep.ci_upper), "deviance": dt(rep.deviance), "null_deviance": dt(np.nan), "pearson_chi2": dt(rep.pearson_chi2),
+         "dispersion": dt(rep.dispersion), "df_resid": int(rep.df_resid), "n_iter": int(rep.n_iter), "report_null": 0,
+         "converged": bool(rep.converged), "n_groups": int(rep.n_groups_used), "n_groups_dropped": int(rep.n_groups_dropped),
+         "n_rows_used": int(rep.n_rows_used), "n_clusters": int(rep.n_groups_used) if std_err != "se" else 0, "std_err_type": std_err}
+    if return_cov:
+        d["cov"] = np.array(rep.cov[:p * p], dtype=np.float64).reshape(p, p).astype(dt)
+    if return_effects:
+        d["effects"], d["effect_keys"] = alpha, effect_keys
+    if return_pred:
+        d["pred"] = pred
     return d
 
 
