@@ -54,6 +54,26 @@ static int glm_sandwich_check(const void* ctx, const T* const* cols, const void*
     return check_cols<T>(cols, n_feat);
 }
 
+// v = c inv meat inv, made symmetric (the mean of the two halves): pp x pp row-major, pp <= kMaxFeatSmall + 1.  The robust GLM report
+// and the fixed-effects GLM (capi_glm_within.hpp) share it: the loop order is part of their results' bits.
+static void sandwich_cov(int pp, const double* inv, const double* meat, double c, double* v) {
+    double half[(kMaxFeatSmall + 1) * (kMaxFeatSmall + 1)];
+    for (int i = 0; i < pp; ++i)
+        for (int j = 0; j < pp; ++j) {
+            double s = 0.0;
+            for (int a = 0; a < pp; ++a) s += inv[i * pp + a] * meat[a * pp + j];
+            half[i * pp + j] = s;
+        }
+    for (int i = 0; i < pp; ++i)
+        for (int j = 0; j < pp; ++j) {
+            double s = 0.0;
+            for (int a = 0; a < pp; ++a) s += half[i * pp + a] * inv[a * pp + j];
+            v[i * pp + j] = c * s;
+        }
+    for (int i = 0; i < pp; ++i)
+        for (int j = i + 1; j < pp; ++j) v[i * pp + j] = v[j * pp + i] = 0.5 * (v[i * pp + j] + v[j * pp + i]);
+}
+
 // `vals` (host, doubles) -> the caller's buffer of T (nullable), `space`-resident; `keep` owns the source of an asynchronous copy
 template <typename T>
 static int glm_sandwich_put(pds_ctx* ctx, bool host, void* user, const double* vals, size_t n, std::vector<std::vector<T>>& keep) {
@@ -156,7 +176,7 @@ static int glm_sandwich_device(pds_ctx* ctx, const std::vector<const T*>& src, c
     if (cluster && n_cl < 2) return fail(PDS_ERR_INVALID, "cluster-robust standard errors need at least two non-empty clusters");
     if ((se_type == PDS_HC1 || se_type == PDS_CLUSTER) && n_pos <= pp) return fail(PDS_ERR_TOO_FEW_ROWS, "#Data <= #features. No conclusive result.");
     const double nan = std::nan("");
-    std::vector<double> inv((size_t)pp * pp), meat((size_t)pp * pp, 0.0), half((size_t)pp * pp), v((size_t)pp * pp);
+    std::vector<double> inv((size_t)pp * pp), meat((size_t)pp * pp, 0.0), v((size_t)pp * pp);
     const double disp = (double)plain[3];
     for (size_t k = 0; k < inv.size(); ++k) inv[k] = (double)cov[k] / disp;  // cov = dispersion I^-1: the dispersion cancels in the sandwich
     for (int i = 0; i < p; ++i) {
@@ -167,20 +187,7 @@ static int glm_sandwich_device(pds_ctx* ctx, const std::vector<const T*>& src, c
     double c = 1.0;
     if (se_type == PDS_HC1) c = (double)n_pos / (double)(n_pos - pp);
     if (se_type == PDS_CLUSTER) c = (double)n_cl / (double)(n_cl - 1) * ((double)(n_pos - 1) / (double)(n_pos - pp));
-    for (int i = 0; i < pp; ++i)
-        for (int j = 0; j < pp; ++j) {
-            double s = 0.0;
-            for (int a = 0; a < pp; ++a) s += inv[(size_t)i * pp + a] * meat[(size_t)a * pp + j];
-            half[(size_t)i * pp + j] = s;
-        }
-    for (int i = 0; i < pp; ++i)
-        for (int j = 0; j < pp; ++j) {
-            double s = 0.0;
-            for (int a = 0; a < pp; ++a) s += half[(size_t)i * pp + a] * inv[(size_t)a * pp + j];
-            v[(size_t)i * pp + j] = c * s;
-        }
-    for (int i = 0; i < pp; ++i)
-        for (int j = i + 1; j < pp; ++j) v[(size_t)i * pp + j] = v[(size_t)j * pp + i] = 0.5 * (v[(size_t)i * pp + j] + v[(size_t)j * pp + i]);
+    sandwich_cov(pp, inv.data(), meat.data(), c, v.data());
     bool null = nu != 0 || rnull != 0;
     for (int j = 0; j < pp && !null; ++j) null = !(std::isfinite(v[(size_t)j * pp + j]) && v[(size_t)j * pp + j] >= 0.0);
     std::vector<double> se(pp, nan), z(pp, nan), pv(pp, nan), lo(pp, nan), hi(pp, nan);

@@ -43,10 +43,7 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
                            const int64_t* offsets, int64_t n_groups, pds_space space, pds_space out_space, int link, int variance, T tol_t,
                            int max_iter, int se_type, pds_glm_within_out* out, const uint32_t* d_perm = nullptr) {
     if (!ctx || !cols || !offsets || !out) return fail(PDS_ERR_INVALID, "null argument");
-    if (se_type >= PDS_HC0 && se_type <= PDS_HC3)
-        return fail(PDS_ERR_UNSUPPORTED, "fixed-effects GLM: HC0 - HC3 standard errors are not available with absorption");
-    if (se_type != PDS_SE && se_type != PDS_CLUSTER && se_type != PDS_CLUSTER0)
-        return fail(PDS_ERR_INVALID, "fixed-effects GLM: se_type is PDS_SE, PDS_CLUSTER or PDS_CLUSTER0");
+    if (int rc = within_check_se(se_type, "fixed-effects GLM")) return rc;
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");
     if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
@@ -54,22 +51,18 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
     if (n_rows <= 0 || n_groups <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int p = n_feat, nc = p + 1;
+    const int p = n_feat;
     const double tol = (double)tol_t;
     const bool meat = se_type != PDS_SE;
     // ---- the offsets on the host: validation, the non-empty groups, the chunks of the long ones
-    std::vector<int64_t> off_copy;
-    const int64_t* h_off = nullptr;
-    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
-    GroupChunkPlan pl;
-    if (int rc = plan_group_chunks(h_off, n_groups, n_rows, split, /*cover=*/true, space == PDS_HOST, /*want_gmap=*/true,
-                                   "absorbed group offsets must be non-decreasing and cover the frame", pl))
+    GroupFramePlan gp;
+    if (int rc = plan_group_frame(ctx, offsets, n_groups, n_rows, space, split, /*cover=*/true, /*want_gmap=*/true,
+                                  "absorbed group offsets must be non-decreasing and cover the frame", gp))
         return rc;
-    const int64_t n_all = n_groups, n_chunks = pl.n_chunks(), n_long = pl.n_long();
-    const bool empties = pl.dropped(), upload_off = pl.upload_off;  // (the device works on the non-empty groups alone)
-    h_off = pl.h_off;
-    n_groups = pl.n_nonempty;
+    const int64_t n_all = n_groups, n_chunks = gp.pl.n_chunks(), n_long = gp.pl.n_long();
+    const bool empties = gp.pl.dropped();  // (the device works on the non-empty groups alone)
+    n_groups = gp.pl.n_nonempty;
     // ---- workspace (its own block: the by-key form calls this with its ordered frame living in ctx->keyed)
     const auto up = Bump::up;
     const bool out_host = out_space == PDS_HOST;
@@ -80,60 +73,32 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
     const size_t n_it = (size_t)glm_within_iter_blocks(ctx, n_groups) + (n_chunks > 0 ? (size_t)glm_within_iter_blocks(ctx, n_chunks) : 0);
     const size_t n_fin = (size_t)glm_within_final_blocks(ctx, n_groups) +
                          (n_chunks > 0 ? (size_t)glm_within_final_blocks(ctx, n_chunks) + (size_t)glm_within_final_blocks(ctx, n_long) : 0);
-    const size_t n_rec = std::max(n_it, n_fin), rec_bytes = (size_t)kMixedRecStride * sizeof(double);
-    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp (, weights) (, offset)]
-    if (weights) src.push_back(weights);
-    if (offset) src.push_back(offset);
-    size_t need = 8192 + up(sizeof(T*) * 20) + 2 * up((size_t)nc * n_groups * 8) + up(3 * (size_t)n_groups * 8) + up((size_t)n_groups * 4) +
-                  up(n_rec * rec_bytes) + up((n_rec / 64 + 1) * rec_bytes) + up(rec_bytes) + 512 + 9 * up((size_t)(n_chunks + n_long + 1) * 8) +
-                  up((size_t)(n_chunks + 1) * (p + 2) * 8) + up((size_t)(n_chunks + 1) * 4) + up((size_t)(n_chunks + 1) * (3 + p) * 8) +
-                  up((size_t)(n_chunks + 1) * kClusterScoreStride * 8) + up(kMaxFeatSmall * 8) + g_outs.bytes() + row_outs.bytes();
-    if (space == PDS_HOST) need += up((size_t)n_rows * sizeof(T)) * src.size();
-    if (upload_off) need += up((size_t)(n_groups + 1) * 8);
-    if (empties) need += up((size_t)n_groups * 8);
-    if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
-    if (space == PDS_HOST)
-        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
-    const T* const d_wo[2] = {weights ? src[n_feat + 1] : nullptr, offset ? src.back() : nullptr};
-    std::vector<const T*> frame(src.begin(), src.begin() + n_feat + 1), tbl;
-    const T** d_tbl = nullptr;
-    if (int rc = kernel_order_table<T>(ctx, w, frame, n_feat, tbl, d_tbl, d_wo)) return rc;
-    const int64_t* d_off = offsets;
-    if (upload_off) {
-        int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_off = t;
-    }
-    const int64_t* d_gmap = nullptr;
-    if (empties && d_alpha) {
-        int64_t* t = w.take<int64_t>((size_t)n_groups);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, pl.gmap.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_gmap = t;
-    }
-    double* d_means[2] = {w.take<double>((size_t)nc * n_groups), w.take<double>((size_t)nc * n_groups)};
-    double* d_gstat = w.take<double>(3 * (size_t)n_groups);
-    int32_t* d_drop = w.take<int32_t>((size_t)n_groups);
-    double* d_partials = w.take<double>(n_rec * kMixedRecStride);
-    double* d_stage = w.take<double>((n_rec / 64 + 1) * kMixedRecStride);
-    double* d_rec = w.take<double>(kMixedRecStride);
-    unsigned* d_flags = w.take<unsigned>(64);
-    double* d_beta = w.take<double>(kMaxFeatSmall);
-    MixedChunks ch;
-    if (int rc = upload_mixed_chunks(ctx, w, pl, p + 2, ch)) return rc;
-    double* d_cpre = n_chunks > 0 ? w.take<double>((size_t)n_chunks * (3 + p)) : nullptr;
-    double* d_scores = n_chunks > 0 ? w.take<double>((size_t)n_chunks * kClusterScoreStride) : nullptr;
-    g_outs.place(w);
-    row_outs.place(w);
+    const T* const wo[2] = {weights, offset};
+    GroupFrameNeeds needs;
+    needs.n_means = 2;  // (an iteration reads one table and writes the other)
+    needs.n_rec = std::max(n_it, n_fin);
+    needs.sum_cols = p + 2;
+    needs.scores = true;
+    needs.gmap = d_alpha != nullptr;
+    // this pipeline's own slices: per group the pre-pass sums (3) and the drop flag, per chunk its pre-pass sums (3 + p); the outputs
+    needs.caller_bytes = up(3 * (size_t)n_groups * 8) + up((size_t)n_groups * 4) + up((size_t)n_chunks * (3 + p) * 8) + g_outs.bytes() +
+                         row_outs.bytes();
+    GroupFrame<T> f;
+    if (int rc = open_group_frame<T>(ctx, gp, cols, wo, n_feat, n_rows, space, needs, f)) return rc;
+    double* d_gstat = f.w.template take<double>(3 * (size_t)n_groups);
+    int32_t* d_drop = f.w.template take<int32_t>((size_t)n_groups);
+    double* d_cpre = n_chunks > 0 ? f.w.template take<double>((size_t)n_chunks * (3 + p)) : nullptr;
+    g_outs.place(f.w);
+    row_outs.place(f.w);
     // ---- stage 1: the pre-pass; the per-group sums are added here in group order
-    if (int rc = launch_glm_within_pre<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, variance, d_cpre, d_gstat, d_drop, d_flags)) return rc;
+    if (int rc = launch_glm_within_pre<T>(ctx, f.d_tbl, p, f.d_off, n_groups, split, f.ch, variance, d_cpre, d_gstat, d_drop, f.d_flags)) return rc;
     std::vector<double> gstat(3 * (size_t)n_groups);
     std::vector<int32_t> drop((size_t)n_groups);
     unsigned flags[2] = {0, 0};
     PDS_HIP_CHECK(hipMemcpyAsync(gstat.data(), d_gstat, gstat.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(drop.data(), d_drop, drop.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl: sources of the copies)
+    PDS_HIP_CHECK(hipMemcpyAsync(flags, f.d_flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (f.tbl, gp: sources of the copies)
     if (flags[1]) return fail(PDS_ERR_INVALID, "fixed-effects GLM: a weight is negative or not finite");
     int64_t n_used = 0, g_used = 0;
     double spw = 0.0, spwy = 0.0;
@@ -157,16 +122,16 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
     const unsigned vary = flags[0];
     // ---- stage 2: the iteration
     double beta[kMaxFeatSmall] = {0}, beta_new[kMaxFeatSmall] = {0}, inv[kMaxFeatSmall * kMaxFeatSmall], rec[kMixedRecStride];
-    PDS_HIP_CHECK(hipMemcpyAsync(d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(f.d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
     int cur = 0, n_iter = 0;
     bool converged = false;
     while (n_iter < max_iter && !converged) {
-        if (int rc = launch_glm_within_iter<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, d_drop, link, variance, n_iter == 0, ybar, d_beta,
-                                               d_means[cur], d_means[cur ^ 1], d_partials, d_stage, d_rec))
+        if (int rc = launch_glm_within_iter<T>(ctx, f.d_tbl, p, f.d_off, n_groups, split, f.ch, d_drop, link, variance, n_iter == 0, ybar, f.d_beta,
+                                               f.d_means[cur], f.d_means[cur ^ 1], f.d_partials, f.d_stage, f.d_rec))
             return rc;
         cur ^= 1;  // (the means this iteration wrote)
         ++n_iter;
-        PDS_HIP_CHECK(hipMemcpyAsync(rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(rec, f.d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < p; ++i) {
             bool ok = std::isfinite(rec[kMixedRecXY + i]);
@@ -181,16 +146,16 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
             beta[j] = beta_new[j];
         }
         converged = delta < tol;
-        PDS_HIP_CHECK(hipMemcpyAsync(d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(f.d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
     }
     // ---- stage 3: the final pass at (beta, the last means)
     if (d_alpha && (empties || g_used != n_groups))  // (all bits set is a NaN in both formats: the alpha of an empty or dropped group)
         PDS_HIP_CHECK(hipMemsetAsync(d_alpha, 0xFF, (size_t)n_all * sizeof(T), ctx->stream));
-    if (int rc = launch_glm_within_final<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, d_scores, d_drop, link, variance, d_beta, d_means[cur], meat,
-                                            d_gmap, d_perm, d_alpha, d_pred, d_partials, d_stage, d_rec))
+    if (int rc = launch_glm_within_final<T>(ctx, f.d_tbl, p, f.d_off, n_groups, split, f.ch, f.d_scores, d_drop, link, variance, f.d_beta, f.d_means[cur],
+                                            meat, f.d_gmap, d_perm, d_alpha, d_pred, f.d_partials, f.d_stage, f.d_rec))
         return rc;
     double fin[kMixedRecStride];
-    PDS_HIP_CHECK(hipMemcpyAsync(fin, d_rec, sizeof(fin), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(fin, f.d_rec, sizeof(fin), hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = staged_copy_back(ctx, g_outs, (size_t)n_all)) return rc;
     if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (beta: source of the copy)
@@ -208,21 +173,10 @@ static int glm_within_impl(pds_ctx* ctx, const T* const* cols, const T* weights,
         for (int k = 0; k < p * p; ++k) v[k] = phi * inv[k];
     } else {
         const double factor = se_type == PDS_CLUSTER ? gd / (gd - 1.0) * ((nd - 1.0) / (nd - (double)p - 1.0)) : 1.0;
-        double half[kMaxFeatSmall * kMaxFeatSmall];
+        double m[kMaxFeatSmall * kMaxFeatSmall];  // the meat out of the record's 16-wide rows
         for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j) {
-                double s = 0.0;
-                for (int a = 0; a < p; ++a) s += inv[i * p + a] * fin[kMixedRecW + a * 16 + j];
-                half[i * p + j] = s;
-            }
-        for (int i = 0; i < p; ++i)
-            for (int j = 0; j < p; ++j) {
-                double s = 0.0;
-                for (int a = 0; a < p; ++a) s += half[i * p + a] * inv[a * p + j];
-                v[i * p + j] = factor * s;
-            }
-        for (int i = 0; i < p; ++i)
-            for (int j = i + 1; j < p; ++j) v[i * p + j] = v[j * p + i] = 0.5 * (v[i * p + j] + v[j * p + i]);
+            for (int j = 0; j < p; ++j) m[i * p + j] = fin[kMixedRecW + i * 16 + j];
+        sandwich_cov(p, inv, m, factor, v);
     }
     for (int i = 0; i < p; ++i) {
         const double se = std::sqrt(v[i * p + i]), zv = beta[i] / se;
@@ -244,27 +198,10 @@ static int glm_within_by_key_impl(pds_ctx* ctx, const T* const* cols, const T* w
                                   int64_t n_rows, pds_space space, int link, int variance, T tol, int max_iter, int se_type, int64_t max_groups,
                                   int64_t* out_keys, pds_glm_within_out* out, int64_t* n_groups) {
     if (!ctx || !cols || !keys || !out || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
-    if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
-    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects GLM: up to 16 feature columns");
-    if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
-    if (int rc = check_cols<T>(cols, n_feat)) return rc;
-    const bool want_alpha = out->alpha != nullptr;
-    if (want_alpha && max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
-    PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    KeyedFrame<T> kf;
-    kf.src = frame_cols<T>(cols, n_feat);
-    if (weights) kf.src.push_back(weights);
-    if (offset) kf.src.push_back(offset);
-    Bump w{};
-    if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_alpha ? max_groups : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
-        return rc;
-    if (int rc = glm_within_impl<T>(ctx, kf.src.data(), weights ? kf.src[n_feat + 1] : nullptr, offset ? kf.src.back() : nullptr, n_feat, n_rows,
-                                    kf.d_offsets, kf.ng, PDS_DEVICE, space, link, variance, tol, max_iter, se_type, out, kf.d_perm))
-        return rc;
-    if (want_alpha && out_keys) {
-        PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                                     ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return PDS_OK;
+    const T* const wo[2] = {weights, offset};
+    return absorbed_by_key<T>(ctx, cols, wo, keys, n_feat, n_rows, space, "fixed-effects GLM", out->alpha != nullptr, max_groups, out_keys, n_groups,
+                              [&](const KeyedFrame<T>& kf) {
+        return glm_within_impl<T>(ctx, kf.src.data(), weights ? kf.src[n_feat + 1] : nullptr, offset ? kf.src.back() : nullptr, n_feat, n_rows,
+                                  kf.d_offsets, kf.ng, PDS_DEVICE, space, link, variance, tol, max_iter, se_type, out, kf.d_perm);
+    });
 }

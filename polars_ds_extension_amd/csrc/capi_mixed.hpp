@@ -132,69 +132,45 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int p = n_feat, nc = p + 1, q = p + 2;
-    // ---- the offsets on the host: row counts, validation, the chunks of the long groups
-    std::vector<int64_t> off_copy;
-    const int64_t* h_off = nullptr;
-    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
+    const int p = n_feat, q = p + 2;
+    // ---- the offsets on the host: row counts, validation, the chunks of the long groups (the device works on the non-empty groups alone)
     const int64_t split = std::max<int64_t>(ctx->opt_mixed_split_rows > 0 ? ctx->opt_mixed_split_rows : kMixedSplitRowsDefault, 64);
-    GroupChunkPlan pl;  // (the device works on the non-empty groups alone)
-    if (int rc = plan_group_chunks(h_off, n_groups, n_rows, split, /*cover=*/false, space == PDS_HOST, /*want_gmap=*/false,
-                                   "group offsets must be non-decreasing and inside the frame", pl))
+    GroupFramePlan gp;
+    if (int rc = plan_group_frame(ctx, offsets, n_groups, n_rows, space, split, /*cover=*/false, /*want_gmap=*/false,
+                                  "group offsets must be non-decreasing and inside the frame", gp))
         return rc;
-    const int64_t n_obs = pl.n_obs, n_nonempty = pl.n_nonempty, n_chunks = pl.n_chunks(), n_long = pl.n_long();
-    const bool upload_off = pl.upload_off;
-    h_off = pl.h_off;
-    n_groups = n_nonempty;
+    const int64_t n_obs = gp.pl.n_obs, n_chunks = gp.pl.n_chunks();
+    n_groups = gp.pl.n_nonempty;
     if (n_obs <= p + 1) return fail(PDS_ERR_TOO_FEW_ROWS, "Not enough rows to fit a mixed model with this many fixed effects.");
-    // ---- workspace
-    const auto up = Bump::up;
+    // ---- workspace: the shared part alone (beta0 lives in its beta slot)
+    static_assert(kMixedQ <= kGroupBetaSlot, "beta0 = [1, x] has room in the frame's beta slot");
     const int n_part = mixed_stats_blocks(ctx, n_groups) + (n_chunks > 0 ? mixed_stats_blocks(ctx, n_chunks) : 0);
     const int n_prof = mixed_profile_blocks(ctx, n_groups);
-    const size_t rec_bytes = (size_t)kMixedRecStride * sizeof(double);
-    const size_t n_rec = (size_t)std::max(n_part, n_prof);
-    size_t need = 4096 + up(sizeof(T*) * 18) + up((size_t)nc * n_groups * 8) + up(n_rec * rec_bytes) + up((n_rec / 64 + 1) * rec_bytes) +
-                  up(rec_bytes) + 512 + 9 * up((size_t)(n_chunks + n_long + 1) * 8) + up((size_t)(n_chunks + 1) * nc * 8) +
-                  up((size_t)(n_chunks + 1) * 4);
-    if (space == PDS_HOST) need += up((size_t)n_rows * sizeof(T)) * nc;
-    if (upload_off) need += up((size_t)(n_groups + 1) * 8);
-    if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
-    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
-    if (space == PDS_HOST)
-        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
-    std::vector<const T*> tbl;
-    const T** d_tbl = nullptr;
-    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
-    fr.d_off = offsets;
-    if (upload_off) {
-        int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        fr.d_off = t;
-    }
-    fr.d_means = w.take<double>((size_t)nc * n_groups);
-    fr.d_partials = w.take<double>(n_rec * kMixedRecStride);
-    fr.d_stage = w.take<double>((n_rec / 64 + 1) * kMixedRecStride);
-    fr.d_rec = w.take<double>(kMixedRecStride);
-    unsigned* d_flags = w.take<unsigned>(64);
-    MixedChunks ch;
-    if (int rc = upload_mixed_chunks(ctx, w, pl, nc, ch)) return rc;
-    double* d_beta0 = w.take<double>(kMixedQ);
+    GroupFrameNeeds needs;
+    needs.n_rec = (size_t)std::max(n_part, n_prof);
+    needs.sum_cols = p + 1;
+    GroupFrame<T> f;
+    if (int rc = open_group_frame<T>(ctx, gp, cols, nullptr, n_feat, n_rows, space, needs, f)) return rc;
+    fr.d_off = f.d_off;
+    fr.d_means = f.d_means[0];
+    fr.d_partials = f.d_partials;
+    fr.d_stage = f.d_stage;
+    fr.d_rec = f.d_rec;
     fr.p = p;
     fr.n_groups = n_groups;
     fr.n_obs = n_obs;
-    fr.n_nonempty = n_nonempty;
+    fr.n_nonempty = n_groups;
     std::memset(fr.beta0, 0, sizeof(fr.beta0));
     // one run of the frame passes: means, between bits and W of [x, y - [1, x] . beta0]
     auto pass = [&](const double* d_b0) -> int {
-        if (int rc = launch_mixed_stats<T>(ctx, d_tbl, p, fr.d_off, n_groups, split, ch, d_b0, fr.d_means, d_flags, fr.d_partials, fr.d_stage,
+        if (int rc = launch_mixed_stats<T>(ctx, f.d_tbl, p, fr.d_off, n_groups, split, f.ch, d_b0, fr.d_means, f.d_flags, fr.d_partials, fr.d_stage,
                                            fr.d_rec))
             return rc;
         double rec[kMixedRecStride];
         unsigned vary = 0;
         PDS_HIP_CHECK(hipMemcpyAsync(rec, fr.d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl, beta0: sources of the copies)
+        PDS_HIP_CHECK(hipMemcpyAsync(&vary, f.d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (f.tbl, gp, beta0: sources of the copies)
         fr.between = ~vary & ((1u << p) - 1u);
         std::memset(fr.w, 0, sizeof(fr.w));
         auto within = [&](int j) { return ((vary >> j) & 1u) != 0; };
@@ -211,8 +187,8 @@ static int mixed_prepare(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t
     if (int rc = mixed_eval(ctx, fr, 1.0, ev)) return rc;  // (a design that is not positive definite, a NaN in y: reported here)
     double b0[kMixedQ] = {0};
     for (int j = 0; j <= p; ++j) b0[j] = ev.beta[j];
-    PDS_HIP_CHECK(hipMemcpyAsync(d_beta0, b0, sizeof(double) * (p + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = pass(d_beta0)) return rc;
+    PDS_HIP_CHECK(hipMemcpyAsync(f.d_beta, b0, sizeof(double) * (p + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = pass(f.d_beta)) return rc;
     for (int j = 0; j <= p; ++j) fr.beta0[j] = b0[j];
     return PDS_OK;
 }

@@ -76,11 +76,12 @@ static int within_solve(int p, const double* rec, unsigned vary, double* beta, d
     return PDS_OK;
 }
 
-static int within_check_se(int se_type) {
+// what: the model's name in front of the message ("fixed-effects regression", "fixed-effects GLM")
+static int within_check_se(int se_type, const char* what = "fixed-effects regression") {
     if (se_type >= PDS_HC0 && se_type <= PDS_HC3)
-        return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: HC0 - HC3 standard errors are not available with absorption");
+        return fail(PDS_ERR_UNSUPPORTED, std::string(what) + ": HC0 - HC3 standard errors are not available with absorption");
     if (se_type != PDS_SE && se_type != PDS_CLUSTER && se_type != PDS_CLUSTER0)
-        return fail(PDS_ERR_INVALID, "fixed-effects regression: se_type is PDS_SE, PDS_CLUSTER or PDS_CLUSTER0");
+        return fail(PDS_ERR_INVALID, std::string(what) + ": se_type is PDS_SE, PDS_CLUSTER or PDS_CLUSTER0");
     return PDS_OK;
 }
 
@@ -114,28 +115,24 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     // a cluster key (capi_within_cluster.hpp): the within pass forms no scores, the meat comes from the gathered row scores
     const bool meat = want_se && se_type != PDS_SE && !cl;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int p = n_feat, nc = p + 1;
+    const int p = n_feat;
     // ---- the offsets on the host: validation, the non-empty groups, the chunks of the long ones
-    std::vector<int64_t> off_copy;
-    const int64_t* h_off = nullptr;
-    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
     // gmap is the place of a kept group among the caller's groups (alpha)
-    GroupChunkPlan pl;
-    if (int rc = plan_group_chunks(h_off, n_groups, n_rows, split, /*cover=*/true, space == PDS_HOST, /*want_gmap=*/true,
-                                   "absorbed group offsets must be non-decreasing and cover the frame", pl))
+    GroupFramePlan gp;
+    if (int rc = plan_group_frame(ctx, offsets, n_groups, n_rows, space, split, /*cover=*/true, /*want_gmap=*/true,
+                                  "absorbed group offsets must be non-decreasing and cover the frame", gp))
         return rc;
-    const int64_t n_nonempty = pl.n_nonempty, n_chunks = pl.n_chunks(), n_long = pl.n_long();
+    const int64_t n_nonempty = gp.pl.n_nonempty, n_chunks = gp.pl.n_chunks(), n_long = gp.pl.n_long();
     const int64_t extra_df = more ? more->extra_df : 0;
     const int64_t n_all = n_groups, df_se = n_rows - n_nonempty - p - extra_df;
     if (extra) extra->n_groups_used = n_nonempty;
     if (se_type != PDS_SE && !cl && n_nonempty < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     if (df_se <= 0) return fail(PDS_ERR_TOO_FEW_ROWS, "fixed-effects regression: #rows - #groups - #features <= 0. No conclusive result.");
-    const bool empties = pl.dropped(), upload_off = pl.upload_off;  // (the device works on the non-empty groups alone)
-    h_off = pl.h_off;
+    const bool empties = gp.pl.dropped();  // (the device works on the non-empty groups alone)
+    const int64_t* h_off = gp.pl.h_off;
     n_groups = n_nonempty;
     // ---- workspace (its own block: the by-key form calls this with its ordered frame living in ctx->keyed)
-    const auto up = Bump::up;
     const bool out_host = out_space == PDS_HOST;
     T *d_alpha = nullptr, *d_pred = nullptr, *d_resid = nullptr;
     StagedOuts g_outs(out_host, (size_t)n_all), row_outs(out_host, (size_t)n_rows);
@@ -148,62 +145,34 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     const size_t n_pass = (size_t)within_pass_blocks(ctx, n_groups) +
                           (n_chunks > 0 ? (size_t)within_pass_blocks(ctx, n_chunks) + (size_t)within_pass_blocks(ctx, n_long) : 0);
     const size_t n_meat = cl ? (size_t)cluster_meat_records(ctx, std::min<int64_t>(n_rows, cl->n_levels)) : 0;
-    const size_t n_rec = std::max(std::max(n_stat, n_pass), n_meat), rec_bytes = (size_t)kMixedRecStride * sizeof(double);
-    size_t need = 8192 + up(sizeof(T*) * 18) + up((size_t)nc * n_groups * 8) + up(n_rec * rec_bytes) + up((n_rec / 64 + 1) * rec_bytes) +
-                  up(rec_bytes) + 512 + 9 * up((size_t)(n_chunks + n_long + 1) * 8) + up((size_t)(n_chunks + 1) * nc * 8) +
-                  up((size_t)(n_chunks + 1) * 4) + up((size_t)(n_chunks + 1) * kClusterScoreStride * 8) + up(kMaxFeatSmall * 8) +
-                  g_outs.bytes() + row_outs.bytes();
-    if (space == PDS_HOST) need += up((size_t)n_rows * sizeof(T)) * nc;
-    if (upload_off) need += up((size_t)(n_groups + 1) * 8);
-    if (empties) need += up((size_t)n_groups * 8);
-    if (cl) need += within_cluster_bytes(*cl, n_rows, p, split);
-    if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
-    Bump w{static_cast<char*>(ctx->wkeyed.ptr)};
-    std::vector<const T*> src = frame_cols<T>(cols, n_feat);  // reference order [y, x1..xp], device resident
-    if (space == PDS_HOST)
-        if (int rc = cols_to_device<T>(ctx, w, src, n_rows)) return rc;
-    std::vector<const T*> tbl;
-    const T** d_tbl = nullptr;
-    if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl)) return rc;
-    const int64_t* d_off = offsets;
-    if (upload_off) {
-        int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, h_off, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_off = t;
-    }
-    const int64_t* d_gmap = nullptr;
-    if (empties && extra && extra->alpha) {
-        int64_t* t = w.take<int64_t>((size_t)n_groups);
-        PDS_HIP_CHECK(hipMemcpyAsync(t, pl.gmap.data(), (size_t)n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_gmap = t;
-    }
-    double* d_means = w.take<double>((size_t)nc * n_groups);
-    double* d_partials = w.take<double>(n_rec * kMixedRecStride);
-    double* d_stage = w.take<double>((n_rec / 64 + 1) * kMixedRecStride);
-    double* d_rec = w.take<double>(kMixedRecStride);
-    unsigned* d_flags = w.take<unsigned>(64);
-    double* d_beta = w.take<double>(kMaxFeatSmall);
-    MixedChunks ch;
-    if (int rc = upload_mixed_chunks(ctx, w, pl, nc, ch)) return rc;
-    double* d_scores = n_chunks > 0 ? w.take<double>((size_t)n_chunks * kClusterScoreStride) : nullptr;
-    g_outs.place(w);
-    row_outs.place(w);
+    GroupFrameNeeds needs;
+    needs.n_rec = std::max(std::max(n_stat, n_pass), n_meat);
+    needs.sum_cols = p + 1;
+    needs.scores = true;
+    needs.gmap = extra && extra->alpha;
+    needs.caller_bytes = g_outs.bytes() + row_outs.bytes() + (cl ? within_cluster_bytes(*cl, n_rows, p, split) : 0);
+    GroupFrame<T> f;
+    if (int rc = open_group_frame<T>(ctx, gp, cols, nullptr, n_feat, n_rows, space, needs, f)) return rc;
+    g_outs.place(f.w);
+    row_outs.place(f.w);
     WithinClusterDev cd;
     if (cl)
-        if (int rc = within_cluster_open(ctx, w, *cl, n_rows, p, split, cd)) return rc;
+        if (int rc = within_cluster_open(ctx, f.w, *cl, n_rows, p, split, cd)) return rc;
     // ---- stage 1: the statistics
-    if (int rc = launch_mixed_stats<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, nullptr, d_means, d_flags, d_partials, d_stage, d_rec)) return rc;
+    if (int rc = launch_mixed_stats<T>(ctx, f.d_tbl, p, f.d_off, n_groups, split, f.ch, nullptr, f.d_means[0], f.d_flags, f.d_partials, f.d_stage,
+                                       f.d_rec))
+        return rc;
     double stat[kMixedRecStride];
     unsigned vary = 0;
     const bool want_overall = extra != nullptr && !more;
     std::vector<double> my;
     if (want_overall) {
         my.resize((size_t)n_groups);
-        PDS_HIP_CHECK(hipMemcpyAsync(my.data(), d_means + (size_t)p * n_groups, (size_t)n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipMemcpyAsync(my.data(), f.d_means[0] + (size_t)p * n_groups, (size_t)n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
-    PDS_HIP_CHECK(hipMemcpyAsync(stat, d_rec, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipMemcpyAsync(&vary, d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl, pl: sources of the copies)
+    PDS_HIP_CHECK(hipMemcpyAsync(stat, f.d_rec, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(&vary, f.d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (f.tbl, gp: sources of the copies)
     if (more && more->css)
         for (int j = 0; j < p; ++j)
             if (!(stat[kMixedRecW + j * 16 + j] > more->min_share * more->css[j]))
@@ -212,18 +181,20 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     // ---- stage 2: the solve
     double beta[kMaxFeatSmall] = {0}, inv[kMaxFeatSmall * kMaxFeatSmall];
     if (int rc = within_solve(p, stat, vary, beta, inv)) return rc;
-    PDS_HIP_CHECK(hipMemcpyAsync(d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(f.d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
     // ---- stage 3: the per-row pass
     if (d_alpha && empties)  // (all bits set is a NaN in both formats: the alpha of an empty group)
         PDS_HIP_CHECK(hipMemsetAsync(d_alpha, 0xFF, (size_t)n_all * sizeof(T), ctx->stream));
-    if (int rc = launch_within_pass<T>(ctx, d_tbl, p, d_off, n_groups, split, ch, d_scores, d_beta, d_means, meat, d_gmap, d_perm, d_alpha, d_pred,
-                                       d_resid, d_partials, d_stage, d_rec))
+    if (int rc = launch_within_pass<T>(ctx, f.d_tbl, p, f.d_off, n_groups, split, f.ch, f.d_scores, f.d_beta, f.d_means[0], meat, f.d_gmap, d_perm,
+                                       d_alpha, d_pred, d_resid, f.d_partials, f.d_stage, f.d_rec))
         return rc;
     double rec[kMixedRecStride], crec[kMixedRecStride];
-    PDS_HIP_CHECK(hipMemcpyAsync(rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-    if (cl) {  // (the records and d_rec are free again: the stream has the copy of `rec` in front of these kernels)
-        if (int rc = within_cluster_meat<T>(ctx, *cl, cd, d_tbl, p, d_off, n_groups, split, ch, d_beta, d_means, d_partials, d_stage, d_rec)) return rc;
-        PDS_HIP_CHECK(hipMemcpyAsync(crec, d_rec, sizeof(crec), hipMemcpyDeviceToHost, ctx->stream));
+    PDS_HIP_CHECK(hipMemcpyAsync(rec, f.d_rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cl) {  // (the records and f.d_rec are free again: the stream has the copy of `rec` in front of these kernels)
+        if (int rc = within_cluster_meat<T>(ctx, *cl, cd, f.d_tbl, p, f.d_off, n_groups, split, f.ch, f.d_beta, f.d_means[0], f.d_partials, f.d_stage,
+                                            f.d_rec))
+            return rc;
+        PDS_HIP_CHECK(hipMemcpyAsync(crec, f.d_rec, sizeof(crec), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (int rc = staged_copy_back(ctx, g_outs, (size_t)n_all)) return rc;
     if (int rc = staged_copy_back(ctx, row_outs, (size_t)n_rows)) return rc;
@@ -290,33 +261,46 @@ static int within_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t n
     return PDS_OK;
 }
 
-// int64 keys in any row order: the shared key-ordering stage (ordered keys move nothing), then the contiguous form on the device frame.
-// max_groups / out_keys matter only when extra->alpha is asked for: alpha and out_keys then have room for max_groups entries.
-template <typename T, typename R>
-static int within_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int se_type,
-                              int64_t max_groups, int64_t* out_keys, R* out, pds_within_out* extra, int64_t* n_groups,
-                              WithinCluster* cl = nullptr) {
-    if (!ctx || !cols || !keys || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
-    if (int rc = within_check_se(se_type)) return rc;
+// The by-key form of an absorbed fit, after the caller's null and se_type checks: int64 keys in any row order go through the shared
+// key-ordering stage (ordered keys move nothing; `more`, nullable: the pair {weights, offset}, each nullable, rides through the gather
+// behind the frame), then inner(kf) runs the contiguous form on the device frame.  max_groups / out_keys matter only with want_alpha:
+// alpha and out_keys then have room for max_groups entries.  what: the model's name in front of a message.
+template <typename T, typename Inner>
+static int absorbed_by_key(pds_ctx* ctx, const T* const* cols, const T* const* more, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space,
+                           const char* what, bool want_alpha, int64_t max_groups, int64_t* out_keys, int64_t* n_groups, Inner&& inner) {
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
-    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "fixed-effects regression: up to 16 feature columns");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, std::string(what) + ": up to 16 feature columns");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
-    const bool want_alpha = extra && extra->alpha;
     if (want_alpha && max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     KeyedFrame<T> kf;
     kf.src = frame_cols<T>(cols, n_feat);
+    for (int k = 0; more && k < 2; ++k)
+        if (more[k]) kf.src.push_back(more[k]);
     Bump w{};
     if (int rc = keyed_frame_open<T>(ctx, keys, n_rows, space, want_alpha ? max_groups : n_rows, [](bool) { return (size_t)0; }, n_groups, kf, w))
         return rc;
-    if (cl) cl->d_code_perm = kf.d_perm;  // (the cluster codes stay in the caller's row order and are gathered through the permutation)
-    if (int rc = within_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, space, se_type, out, extra, kf.d_perm, nullptr, cl))
-        return rc;
+    if (int rc = inner(kf)) return rc;
     if (want_alpha && out_keys) {
         PDS_HIP_CHECK(hipMemcpyAsync(out_keys, kf.d_unique, (size_t)kf.ng * 8, space == PDS_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                      ctx->stream));
         PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PDS_OK;
+}
+
+template <typename T, typename R>
+static int within_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* keys, int n_feat, int64_t n_rows, pds_space space, int se_type,
+                              int64_t max_groups, int64_t* out_keys, R* out, pds_within_out* extra, int64_t* n_groups,
+                              WithinCluster* cl = nullptr) {
+    if (!ctx || !cols || !keys || !out || !out->beta || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
+    if (int rc = within_check_se(se_type)) return rc;
+    const auto inner = [&](const KeyedFrame<T>& kf) {
+        if (cl) cl->d_code_perm = kf.d_perm;  // (the cluster codes stay in the caller's row order and are gathered through the permutation)
+        return within_impl<T, R>(ctx, kf.src.data(), n_feat, n_rows, kf.d_offsets, kf.ng, PDS_DEVICE, space, se_type, out, extra, kf.d_perm, nullptr,
+                                 cl);
+    };
+    return absorbed_by_key<T>(ctx, cols, nullptr, keys, n_feat, n_rows, space, "fixed-effects regression", extra && extra->alpha, max_groups, out_keys,
+                              n_groups, inner);
 }

@@ -85,17 +85,15 @@ static int within2_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     const int p = n_feat, nc = p + 1;
     const int64_t n = n_rows;
     // ---- factor 1: the offsets on the host, the non-empty levels, the chunks of the long ones
-    std::vector<int64_t> off_copy;
-    const int64_t* h_off = nullptr;
-    if (int rc = host_offsets(ctx, offsets, n_groups, space, off_copy, h_off)) return rc;
     const int64_t split = std::max<int64_t>(ctx->opt_within_split_rows > 0 ? ctx->opt_within_split_rows : kWithinSplitRowsDefault, 64);
     // the effects of factor 1 go out at the caller's group indices: gmap is the place of a kept group among them
     const bool want_fx1 = fx && (fx->effects1 || fx->component1), want_fx = fx && (want_fx1 || fx->effects2 || fx->component2);
-    GroupChunkPlan pl;
-    if (int rc = plan_group_chunks(h_off, n_groups, n, split, /*cover=*/true, /*offsets_on_host=*/true, /*want_gmap=*/want_fx,
-                                   "absorbed group offsets must be non-decreasing and cover the frame", pl))
+    GroupFramePlan gp;  // (the plan step alone: the offsets of the non-empty levels are always sent, with this pipeline's own workspace)
+    if (int rc = plan_group_frame(ctx, offsets, n_groups, n, space, split, /*cover=*/true, /*want_gmap=*/want_fx,
+                                  "absorbed group offsets must be non-decreasing and cover the frame", gp))
         return rc;
-    h_off = pl.h_off;
+    const GroupChunkPlan& pl = gp.pl;
+    const int64_t* h_off = pl.h_off;
     const int64_t n1 = pl.n_nonempty, n_chunks1 = pl.n_chunks(), n_long1 = pl.n_long();
     if (se_type != PDS_SE && !cl && n1 < 2) return fail(PDS_ERR_INVALID, "standard errors clustered on the absorbed key need at least two non-empty groups");
     // ---- workspace (ctx->ws: the by-key form's ordered frame lives in ctx->keyed, the final stage works in ctx->wkeyed)

@@ -893,35 +893,20 @@ def _lin_reg_within(x, target, add_bias, weights, std_err, feature_names, absorb
                 _lib.check(ctx.fn("pds_lin_reg_within2_cl_by_key")(ctx._h, cols.cols, k_p, codes2_p, C.c_int64(n_levels2), p, C.c_int64(n), cols.space,
                                                                    se_code, C.c_double(float(absorb_tol)), int(absorb_max_iter), C.byref(rep),
                                                                    C.byref(extra), C.byref(ng), None, C.byref(ck)))
-    elif absorb is not None:
-        k, k_p = _key_arg(cols, absorb)
-
-        def call(cap, keys_p, ng_p):
-            alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, C.c_void_p(None))
-            extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
-            name = "pds_lin_reg_within_by_key" if ck is None else "pds_lin_reg_within_cl_by_key"
-            rc = ctx.fn(name)(ctx._h, cols.cols, k_p, p, C.c_int64(n), cols.space, se_code, C.c_int64(cap),
-                              keys_p if return_effects else C.c_void_p(None), C.byref(rep), C.byref(extra), ng_p, *cl_args)
-            return rc, (alpha, extra)
-
-        if return_effects:
-            effect_keys, (alpha, extra), g = _by_key_retry(cols, max_groups, call)
-            alpha = alpha[:g]
-        else:
-            ng = C.c_int64(0)
-            rc, (alpha, extra) = call(n, None, C.byref(ng))
-            _lib.check(rc)
     else:
-        off, off_p = _offsets_arg(cols, absorb_offsets)
-        if off.ndim != 1 or int(off.shape[0]) < 2:
-            raise ValueError("`absorb_offsets` must be 1-D with at least two entries")
-        ng_all = int(off.shape[0]) - 1
-        alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, C.c_void_p(None))
-        extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
-        name = "pds_lin_reg_within_grouped" if ck is None else "pds_lin_reg_within_cl_grouped"
-        _lib.check(ctx.fn(name)(ctx._h, cols.cols, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, se_code, C.byref(rep), C.byref(extra),
-                                *cl_args))
-        effect_keys = np.arange(ng_all, dtype=np.int64)
+        form = "within" if ck is None else "within_cl"
+
+        def by_key(k_p, cap, alpha_p, keys_p, ng_p):
+            extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
+            return ctx.fn(f"pds_lin_reg_{form}_by_key")(ctx._h, cols.cols, k_p, p, C.c_int64(n), cols.space, se_code, C.c_int64(cap), keys_p,
+                                                        C.byref(rep), C.byref(extra), ng_p, *cl_args), extra
+
+        def grouped(off_p, ng_all, alpha_p):
+            extra = _lib.WithinOut(alpha_p, pred_p, resid_p, 0.0, 0, 0)
+            return ctx.fn(f"pds_lin_reg_{form}_grouped")(ctx._h, cols.cols, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, se_code,
+                                                         C.byref(rep), C.byref(extra), *cl_args), extra
+
+        effect_keys, alpha, extra = _absorbed_call(cols, absorb, absorb_offsets, return_effects, max_groups, by_key, grouped)
     if fit_only:
         out = {"beta": outs["beta"]}
     else:
@@ -1603,6 +1588,40 @@ def _by_key_retry(cols: "_Cols", max_groups, call):
         return keys[:g], outs, g
 
 
+def _absorbed_call(cols: "_Cols", absorb, absorb_offsets, return_effects, max_groups, by_key, grouped):
+    """
+    The one-key absorbed call that may return effects, by `absorb` (a key column) or by `absorb_offsets`.
+    `by_key(k_p, cap, alpha_p, keys_p, ng_p)` and `grouped(off_p, n_groups, alpha_p)` make the C call and return (rc, outputs); the
+    effects' buffer and its size are chosen here: by key, room for `max_groups` groups with the retry of _by_key_retry when effects
+    are wanted, else a single call with cap = n_rows; by offsets, one entry per group and effect_keys = the group indices.
+    Returns (effect_keys, effects, the outputs of the call that fitted); both effects entries are None when none are wanted by key.
+    """
+    null = C.c_void_p(None)
+    if absorb is None:
+        off, off_p = _offsets_arg(cols, absorb_offsets)
+        if off.ndim != 1 or int(off.shape[0]) < 2:
+            raise ValueError("`absorb_offsets` must be 1-D with at least two entries")
+        ng_all = int(off.shape[0]) - 1
+        alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, null)
+        rc, outs = grouped(off_p, ng_all, alpha_p)
+        _lib.check(rc)
+        return np.arange(ng_all, dtype=np.int64), alpha, outs
+    k, k_p = _key_arg(cols, absorb)
+
+    def call(cap, keys_p, ng_p):
+        alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, null)
+        rc, outs = by_key(k_p, cap, alpha_p, keys_p if return_effects else null, ng_p)
+        return rc, (alpha, outs)
+
+    if return_effects:
+        effect_keys, (alpha, outs), g = _by_key_retry(cols, max_groups, call)
+        return effect_keys, alpha[:g], outs
+    ng = C.c_int64(0)
+    rc, (_, outs) = call(cols.n_rows, None, C.byref(ng))
+    _lib.check(rc)
+    return None, None, outs
+
+
 def lin_reg_by_pred(*x, target, group_offsets, add_bias: bool = False, l1_reg: float = 0.0, l2_reg: float = 0.0, tol: float = 1e-5,
                     solver: str = "qr", max_iter: int = 200, positive: bool = False, singular_x_tol: float | None = None,
                     weights=None, ctx: Context | None = None):
@@ -2254,36 +2273,21 @@ def _glm_within(x, target, family, add_bias, tol, max_iter, std_err, cluster, cl
     se_code = C.c_int(_lib.WITHIN_SE_TYPES[std_err])
     pred, pred_p = _out_like(cols, n) if return_pred else (None, C.c_void_p(None))
     tail = (C.c_int(link), C.c_int(var), _tol_arg(tol), C.c_int(int(max_iter)), se_code)
-    if absorb is not None:
-        k, k_p = _key_arg(cols, absorb)
 
-        def call(cap, keys_p, ng_p):
-            alpha, alpha_p = _out_like(cols, cap) if return_effects else (None, C.c_void_p(None))
-            rep = _lib.GlmWithinOut()
-            rep.alpha, rep.pred = alpha_p, pred_p
-            rc = ctx.fn("pds_glm_within_by_key")(ctx._h, cols.cols, w_p, o_p, k_p, p, C.c_int64(n), cols.space, *tail, C.c_int64(cap),
-                                                 keys_p if return_effects else C.c_void_p(None), C.byref(rep), ng_p)
-            return rc, (alpha, rep)
-
-        if return_effects:
-            effect_keys, (alpha, rep), g = _by_key_retry(cols, max_groups, call)
-            alpha = alpha[:g]
-        else:
-            ng = C.c_int64(0)
-            rc, (alpha, rep) = call(n, None, C.byref(ng))
-            _lib.check(rc)
-    else:
-        off, off_p = _offsets_arg(cols, absorb_offsets)
-        if off.ndim != 1 or int(off.shape[0]) < 2:
-            raise ValueError("`absorb_offsets` must be 1-D with at least two entries")
-        ng_all = int(off.shape[0]) - 1
-        alpha, alpha_p = _out_like(cols, ng_all) if return_effects else (None, C.c_void_p(None))
+    def by_key(k_p, cap, alpha_p, keys_p, ng_p):
         rep = _lib.GlmWithinOut()
         rep.alpha, rep.pred = alpha_p, pred_p
-        _lib.check(ctx.fn("pds_glm_within_grouped")(ctx._h, cols.cols, w_p, o_p, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, *tail,
-                                                    C.byref(rep)))
-        effect_keys = np.arange(ng_all, dtype=np.int64)
-    names = list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(p)]
+        return ctx.fn("pds_glm_within_by_key")(ctx._h, cols.cols, w_p, o_p, k_p, p, C.c_int64(n), cols.space, *tail, C.c_int64(cap), keys_p,
+                                               C.byref(rep), ng_p), rep
+
+    def grouped(off_p, ng_all, alpha_p):
+        rep = _lib.GlmWithinOut()
+        rep.alpha, rep.pred = alpha_p, pred_p
+        return ctx.fn("pds_glm_within_grouped")(ctx._h, cols.cols, w_p, o_p, p, C.c_int64(n), off_p, C.c_int64(ng_all), cols.space, *tail,
+                                                C.byref(rep)), rep
+
+    effect_keys, alpha, rep = _absorbed_call(cols, absorb, absorb_offsets, return_effects, max_groups, by_key, grouped)
+    names =list(feature_names) if feature_names is not None else [f"x{i + 1}" for i in range(p)]
     vec = lambda field: np.array(field[:p], dtype=np.float64).astype(dt)  # noqa: E731
     d = {"features": names, "beta": vec(rep.beta), "std_err": vec(rep.std_err), "z": vec(rep.z), "p>|z|": vec(rep.p), "0.025": vec(rep.ci_lower),
          "0.975": vec(rep.ci_upper), "deviance": dt(rep.deviance), "null_deviance": dt(np.nan), "pearson_chi2": dt(rep.pearson_chi2),

@@ -194,19 +194,21 @@ def test_f32_frame(pds, p):
     assert np.isfinite(prof["deviance"][0])
 
 
-def test_empty_groups(pds):
-    """Empty groups in the offsets change no output bit and are not counted."""
+def test_empty_groups(pds, contexts):
+    """Empty groups in the offsets change no output bit and are not counted, with whole groups and with the long ones cut into chunks
+    (a host frame, empty groups and chunks in one call)."""
     F, y, off, codes = mc.ragged_frame(4)
     cols = mc.columns(F)
-    base = pds.mixed_reml(*cols, target=y, group_offsets=off)
     padded = np.concatenate([[0, 0], off[:20], [off[19], off[19]], off[20:], [off[-1]]])
-    got = pds.mixed_reml(*cols, target=y, group_offsets=padded)
-    assert got["n_groups"] == len(off) - 1 == base["n_groups"]
-    _same_bits(got, base)
-    a = pds.mixed_reml_profile(*cols, target=y, group_offsets=off, gammas=mc.GAMMAS)
-    b = pds.mixed_reml_profile(*cols, target=y, group_offsets=padded, gammas=mc.GAMMAS)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+    for ctx in contexts.values():
+        base = pds.mixed_reml(*cols, target=y, group_offsets=off, ctx=ctx)
+        got = pds.mixed_reml(*cols, target=y, group_offsets=padded, ctx=ctx)
+        assert got["n_groups"] == len(off) - 1 == base["n_groups"]
+        _same_bits(got, base)
+        a = pds.mixed_reml_profile(*cols, target=y, group_offsets=off, gammas=mc.GAMMAS, ctx=ctx)
+        b = pds.mixed_reml_profile(*cols, target=y, group_offsets=padded, gammas=mc.GAMMAS, ctx=ctx)
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k
 
 
 def test_all_singletons(pds):
