@@ -24,7 +24,23 @@
  *   - every function returns PDS_OK (0) or a negative pds_status; pds_last_error() returns the
  *     message (thread-local), with the reference's error strings where the reference has one.
  *   - all launches go to the stream of the context (pds_ctx_set_stream); calls are synchronous with
- *     respect to the host on return (results are ready), except the *_async moment builders.
+ *     respect to the host on return (results are ready), except the *_async moment builders and the
+ *     stream-ordered return described next.
+ *   - Synchronisation.  pds_lr_grouped_f64 / _f32 may return STREAM-ORDERED: all of the call's work is queued on the context's
+ *     stream and the function returns without waiting for it, as a stream-taking library does.  Whatever the caller queues on that
+ *     stream afterwards -- a kernel that reads `coeffs`, a copy to the host, the next pds_* call -- runs behind it; a host read
+ *     of the outputs needs pds_ctx_synchronize (or the caller's own synchronisation of the stream) first, and the inputs must
+ *     stay alive and unchanged until then.  This happens only when ALL of the following hold, and every other call blocks as
+ *     before:
+ *       . the context's stream was handed in with pds_ctx_set_stream (a context on its private stream always blocks: nobody
+ *         else can order work behind that stream);
+ *       . space == PDS_DEVICE and `coeffs` is given (every input and output in device space);
+ *       . OLS / ridge with the rank gate on and up to 16 features, i.e. the fused kernel's route, with solver "qr" and at most
+ *         16 coefficients, or solver "choleskey" ("svd" runs on host threads; 16 features with an intercept re-solve their
+ *         marked groups on a solver the host drives);
+ *       . the timing hooks (pds_ctx_set_timing) are off and context option "blocking_return" is 0.
+ *     The results are the same bits either way.  One context serves one stream at a time: pds_ctx_set_stream waits for the
+ *     old stream first.
  *   - f64 symbols end in _f64, the f32 twins in _f32 (LIN_REG_EXPR_F64=False path, config.py:15-16).
  */
 #ifndef PDS_LSTSQ_H
@@ -116,6 +132,10 @@ int pds_ctx_num_cus(const pds_ctx* ctx);
  *                                             pds_grouped_fused_split).  Neither option changes a result bit: which wave fits a group
  *                                             does not enter the group's arithmetic.
  *   "grouped_multi_route" / "grouped_multi_waves"  pds_lr_multi_grouped_* / pds_lr_multi_by_key_*: see there (0 / 1 / 2; a count).
+ *   "blocking_return"                         1: every call synchronises before it returns, also the ones that may return
+ *                                             stream-ordered (see "Synchronisation" at the top); 0, the default: they may.  Setting
+ *                                             it waits for the stream.  For tests, A/B runs and callers that read results from the host
+ *                                             right away.
  *   "rolling_waves"                           pds_rolling_lr_* / pds_recursive_lr_* and their grouped forms, up to 12 coefficients (up to 8
  *                                             when grouped): cap on the number of waves any launch of the tiled kernels starts (<= 0: the
  *                                             default grid; two-wave blocks round down to whole blocks, at least one).  A wave then walks

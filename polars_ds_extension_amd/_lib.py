@@ -229,6 +229,9 @@ def load() -> C.CDLL:
         if hasattr(lib, "pds_absorb_components_i32"):
             # ctx, codes1, n_levels1, codes2, n_levels2, n_rows, space, component1, component2, n1, n2, n_components, n_rounds
             lib.pds_absorb_components_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 6
+        if hasattr(lib, "pds_debug_mark_state"):
+            lib.pds_debug_mark_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+            lib.pds_debug_last_return_async.argtypes = [C.c_void_p]
         if hasattr(lib, "pds_ctx_workspace_bytes"):
             lib.pds_ctx_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
             lib.pds_ctx_workspace_bytes.restype = C.c_longlong

@@ -115,6 +115,7 @@ void pds_ctx_destroy(pds_ctx* ctx) {
     if (ctx->keyed.ptr) (void)hipFree(ctx->keyed.ptr);
     if (ctx->wkeyed.ptr) (void)hipFree(ctx->wkeyed.ptr);
     if (ctx->mark_count) (void)hipFree(ctx->mark_count);
+    if (ctx->col_table_dev) (void)hipFree(ctx->col_table_dev);
     if (ctx->wait_timeouts) (void)hipFree(ctx->wait_timeouts);
     if (ctx->mark_host) (void)hipHostFree(ctx->mark_host);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -136,6 +137,8 @@ int pds_ctx_set_stream(pds_ctx* ctx, void* hip_stream) {
     // NULL is a valid hipStream_t: the (legacy) default stream, which is what torch uses unless told otherwise
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
     ctx->own_stream = false;
+    ctx->caller_stream = true;  // (the caller orders its own work on it: device-resident grouped fits may return stream-ordered)
+    ctx->col_table_valid = false;  // (the cached pointer table was written on the old stream: the next call writes it again)
     return PDS_OK;
 }
 
@@ -170,7 +173,11 @@ int pds_ctx_set_option(pds_ctx* ctx, const char* name, long long value) {
         ctx->opt_multi_route = (int64_t)value;
     } else if (n == "grouped_multi_waves") ctx->opt_multi_waves = value > 0 ? (int64_t)value : 0;
     else if (n == "rolling_waves") ctx->opt_rolling_waves = value > 0 ? (int64_t)value : 0;
-    else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
+    else if (n == "blocking_return") {
+        if (value != 0 && value != 1) return fail(PDS_ERR_INVALID, "blocking_return: 0 (stream-ordered where the header allows it) or 1 (always synchronise)");
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (what earlier stream-ordered calls left queued)
+        ctx->opt_blocking_return = (int64_t)value;
+    } else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }
 
@@ -191,6 +198,7 @@ int pds_ctx_get_option(const pds_ctx* ctx, const char* name, long long* value) {
     else if (n == "grouped_multi_route") *value = ctx->opt_multi_route;
     else if (n == "grouped_multi_waves") *value = ctx->opt_multi_waves;
     else if (n == "rolling_waves") *value = ctx->opt_rolling_waves;
+    else if (n == "blocking_return") *value = ctx->opt_blocking_return;
     else return fail(PDS_ERR_INVALID, "unknown context option: " + n);
     return PDS_OK;
 }
@@ -876,12 +884,18 @@ int pds_lin_reg_report_nullable_f32(pds_ctx* ctx, const float* const* cols, cons
 int pds_lr_grouped_f64(pds_ctx* ctx, const double* const* cols, int n_feat, int64_t n_rows,
                        const int64_t* group_offsets, int64_t n_groups, pds_space space, const pds_lr_params* prm,
                        double* coeffs, uint8_t* is_null) {
-    return grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, prm, coeffs, is_null);
+    const int rc = grouped_impl<double>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, prm, coeffs, is_null, false, nullptr,
+                                        nullptr, PDS_NULL_RAISE, 0.0, nullptr, nullptr, nullptr, /*may_stay_on_stream=*/true);
+    if (rc && ctx) ctx->col_table_valid = false;  // (a failed call: nothing it queued is trusted to have run)
+    return rc;
 }
 int pds_lr_grouped_f32(pds_ctx* ctx, const float* const* cols, int n_feat, int64_t n_rows,
                        const int64_t* group_offsets, int64_t n_groups, pds_space space, const pds_lr_params* prm,
                        float* coeffs, uint8_t* is_null) {
-    return grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, prm, coeffs, is_null);
+    const int rc = grouped_impl<float>(ctx, cols, n_feat, n_rows, group_offsets, n_groups, space, prm, coeffs, is_null, false, nullptr,
+                                       nullptr, PDS_NULL_RAISE, 0.0f, nullptr, nullptr, nullptr, /*may_stay_on_stream=*/true);
+    if (rc && ctx) ctx->col_table_valid = false;
+    return rc;
 }
 
 int pds_lr_grouped_nullable_f64(pds_ctx* ctx, const double* const* cols, const uint8_t* const* validity,
@@ -1261,6 +1275,18 @@ int pds_gather_f32(pds_ctx* const* ctxs, int n_ctx, const float* const* src, con
 }
 int pds_debug_last_multi_route(void) { return pds::g_multi_route; }
 int pds_debug_last_grouped_route(void) { return pds::g_grouped_route; }
+// (tests) whether the context's last pds_lr_grouped_* call returned stream-ordered, and -- after waiting for the stream -- the two
+// words of the marked-group state: [0] groups marked and not yet re-solved, [1] fix-up blocks counted as gone; both rest at zero
+int pds_debug_last_return_async(const pds_ctx* ctx) { return ctx ? ctx->last_return_async : 0; }
+int pds_debug_mark_state(pds_ctx* ctx, unsigned* out2) {
+    if (!ctx || !out2) return pds::fail(PDS_ERR_INVALID, "null argument");
+    out2[0] = out2[1] = 0u;
+    PDS_HIP_CHECK(hipSetDevice(ctx->device));
+    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!ctx->mark_count) return PDS_OK;
+    PDS_HIP_CHECK(hipMemcpy(out2, ctx->mark_count, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return PDS_OK;
+}
 int pds_debug_last_by_key_route(int* info /* 4 ints, nullable */) {
     if (info)
         for (int i = 0; i < 4; ++i) info[i] = pds::g_by_key_info[i];

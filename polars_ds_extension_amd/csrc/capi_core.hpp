@@ -106,9 +106,21 @@ void* ws_take(pds_ctx* ctx, size_t bytes) {
 
 constexpr size_t kSmallFrameBytes = (size_t)1 << 20;  // host frames up to this size are staged through pinned memory
 
+// The 18-entry column pointer table of a device-resident frame, written on the stream from kernel arguments.  A hipMemcpyAsync out
+// of the caller's stack would have the host wait for everything queued before it (pageable source) -- the host round trip a
+// stream-ordered call exists to avoid -- and its source would have to outlive the call.
+struct ColTable18 {
+    const void* p[18];
+};
+__global__ void write_col_table_kernel(ColTable18 t, const void** __restrict__ dst) {
+    if (threadIdx.x < 18) dst[threadIdx.x] = t.p[threadIdx.x];
+}
+// a call on a stream the caller handed in may leave its work queued (include/pds_lstsq.h, "Synchronisation")
+static inline bool ctx_stream_ordered(const pds_ctx* ctx) { return ctx->caller_stream && !ctx->opt_blocking_return && !ctx->timing; }
+
 template <typename T>
 int make_device_cols(pds_ctx* ctx, const T* const* cols, const T* weights, int n_feat, int64_t n_rows,
-                     pds_space space, DeviceCols<T>& out) {
+                     pds_space space, DeviceCols<T>& out, bool table_on_stream) {
     const int nc = n_feat + 1 + (weights ? 1 : 0);
     out.nc = nc;
     out.h_ptrs.resize(nc);
@@ -162,9 +174,28 @@ int make_device_cols(pds_ctx* ctx, const T* const* cols, const T* weights, int n
     // the device table always has 18 readable entries (16 features, y, w); unused ones alias column 0 so that
     // kernels may fetch the whole table with wide scalar loads
     out.h_ptrs.resize(std::max(nc, 18), out.h_ptrs[0]);
+    if (table_on_stream && space == PDS_DEVICE && out.h_ptrs.size() == 18) {
+        // The table lives in a slot of the context, not in the call's workspace, and is rewritten -- on the stream, behind the kernels
+        // of earlier calls that read it -- only when a pointer differs: the second fit of a resident frame queues nothing here.
+        // (ONE slot: for calls that hold one table at a time -- the caller asks for it.  Nothing else writes the slot.  The cache
+        //  trusts a queued write to have run: pds_ctx_set_stream and a pds_lr_grouped_* call that fails invalidate it, and an
+        //  asynchronous fault of an earlier kernel is sticky in HIP -- every later call on the context fails.)
+        if (!ctx->col_table_dev) PDS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->col_table_dev), 256));
+        ColTable18 t;
+        for (int c = 0; c < 18; ++c) t.p[c] = out.h_ptrs[c];
+        if (!ctx->col_table_valid || std::memcmp(t.p, ctx->col_table_host, sizeof(t.p)) != 0) {
+            ctx->col_table_valid = false;
+            hipLaunchKernelGGL(write_col_table_kernel, dim3(1), dim3(64), 0, ctx->stream, t, ctx->col_table_dev);
+            PDS_HIP_CHECK(hipGetLastError());
+            std::memcpy(ctx->col_table_host, t.p, sizeof(t.p));
+            ctx->col_table_valid = true;
+        }
+        out.d_ptrs = reinterpret_cast<const T**>(ctx->col_table_dev);
+        return PDS_OK;
+    }
     out.d_ptrs = reinterpret_cast<const T**>(ws_take(ctx, sizeof(T*) * out.h_ptrs.size()));
     PDS_HIP_CHECK(hipMemcpyAsync(out.d_ptrs, out.h_ptrs.data(), sizeof(T*) * out.h_ptrs.size(), hipMemcpyHostToDevice, ctx->stream));
-    // h_ptrs lives in `out` (caller's stack) until the call returns, and every API call synchronises
+    // h_ptrs lives in `out` (caller's stack) until the call returns, and every call that takes this copy synchronises
     // before returning, so the async copy source stays valid.
     return PDS_OK;
 }

@@ -90,8 +90,12 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
                         int policy = PDS_NULL_RAISE, T fill_value = T(0),
                         // grouped pl_lr_pred (grouped_pred.hip): per-row outputs in the frame's row order, `space`-resident, each
                         // nullable; `coeffs` may then be null as well.  Not with the nullable form (its rows are compacted).
-                        T* pred = nullptr, T* resid = nullptr, uint8_t* row_null = nullptr) {
+                        T* pred = nullptr, T* resid = nullptr, uint8_t* row_null = nullptr,
+                        // the public device-resident entry points: the call may end stream-ordered (include/pds_lstsq.h,
+                        // "Synchronisation").  Internal callers queue more work and synchronise themselves: they leave it off.
+                        bool may_stay_on_stream = false) {
     const bool want_pred = pred || resid || row_null;
+    if (ctx) ctx->last_return_async = 0;
     g_grouped_route = 0;  // (the hook reports THIS call's route: the routes that do not set it leave 0, not the previous call's value)
     if (!ctx || !cols || !offsets || !prm || (!coeffs && !want_pred)) return fail(PDS_ERR_INVALID, "null argument");
     if (want_pred && nullable) return fail(PDS_ERR_UNSUPPORTED, "grouped pred: null-free frames only");
@@ -128,8 +132,12 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
         if (space == PDS_HOST) need += (size_t)(n_feat + 1) * ((size_t)n_rows / 8 + 4096);
     }
     if (int rc = ws_reserve(ctx, need)) return rc;
+    // Stream-ordered return: every input and output in device space, nothing staged, nothing compacted, on a stream the caller
+    // handed in.  Whether the chosen route kept everything on the stream is known after it ran (on_stream).
+    const bool want_stream = may_stay_on_stream && ctx_stream_ordered(ctx) && space == PDS_DEVICE && coeffs && !nullable && !want_pred;
+    bool on_stream = false;
     DeviceCols<T> dc;
-    if (int rc = make_device_cols<T>(ctx, cols, (const T*)nullptr, n_feat, n_rows, space, dc)) return rc;
+    if (int rc = make_device_cols<T>(ctx, cols, (const T*)nullptr, n_feat, n_rows, space, dc, want_stream)) return rc;
     const int64_t* d_off = offsets;
     T* d_coeffs = coeffs;
     uint8_t* d_null = is_null;
@@ -232,7 +240,8 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
                 return rc;
         }
     } else if (n_feat <= 16 && !want_piv && !(unfused_env && unfused_env[0] == '1') && n_groups < (1ll << 31)) {
-        if (int rc = launch_grouped_fused<T>(ctx, dc, n_feat, n_rows, d_off, n_groups, sp, d_coeffs, d_null, d_mom, chunk)) return rc;
+        on_stream = want_stream;
+        if (int rc = launch_grouped_fused<T>(ctx, dc, n_feat, n_rows, d_off, n_groups, sp, d_coeffs, d_null, d_mom, chunk, &on_stream)) return rc;
     } else {
         // 17 .. 32 f64 features, rank gate on (round 4): one stream, the solves in the streaming waves, no moment records
         // (grouped_mid.hip); PDS_GROUPED_MID_FUSED=0: the record pipeline below (A/B); it also takes over when more systems sit
@@ -288,6 +297,13 @@ static int grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int64_t 
     if (space == PDS_HOST) {
         if (coeffs) PDS_HIP_CHECK(hipMemcpyAsync(coeffs, d_coeffs, (size_t)n_groups * pp * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         if (is_null) PDS_HIP_CHECK(hipMemcpyAsync(is_null, d_null, (size_t)n_groups, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (want_stream && on_stream) {
+        // everything this call needs is queued on the caller's stream; the workspace slices it used are reused by the next call ON
+        // THE SAME STREAM, i.e. behind it (ws_reserve / ensure_ws synchronise before they free anything)
+        ctx->last_return_async = 1;
+        ctx->async_pending = true;
+        return PDS_OK;
     }
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PDS_OK;

@@ -144,6 +144,18 @@ struct pds_ctx {
     int64_t opt_within_split_rows = 0;  // "within_split_rows": absorbed groups above this many rows are cut into row chunks (0: the default)
     int64_t opt_within2_accel = 0;      // "within2_accel": 0 plain alternating sweeps, 1 Irons-Tuck cycles (capi_within2.hpp)
     int64_t opt_rolling_waves = 0;      // "rolling_waves": cap on the waves a launch of the tiled rolling / expanding kernels starts (0: the default grid)
+    // Stream-ordered return (include/pds_lstsq.h, "Synchronisation"): on a stream the caller handed in, the device-resident grouped
+    // fit of up to 16 features leaves its work queued and returns.  mark_count[1] counts the blocks of the marked-group fix-up
+    // kernel that have left (the last one puts both words back to zero).
+    bool caller_stream = false;         // the stream came from pds_ctx_set_stream
+    int64_t opt_blocking_return = 0;    // "blocking_return": 1 = every call synchronises before it returns (tests, A/B)
+    int last_return_async = 0;          // the last pds_lr_grouped_* call returned with work still queued (pds_debug_last_return_async)
+    // the column pointer table of stream-ordered calls: a slot of its own, written on the stream (write_col_table_kernel) only when
+    // the pointers differ from the ones it holds -- a resident frame fitted again and again writes it once
+    const void** col_table_dev = nullptr;
+    const void* col_table_host[18] = {};
+    bool col_table_valid = false;
+    bool async_pending = false;         // a stream-ordered call returned and the context has not waited for the stream since
 };
 
 namespace pds {
@@ -188,7 +200,10 @@ struct DeviceCols {
 // order on device: x_0..x_{p-1}, y, [w]
 template <typename T>
 int make_device_cols(pds_ctx* ctx, const T* const* cols /*[y,x1..xp]*/, const T* weights, int n_feat,
-                     int64_t n_rows, pds_space space, DeviceCols<T>& out);
+                     int64_t n_rows, pds_space space, DeviceCols<T>& out,
+                     // device-resident frames of up to 18 columns: the pointer table goes to the context's own slot, written by a
+                     // kernel on the stream (no host-side copy source, nothing for the host to wait for) -- stream-ordered calls
+                     bool table_on_stream = false);
 
 // one IRLS step folded into the Gram pass (moments.hip WM = 3): link / variance ids as in pds_lstsq.h, init = first iteration
 struct IrlsArgs {
@@ -247,11 +262,14 @@ int launch_grouped_moments(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, co
 struct SolveParams;
 // grouped_fused.hip: per-group Gram + gated Cholesky in one streaming kernel (p <= 16, OLS / ridge); unless the caller asked
 // for "choleskey", groups next to the gate go through a second, pivoted-QR pass (d_mom_scratch: room for `scratch_groups`
-// moment records of (p+2)^2 values; the pass is chunked by it)
+// moment records of (p+2)^2 values; the pass is chunked by it).  stay_on_stream (nullable, in / out): in = the caller would like
+// the call to end without a host synchronisation; then the marked groups of a "qr" fit with up to 16 coefficients are re-solved by
+// a kernel queued behind the stream (fixup_marked_kernel) instead of the host-driven pass.  out = nothing in the call waited for the
+// device and nothing of it is left for the host to do.
 template <typename T>
 int launch_grouped_fused(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, const int64_t* d_offsets,
                          int64_t n_groups, const SolveParams& sp, T* d_coeffs, uint8_t* d_flags, T* d_mom_scratch,
-                         int64_t scratch_groups);
+                         int64_t scratch_groups, bool* stay_on_stream = nullptr);
 
 // ---- solve.hip ----
 struct SolveParams {

@@ -37,21 +37,29 @@ __device__ unsigned long long g_phase_cycles[8];
 #define PDS_T1(k) do {} while (0)
 #endif
 // -DPDS_PROFILE_TAIL (implied by PDS_PROFILE_PHASES): every wave leaves when it started and ended on the constant 100 MHz clock
-// all XCDs share, its residency in shader clocks and the XCD it ran on -- two stamps per wave and nothing inside the loop, so the
-// launch runs as the product kernel does (development; `python tools/phase_profile.py tail` reads them).  The stamps go to a buffer
-// of their own that nothing else reads.
+// all XCDs share, its residency in shader clocks and the XCD it ran on, and when its first tile load had been issued (both offsets
+// searches behind it) -- three stamps per wave and nothing inside the loop, so the launch runs as the product kernel does
+// (development; `python tools/phase_profile.py tail` reads them).  The stamps go to a buffer of their own that nothing else reads.
 #if defined(PDS_PROFILE_PHASES) || defined(PDS_PROFILE_TAIL)
 #define PDS_WAVE_STAMPS 1
 constexpr int kStampWaves = 4096;
-__device__ unsigned long long g_wave_stamps[4 * kStampWaves];  // per wave: start, end (100 MHz), shader clocks, valid << 63 | HW_ID << 8 | XCD id
+constexpr int kStampWords = 5;
+__device__ unsigned long long g_wave_stamps[kStampWords * kStampWaves];  // per wave: start, end (100 MHz), shader clocks, valid << 63 | HW_ID << 8 | XCD id, first load issued (100 MHz)
 static int g_stamp_grid = 0;                                  // grid of the last launch
 #define PDS_STAMP_BEGIN()                                                             \
     const unsigned long long _st_rt = __builtin_amdgcn_s_memrealtime();               \
+    unsigned long long _st_fl = _st_rt;                                               \
     const unsigned long long _st_mt = __builtin_amdgcn_s_memtime()
+#define PDS_STAMP_FIRST_LOAD()                        \
+    do {                                              \
+        asm volatile("" ::: "memory");                \
+        _st_fl = __builtin_amdgcn_s_memrealtime();    \
+    } while (0)
 #define PDS_STAMP_END()                                                                                                     \
     do {                                                                                                                    \
         if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kStampWaves) {                                                \
-            unsigned long long* _s = g_wave_stamps + 4 * (size_t)blockIdx.x;                                                \
+            unsigned long long* _s = g_wave_stamps + kStampWords * (size_t)blockIdx.x;                                      \
+            _s[4] = _st_fl;                                                                                                 \
             _s[0] = _st_rt;                                                                                                 \
             _s[1] = __builtin_amdgcn_s_memrealtime();                                                                       \
             _s[2] = __builtin_amdgcn_s_memtime() - _st_mt;                                                                  \
@@ -61,10 +69,11 @@ static int g_stamp_grid = 0;                                  // grid of the las
     } while (0)
 #define PDS_STAMP_SKIP()                                                                                  \
     do {                                                                                                  \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kStampWaves) g_wave_stamps[4 * (size_t)blockIdx.x + 3] = 0ull; \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kStampWaves) g_wave_stamps[kStampWords * (size_t)blockIdx.x + 3] = 0ull; \
     } while (0)
 #else
 #define PDS_STAMP_BEGIN() do {} while (0)
+#define PDS_STAMP_FIRST_LOAD() do {} while (0)
 #define PDS_STAMP_END() do {} while (0)
 #define PDS_STAMP_SKIP() do {} while (0)
 #endif
@@ -530,6 +539,7 @@ __global__ __launch_bounds__(64) void grouped_stream_kernel(const T* const* __re
     // (A flat state machine with flush / solve instantiated once each was tried: 4.7k instead of 10.9k static
     //  instructions but 255 live VGPRs and 8 % slower than this nested form at 219.)
     if (t_first <= t_last) load_tile(t_first);
+    PDS_STAMP_FIRST_LOAD();
     // One flush site: a group is flushed as soon as its last row has been consumed (the loop condition also holds while
     // the current group is complete), so groups that end exactly at rhi and trailing empty groups are handled by the last
     // pass; a wave whose groups are all empty makes one pass without a tile.  (Two inlined copies of flush + solve were
@@ -670,11 +680,122 @@ __global__ void scatter_marked_kernel(const T* __restrict__ co_c, const uint8_t*
     if (c == 0) flags[g] = fl_c[k] ? 1 : 0;
 }
 
+// ---- the same second pass without the host: queued behind the streaming kernel whether or not anything was marked.  A fixed grid of
+// single-wave blocks strides over batches of 64 / LPS marked groups; with the count at zero every block leaves at once.  Per batch
+// the wave rebuilds each group's Gram record exactly as grouped_moments_kernel does (same tile loads, same consume_tile / wave_record
+// calls, the record rounded to T) -- into LDS, so no record scratch exists and the count has no ceiling -- then the sub-groups solve
+// their systems side by side as solve_reg_kernel does and store straight to the groups' rows (what scatter_marked_kernel did).  The
+// last block to leave puts the count (state[0]) and the leave counter (state[1]) back to zero for the next call.
+constexpr int kFixupRecBytes = 4 * kFQ * kFQ * 8;  // 64 / LPS records of (p + 2)^2 values: the largest is 4 x 18 x 18 doubles
+template <typename T, int LPS>
+__global__ __launch_bounds__(64) void fixup_marked_kernel(const T* const* __restrict__ cols, int p, const int64_t* __restrict__ offsets,
+                                                          SolveRegDev sp, const int32_t* __restrict__ list, unsigned* __restrict__ state,
+                                                          unsigned* __restrict__ mark_host_flag, T* __restrict__ coeffs,
+                                                          uint8_t* __restrict__ flags) {
+    constexpr int SPW = 64 / LPS;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    // (nothing changes the count while this kernel runs: every block reads the same value.  At zero there is nothing to re-solve and
+    //  nothing to put back -- no block touches the leave counter either, which costs 256 atomics on one address: 7.6 us -> the bare launch)
+    const unsigned count = __hip_atomic_load(&state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (count == 0u) return;
+    {
+        char* wl = smem;
+        double* rec = reinterpret_cast<double*>(wl);  // aliases the (dead) tile between two groups
+        T* recs = reinterpret_cast<T*>(smem + kWaveLds);
+        const int pp = sp.pp, q = p + 2;
+        const int sub = lane / LPS, j = lane % LPS;
+        ColPtrs<T> cp;
+        fetch_col_ptrs<T, false>(cols, p, cp);
+        const unsigned nbatch = (count + (unsigned)SPW - 1u) / (unsigned)SPW;
+        for (unsigned b = blockIdx.x; b < nbatch; b += gridDim.x) {
+            const unsigned k0 = b * (unsigned)SPW;
+            const int nk = (int)min((unsigned)SPW, count - k0);
+            for (int s = 0; s < nk; ++s) {
+                const int64_t gg = (int64_t)list[k0 + s];
+                const int64_t r0 = offsets[gg], rend = offsets[gg + 1], ng = rend - r0;
+                WaveAcc acc;
+                zero_acc(acc);
+                int64_t done = 0;
+                do {  // 128 rows at a time, from the group's first row
+                    GroupRegs<T> regs;
+                    load_group_tile<T>(cp, p, r0 + done, rend, lane, regs);
+                    PDS_WAVE_LDS_SYNC();
+                    store_group_lds<T>(wl, p, lane, regs);
+                    const int64_t left = ng - done;
+                    const int rows = (int)(left < 128 ? left : 128);
+                    consume_tile<T, false>(wl, lane, (rows + 3) >> 2, acc);
+                    done += 128;
+                } while (done < ng);
+                PDS_WAVE_LDS_SYNC();
+                wave_record<T>(acc, lane, rec);
+                PDS_WAVE_LDS_SYNC();
+                T* o = recs + s * (q * q);
+                for (int idx = lane; idx < q * q; idx += 64) {
+                    int i = idx % q, jj = idx / q;
+                    if (i > jj) { int tmp = i; i = jj; jj = tmp; }
+                    double v;
+                    if (jj < p) v = rec[kPartD + i + 16 * jj];
+                    else if (jj == p) v = (i < p) ? rec[kPartCS + i] : (double)ng;
+                    else v = (i < p) ? rec[kPartXY + i] : (i == p ? rec[kPartYS] : rec[kPartYY]);
+                    o[idx] = (T)v;
+                }
+                PDS_WAVE_LDS_SYNC();
+            }
+            // ---- the batch's systems, one per sub-group (solve_reg_kernel's body, pivoted QR, records in LDS)
+            const bool live = sub < nk;
+            const T* M = recs + (live ? sub : 0) * (q * q);
+            auto elem = [&](int i, int k) __attribute__((always_inline)) -> double { return (double)M[i + k * q]; };
+            const bool colv = j < pp;
+            double dj = colv ? elem(j, j) : 1.0;
+            const bool lam = sp.lambda > 0.0 && colv && (j < p || sp.lambda_on_bias);
+            if (lam) dj += sp.lambda;
+            bool is_null = false;
+            int pj = j;
+            double zj = 0.0;
+            double a[LPS], bb[LPS];
+#pragma unroll
+            for (int i = 0; i < LPS; ++i) {
+                a[i] = (colv && i < pp) ? elem(i, j) : 0.0;
+                if (lam && i == j) a[i] += sp.lambda;
+                bb[i] = (i < pp) ? elem(i, p + 1) : 0.0;
+            }
+            solve_core<LPS>(a, bb, dj, j, lane, sp, is_null, pj, zj);
+            const int64_t sys = live ? (int64_t)list[k0 + sub] : 0;
+            if (live && colv) coeffs[sys * (int64_t)pp + pj] = is_null ? (T)__builtin_nan("") : (T)zj;
+            if (live && j == 0) flags[sys] = is_null ? 1 : 0;
+            PDS_WAVE_LDS_SYNC();
+        }
+    }
+    if (lane == 0) {
+        // (acq_rel: this block's read of the count is over before the block counts as gone)
+        const unsigned gone = __hip_atomic_fetch_add(&state[1], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (gone == gridDim.x - 1u) {
+            __hip_atomic_store(&state[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&state[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // (and the host-mapped word the streaming kernel raised: a later host-driven call finds it as its own launch left it)
+            __hip_atomic_store(mark_host_flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+template <typename T, int LPS>
+static int launch_fixup_lps(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, const int64_t* d_offsets, const SolveRegDev& sq,
+                            const int32_t* d_list, unsigned* d_state, unsigned* d_host, T* d_coeffs, uint8_t* d_flags) {
+    const unsigned nb = (unsigned)std::max(1, std::min(ctx->num_cus, 1024));
+    hipLaunchKernelGGL((fixup_marked_kernel<T, LPS>), dim3(nb), dim3(64), (size_t)kWaveLds + kFixupRecBytes, ctx->stream, dc.d_ptrs, n_feat,
+                       d_offsets, sq, d_list, d_state, d_host, d_coeffs, d_flags);
+    PDS_HIP_CHECK(hipGetLastError());
+    return PDS_OK;
+}
+
 // OLS / ridge, p <= 16 features (+ intercept)
 template <typename T>
 int launch_grouped_fused(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int64_t n_rows, const int64_t* d_offsets,
                          int64_t n_groups, const SolveParams& sp, T* d_coeffs, uint8_t* d_flags, T* d_mom_scratch,
-                         int64_t scratch_groups) {
+                         int64_t scratch_groups, bool* stay_on_stream) {
+    const bool want_stream = stay_on_stream && *stay_on_stream;
+    if (stay_on_stream) *stay_on_stream = false;
     SolveRegDev sd;
     sd.p = sp.p;
     sd.bias = sp.add_bias ? 1 : 0;
@@ -696,24 +817,59 @@ int launch_grouped_fused(pds_ctx* ctx, const DeviceCols<T>& dc, int n_feat, int6
     int32_t* d_list = nullptr;
     unsigned* d_count = nullptr;
     unsigned* d_host = nullptr;
+    // the pass behind the stream serves what launch_solve_marked would hand to solve_reg_kernel: "qr", up to 16 coefficients ("svd"
+    // runs on host threads, 16 features + intercept on the LDS solver: both keep the host-driven pass and its synchronisations)
+    const bool dev_fixup = want_stream && second_pass && sp.solver == PDS_SOLVER_QR && sd.pp <= 16;
     if (second_pass) {
         if (int rc0 = ensure_mark_state(ctx)) return rc0;
         d_list = reinterpret_cast<int32_t*>(ws_take(ctx, (size_t)n_groups * sizeof(int32_t)));
         if (!d_list) return fail(PDS_ERR_HIP, "workspace allocation failed");
         d_count = ctx->mark_count;
         d_host = ctx->mark_host_dev;
-        *ctx->mark_host = 0u;  // (host-mapped word; the previous call synchronised before it returned)
+        // The host-mapped word is only looked at by the host-driven pass.  A call that uses the pass behind the stream never touches
+        // it from the host; its fix-up kernel puts it back to zero together with the count.  Should such a call still be queued, the
+        // host-driven route -- which blocks anyway -- waits for it first, so the store below never meets a running kernel.
+        if (!dev_fixup && ctx->async_pending) {
+            PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            ctx->async_pending = false;
+        }
+        if (!dev_fixup) *ctx->mark_host = 0u;
         // The counter is back at zero after every call that ran to its end (below).  A call that failed between its launch and
         // that point leaves it wherever the kernel took it; the next launch would then append behind stale slots -- past the
-        // end of its list.  So such a context re-zeroes the counter first (costs nothing on the common path).
-        if (ctx->mark_dirty) PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
+        // end of its list.  So such a context re-zeroes the counter (and the fix-up kernel's leave counter beside it) first (costs
+        // nothing on the common path).
+        if (ctx->mark_dirty) PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned), ctx->stream));
         ctx->mark_dirty = true;
     }
     int rc;
     if (sd.p <= 4) rc = launch_stream_lps<T, 4>(ctx, dc, n_feat, d_offsets, n_groups, n_rows, sd, chol, d_coeffs, d_flags, d_list, d_count, d_host);
     else if (sd.p <= 8) rc = launch_stream_lps<T, 8>(ctx, dc, n_feat, d_offsets, n_groups, n_rows, sd, chol, d_coeffs, d_flags, d_list, d_count, d_host);
     else rc = launch_stream_lps<T, 16>(ctx, dc, n_feat, d_offsets, n_groups, n_rows, sd, chol, d_coeffs, d_flags, d_list, d_count, d_host);
-    if (rc || !second_pass) return rc;
+    if (rc) return rc;
+    if (!second_pass) {
+        if (stay_on_stream) *stay_on_stream = want_stream;  // ("choleskey": the kernel's answers are final)
+        return PDS_OK;
+    }
+    if (dev_fixup) {
+        // ---- marked groups, without the host: the solver parameters are launch_solve_reg's for the pivoted QR
+        SolveRegDev sq;
+        sq.p = sp.p;
+        sq.bias = sd.bias;
+        sq.pp = sd.pp;
+        sq.lambda_on_bias = sp.lambda_on_bias;
+        sq.lambda = sp.lambda;
+        sq.gate_on = sd.gate_on;
+        sq.ln_tol = sd.ln_tol;
+        sq.inv_tol = sd.inv_tol;
+        int rcf;
+        if (sq.pp <= 4) rcf = launch_fixup_lps<T, 4>(ctx, dc, n_feat, d_offsets, sq, d_list, d_count, d_host, d_coeffs, d_flags);
+        else if (sq.pp <= 8) rcf = launch_fixup_lps<T, 8>(ctx, dc, n_feat, d_offsets, sq, d_list, d_count, d_host, d_coeffs, d_flags);
+        else rcf = launch_fixup_lps<T, 16>(ctx, dc, n_feat, d_offsets, sq, d_list, d_count, d_host, d_coeffs, d_flags);
+        if (rcf) return rcf;
+        ctx->mark_dirty = false;  // (the kernel's last block re-zeroes the counter on the stream)
+        *stay_on_stream = true;
+        return PDS_OK;
+    }
     // ---- marked groups: Gram records (indexed grouped build) -> pivoted Householder QR with the log-det gate -> scatter.
     // Whether there are any is read from the host-mapped word after the kernel has finished (the entry points synchronise
     // before they return anyway); the common case -- none -- costs no launch, no copy and no counter read-back.
@@ -755,19 +911,21 @@ extern "C" int pds_debug_phase_cycles(unsigned long long* out, int reset) {
 #endif
 
 #ifdef PDS_WAVE_STAMPS
-// the stamps of the last fused launch (four words per wave, see g_wave_stamps); returns the number of waves copied.  The caller has
-// synchronised: the grouped entry points do before they return.
+extern "C" int pds_debug_wave_stamp_words(void) { return kStampWords; }
+// the stamps of the last fused launch (kStampWords words per wave, see g_wave_stamps); returns the number of waves copied.  Waits for
+// the device first: a stream-ordered call may have returned with the launch still running.
 extern "C" int pds_debug_wave_stamps(unsigned long long* out, int max_waves) {
     const int n = std::min(std::min(g_stamp_grid, kStampWaves), max_waves);
     if (n <= 0) return 0;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_stamps), (size_t)n * 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_stamps), (size_t)n * kStampWords * sizeof(unsigned long long)) != hipSuccess) return -1;
     return n;
 }
 #endif
 
 template int launch_grouped_fused<double>(pds_ctx*, const DeviceCols<double>&, int, int64_t, const int64_t*, int64_t,
-                                          const SolveParams&, double*, uint8_t*, double*, int64_t);
+                                          const SolveParams&, double*, uint8_t*, double*, int64_t, bool*);
 template int launch_grouped_fused<float>(pds_ctx*, const DeviceCols<float>&, int, int64_t, const int64_t*, int64_t,
-                                         const SolveParams&, float*, uint8_t*, float*, int64_t);
+                                         const SolveParams&, float*, uint8_t*, float*, int64_t, bool*);
 
 }  // namespace pds

@@ -80,7 +80,11 @@ class _Cols:
 class Context:
     """One pds_ctx: a device, a stream, HBM workspace.  Not thread-safe; use one per thread."""
 
-    def __init__(self, device: int = 0, stream=None):
+    def __init__(self, device: int = 0, stream=None, follow_torch: bool = True):
+        """follow_torch=False: the context stays on the stream it has (its private one unless `stream` / `set_stream` says otherwise)
+        instead of moving to torch's current stream with every device-resident call; the caller then orders the inputs' producers
+        and the results' consumers against that stream itself.  Calls on the private stream always block until the results are ready."""
+        self._follow_torch = bool(follow_torch)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         _lib.check(self._lib.pds_ctx_create(int(device), C.byref(self._h)))
@@ -99,6 +103,8 @@ class Context:
         Device-resident inputs are produced by work queued on torch's current stream: run on that stream
         so the kernels are ordered after the producers (and torch consumers after the kernels).
         """
+        if not getattr(self, "_follow_torch", True):
+            return
         import torch
 
         raw = int(torch.cuda.current_stream(device).cuda_stream)
@@ -113,7 +119,9 @@ class Context:
         """Behaviour switches of the context (include/pds_lstsq.h, pds_ctx_set_option): "keyed_sort", "wide_f32_native", "report_chunk_groups",
         "glm_split_rows", "mixed_split_rows", "cluster_split_rows", "cluster_waves", "within_split_rows", "grouped_fused_waves", "grouped_fused_late_permille", "grouped_multi_route",
         "grouped_multi_waves", "within2_accel" (0: plain sweeps of the two-key fixed-effects calls, the default; 1: Irons-Tuck cycles),
-        "rolling_waves" (cap on the waves a launch of the tiled rolling / expanding kernels starts; it changes no result bit); the
+        "rolling_waves" (cap on the waves a launch of the tiled rolling / expanding kernels starts; it changes no result bit),
+        "blocking_return" (1: every call synchronises before it returns, also the device-resident `lin_reg_by` that otherwise leaves
+        its work queued on the stream); the
         defaults came from PDS_KEYED_SORT / PDS_WIDE_F32_NATIVE when the context was created."""
         _lib.check(self._lib.pds_ctx_set_option(self._h, str(name).encode(), C.c_longlong(int(value))))
 
@@ -122,6 +130,18 @@ class Context:
         v = C.c_longlong(0)
         _lib.check(self._lib.pds_ctx_get_option(self._h, str(name).encode(), C.byref(v)))
         return int(v.value)
+
+    def last_return_async(self) -> bool:
+        """Whether the context's last `lin_reg_by` over device columns returned stream-ordered (its work still queued on the stream;
+        include/pds_lstsq.h, "Synchronisation") instead of synchronising first.  Option "blocking_return" = 1 forces the latter."""
+        return bool(self._lib.pds_debug_last_return_async(self._h))
+
+    def mark_state(self) -> tuple:
+        """(tests) Waits for the stream, then reads the hand-over words between the fused grouped kernel and its marked-group pass:
+        (groups marked and not yet re-solved, fix-up blocks counted as gone).  Both rest at zero between calls."""
+        w = (C.c_uint * 2)()
+        _lib.check(self._lib.pds_debug_mark_state(self._h, w))
+        return int(w[0]), int(w[1])
 
     @property
     def num_cus(self) -> int:

@@ -7,10 +7,13 @@
 
     python tools/phase_profile.py [phases] [tail] [--launches 30] [--p 16,8] [--rows 100] [--groups 1000000]
                                   [--waves W] [--late-permille S]       (context options grouped_fused_waves / _late_permille)
+                                  [--frame c3]                          (tools/synth.py's ragged C3 frame, 8 features, instead)
 
 `tail` answers: how long does the launch wait for its slowest wave?  idle share = 1 - mean(end - start) / (max end - min start),
 split into the ramp (waves that start late) and the tail (waves that end early), per XCD, over >= 30 launches, next to the launch
-time's own min / median / max from the context's HIP-event brackets of the same launches."""
+time's own min / median / max from the context's HIP-event brackets of the same launches.  It also prints how long every wave takes
+from its start to having issued its first tile load -- the two searches of the offsets sit in between -- as a distribution over
+waves and as a share of the launch."""
 import argparse
 import ctypes as C
 import sys
@@ -30,7 +33,8 @@ ap.add_argument("--rows", type=int, default=100)
 ap.add_argument("--groups", type=int, default=1_000_000)
 ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--late-permille", type=int, default=0)
-ap.add_argument("--dump", default=None, help="tail: also write the raw stamps of every launch to DUMP_p<P>.npy (launches x waves x 4 words)")
+ap.add_argument("--dump", default=None, help="tail: also write the raw stamps of every launch to DUMP_p<P>.npy (launches x waves x words)")
+ap.add_argument("--frame", default="equal", choices=["equal", "c3"], help="equal: --groups groups of --rows rows; c3: synth.c3_frame(--groups, 8)")
 args = ap.parse_args()
 what = set(args.what) or {"phases"}
 G, R = args.groups, args.rows
@@ -42,11 +46,19 @@ ctx.set_stream(torch.cuda.current_stream(dev))
 for name, v in (("grouped_fused_waves", args.waves), ("grouped_fused_late_permille", args.late_permille)):
     if v:
         ctx.set_option(name, v)
-gen = torch.Generator(device=dev)
-gen.manual_seed(1)
-xs = [torch.randn(N, dtype=torch.float64, device=dev, generator=gen) for _ in range(max(PS))]
-y = sum(x * 0.1 for x in xs) + 0.1 * torch.randn(N, dtype=torch.float64, device=dev, generator=gen)
-off = torch.arange(0, N + 1, R, dtype=torch.int64, device=dev)
+if args.frame == "c3":
+    import synth
+
+    PS = [8]
+    fr = synth.c3_frame(G, 8, seed=2, device=dev)
+    xs, y, off = fr["xs"], fr["y"], fr["offsets"]
+    N = fr["n_rows"]
+else:
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    xs = [torch.randn(N, dtype=torch.float64, device=dev, generator=gen) for _ in range(max(PS))]
+    y = sum(x * 0.1 for x in xs) + 0.1 * torch.randn(N, dtype=torch.float64, device=dev, generator=gen)
+    off = torch.arange(0, N + 1, R, dtype=torch.int64, device=dev)
 so = _lib.load()
 
 
@@ -84,7 +96,9 @@ def tail(P):
         sys.exit("tail: the library was not built with EXTRA=-DPDS_PROFILE_TAIL (or -DPDS_PROFILE_PHASES)")
     so.pds_debug_wave_stamps.argtypes = [C.c_void_p, C.c_int]
     cap = 4096
-    raw = np.zeros((cap, 4), dtype=np.uint64)
+    words = so.pds_debug_wave_stamp_words() if hasattr(so, "pds_debug_wave_stamp_words") else 4  # (5: with the first-load stamp)
+    raw = np.zeros((cap, words), dtype=np.uint64)
+    first_load = []  # per launch: (first load issued - start) of every live wave, us
     f = lambda: pds.lin_reg_by(*xs[:P], target=y, group_offsets=off, ctx=ctx)
     for _ in range(3):
         f()
@@ -103,7 +117,7 @@ def tail(P):
     clk = []
     dumped = []
     for _ in range(L):
-        f()  # (the entry point synchronises before it returns)
+        f()  # (the entry point synchronises before it returns: the timing hooks are on)
         n = so.pds_debug_wave_stamps(raw.ctypes.data_as(C.c_void_p), cap)
         if n <= 0:
             sys.exit("tail: no stamps came back")
@@ -118,6 +132,8 @@ def tail(P):
         n_waves = int(live.sum())
         t0, t1 = st.min(), en.max()
         span = (t1 - t0) / 100.0  # us (100 MHz)
+        if words >= 5:
+            first_load.append(np.append((a[live, 4] - st) / 100.0, span))
         busy = (en - st) / 100.0
         s_rel, e_rel = (st - t0) / 100.0, (en - t0) / 100.0
         rows.append((span, 1.0 - busy.mean() / span, s_rel.mean() / span, (span - e_rel).mean() / span, e_rel.min(), q(e_rel, 50), q(e_rel, 95),
@@ -136,7 +152,8 @@ def tail(P):
     ctx.get_timing(reset=True)
     r = np.array(rows)
     med = lambda k: float(np.median(r[:, k]))
-    print(f"== tail, {G} groups x {R} rows x {P} f64, {n_waves} waves, {L} launches")
+    print(f"== tail, {G} groups x {R} rows x {P} f64, {n_waves} waves, {L} launches" if args.frame == "equal" else
+          f"== tail, C3 frame: {G} ragged groups, {N} rows x {P} f64, {n_waves} waves, {L} launches")
     print(f"launch time (HIP events), ms: min {ms.min():.4f}  median {np.median(ms):.4f}  max {ms.max():.4f}   "
           f"spread (max - min) / median {100.0 * (ms.max() - ms.min()) / np.median(ms):.2f} %   ({len(ms)} brackets)")
     print(f"first start -> last end, us:  min {r[:, 0].min():.1f}  median {med(0):.1f}  max {r[:, 0].max():.1f}      "
@@ -146,6 +163,13 @@ def tail(P):
     print(f"   of which tail (last end - mean end)                      median {100 * med(3):.2f} %")
     print(f"start tick after the first start, us (median over launches): median {med(9):.1f}  max {med(8):.1f}")
     print(f"end tick after the first start, us (median over launches):   min {med(4):.1f}  median {med(5):.1f}  p95 {med(6):.1f}  max {med(7):.1f}")
+    if first_load:
+        fl = np.array([(q(v[:-1], 5), q(v[:-1], 50), q(v[:-1], 95), v[:-1].max(), v[:-1].mean(), v[-1]) for v in first_load])
+        m = lambda k: float(np.median(fl[:, k]))
+        print(f"start -> first tile load issued, us per wave (median over launches): p5 {m(0):.2f}  median {m(1):.2f}  p95 {m(2):.2f}  max {m(3):.2f}  "
+              f"mean {m(4):.2f}")
+        print(f"   median wave as a share of the launch (first start -> last end): {100 * float(np.median(fl[:, 1] / fl[:, 5])):.3f} %   "
+              f"mean wave: {100 * float(np.median(fl[:, 4] / fl[:, 5])):.3f} %   (the 100 MHz clock resolves 0.01 us)")
     print("waves by how long before the launch's last end they ended (all launches):")
     for k in range(12):
         hi = "inf" if k == 11 else f"{edges_us[k + 1]:.0f}"
