@@ -9,6 +9,53 @@
 // Groups above this many rows leave the one-wave-per-group kernel for the full-device iteration (glm_irls_impl on the group's row
 // range: launches and a blocking copy per iteration and group, but every CU on the one group).  Context option "glm_split_rows".
 constexpr int64_t kGlmSplitRowsDefault = 16384;
+static int64_t glm_split_rows(const pds_ctx* ctx) {
+    return std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
+}
+// the most groups of more than `split` rows a frame can hold
+static int64_t glm_long_cap(int64_t n_groups, int64_t n_rows, int64_t split) { return std::min<int64_t>(n_groups, n_rows / split + 1); }
+// entries of the column table (kernel_order_table): 18, and two more with prior weights / offsets
+static int glm_table_slots(bool wo) { return wo ? 20 : 18; }
+
+// The long-group protocol of the fit and of the report (capi_glm_report.hpp): the kernel appends the groups above the split
+// threshold to a list in device memory, in any order, and counts them; the host takes the list back in ascending order.
+struct GlmLongGroups {
+    GlmLongList dev{};
+    static size_t bytes(int64_t cap) { return Bump::up((size_t)cap * 8) + 256; }  // the workspace term: the list and the count block
+    int take(pds_ctx* ctx, Bump& w, int64_t cap) {
+        dev.d_list = w.take<int64_t>((size_t)cap);
+        dev.d_count = w.take<unsigned>(64);
+        dev.cap = cap;
+        PDS_HIP_CHECK(hipMemsetAsync(dev.d_count, 0, sizeof(unsigned), ctx->stream));
+        return PDS_OK;
+    }
+    // After the launch.  The synchronisation here is also the one both callers rely on for the host source of the column table's
+    // asynchronous copy (kernel_order_table): the table's vector must live until this returns.
+    int fetch(pds_ctx* ctx, std::vector<int64_t>& sorted) {
+        unsigned h_count = 0;
+        PDS_HIP_CHECK(hipMemcpyAsync(&h_count, dev.d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+        PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if ((int64_t)h_count > dev.cap) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
+        sorted.resize(h_count);
+        if (h_count == 0) return PDS_OK;
+        PDS_HIP_CHECK(hipMemcpy(sorted.data(), dev.d_list, (size_t)h_count * 8, hipMemcpyDeviceToHost));
+        std::sort(sorted.begin(), sorted.end());
+        return PDS_OK;
+    }
+};
+
+// the argument checks every grouped GLM entry shares; `what` names the entry in the message ("grouped GLM (IRLS)", "grouped GLM report")
+static int glm_args_check(const char* what, int n_feat, int max_iter, int link, int variance) {
+    if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");  // linear_models.py:756-757
+    if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
+    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, std::string(what) + ": up to 16 feature columns");
+    return PDS_OK;
+}
+static int glm_penalty_check(bool wo, double l1_reg, double l2_reg) {
+    if (wo && (l1_reg > 0 || l2_reg > 0))
+        return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): l1_reg / l2_reg together with weights / offset is not built");
+    return PDS_OK;
+}
 
 // d_perm (device, nullable): row r of the frame in
 // group order is row d_perm[r] of pred / row_null.  Its buffers come out of ctx->wkeyed: the full-device iteration of a long group
@@ -23,19 +70,16 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     if (!ctx || !cols || !offsets || !coeffs || !n_iter || !is_null) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_groups <= 0 || n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
-    if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");  // linear_models.py:756-757
-    if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
-    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
+    if (int rc = glm_args_check("grouped GLM (IRLS)", n_feat, max_iter, link, variance)) return rc;
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
     const bool wo = weights || offset;
-    if (wo && (l1_reg > 0 || l2_reg > 0))
-        return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): l1_reg / l2_reg together with weights / offset is not built");
+    if (int rc = glm_penalty_check(wo, (double)l1_reg, (double)l2_reg)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int bias = add_bias ? 1 : 0, pp = n_feat + bias, nc = n_feat + 1 + (weights ? 1 : 0) + (offset ? 1 : 0);
     const bool host_frame = space == PDS_HOST;
     const bool host_out = space == PDS_HOST;
-    const int64_t split = std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
-    const int64_t long_cap = std::min<int64_t>(n_groups, n_rows / split + 1);
+    const int64_t split = glm_split_rows(ctx);
+    const int64_t long_cap = glm_long_cap(n_groups, n_rows, split);
     const auto up = Bump::up;
     const size_t col_bytes = up((size_t)n_rows * sizeof(T));
     T *d_co, *d_pred;
@@ -47,7 +91,7 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     outs.add(&d_nu, is_null, 1);
     row_outs.add(&d_pred, pred, 1);
     row_outs.add(&d_rn, row_null, 1);
-    size_t need = 4096 + up(sizeof(T*) * (wo ? 20 : 18)) + up((size_t)long_cap * 8) + 256 + outs.bytes() + row_outs.bytes();
+    size_t need = 4096 + up(sizeof(T*) * glm_table_slots(wo)) + GlmLongGroups::bytes(long_cap) + outs.bytes() + row_outs.bytes();
     if (host_frame) need += col_bytes * nc;
     if (host_out) need += up((size_t)(n_groups + 1) * 8);
     if (int rc = ensure_ws(ctx, ctx->wkeyed, need)) return rc;
@@ -62,9 +106,8 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     const T** d_tbl = nullptr;
     const T* const d_wo[2] = {weights ? src[n_feat + 1] : nullptr, offset ? src[nc - 1] : nullptr};  // (device resident by now)
     if (int rc = kernel_order_table<T>(ctx, w, src, n_feat, tbl, d_tbl, wo ? d_wo : nullptr)) return rc;
-    int64_t* d_long = w.take<int64_t>((size_t)long_cap);
-    unsigned* d_count = w.take<unsigned>(64);
-    PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
+    GlmLongGroups lng;
+    if (int rc = lng.take(ctx, w, long_cap)) return rc;
     const int64_t* d_off = offsets;
     if (host_out) {
         int64_t* t = w.take<int64_t>((size_t)n_groups + 1);
@@ -73,27 +116,16 @@ static int glm_grouped_impl(pds_ctx* ctx, const T* const* cols, int n_feat, int6
     }
     outs.place(w);
     row_outs.place(w);
-    if (wo) {
-        if (int rc = launch_grouped_irls_wo<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter, split,
-                                               d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap))
-            return rc;
-    } else if (int rc = launch_grouped_irls<T>(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, (double)tol, max_iter,
-                                               split, d_co, d_it, d_nu, d_pred, d_rn, d_perm, d_long, d_count, long_cap, (double)l1_reg,
-                                               (double)l2_reg)) {
-        return rc;
-    }
-    unsigned h_count = 0;
-    PDS_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-    if (h_count > 0) {
+    const GlmGroupsDev<T> groups{d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, split, wo};
+    const GlmFitDev<T> fit{(double)tol, max_iter, (double)l1_reg, (double)l2_reg, d_co, d_it, d_nu, d_pred, d_rn, d_perm};
+    if (int rc = launch_grouped_irls<T>(ctx, groups, fit, lng.dev)) return rc;
+    std::vector<int64_t> lg;
+    if (int rc = lng.fetch(ctx, lg)) return rc;  // (synchronises: tbl was the source of the table copy)
+    if (!lg.empty()) {
         // ---- long groups, in ascending order: the full-device iteration on the group's row range, its row of the outputs from the host
-        if ((int64_t)h_count > long_cap) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
-        std::vector<int64_t> lg(h_count);
-        PDS_HIP_CHECK(hipMemcpy(lg.data(), d_long, (size_t)h_count * 8, hipMemcpyDeviceToHost));
-        std::sort(lg.begin(), lg.end());
-        std::vector<T> hb((size_t)h_count * pp);
-        std::vector<int32_t> hi(h_count);
-        std::vector<uint8_t> hn(h_count);
+        std::vector<T> hb(lg.size() * pp);
+        std::vector<int32_t> hi(lg.size());
+        std::vector<uint8_t> hn(lg.size());
         for (size_t k = 0; k < lg.size(); ++k) {
             const int64_t g = lg[k];
             int64_t rr[2];
@@ -147,13 +179,10 @@ static int glm_by_key_impl(pds_ctx* ctx, const T* const* cols, const int64_t* ke
     if (!ctx || !cols || !keys || !out_keys || !coeffs || !n_iter || !is_null || !n_groups) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
     if (n_rows <= 0) return fail(PDS_ERR_EMPTY, "Empty data");
-    if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");
-    if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
-    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
+    if (int rc = glm_args_check("grouped GLM (IRLS)", n_feat, max_iter, link, variance)) return rc;
     if (max_groups < 1) return fail(PDS_ERR_INVALID, "max_groups must be positive");
     if (int rc = check_cols<T>(cols, n_feat)) return rc;
-    if ((weights || offset) && (l1_reg > 0 || l2_reg > 0))
-        return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): l1_reg / l2_reg together with weights / offset is not built");
+    if (int rc = glm_penalty_check(weights || offset, (double)l1_reg, (double)l2_reg)) return rc;
     PDS_HIP_CHECK(hipSetDevice(ctx->device));
     const int pp = n_feat + (add_bias ? 1 : 0);
     T *d_co, *d_pred;

@@ -42,12 +42,12 @@ static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int
                                      max_iter, d_co, d_it, d_nu, (T*)nullptr, (uint8_t*)nullptr, nullptr, d_pw, d_o))
         return rc;
     const int bias = add_bias ? 1 : 0;
-    const int64_t split = std::max<int64_t>(ctx->opt_glm_split_rows > 0 ? ctx->opt_glm_split_rows : kGlmSplitRowsDefault, 64);
+    const int64_t split = glm_split_rows(ctx);
     const int64_t piece_rows = std::min(split, kGlmReportPieceRows);
-    const int64_t long_cap = std::min<int64_t>(n_groups, n_rows / split + 1);
+    const int64_t long_cap = glm_long_cap(n_groups, n_rows, split);
     const int64_t piece_cap = n_rows / piece_rows + long_cap + 1;
     const auto up = Bump::up;
-    const size_t need = 4096 + up(sizeof(T*) * (wo ? 20 : 18)) + up((size_t)long_cap * 8) + 256 + 2 * up((size_t)piece_cap * 24) +
+    const size_t need = 4096 + up(sizeof(T*) * glm_table_slots(wo)) + GlmLongGroups::bytes(long_cap) + 2 * up((size_t)piece_cap * 24) +
                         up((size_t)piece_cap * kGlmReportRec * 8);
     if (int rc = ws_reserve(ctx, need)) return rc;
     Bump w{static_cast<char*>(ctx->ws.ptr)};
@@ -56,24 +56,17 @@ static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int
     const T* const d_wo[2] = {d_pw, d_o};
     std::vector<const T*> frame(src.begin(), src.begin() + n_feat + 1);  // (src may carry the two columns behind the frame)
     if (int rc = kernel_order_table<T>(ctx, w, frame, n_feat, tbl, d_tbl, wo ? d_wo : nullptr)) return rc;
-    int64_t* d_long = w.take<int64_t>((size_t)long_cap);
-    unsigned* d_count = w.take<unsigned>(64);
+    GlmLongGroups lng;
+    if (int rc = lng.take(ctx, w, long_cap)) return rc;
     int64_t* d_pieces = w.take<int64_t>((size_t)piece_cap * 3);
     int64_t* d_fin = w.take<int64_t>((size_t)piece_cap * 3);
     double* d_rec = w.take<double>((size_t)piece_cap * kGlmReportRec);
-    PDS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned), ctx->stream));
-    const auto report = wo ? launch_grouped_glm_report_wo<T> : launch_grouped_glm_report<T>;
-    if (int rc = report(ctx, d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, split, d_co, d_nu, d, d_long, d_count, long_cap))
-        return rc;
-    unsigned h_count = 0;
-    PDS_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (tbl: source of the table copy)
-    if (h_count == 0) return PDS_OK;
+    const GlmGroupsDev<T> groups{d_tbl, n_feat, bias, n_rows, d_off, n_groups, link, variance, split, wo};
+    if (int rc = launch_grouped_glm_report<T>(ctx, groups, d_co, d_nu, d, lng.dev)) return rc;
+    std::vector<int64_t> lg, pieces, fin;
+    if (int rc = lng.fetch(ctx, lg)) return rc;  // (synchronises: tbl was the source of the table copy)
+    if (lg.empty()) return PDS_OK;
     // ---- long groups, in ascending order: pieces of at most piece_rows rows, one record each, added per group in piece order
-    if ((int64_t)h_count > long_cap) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
-    std::vector<int64_t> lg(h_count), pieces, fin;
-    PDS_HIP_CHECK(hipMemcpy(lg.data(), d_long, (size_t)h_count * 8, hipMemcpyDeviceToHost));
-    std::sort(lg.begin(), lg.end());
     for (const int64_t g : lg) {
         int64_t rr[2];
         PDS_HIP_CHECK(hipMemcpy(rr, d_off + g, 16, hipMemcpyDeviceToHost));
@@ -92,8 +85,7 @@ static int glm_report_device(pds_ctx* ctx, const std::vector<const T*>& src, int
     if (n_pieces > piece_cap) return fail(PDS_ERR_INVALID, "group offsets must be non-decreasing and inside the frame");
     PDS_HIP_CHECK(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     PDS_HIP_CHECK(hipMemcpyAsync(d_fin, fin.data(), fin.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    const auto pieced = wo ? launch_grouped_glm_report_wo_pieces<T> : launch_grouped_glm_report_pieces<T>;
-    if (int rc = pieced(ctx, d_tbl, n_feat, bias, d_off, link, variance, d_co, d, d_pieces, n_pieces, d_fin, n_fin, d_rec)) return rc;
+    if (int rc = launch_grouped_glm_report_pieces<T>(ctx, groups, d_co, d, d_pieces, n_pieces, d_fin, n_fin, d_rec)) return rc;
     PDS_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (pieces / fin: sources of the copies)
     return PDS_OK;
 }
@@ -102,10 +94,7 @@ static int glm_report_check(const void* ctx, const void* cols, const void* coeff
                             int n_feat, int max_iter, int link, int variance) {
     if (!ctx || !cols || !coeffs || !n_iter || !is_null || !out) return fail(PDS_ERR_INVALID, "null argument");
     if (n_feat < 1) return fail(PDS_ERR_INVALID, "need at least one feature column");
-    if (max_iter < 1) return fail(PDS_ERR_INVALID, "`max_iter` must be > 1.");
-    if (link < 0 || link > 3 || variance < 0 || variance > 3) return fail(PDS_ERR_INVALID, "unknown link / variance function");
-    if (n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
-    return PDS_OK;
+    return glm_args_check("grouped GLM report", n_feat, max_iter, link, variance);
 }
 
 // A host frame is staged once (ctx->stage: columns, offsets, the fit's and the report's outputs) and fitted and reported as a device

@@ -345,23 +345,45 @@ template <typename T>
 int launch_grouped_pred_by_id_table(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_keys,
                                     const int64_t* d_kmin, const uint32_t* d_ids /* dense id of group g */, int64_t n_groups, const T* d_coeffs,
                                     const uint8_t* d_flags, T* d_table /* n_ids x grouped_pred_table_stride(p') workspace */, T* d_pred, T* d_resid, uint8_t* d_row_null);  // grouped_pred.hip
-// ---- grouped_irls.hip: a GLM per group (IRLS), one wave per group, all iterations on chip; 1 .. 16 features.  Groups of more than
-// `split_rows` rows are not fitted: their indices are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it).
-// l1_reg / l2_reg > 0: the elastic-net penalised fit (features only, scaled by the group's row count); both <= 0: the kernel as it
-// was without them.
+// ---- the grouped GLM kernels (grouped_irls.hip, grouped_glm_report.hip): one description of a launch, shared by the fit and the report.
+// The frame as the kernels see it: d_cols holds x_0 .. x_{p-1}, y (18 entries) and, with `wo`, the prior weights and the offsets
+// behind y (20 entries), of which either may be null (weights 1, offsets 0).  1 .. 16 features.
 template <typename T>
-int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                        int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
-                        int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
-                        const uint32_t* d_perm /*nullable: row r of the frame in group order is row d_perm[r] of the outputs*/,
-                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg = 0.0, double l2_reg = 0.0);
-// The weighted / offset form (grouped_irls_wo.hip): d_cols holds n_feat + 3 entries, x_0 .. x_{p-1}, y, prior weights, offsets, of
-// which the last two may be null (weights 1, offsets 0).  Unpenalised; groups of more than `split_rows` rows go to d_long_list, as above.
+struct GlmGroupsDev {
+    const T* const* d_cols;
+    int n_feat, bias;
+    int64_t n_rows;
+    const int64_t* d_off;
+    int64_t n_groups;
+    int link, variance;
+    int64_t split_rows;
+    bool wo;  // the weighted / offset kernels; the table carries the two extra entries
+};
+// Groups of more than `split_rows` rows are not walked by one wave: their indices are appended to d_list (any order, *d_count of
+// them, of which the first `cap` are stored; the caller zeroes the count).
+struct GlmLongList {
+    int64_t* d_list;
+    unsigned* d_count;
+    int64_t cap;
+};
+// the fit's controls and outputs.  l1_reg / l2_reg > 0: the elastic-net penalised fit (features only, scaled by the group's row
+// count); a penalty <= 0 means none.
 template <typename T>
-int launch_grouped_irls_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                           int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
-                           int32_t* d_n_iter, uint8_t* d_null, T* d_pred /*nullable*/, uint8_t* d_row_null /*nullable*/,
-                           const uint32_t* d_perm /*nullable*/, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+struct GlmFitDev {
+    double tol;
+    int max_iter;
+    double l1_reg, l2_reg;
+    T* d_coeffs;
+    int32_t* d_n_iter;
+    uint8_t* d_null;
+    T* d_pred;               // nullable
+    uint8_t* d_row_null;     // nullable
+    const uint32_t* d_perm;  // nullable: row r of the frame in group order is row d_perm[r] of pred / row_null
+};
+// ---- grouped_irls.hip: a GLM per group (IRLS), one wave per group, all iterations on chip.  The one fit launcher: it picks the
+// kernel set -- weighted / offset (groups.wo: unpenalised), coordinate descent (l1_reg > 0), ridge (l2_reg > 0), plain.
+template <typename T>
+int launch_grouped_irls(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const GlmFitDev<T>& fit, const GlmLongList& long_list);
 // glm_wo_model.hip: the one-model iteration with prior weights d_pw and offsets d_off (device, each nullable).  The side sums of the
 // first pass, d_out4 = {rows of positive weight, weights that are negative or not finite, sum pw, sum pw y}; and the weight and the
 // working response of one IRLS step as two columns, which the weighted Gram build then reads (every width).
@@ -381,36 +403,25 @@ int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int 
                           const T* d_offset = nullptr /*an offset per row of the frame, added to x . beta*/);
 // ---- grouped_glm_report.hip: the report of a GLM per group at the coefficients in d_coeffs (se, z, p, CI, cov, deviances,
 // dispersion: the definitions stand at the head of that file), one wave per group; 1 .. 16 features.  Every output is nullable.
-// Groups of more than `split_rows` rows are appended to d_long_list (any order, *d_long_count of them; the caller zeroes it) and
-// reported by launch_grouped_glm_report_pieces: d_pieces [n_pieces][3] = (group, first row, end row), d_fin [n_fin][3] = (group,
-// first piece, pieces), d_rec n_pieces records of kGlmReportRec doubles.
+// Groups of more than `split_rows` rows are appended to the long list and reported by launch_grouped_glm_report_pieces: d_pieces
+// [n_pieces][3] = (group, first row, end row), d_fin [n_fin][3] = (group, first piece, pieces), d_rec n_pieces records of
+// kGlmReportRec doubles.  Both launchers take the weighted / offset kernels (grouped_glm_report_wo.hip) when groups.wo is set.
 template <typename T>
 struct GlmReportDev {
     T *se, *z, *p, *lo, *hi, *cov, *deviance, *null_deviance, *pearson, *dispersion;
     int64_t* df_resid;
     uint8_t* report_null;
 };
-// a piece's record: [0,256) I [i * 16 + j]; [256,272) X'w; 272 sum w; 273 sum (y - y0); 274 pearson; 275 deviance; 276 the family sum
-// (the weighted / offset form: 273 .. 276 weighted by pw; 277 sum pw; 278 rows of positive weight)
+// a piece's record: [0,256) I [i * 16 + j]; [256,272) X'w; from 272 the scalar sums in the order of grouped_glm_report.hip's GrSum:
+// sum w, sum (y - y0), pearson, deviance, the family sum (the weighted / offset form: the last four weighted by pw; then sum pw and
+// the rows of positive weight)
 constexpr int kGlmReportRec = 280;
 template <typename T>
-int launch_grouped_glm_report(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                              int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
-                              const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
+int launch_grouped_glm_report(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const T* d_coeffs, const uint8_t* d_null,
+                              const GlmReportDev<T>& out, const GlmLongList& long_list);
 template <typename T>
-int launch_grouped_glm_report_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
-                                     int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
-                                     int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
-// grouped_glm_report_wo.hip: the same two with prior weights and offsets: d_cols holds n_feat + 3 entries, x_0 .. x_{p-1}, y, pw, o,
-// of which the last two may be null
-template <typename T>
-int launch_grouped_glm_report_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                                 int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
-                                 const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap);
-template <typename T>
-int launch_grouped_glm_report_wo_pieces(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
-                                        int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
-                                        int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
+int launch_grouped_glm_report_pieces(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const T* d_coeffs, const GlmReportDev<T>& out,
+                                     const int64_t* d_pieces, int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
 // ---- grouped_rcond.hip: lin_reg_w_rcond per group, one wave per group: Gram, one-sided Jacobi of X'X (+ l2_reg) and the minimum-norm
 // solve on chip; 1 .. 16 features.  d_coeffs / d_svals [n_groups][p'] (bias last; singular values descending), d_null [n_groups].
 // rcond is the caller's value: the floor eps_T max(n_g, p') is applied per group.

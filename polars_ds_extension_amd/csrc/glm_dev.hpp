@@ -43,4 +43,19 @@ __device__ __forceinline__ T glm_var(int variance, T mu) {
     }
 }
 
+// ---- deviances (f64: the report kernels of grouped_glm_report.hip and the final pass of glm_within.hip)
+__device__ __forceinline__ double glm_xlogy(double a, double b) { return a > 0.0 ? a * log(b) : 0.0; }  // (0 ln 0 = 0)
+
+// a row's deviance term.  (gr_accumulate of grouped_glm_report.hip spells the same four terms in its own switch, next to the family
+// sum's: returned from a helper and added behind the switch they compile to other instructions there.)
+__device__ __forceinline__ double glm_unit_deviance(int variance, double y, double mu) {
+    const double e = y - mu;
+    switch (variance) {
+        case 1: return 2.0 * (glm_xlogy(y, y / mu) - e);
+        case 2: return 2.0 * (glm_xlogy(y, y / mu) + glm_xlogy(1.0 - y, (1.0 - y) / (1.0 - mu)));
+        case 3: return 2.0 * (e / mu - log(y / mu));
+        default: return e * e;
+    }
+}
+
 }  // namespace pds

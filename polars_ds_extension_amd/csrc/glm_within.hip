@@ -456,18 +456,6 @@ __global__ __launch_bounds__(64) void gw_chunk_scatter_kernel(const T* const* __
 }
 
 // ---- the final pass
-__device__ __forceinline__ double gw_xlogy(double a, double b) { return a > 0.0 ? a * log(b) : 0.0; }  // (0 ln 0 = 0)
-
-__device__ __forceinline__ double gw_unit_deviance(int variance, double y, double mu) {
-    const double e = y - mu;
-    switch (variance) {
-        case 1: return 2.0 * (gw_xlogy(y, y / mu) - e);
-        case 2: return 2.0 * (gw_xlogy(y, y / mu) + gw_xlogy(1.0 - y, (1.0 - y) / (1.0 - mu)));
-        case 3: return 2.0 * (e / mu - log(y / mu));
-        default: return e * e;
-    }
-}
-
 // where the rows' means go: pred (nullable); perm (nullable): row r of the frame the kernels read is row perm[r] of the caller's
 template <typename T>
 struct GwRowOut {
@@ -505,7 +493,7 @@ __device__ __forceinline__ void gw_final_stream(const GwFrame<T, P>& fr, const d
         const bool pos = live && pw > 0.0;
         const double e = y - mu;
         const double rs = pos ? pw * e / (v * d) : 0.0;  // (a select: a dead lane's or a zero-weight row's r reaches no sum)
-        two_sum(dv.s, dv.c, pos ? pw * gw_unit_deviance(fr.variance, y, mu) : 0.0);
+        two_sum(dv.s, dv.c, pos ? pw * glm_unit_deviance(fr.variance, y, mu) : 0.0);
         two_sum(pe.s, pe.c, pos ? pw * (e * e / v) : 0.0);
         if (live && ro.pred) ro.pred[ro_i] = (T)mu;
         if constexpr (MEAT) {

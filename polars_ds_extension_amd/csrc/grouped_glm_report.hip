@@ -30,9 +30,12 @@
 // record (I, X'w and the five sums) and grouped_glm_report_fold_kernel -- one wave per long group -- adds the records in piece order
 // and runs the same epilogue: deterministic whatever the schedule.
 //
-// The weighted / offset form (WO: grouped_glm_report_wo.hip compiles this file with PDS_GLM_REPORT_WO and holds its kernels, the
-// kernels above keep their names and objects): a prior weight pw_i and an offset o_i per row, entries P + 1 and P + 2 of the column
-// table, each nullable.  eta_i = x_i . beta + o_i; I = sum pw_i w~_i x_i x_i' with w~ = 1 / (g'^2 V); pearson_chi2 =
+// The three kernels are templates on <T, P, WO>.  WO is the weighted / offset form: a prior weight pw_i and an offset o_i per row,
+// entries P + 1 and P + 2 of the column table, each nullable (the WO = false kernels never read those two entries: their table
+// ends at y).  This file is compiled twice so that the two sets of 96 kernels build side by side: as it stands it holds the
+// WO = false kernels and the launchers of common.hpp, which pick the set from GlmGroupsDev::wo; grouped_glm_report_wo.hip compiles
+// it with PDS_GLM_REPORT_WO and holds the WO = true kernels.  The macro selects nothing but which value of WO is instantiated.
+// WO: eta_i = x_i . beta + o_i; I = sum pw_i w~_i x_i x_i' with w~ = 1 / (g'^2 V); pearson_chi2 =
 // sum pw_i (y_i - mu_i)^2 / V; deviance = sum pw_i d_i; df_resid = n+ - p' with n+ the rows of positive weight; null_deviance: the
 // closed form above with weighted sums (n -> sum pw, sum y -> sum pw y, the family sum weighted; the gaussian shift is the group's
 // first y of positive weight), NaN when an offset is given.  A piece's record gains sum pw (277) and n+ (278).
@@ -40,6 +43,7 @@
 #include "wave_tile_dev.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 #ifndef PDS_GLM_REPORT_WO
 #define PDS_GLM_REPORT_WO 0
@@ -54,12 +58,28 @@ constexpr int kGrG = 18;                         // row stride of the staged mat
 constexpr int kGrLds = 16 * kGrStride + 64 + 18 + 17 * kGrG + 8;
 constexpr double kGrZ975 = 1.959963984540054;
 
+// The scalar sums of a group or a piece, in the order a piece's record holds them (from kGrRecSums on): sum w, sum (y - y0), pearson,
+// deviance, the family sum of the null deviance; WO: then sum pw and the rows of positive weight (sy, pe, dv, fs weighted by pw)
+enum GrSum { kGrSw, kGrSy, kGrPe, kGrDv, kGrFs, kGrSpw, kGrNpos, kGrSumMax };
+template <bool WO>
+constexpr int kGrSumCount = WO ? kGrSumMax : kGrSpw;
 struct GrSums {
-    double sw, sy, pe, dv, fs;  // sum w, sum (y - y0), pearson, deviance, the family sum of the null deviance
-    double spw, npos;           // WO: sum pw, rows of positive weight (sy, pe, dv, fs are then weighted by pw)
+    double v[kGrSumMax];
+    __device__ __forceinline__ double& operator[](int i) { return v[i]; }
+    __device__ __forceinline__ double operator[](int i) const { return v[i]; }
 };
-
-__device__ __forceinline__ double gr_xlogy(double a, double b) { return a > 0.0 ? a * log(b) : 0.0; }  // (0 ln 0 = 0)
+// f(i) for i = 0 .. kGrSumCount<WO> - 1, i a constant in every call: the loop over a record's sums.  (Under a run-time loop the fold
+// kernel's copy of the sums stays in memory until the optimiser has unrolled it, and its listing is no longer the spelt-out loads'.)
+template <bool WO, int N = kGrSumCount<WO>, typename F>
+__device__ __forceinline__ void gr_each_sum(F&& f) {
+    if constexpr (N > 0) {
+        gr_each_sum<WO, N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+constexpr int kGrRecSide = 256;              // a record: I [i * 16 + j], then X'w from here,
+constexpr int kGrRecSums = kGrRecSide + 16;  // then the sums
+static_assert(kGrRecSums + kGrSumMax <= kGlmReportRec, "a piece's record holds I, X'w and every sum");
 
 // the wave-private carving of a block's LDS
 struct GrLds {
@@ -67,11 +87,21 @@ struct GrLds {
     __device__ explicit GrLds(double* base) : xt(base), wt(xt + 16 * kGrStride), bs(wt + 64), gm(bs + 18), sm(gm + 17 * kGrG) {}
 };
 
+// a term of a sum: weighted by pw in the WO form, as it is otherwise (no product by 1: the unweighted sums keep their operations)
+template <bool WO>
+__device__ __forceinline__ double gr_wt(double pw, double t) {
+    if constexpr (WO) {
+        return pw * t;
+    } else {
+        return t;
+    }
+}
+
 // rows [r0, r1) of one group at the coefficients in l.bs: I into acc, X'w into column 0 of acc2, the sums (folded) into s
-template <typename T, int P, bool WO = false>
+template <typename T, int P, bool WO>
 __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy, int64_t r0, int64_t r1, double y0, int bias, int link,
                                               int variance, const GrLds& l, int lane, d4& acc, d4& acc2, GrSums& s,
-                                              const T* pwp = nullptr, const T* ofp = nullptr) {
+                                              const T* pwp, const T* ofp) {
     double sw = 0.0, sy = 0.0, pe = 0.0, dv = 0.0, fs = 0.0;
     [[maybe_unused]] double spw = 0.0, npos = 0.0;
     for (int64_t base = r0; base < r1; base += 64) {
@@ -86,66 +116,43 @@ __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy
             eta = fma(xv, l.bs[c], eta);
         }
         double w = 0.0;
+        [[maybe_unused]] double pwv = 1.0;
+        bool on = live;
         if constexpr (WO) {
-            const double pwv = live ? (pwp ? (double)as_global(pwp)[r] : 1.0) : 0.0;
+            pwv = live ? (pwp ? (double)as_global(pwp)[r] : 1.0) : 0.0;
             if (live && ofp) eta += (double)as_global(ofp)[r];
-            if (pwv > 0.0) {  // (a row of weight 0 contributes nothing whatever its y holds)
-                const double yv = (double)cy[r];
-                const double mu = glm_inv<double>(link, eta);
-                const double d = glm_deriv<double>(link, mu);
-                const double v = glm_var<double>(variance, mu);
-                w = pwv / (d * d * v);
-                const double e = yv - mu;
-                pe += pwv * (e * e / v);
-                const double dy = yv - y0;
-                sy += pwv * dy;
-                spw += pwv;
-                npos += 1.0;
-                switch (variance) {
-                    case 1:
-                        dv += pwv * (2.0 * (gr_xlogy(yv, yv / mu) - e));
-                        fs += pwv * gr_xlogy(yv, yv);
-                        break;
-                    case 2:
-                        dv += pwv * (2.0 * (gr_xlogy(yv, yv / mu) + gr_xlogy(1.0 - yv, (1.0 - yv) / (1.0 - mu))));
-                        fs += pwv * (gr_xlogy(yv, yv) + gr_xlogy(1.0 - yv, 1.0 - yv));
-                        break;
-                    case 3:
-                        dv += pwv * (2.0 * (e / mu - log(yv / mu)));
-                        fs += pwv * log(yv);
-                        break;
-                    default:
-                        dv += pwv * (e * e);
-                        fs += pwv * (dy * dy);
-                        break;
-                }
-            }
-        } else if (live) {
+            on = pwv > 0.0;  // (a row of weight 0 contributes nothing whatever its y holds)
+        }
+        if (on) {
             const double yv = (double)cy[r];
             const double mu = glm_inv<double>(link, eta);
             const double d = glm_deriv<double>(link, mu);
             const double v = glm_var<double>(variance, mu);
-            w = 1.0 / (d * d * v);
+            w = (WO ? pwv : 1.0) / (d * d * v);
             const double e = yv - mu;
-            pe += e * e / v;
+            pe += gr_wt<WO>(pwv, e * e / v);
             const double dy = yv - y0;
-            sy += dy;
-            switch (variance) {
+            sy += gr_wt<WO>(pwv, dy);
+            if constexpr (WO) {
+                spw += pwv;
+                npos += 1.0;
+            }
+            switch (variance) {  // the deviance term (glm_unit_deviance) and the family sum's
                 case 1:
-                    dv += 2.0 * (gr_xlogy(yv, yv / mu) - e);
-                    fs += gr_xlogy(yv, yv);
+                    dv += gr_wt<WO>(pwv, 2.0 * (glm_xlogy(yv, yv / mu) - e));
+                    fs += gr_wt<WO>(pwv, glm_xlogy(yv, yv));
                     break;
                 case 2:
-                    dv += 2.0 * (gr_xlogy(yv, yv / mu) + gr_xlogy(1.0 - yv, (1.0 - yv) / (1.0 - mu)));
-                    fs += gr_xlogy(yv, yv) + gr_xlogy(1.0 - yv, 1.0 - yv);
+                    dv += gr_wt<WO>(pwv, 2.0 * (glm_xlogy(yv, yv / mu) + glm_xlogy(1.0 - yv, (1.0 - yv) / (1.0 - mu))));
+                    fs += gr_wt<WO>(pwv, glm_xlogy(yv, yv) + glm_xlogy(1.0 - yv, 1.0 - yv));
                     break;
                 case 3:
-                    dv += 2.0 * (e / mu - log(yv / mu));
-                    fs += log(yv);
+                    dv += gr_wt<WO>(pwv, 2.0 * (e / mu - log(yv / mu)));
+                    fs += gr_wt<WO>(pwv, log(yv));
                     break;
                 default:
-                    dv += e * e;
-                    fs += dy * dy;
+                    dv += gr_wt<WO>(pwv, e * e);
+                    fs += gr_wt<WO>(pwv, dy * dy);
                     break;
             }
         }
@@ -157,14 +164,14 @@ __device__ __forceinline__ void gr_accumulate(const gptr<T> (&cx)[P], gptr<T> cy
             [&](int c, int row, double wv) { return c == 0 ? wv : 0.0; },  // B column 0 = w: the bias row X'w
             acc, acc2);
     }
-    s.sw = wave_sum(sw);
-    s.sy = wave_sum(sy);
-    s.pe = wave_sum(pe);
-    s.dv = wave_sum(dv);
-    s.fs = wave_sum(fs);
+    s[kGrSw] = wave_sum(sw);
+    s[kGrSy] = wave_sum(sy);
+    s[kGrPe] = wave_sum(pe);
+    s[kGrDv] = wave_sum(dv);
+    s[kGrFs] = wave_sum(fs);
     if constexpr (WO) {
-        s.spw = wave_sum(spw);
-        s.npos = wave_sum(npos);
+        s[kGrSpw] = wave_sum(spw);
+        s[kGrNpos] = wave_sum(npos);
     }
 }
 
@@ -193,9 +200,9 @@ __device__ __forceinline__ void gr_write_null(const GlmReportDev<T>& o, int64_t 
 }
 
 // l.gm holds I (index 16 = bias), l.bs the coefficients, s the group's sums: invert, derive, write
-template <typename T, int P, bool WO = false>
+template <typename T, int P, bool WO>
 __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g, int64_t n, int bias, int variance, double y0, const GrLds& l,
-                                            const GrSums& s, int lane, bool has_offset = false) {
+                                            const GrSums& s, int lane, bool has_offset) {
     const int pp = P + bias, ne = pp * pp;
     auto m = [](int j) { return j < P ? j : 16; };
     bool bad = false;
@@ -231,25 +238,25 @@ __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g,
         return;
     }
     const double nanv = __builtin_nan("");
-    const double nn = WO ? s.spw : (double)n;  // (WO: sum pw stands where the row count stood; s.sy, s.fs are weighted)
-    const int64_t df = (WO ? (int64_t)s.npos : n) - pp;
-    const double phi = (variance == 1 || variance == 2) ? 1.0 : (df > 0 ? s.pe / (double)df : nanv);
-    const double sy = s.sy + nn * y0;  // sum y
+    const double nn = WO ? s[kGrSpw] : (double)n;  // (WO: sum pw stands where the row count stood; sy, fs are weighted)
+    const int64_t df = (WO ? (int64_t)s[kGrNpos] : n) - pp;
+    const double phi = (variance == 1 || variance == 2) ? 1.0 : (df > 0 ? s[kGrPe] / (double)df : nanv);
+    const double sy = s[kGrSy] + nn * y0;  // sum y
     double nd;
     if (bias) {
         const double ym = sy / nn;
         switch (variance) {
-            case 1: nd = 2.0 * (s.fs - gr_xlogy(sy, ym)); break;
-            case 2: nd = 2.0 * (s.fs - gr_xlogy(sy, ym) - gr_xlogy(nn - sy, 1.0 - ym)); break;
-            case 3: nd = 2.0 * (nn * log(ym) - s.fs); break;
-            default: nd = s.fs - s.sy * s.sy / nn; break;
+            case 1: nd = 2.0 * (s[kGrFs] - glm_xlogy(sy, ym)); break;
+            case 2: nd = 2.0 * (s[kGrFs] - glm_xlogy(sy, ym) - glm_xlogy(nn - sy, 1.0 - ym)); break;
+            case 3: nd = 2.0 * (nn * log(ym) - s[kGrFs]); break;
+            default: nd = s[kGrFs] - s[kGrSy] * s[kGrSy] / nn; break;
         }
     } else {
         switch (variance) {
-            case 1: nd = 2.0 * (s.fs - sy + nn); break;
-            case 2: nd = 2.0 * (s.fs + nn * 0.693147180559945309417); break;
+            case 1: nd = 2.0 * (s[kGrFs] - sy + nn); break;
+            case 2: nd = 2.0 * (s[kGrFs] + nn * 0.693147180559945309417); break;
             case 3: nd = nanv; break;
-            default: nd = s.fs; break;  // (y0 = 0 without a bias: sum y^2)
+            default: nd = s[kGrFs]; break;  // (y0 = 0 without a bias: sum y^2)
         }
     }
     if (WO && has_offset) nd = nanv;  // (the intercept-only model under an offset needs an iteration of its own)
@@ -271,9 +278,9 @@ __device__ __forceinline__ void gr_epilogue(const GlmReportDev<T>& o, int64_t g,
             o.cov[g * ne + e] = (T)(phi * l.gm[m(i) * kGrG + m(j)]);
         }
     if (lane == 0) {
-        if (o.deviance) o.deviance[g] = (T)s.dv;
+        if (o.deviance) o.deviance[g] = (T)s[kGrDv];
         if (o.null_deviance) o.null_deviance[g] = (T)nd;
-        if (o.pearson) o.pearson[g] = (T)s.pe;
+        if (o.pearson) o.pearson[g] = (T)s[kGrPe];
         if (o.dispersion) o.dispersion[g] = (T)phi;
         if (o.df_resid) o.df_resid[g] = df;
         if (o.report_null) o.report_null[g] = 0;
@@ -315,7 +322,27 @@ __device__ __forceinline__ double gr_shift_wo(gptr<T> cy, const T* pwp, int64_t 
     return 0.0;
 }
 
-template <typename T, int P>
+// WO: cols[P + 1] = pw, cols[P + 2] = o (each nullable); the unweighted table ends at y and is not read beyond it
+template <typename T, int P, bool WO>
+struct GrWoCols {
+    const T *pw = nullptr, *of = nullptr;
+    __device__ explicit GrWoCols(const T* const* __restrict__ cols) {
+        if constexpr (WO) {
+            pw = cols[P + 1];
+            of = cols[P + 2];
+        }
+    }
+    // the shift of the group of rows [r0, r1)
+    __device__ __forceinline__ double shift(gptr<T> cy, int64_t r0, int64_t r1, int bias, int variance, int lane) const {
+        if constexpr (WO) {
+            return gr_shift_wo<T>(cy, pw, r0, r1, bias, variance, lane);
+        } else {
+            return gr_shift<T>(cy, r0, bias, variance);
+        }
+    }
+};
+
+template <typename T, int P, bool WO>
 __global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* __restrict__ cols, int bias, int64_t n_rows,
                                                                 const int64_t* __restrict__ off, int64_t n_groups, int link,
                                                                 int variance, int64_t split_rows, const T* __restrict__ coeffs,
@@ -330,10 +357,11 @@ __global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* 
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
+    const GrWoCols<T, P, WO> wc(cols);
     for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
         const int64_t r0 = off[g], n = off[g + 1] - r0;
         const bool bad = r0 < 0 || n < 0 || r0 + n > n_rows;  // (offsets that leave the frame: nothing is read)
-        if (bad || n < pp || is_null[g]) {
+        if (bad || n < pp || is_null[g]) {  // (WO: a group that fails the weight rule is a null fit)
             gr_write_null<T>(o, g, bad ? 0 : n, pp, lane);
             continue;
         }
@@ -342,10 +370,10 @@ __global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* 
             continue;
         }
         gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        const double y0 = gr_shift<T>(cy, r0, bias, variance);
+        const double y0 = wc.shift(cy, r0, r0 + n, bias, variance, lane);
         d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
         GrSums s;
-        gr_accumulate<T, P>(cx, cy, r0, r0 + n, y0, bias, link, variance, l, lane, acc, acc2, s);
+        gr_accumulate<T, P, WO>(cx, cy, r0, r0 + n, y0, bias, link, variance, l, lane, acc, acc2, s, wc.pw, wc.of);
         PDS_WAVE_LDS_SYNC();
         wave_tile_for_d(
             lane,
@@ -357,14 +385,14 @@ __global__ __launch_bounds__(64) void grouped_glm_report_kernel(const T* const* 
                 }
             },
             acc, acc2);
-        if (lane == 0) l.gm[16 * kGrG + 16] = s.sw;
+        if (lane == 0) l.gm[16 * kGrG + 16] = s[kGrSw];
         PDS_WAVE_LDS_SYNC();
-        gr_epilogue<T, P>(o, g, n, bias, variance, y0, l, s, lane);
+        gr_epilogue<T, P, WO>(o, g, n, bias, variance, y0, l, s, lane, wc.of != nullptr);
     }
 }
 
 // piece k = rows [pieces[3 k + 1], pieces[3 k + 2]) of group pieces[3 k]: its record rec[k * kGlmReportRec ..]
-template <typename T, int P>
+template <typename T, int P, bool WO>
 __global__ __launch_bounds__(64) void grouped_glm_report_piece_kernel(const T* const* __restrict__ cols, int bias,
                                                                       const int64_t* __restrict__ off, int link, int variance,
                                                                       const T* __restrict__ coeffs, const int64_t* __restrict__ pieces,
@@ -376,33 +404,30 @@ __global__ __launch_bounds__(64) void grouped_glm_report_piece_kernel(const T* c
 #pragma unroll
     for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
     const gptr<T> cy = as_global(cols[P]);
+    const GrWoCols<T, P, WO> wc(cols);
     for (int64_t k = blockIdx.x; k < n_pieces; k += gridDim.x) {
         const int64_t g = pieces[3 * k], r0 = pieces[3 * k + 1], r1 = pieces[3 * k + 2];
         gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        const double y0 = gr_shift<T>(cy, off[g], bias, variance);
+        const double y0 = wc.shift(cy, off[g], off[g + 1], bias, variance, lane);  // (the group's, not the piece's)
         d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
         GrSums s;
-        gr_accumulate<T, P>(cx, cy, r0, r1, y0, bias, link, variance, l, lane, acc, acc2, s);
+        gr_accumulate<T, P, WO>(cx, cy, r0, r1, y0, bias, link, variance, l, lane, acc, acc2, s, wc.pw, wc.of);
         double* out = rec + k * kGlmReportRec;
         wave_tile_for_d(
             lane,
             [&](int i, int c, double v, double side) {
                 out[i * 16 + c] = v;
-                if (c == 0) out[256 + i] = side;
+                if (c == 0) out[kGrRecSide + i] = side;
             },
             acc, acc2);
         if (lane == 0) {
-            out[272] = s.sw;
-            out[273] = s.sy;
-            out[274] = s.pe;
-            out[275] = s.dv;
-            out[276] = s.fs;
+            gr_each_sum<WO>([&](auto i) { out[kGrRecSums + i] = s[i]; });
         }
     }
 }
 
 // long group j = fin[3 j]: its records fin[3 j + 1] .. + fin[3 j + 2], added in piece order, then the epilogue of the one-wave route
-template <typename T, int P>
+template <typename T, int P, bool WO>
 __global__ __launch_bounds__(64) void grouped_glm_report_fold_kernel(const T* const* __restrict__ cols, int bias,
                                                                      const int64_t* __restrict__ off, int variance,
                                                                      const T* __restrict__ coeffs, const int64_t* __restrict__ fin,
@@ -411,229 +436,107 @@ __global__ __launch_bounds__(64) void grouped_glm_report_fold_kernel(const T* co
     const GrLds l(lds);
     const int lane = threadIdx.x;
     const gptr<T> cy = as_global(cols[P]);
+    const GrWoCols<T, P, WO> wc(cols);
     for (int64_t j = blockIdx.x; j < n_fin; j += gridDim.x) {
         const int64_t g = fin[3 * j], first = fin[3 * j + 1], cnt = fin[3 * j + 2];
         gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        for (int e = lane; e < 277; e += 64) {
+        for (int e = lane; e < kGrRecSums + kGrSumCount<WO>; e += 64) {
             double v = 0.0;
             for (int64_t k = 0; k < cnt; ++k) v += rec[(first + k) * kGlmReportRec + e];
-            if (e < 256) {
+            if (e < kGrRecSide) {
                 l.gm[(e >> 4) * kGrG + (e & 15)] = v;
-            } else if (e < 272) {
-                l.gm[(e - 256) * kGrG + 16] = v;
-                l.gm[16 * kGrG + (e - 256)] = v;
+            } else if (e < kGrRecSums) {
+                l.gm[(e - kGrRecSide) * kGrG + 16] = v;
+                l.gm[16 * kGrG + (e - kGrRecSide)] = v;
             } else {
-                if (e == 272) l.gm[16 * kGrG + 16] = v;
-                l.sm[e - 272] = v;
+                if (e == kGrRecSums + kGrSw) l.gm[16 * kGrG + 16] = v;
+                l.sm[e - kGrRecSums] = v;
             }
         }
         PDS_WAVE_LDS_SYNC();
         GrSums s;
-        s.sw = l.sm[0];
-        s.sy = l.sm[1];
-        s.pe = l.sm[2];
-        s.dv = l.sm[3];
-        s.fs = l.sm[4];
-        const int64_t r0 = off[g];
-        gr_epilogue<T, P>(o, g, off[g + 1] - r0, bias, variance, gr_shift<T>(cy, r0, bias, variance), l, s, lane);
-    }
-}
-
-
-// ---- the weighted / offset form of the three kernels: cols[P + 1] = pw, cols[P + 2] = o (each nullable)
-template <typename T, int P>
-__global__ __launch_bounds__(64) void grouped_glm_report_wo_kernel(const T* const* __restrict__ cols, int bias, int64_t n_rows,
-                                                                   const int64_t* __restrict__ off, int64_t n_groups, int link,
-                                                                   int variance, int64_t split_rows, const T* __restrict__ coeffs,
-                                                                   const uint8_t* __restrict__ is_null, GlmReportDev<T> o,
-                                                                   int64_t* __restrict__ long_list, unsigned* __restrict__ long_count,
-                                                                   int64_t long_cap) {
-    __shared__ double lds[kGrLds];
-    const GrLds l(lds);
-    const int lane = threadIdx.x;
-    const int pp = P + bias;
-    gptr<T> cx[P];
-#pragma unroll
-    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
-    const gptr<T> cy = as_global(cols[P]);
-    const T* const pwp = cols[P + 1];
-    const T* const ofp = cols[P + 2];
-    for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
-        const int64_t r0 = off[g], n = off[g + 1] - r0;
-        const bool bad = r0 < 0 || n < 0 || r0 + n > n_rows;
-        if (bad || n < pp || is_null[g]) {  // (a group that fails the weight rule is a null fit)
-            gr_write_null<T>(o, g, bad ? 0 : n, pp, lane);
-            continue;
-        }
-        if (n > split_rows) {
-            gr_append_long(long_list, long_count, long_cap, g, lane);
-            continue;
-        }
-        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        const double y0 = gr_shift_wo<T>(cy, pwp, r0, r0 + n, bias, variance, lane);
-        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
-        GrSums s;
-        gr_accumulate<T, P, true>(cx, cy, r0, r0 + n, y0, bias, link, variance, l, lane, acc, acc2, s, pwp, ofp);
-        PDS_WAVE_LDS_SYNC();
-        wave_tile_for_d(
-            lane,
-            [&](int i, int c, double v, double side) {
-                l.gm[i * kGrG + c] = v;
-                if (c == 0) {
-                    l.gm[i * kGrG + 16] = side;
-                    l.gm[16 * kGrG + i] = side;
-                }
-            },
-            acc, acc2);
-        if (lane == 0) l.gm[16 * kGrG + 16] = s.sw;
-        PDS_WAVE_LDS_SYNC();
-        gr_epilogue<T, P, true>(o, g, n, bias, variance, y0, l, s, lane, ofp != nullptr);
-    }
-}
-
-template <typename T, int P>
-__global__ __launch_bounds__(64) void grouped_glm_report_wo_piece_kernel(const T* const* __restrict__ cols, int bias,
-                                                                         const int64_t* __restrict__ off, int link, int variance,
-                                                                         const T* __restrict__ coeffs, const int64_t* __restrict__ pieces,
-                                                                         int64_t n_pieces, double* __restrict__ rec) {
-    __shared__ double lds[kGrLds];
-    const GrLds l(lds);
-    const int lane = threadIdx.x;
-    gptr<T> cx[P];
-#pragma unroll
-    for (int c = 0; c < P; ++c) cx[c] = as_global(cols[c]);
-    const gptr<T> cy = as_global(cols[P]);
-    const T* const pwp = cols[P + 1];
-    const T* const ofp = cols[P + 2];
-    for (int64_t k = blockIdx.x; k < n_pieces; k += gridDim.x) {
-        const int64_t g = pieces[3 * k], r0 = pieces[3 * k + 1], r1 = pieces[3 * k + 2];
-        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        const double y0 = gr_shift_wo<T>(cy, pwp, off[g], off[g + 1], bias, variance, lane);
-        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
-        GrSums s;
-        gr_accumulate<T, P, true>(cx, cy, r0, r1, y0, bias, link, variance, l, lane, acc, acc2, s, pwp, ofp);
-        double* out = rec + k * kGlmReportRec;
-        wave_tile_for_d(
-            lane,
-            [&](int i, int c, double v, double side) {
-                out[i * 16 + c] = v;
-                if (c == 0) out[256 + i] = side;
-            },
-            acc, acc2);
-        if (lane == 0) {
-            out[272] = s.sw;
-            out[273] = s.sy;
-            out[274] = s.pe;
-            out[275] = s.dv;
-            out[276] = s.fs;
-            out[277] = s.spw;
-            out[278] = s.npos;
-        }
-    }
-}
-
-template <typename T, int P>
-__global__ __launch_bounds__(64) void grouped_glm_report_wo_fold_kernel(const T* const* __restrict__ cols, int bias,
-                                                                        const int64_t* __restrict__ off, int variance,
-                                                                        const T* __restrict__ coeffs, const int64_t* __restrict__ fin,
-                                                                        int64_t n_fin, const double* __restrict__ rec, GlmReportDev<T> o) {
-    __shared__ double lds[kGrLds];
-    const GrLds l(lds);
-    const int lane = threadIdx.x;
-    const gptr<T> cy = as_global(cols[P]);
-    const T* const pwp = cols[P + 1];
-    const T* const ofp = cols[P + 2];
-    for (int64_t j = blockIdx.x; j < n_fin; j += gridDim.x) {
-        const int64_t g = fin[3 * j], first = fin[3 * j + 1], cnt = fin[3 * j + 2];
-        gr_load_beta<T, P>(coeffs, g, bias, l, lane);
-        for (int e = lane; e < 279; e += 64) {
-            double v = 0.0;
-            for (int64_t k = 0; k < cnt; ++k) v += rec[(first + k) * kGlmReportRec + e];
-            if (e < 256) {
-                l.gm[(e >> 4) * kGrG + (e & 15)] = v;
-            } else if (e < 272) {
-                l.gm[(e - 256) * kGrG + 16] = v;
-                l.gm[16 * kGrG + (e - 256)] = v;
-            } else {
-                if (e == 272) l.gm[16 * kGrG + 16] = v;
-                l.sm[e - 272] = v;
-            }
-        }
-        PDS_WAVE_LDS_SYNC();
-        GrSums s;
-        s.sw = l.sm[0];
-        s.sy = l.sm[1];
-        s.pe = l.sm[2];
-        s.dv = l.sm[3];
-        s.fs = l.sm[4];
-        s.spw = l.sm[5];
-        s.npos = l.sm[6];
+        gr_each_sum<WO>([&](auto i) { s[i] = l.sm[i]; });
         const int64_t r0 = off[g], r1 = off[g + 1];
-        gr_epilogue<T, P, true>(o, g, r1 - r0, bias, variance, gr_shift_wo<T>(cy, pwp, r0, r1, bias, variance, lane), l, s, lane,
-                                ofp != nullptr);
+        gr_epilogue<T, P, WO>(o, g, r1 - r0, bias, variance, wc.shift(cy, r0, r1, bias, variance, lane), l, s, lane,
+                              wc.of != nullptr);
     }
 }
 
 }  // namespace
 
-#if PDS_GLM_REPORT_WO
-#define PDS_GR_K(name) grouped_glm_report_wo_##name
-#define PDS_GR_L(name) launch_grouped_glm_report_wo##name
-#else
-#define PDS_GR_K(name) grouped_glm_report_##name
-#define PDS_GR_L(name) launch_grouped_glm_report##name
-#endif
+// What each of the two objects exports: the launches of its own kernels, WO = PDS_GLM_REPORT_WO
+template <typename T, bool WO>
+struct GroupedGlmReportSet {
+    static int launch(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const T* d_coeffs, const uint8_t* d_null, const GlmReportDev<T>& out,
+                      const GlmLongList& ll);
+    static int launch_pieces(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
+                             int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec);
+};
 
-template <typename T>
-int PDS_GR_L()(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                              int64_t n_groups, int link, int variance, int64_t split_rows, const T* d_coeffs, const uint8_t* d_null,
-                              const GlmReportDev<T>& out, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
-    if (n_groups <= 0) return PDS_OK;
-    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+template <typename T, bool WO>
+int GroupedGlmReportSet<T, WO>::launch(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const T* d_coeffs, const uint8_t* d_null,
+                                       const GlmReportDev<T>& out, const GlmLongList& ll) {
     KernelTimer timer(ctx, kKindPass2);
-    const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
-    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
-        hipLaunchKernelGGL((PDS_GR_K(kernel)<T, decltype(pc)::value>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows,
-                           d_off, n_groups, link, variance, split_rows, d_coeffs, d_null, out, d_long_list, d_long_count,
-                           long_cap);
+    const int nb = (int)std::min<int64_t>(gr.n_groups, (int64_t)ctx->num_cus * 32);
+    dispatch_width<1, kMaxFeatSmall>(gr.n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((grouped_glm_report_kernel<T, decltype(pc)::value, WO>), dim3(nb), dim3(64), 0, ctx->stream, gr.d_cols, gr.bias,
+                           gr.n_rows, gr.d_off, gr.n_groups, gr.link, gr.variance, gr.split_rows, d_coeffs, d_null, out, ll.d_list,
+                           ll.d_count, ll.cap);
     });
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
 
-template <typename T>
-int PDS_GR_L(_pieces)(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, const int64_t* d_off, int link,
-                                     int variance, const T* d_coeffs, const GlmReportDev<T>& out, const int64_t* d_pieces,
-                                     int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec) {
-    if (n_pieces <= 0 || n_fin <= 0) return PDS_OK;
-    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+template <typename T, bool WO>
+int GroupedGlmReportSet<T, WO>::launch_pieces(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const T* d_coeffs, const GlmReportDev<T>& out,
+                                              const int64_t* d_pieces, int64_t n_pieces, const int64_t* d_fin, int64_t n_fin,
+                                              double* d_rec) {
     KernelTimer timer(ctx, kKindPass2);
     const int nbp = (int)std::min<int64_t>(n_pieces, (int64_t)ctx->num_cus * 32);
     const int nbf = (int)std::min<int64_t>(n_fin, (int64_t)ctx->num_cus * 32);
-    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
+    dispatch_width<1, kMaxFeatSmall>(gr.n_feat, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        hipLaunchKernelGGL((PDS_GR_K(piece_kernel)<T, P>), dim3(nbp), dim3(64), 0, ctx->stream, d_cols, bias, d_off, link, variance,
-                           d_coeffs, d_pieces, n_pieces, d_rec);
-        hipLaunchKernelGGL((PDS_GR_K(fold_kernel)<T, P>), dim3(nbf), dim3(64), 0, ctx->stream, d_cols, bias, d_off, variance,
-                           d_coeffs, d_fin, n_fin, d_rec, out);
+        hipLaunchKernelGGL((grouped_glm_report_piece_kernel<T, P, WO>), dim3(nbp), dim3(64), 0, ctx->stream, gr.d_cols, gr.bias, gr.d_off,
+                           gr.link, gr.variance, d_coeffs, d_pieces, n_pieces, d_rec);
+        hipLaunchKernelGGL((grouped_glm_report_fold_kernel<T, P, WO>), dim3(nbf), dim3(64), 0, ctx->stream, gr.d_cols, gr.bias, gr.d_off,
+                           gr.variance, d_coeffs, d_fin, n_fin, d_rec, out);
     });
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
+template struct GroupedGlmReportSet<double, PDS_GLM_REPORT_WO != 0>;
+template struct GroupedGlmReportSet<float, PDS_GLM_REPORT_WO != 0>;
 
-#define PDS_GR_ARGS(T)                                                                                                                  \
-    pds_ctx*, const T* const*, int, int, int64_t, const int64_t*, int64_t, int, int, int64_t, const T*, const uint8_t*, const GlmReportDev<T>&, \
-        int64_t*, unsigned*, int64_t
-#define PDS_GR_PIECE_ARGS(T)                                                                                                         \
-    pds_ctx*, const T* const*, int, int, const int64_t*, int, int, const T*, const GlmReportDev<T>&, const int64_t*, int64_t, const int64_t*, \
-        int64_t, double*
-template int PDS_GR_L()<double>(PDS_GR_ARGS(double));
-template int PDS_GR_L()<float>(PDS_GR_ARGS(float));
-template int PDS_GR_L(_pieces)<double>(PDS_GR_PIECE_ARGS(double));
-template int PDS_GR_L(_pieces)<float>(PDS_GR_PIECE_ARGS(float));
-#undef PDS_GR_ARGS
-#undef PDS_GR_PIECE_ARGS
-#undef PDS_GR_K
-#undef PDS_GR_L
+#if !PDS_GLM_REPORT_WO
+extern template struct GroupedGlmReportSet<double, true>;  // (grouped_glm_report_wo.hip)
+extern template struct GroupedGlmReportSet<float, true>;
+
+template <typename T>
+int launch_grouped_glm_report(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const T* d_coeffs, const uint8_t* d_null,
+                              const GlmReportDev<T>& out, const GlmLongList& long_list) {
+    if (groups.n_groups <= 0) return PDS_OK;
+    if (groups.n_feat < 1 || groups.n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+    return groups.wo ? GroupedGlmReportSet<T, true>::launch(ctx, groups, d_coeffs, d_null, out, long_list)
+                     : GroupedGlmReportSet<T, false>::launch(ctx, groups, d_coeffs, d_null, out, long_list);
+}
+
+template <typename T>
+int launch_grouped_glm_report_pieces(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const T* d_coeffs, const GlmReportDev<T>& out,
+                                     const int64_t* d_pieces, int64_t n_pieces, const int64_t* d_fin, int64_t n_fin, double* d_rec) {
+    if (n_pieces <= 0 || n_fin <= 0) return PDS_OK;
+    if (groups.n_feat < 1 || groups.n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM report: up to 16 feature columns");
+    return groups.wo ? GroupedGlmReportSet<T, true>::launch_pieces(ctx, groups, d_coeffs, out, d_pieces, n_pieces, d_fin, n_fin, d_rec)
+                     : GroupedGlmReportSet<T, false>::launch_pieces(ctx, groups, d_coeffs, out, d_pieces, n_pieces, d_fin, n_fin, d_rec);
+}
+
+template int launch_grouped_glm_report<double>(pds_ctx*, const GlmGroupsDev<double>&, const double*, const uint8_t*, const GlmReportDev<double>&,
+                                               const GlmLongList&);
+template int launch_grouped_glm_report<float>(pds_ctx*, const GlmGroupsDev<float>&, const float*, const uint8_t*, const GlmReportDev<float>&,
+                                              const GlmLongList&);
+template int launch_grouped_glm_report_pieces<double>(pds_ctx*, const GlmGroupsDev<double>&, const double*, const GlmReportDev<double>&,
+                                                      const int64_t*, int64_t, const int64_t*, int64_t, double*);
+template int launch_grouped_glm_report_pieces<float>(pds_ctx*, const GlmGroupsDev<float>&, const float*, const GlmReportDev<float>&,
+                                                     const int64_t*, int64_t, const int64_t*, int64_t, double*);
+#endif
 
 }  // namespace pds

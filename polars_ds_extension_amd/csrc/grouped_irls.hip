@@ -440,75 +440,51 @@ __global__ __launch_bounds__(256) void glm_pred_range_kernel(const T* const* __r
     }
 }
 
+}  // namespace
+
+// What each of the four objects exports: the launch of its own kernel set, PEN = PDS_GROUPED_IRLS_PEN.  The kernel keeps its flat
+// parameter list (its registers are counted, above), so the description is unpacked here.
 template <typename T, int PEN>
-int gi_launch(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off, int64_t n_groups, int link,
-              int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs, int32_t* d_n_iter, uint8_t* d_null, T* d_pred,
-              uint8_t* d_row_null, const uint32_t* d_perm, int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg,
-              double l2_reg) {
+struct GroupedIrlsSet {
+    static int launch(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const GlmFitDev<T>& fit, const GlmLongList& ll);
+};
+
+template <typename T, int PEN>
+int GroupedIrlsSet<T, PEN>::launch(pds_ctx* ctx, const GlmGroupsDev<T>& gr, const GlmFitDev<T>& fit, const GlmLongList& ll) {
     KernelTimer timer(ctx, kKindIter);
-    const int nb = (int)std::min<int64_t>(n_groups, (int64_t)ctx->num_cus * 32);
-    dispatch_width<1, kMaxFeatSmall>(n_feat, [&](auto pc) {
-        hipLaunchKernelGGL((grouped_irls_kernel<T, decltype(pc)::value, PEN>), dim3(nb), dim3(64), 0, ctx->stream, d_cols, bias, n_rows, d_off,
-                           n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter, d_null, d_pred, d_row_null, d_perm,
-                           d_long_list, d_long_count, long_cap, l1_reg, l2_reg);
+    const int nb = (int)std::min<int64_t>(gr.n_groups, (int64_t)ctx->num_cus * 32);
+    dispatch_width<1, kMaxFeatSmall>(gr.n_feat, [&](auto pc) {
+        hipLaunchKernelGGL((grouped_irls_kernel<T, decltype(pc)::value, PEN>), dim3(nb), dim3(64), 0, ctx->stream, gr.d_cols, gr.bias,
+                           gr.n_rows, gr.d_off, gr.n_groups, gr.link, gr.variance, fit.tol, fit.max_iter, gr.split_rows, fit.d_coeffs,
+                           fit.d_n_iter, fit.d_null, fit.d_pred, fit.d_row_null, fit.d_perm, ll.d_list, ll.d_count, ll.cap, fit.l1_reg,
+                           fit.l2_reg);
     });
     PDS_HIP_CHECK(hipGetLastError());
     return PDS_OK;
 }
+template struct GroupedIrlsSet<double, PDS_GROUPED_IRLS_PEN>;
+template struct GroupedIrlsSet<float, PDS_GROUPED_IRLS_PEN>;
 
-}  // namespace
-
-#define PDS_GI_ARGS(T)                                                                                                                   \
-    pds_ctx*, const T* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int, int64_t, T*, int32_t*, uint8_t*, T*, \
-        uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t, double, double
-
-#if PDS_GROUPED_IRLS_PEN == 3
-// the weighted / offset kernels (grouped_irls_wo.hip): d_cols holds P + 3 entries, x_0 .. x_{p-1}, y, pw (nullable), o (nullable)
-template <typename T>
-int launch_grouped_irls_wo(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                           int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
-                           int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
-                           int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap) {
-    if (n_groups <= 0) return PDS_OK;
-    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
-    return gi_launch<T, kGiWo>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs,
-                               d_n_iter, d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, 0.0, 0.0);
-}
-template int launch_grouped_irls_wo<double>(pds_ctx*, const double* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
-                                            int64_t, double*, int32_t*, uint8_t*, double*, uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t);
-template int launch_grouped_irls_wo<float>(pds_ctx*, const float* const*, int, int, int64_t, const int64_t*, int64_t, int, int, double, int,
-                                           int64_t, float*, int32_t*, uint8_t*, float*, uint8_t*, const uint32_t*, int64_t*, unsigned*, int64_t);
-#elif PDS_GROUPED_IRLS_PEN
-// the kernels of one penalised mode (grouped_irls_ridge.hip, grouped_irls_cd.hip)
-template <typename T, int PEN>
-int launch_grouped_irls_pen(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                            int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
-                            int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
-                            int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg, double l2_reg) {
-    return gi_launch<T, PEN>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
-                             d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, l1_reg, l2_reg);
-}
-template int launch_grouped_irls_pen<double, PDS_GROUPED_IRLS_PEN>(PDS_GI_ARGS(double));
-template int launch_grouped_irls_pen<float, PDS_GROUPED_IRLS_PEN>(PDS_GI_ARGS(float));
-#else
-template <typename T, int PEN>
-int launch_grouped_irls_pen(PDS_GI_ARGS(T));
+#if PDS_GROUPED_IRLS_PEN == 0
+// (the other three sets: grouped_irls_ridge.hip, grouped_irls_cd.hip, grouped_irls_wo.hip)
+extern template struct GroupedIrlsSet<double, 1>;
+extern template struct GroupedIrlsSet<float, 1>;
+extern template struct GroupedIrlsSet<double, 2>;
+extern template struct GroupedIrlsSet<float, 2>;
+extern template struct GroupedIrlsSet<double, kGiWo>;
+extern template struct GroupedIrlsSet<float, kGiWo>;
 
 template <typename T>
-int launch_grouped_irls(pds_ctx* ctx, const T* const* d_cols, int n_feat, int bias, int64_t n_rows, const int64_t* d_off,
-                        int64_t n_groups, int link, int variance, double tol, int max_iter, int64_t split_rows, T* d_coeffs,
-                        int32_t* d_n_iter, uint8_t* d_null, T* d_pred, uint8_t* d_row_null, const uint32_t* d_perm,
-                        int64_t* d_long_list, unsigned* d_long_count, int64_t long_cap, double l1_reg, double l2_reg) {
-    if (n_groups <= 0) return PDS_OK;
-    if (n_feat < 1 || n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
-    if (l1_reg > 0.0 || l2_reg > 0.0) {  // (a penalty <= 0 means none)
-        auto launch = l1_reg > 0.0 ? launch_grouped_irls_pen<T, 2> : launch_grouped_irls_pen<T, 1>;
-        return launch(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
-                      d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, l1_reg > 0.0 ? l1_reg : 0.0,
-                      l2_reg > 0.0 ? l2_reg : 0.0);
-    }
-    return gi_launch<T, 0>(ctx, d_cols, n_feat, bias, n_rows, d_off, n_groups, link, variance, tol, max_iter, split_rows, d_coeffs, d_n_iter,
-                           d_null, d_pred, d_row_null, d_perm, d_long_list, d_long_count, long_cap, 0.0, 0.0);
+int launch_grouped_irls(pds_ctx* ctx, const GlmGroupsDev<T>& groups, const GlmFitDev<T>& fit, const GlmLongList& long_list) {
+    if (groups.n_groups <= 0) return PDS_OK;
+    if (groups.n_feat < 1 || groups.n_feat > kMaxFeatSmall) return fail(PDS_ERR_UNSUPPORTED, "grouped GLM (IRLS): up to 16 feature columns");
+    GlmFitDev<T> f = fit;  // (a penalty <= 0 means none; the weighted / offset kernels are unpenalised)
+    f.l1_reg = !groups.wo && fit.l1_reg > 0.0 ? fit.l1_reg : 0.0;
+    f.l2_reg = !groups.wo && fit.l2_reg > 0.0 ? fit.l2_reg : 0.0;
+    if (groups.wo) return GroupedIrlsSet<T, kGiWo>::launch(ctx, groups, f, long_list);
+    if (f.l1_reg > 0.0) return GroupedIrlsSet<T, 2>::launch(ctx, groups, f, long_list);
+    if (f.l2_reg > 0.0) return GroupedIrlsSet<T, 1>::launch(ctx, groups, f, long_list);
+    return GroupedIrlsSet<T, 0>::launch(ctx, groups, f, long_list);
 }
 
 template <typename T>
@@ -523,13 +499,12 @@ int launch_glm_pred_range(pds_ctx* ctx, const T* const* d_cols, int n_feat, int 
     return PDS_OK;
 }
 
-template int launch_grouped_irls<double>(PDS_GI_ARGS(double));
-template int launch_grouped_irls<float>(PDS_GI_ARGS(float));
+template int launch_grouped_irls<double>(pds_ctx*, const GlmGroupsDev<double>&, const GlmFitDev<double>&, const GlmLongList&);
+template int launch_grouped_irls<float>(pds_ctx*, const GlmGroupsDev<float>&, const GlmFitDev<float>&, const GlmLongList&);
 template int launch_glm_pred_range<double>(pds_ctx*, const double* const*, int, int, int64_t, int64_t, const double*, const uint8_t*, int,
                                            double*, uint8_t*, const uint32_t*, const double*);
 template int launch_glm_pred_range<float>(pds_ctx*, const float* const*, int, int, int64_t, int64_t, const float*, const uint8_t*, int,
                                           float*, uint8_t*, const uint32_t*, const float*);
 #endif
-#undef PDS_GI_ARGS
 
 }  // namespace pds
